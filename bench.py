@@ -5,6 +5,14 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it
 torch.distributed.run, one rank per GPU.  A "step" advances every lane (independent stereo stream) of every rank by
 one frame: value = N * lanes * K / t, t = max over ranks of the barrier-bracketed wall time of the K steps.
 All frames are rendered and resident in HBM before the timed region; nothing is copied host->device inside it.
+
+A plain run does only what `value` needs: render, set up, warm up, time the K steps, write --dump-outputs, print the line.
+Its frames come from a pool that does not grow with K, so that setting up takes the same few seconds for any K (rendering
+costs ~24 ms per pair): T trajectories of (lanes / T - 1 + POOL_SWING) frames; stream s, slot q = s // T of trajectory s % T,
+plays frame q + f(step), f walking 0 .. POOL_SWING - 1 and back.  The streams of a trajectory move in lockstep one frame
+apart: no two streams read the same frame in a step, and every stream sees consecutive poses, forwards and backwards.
+
+--full measures and checks everything else, and its frames are those of rounds 4-6 (what follows).
 Every stream sees a NEW frame at every step of the run (round 4): --trajectories T trajectories of F frames each are rendered
 through a long "street" world (stereo_vo_amd/synth.py), stream s plays trajectory s % T from frame 7 (s // T) on, and F is
 chosen so that no stream ever wraps (F >= 200).  The speculative FAST threshold of k_fast is therefore always applied to a frame
@@ -16,8 +24,8 @@ stage 2 of the next on a second HIP stream; kernel times below are per launch = 
 Streams shard by independent stream across ranks with no data-path collective ("weak" scaling); the per-frame
 result records are all-gathered over RCCL as in configs[3] (512 B-class, latency only).
 
-Rank 0 prints ONE JSON line with the `roofline` of the dominant kernel (HIP events recorded around every kernel on
-the stream it runs on) and the `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, N=1 only).
+Rank 0 prints ONE JSON line; with --full it carries the `roofline` of the dominant kernel (HIP events recorded around every
+kernel on the stream it runs on) and the `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, N=1 only).
 """
 import argparse
 import json
@@ -157,6 +165,56 @@ def lane_frame(lane, step, trajectories, n_frames):
     return j, frame_schedule(k, n_frames)
 
 
+POOL_SWING = 32        # plain run: frames a stream walks before it turns back (module docstring)
+
+
+def pool_frames(lanes, trajectories):
+    """Frames per trajectory of the plain run's pool: one start frame per stream slot, then POOL_SWING - 1 more."""
+    return (lanes + trajectories - 1) // trajectories - 1 + POOL_SWING
+
+
+def pool_frame(lane, step, trajectories):
+    """(trajectory, frame) stream `lane` is shown at `step` in the plain run: slot q = lane // T of trajectory lane % T plays frame
+    q + frame_schedule(step, POOL_SWING), so the streams of a trajectory move in lockstep, one frame apart."""
+    return lane % trajectories, lane // trajectories + frame_schedule(step, POOL_SWING)
+
+
+DUMP_LANES = 8                 # streams whose lists --dump-outputs writes, a fixed seeded sample
+DUMP_LIST_BYTES = 48 << 20     # what those lists may take at the contexts' capacity; the records come on top (< 64 MB in all)
+
+
+def _columns(a):
+    """structured array (keypoints, pairings, index pairs) -> float64 [n, fields], exact for its f32 / i32 fields"""
+    return np.stack([a[f].astype(np.float64) for f in a.dtype.names], axis=1)
+
+
+def dump_outputs(path, batch, records, max_kps):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy.  result_<field> = that field of every
+    stream's svo_result record (all ranks, stream order, float64); lane<g>_o<octave>_* = the current frame's keypoints and
+    descriptors (left, right), pairings and tracked pairs, lane<g>_residuals = the pose fit's residuals, of a fixed seeded sample
+    of this rank's streams (float64; descriptors float32).  Returns the bytes written."""
+    rec = np.ascontiguousarray(records).view(np.dtype(Result)).reshape(-1)
+    out = {"result_" + name: rec[name].astype(np.float64) for name in rec.dtype.names}
+    # bytes one stream's lists can take: keypoints 7 x 8 + descriptor 32 x 4 per side, pairing 32, tracked pair 16, residuals 32
+    n = max(1, min(DUMP_LANES, batch.B, DUMP_LIST_BYTES // (max_kps * (2 * (56 + 128) + 32 + 16 + 32))))
+    for g in sorted(int(g) for g in np.random.RandomState(0).permutation(batch.B)[:n]):
+        ctx, l = batch.lane(g)
+        for o in range(max(1, int(rec["n_octaves"][g]))):
+            for side, name in ((0, "left"), (1, "right")):
+                k, d = ctx.keypoints(l, 0, side, o)
+                out["lane%03d_o%d_keypoints_%s" % (g, o, name)] = _columns(k)
+                out["lane%03d_o%d_descriptors_%s" % (g, o, name)] = d.astype(np.float32)
+            out["lane%03d_o%d_pairings" % (g, o)] = _columns(ctx.matches(l, 0, o))
+            out["lane%03d_o%d_tracked" % (g, o)] = _columns(ctx.tracked(l, o))
+        out["lane%03d_residuals" % g] = ctx.residuals(l).astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total < 64 << 20, "--dump-outputs: %d bytes" % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
 def gather_records(local, world_size):
     """All-gather of the per-rank result records (uint8 tensor [lanes, sizeof(svo_result)]) -> [world*lanes, ...]."""
     if world_size == 1:
@@ -206,17 +264,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--lanes", type=int, default=192, help="independent stereo streams per GPU (all contexts together)")
     ap.add_argument("--contexts", type=int, default=2, help="contexts per GPU, each on its own HIP stream with lanes/contexts streams: the latency-bound per-stream kernels of one overlap the throughput kernels of the other")
-    ap.add_argument("--frames", type=int, default=0, help="frames rendered per trajectory; 0 (default) = as many as it takes for no stream ever to see a frame twice (>= 200)")
-    ap.add_argument("--trajectories", type=int, default=8, help="distinct camera trajectories rendered per rank; stream s plays trajectory s %% T from frame 7 * (s // T) on")
-    ap.add_argument("--long-steps", type=int, default=100, help="N=1: when --steps is smaller than this, one more timed leg of this many steps (after --warmup untimed ones, estimators reset, the same streams from their first frame on: no stream sees a frame twice inside the leg), reported as `long_run` -- so that a short --steps run still carries a measurement over a few hundred milliseconds; 0 = skip")
-    ap.add_argument("--cut-steps", type=int, default=60, help="steps of the scene-cut leg (every stream jumps to another trajectory every 20 frames, estimators reset as an application would); N=1 only; 0 = skip")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides `value` as well: the per-kernel table and roofline, the legs below, --timeline; and time frames no stream sees twice (--frames 0).  Off (default): a plain run, only what `value` needs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them computed as DIR/<name>.npy (every stream's result record; the lists of a fixed sample of streams): see dump_outputs()")
+    ap.add_argument("--frames", type=int, default=0, help="frames rendered per trajectory, stream s plays trajectory s %% T from frame 7 * (s // T) on, back and forth; 0 (default) = the plain run's pool (module docstring), with --full as many as it takes for no stream ever to see a frame twice (>= 200)")
+    ap.add_argument("--trajectories", type=int, default=8, help="distinct camera trajectories rendered per rank; stream s plays trajectory s %% T")
+    ap.add_argument("--long-steps", type=int, default=100, help="--full, N=1: when --steps is smaller than this, one more timed leg of this many steps (after --warmup untimed ones, estimators reset, the same streams from their first frame on: no stream sees a frame twice inside the leg), reported as `long_run` -- so that a short --steps run still carries a measurement over a few hundred milliseconds; 0 = skip")
+    ap.add_argument("--cut-steps", type=int, default=60, help="--full: steps of the scene-cut leg (every stream jumps to another trajectory every 20 frames, estimators reset as an application would); N=1 only; 0 = skip")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=960)
     ap.add_argument("--orb-nfeats", type=int, default=2000)
-    ap.add_argument("--cpu-frames", type=int, default=128, help="upper bound on the frames per probe stream replayed on the CPU oracle (baseline timing + parity probe; 0 = skip)")
-    ap.add_argument("--host-fed-steps", type=int, default=16, help="steps of the host-fed leg (page-locked host frames uploaded per step on the contexts' copy streams; 0 = skip); N=1 only")
-    ap.add_argument("--single-stream", type=int, default=1, help="1: also time ONE stream alone (plain launches, hipGraph replay, frames dealt to 2 / 3 contexts); N=1, config2 only")
-    ap.add_argument("--exclusive", type=int, default=1, help="1: after the timed region, time the roofline kernel again with one context alone on the GPU (roofline.exclusive); 0 = skip (profiling runs)")
+    ap.add_argument("--cpu-frames", type=int, default=128, help="--full: upper bound on the frames per probe stream replayed on the CPU oracle (baseline timing + parity probe; 0 = skip)")
+    ap.add_argument("--host-fed-steps", type=int, default=16, help="--full: steps of the host-fed leg (page-locked host frames uploaded per step on the contexts' copy streams; 0 = skip); N=1 only")
+    ap.add_argument("--single-stream", type=int, default=1, help="--full: 1 = also time ONE stream alone (plain launches, hipGraph replay, frames dealt to 2 / 3 contexts); N=1, config2 only")
+    ap.add_argument("--exclusive", type=int, default=1, help="--full: 1 = after the timed region, time the roofline kernel again with one context alone on the GPU (roofline.exclusive); 0 = skip (profiling runs)")
     ap.add_argument("--dump-records", default="", help="test hook: every rank writes its own and the gathered result records of the last step to <path>.rank<r>.npz")
     ap.add_argument("--schedule", default="pipelined", choices=["pipelined", "free"], help="pipelined: detect phases of the contexts serialised, stages 3-5 overlap the next context's detect; free: contexts run unsynchronised")
     ap.add_argument("--post-on-rest", type=int, default=1, help="0: all of stage 2 on the detect stream; 1 (default): the NMS / row-sort block of stage 2 and the description run on the overlap stream(s) with stages 3-5; 2: on a third stream of its own; 3: as 1, together with the per-level selection (the detect stream keeps pyramid + FAST only)")
@@ -226,13 +286,18 @@ def main():
     ap.add_argument("--detect-ahead", type=int, default=1, help="1 (default): a context's detector of frame t + 1 starts once the description of frame t has read the detector's scratch (it overlaps that context's own stages 3-5); 0: it waits for the whole frame t (rounds 1-3)")
     ap.add_argument("--max-kps", type=int, default=4096, help="keypoint capacity per image of the contexts (svo_config.max_kps)")
     ap.add_argument("--scene", default="street", choices=["street", "planes", "relief"], help="synthetic scene type (stereo_vo_amd/synth.py): street (default, round 4) = ground + far wall + a facade every 4.5 m along a world as long as the trajectory; planes = wall + ground + facades (rounds 1-3: a ~1 m world, needs --frames 6); relief = planes plus 28 billboards at 4..22 m")
-    ap.add_argument("--relief-lanes", type=int, default=16, help="N=1, config2: streams of the extra leg on the OTHER scene type (reported as `other_scene`: pass-through counters and pose error against ground truth beside the timed scene's); 0 = skip")
-    ap.add_argument("--other-workloads", type=int, default=1, help="1: after everything else, short timed legs of the other single-GPU configurations (BASELINE.json configs[2] KITTI shape, configs[4] 2048x1536 FAST+ORB) as sub-processes, reported as `other_workloads`; N=1, config2 only")
-    ap.add_argument("--timeline", type=int, default=0, help="N: create the contexts under SVO_TIMELINE=1 and, after the timed region, run N (<= 14) more steps whose launches are reported as `timeline` (what was in flight, from wall-clock stamps inside the kernels); the stamps cost a little, so a line with --timeline is not the headline")
+    ap.add_argument("--relief-lanes", type=int, default=16, help="--full, N=1, config2: streams of the extra leg on the OTHER scene type (reported as `other_scene`: pass-through counters and pose error against ground truth beside the timed scene's); 0 = skip")
+    ap.add_argument("--other-workloads", type=int, default=1, help="--full: 1 = after everything else, short timed legs of the other single-GPU configurations (BASELINE.json configs[2] KITTI shape, configs[4] 2048x1536 FAST+ORB) as sub-processes, reported as `other_workloads`; N=1, config2 only")
+    ap.add_argument("--timeline", type=int, default=0, help="--full only: N = create the contexts under SVO_TIMELINE=1 and, after the timed region, run N (<= 14) more steps whose launches are reported as `timeline` (what was in flight, from wall-clock stamps inside the kernels); the stamps cost a little, so a line with --timeline is not the headline")
     ap.add_argument("--timeline-csv", default="", help="with --timeline: also write every launch hull of those steps to this CSV")
     ap.add_argument("--workload", default="config2", choices=["config2", "config3", "config5"],
                     help="BASELINE.json configs[1] (default, the metric's configuration), configs[2] KITTI shape, configs[4] 2048x1536 FAST+ORB 3 octaves")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if args.timeline and not args.full:
+        raise SystemExit("bench.py: --timeline is part of a --full run")
+    full = args.full
     detect_fast_orb, n_octaves, kitti = False, 1, False
     if args.workload == "config3":
         args.width, args.height, args.orb_nfeats, kitti = 1241, 376, 900, True
@@ -268,9 +333,10 @@ def main():
     W, H, B = args.width, args.height, args.lanes
     T = max(1, min(args.trajectories, B))
     total_steps = args.warmup + args.steps
-    long_steps = args.long_steps if (world == 1 and args.long_steps > args.steps) else 0
+    long_steps = args.long_steps if (full and world == 1 and args.long_steps > args.steps) else 0
     plan_steps = max(total_steps + min(max(args.timeline, 0), 14), args.warmup + long_steps)           # frames / pointer tables cover the longer of the legs
-    F = args.frames if args.frames > 0 else frames_needed(B, T, plan_steps)
+    pooled = args.frames == 0 and not full
+    F = args.frames if args.frames > 0 else (pool_frames(B, T) if pooled else frames_needed(B, T, plan_steps))
     focal = 718.856 if kitti else 800.0 * W / 1280.0
     baseline = 0.537 if kitti else 0.12
     cxy = dict(cx=607.19, cy=185.22) if kitti else {}
@@ -285,7 +351,7 @@ def main():
     t_render_end = time.perf_counter()
 
     def frame_of(lane, step):
-        j, t = lane_frame(lane, step, T, F)
+        j, t = pool_frame(lane, step, T) if pooled else lane_frame(lane, step, T, F)
         return frames[j][t]
 
     def ptrs_at_step(step):
@@ -303,9 +369,11 @@ def main():
     if args.timeline > 0:
         os.environ["SVO_TIMELINE"] = "1"
     batch = StreamBatch(p, cam, W, H, B, NC, device=local_rank, schedule=args.schedule, post_on_rest=("own" if args.post_on_rest == 2 else ("select" if args.post_on_rest == 3 else bool(args.post_on_rest))),
-                        det_priority=args.det_priority, kernel_times=True, max_octaves=n_octaves, det_streams=args.det_streams, rest_streams=args.rest_streams, max_kps=args.max_kps, detect_ahead=bool(args.detect_ahead))
+                        det_priority=args.det_priority, kernel_times=full, max_octaves=n_octaves, det_streams=args.det_streams, rest_streams=args.rest_streams, max_kps=args.max_kps, detect_ahead=bool(args.detect_ahead))
     Bc, pipelined, ctxs = batch.Bc, batch.pipelined, batch.ctxs
-    ptrs_by_step = [ptrs_at_step(i) for i in range(plan_steps)]          # built ahead: the timed loop only indexes it
+    # a plain run's schedule repeats after 2 (n - 1) steps (frame_schedule over n frames): that many tables serve any --steps
+    n_tables = plan_steps if full else min(plan_steps, max(1, 2 * ((POOL_SWING if pooled else F) - 1)))
+    ptrs_by_step = [ptrs_at_step(i) for i in range(n_tables)]            # built ahead: the timed loop only indexes it
 
     frames_by_step = [batch.prepare(q) for q in ptrs_by_step]            # the ctypes frame tables too: the host's share of a step is then the launches
     gather_done = [torch.cuda.Event(), torch.cuda.Event()]
@@ -318,7 +386,7 @@ def main():
             batch.flip_records()
             if i >= 2:
                 batch.hold_for(gather_done[i & 1])       # the all-gather that read this buffer two steps ago
-        batch.step_prepared(frames_by_step[i])
+        batch.step_prepared(frames_by_step[i % n_tables])
         if world > 1:          # the all-gather runs on torch's current stream: it waits for every context's last work
             batch.make_wait(torch.cuda.current_stream(dev))
         out = gather_records(batch.rec, world)
@@ -369,17 +437,18 @@ def main():
         step(i)
     torch.cuda.synchronize()
 
-    # The warm-up steps time every kernel (the per-kernel table and the choice of the roofline kernel); the timed region
+    # --full: the warm-up steps time every kernel (the per-kernel table and the choice of the roofline kernel); the timed region
     # keeps the two events per launch only around that one kernel, whose duration it has to measure live.
-    for c_ in ctxs:
-        c_.wait()
-    kt_warm = batch.pooled_kernel_times()
-    detect_kernels = ("resize", "fast", "select") + (() if args.post_on_rest else ("describe", "nms_rowsort"))      # what the detect stream carries
-    pool = [k for k in kt_warm if kt_warm[k][1] > 0 and (k in detect_kernels or not pipelined)]
-    dom = max(pool, key=lambda k: kt_warm[k][0] / kt_warm[k][1] / (7 if k == "resize" else 1)) if pool else "fast"      # per LAUNCH: the resize span covers seven
-    for c_ in ctxs:
-        c_.kernel_times_select(dom)
-        c_.kernel_times_reset()
+    if full:
+        for c_ in ctxs:
+            c_.wait()
+        kt_warm = batch.pooled_kernel_times()
+        detect_kernels = ("resize", "fast", "select") + (() if args.post_on_rest else ("describe", "nms_rowsort"))      # what the detect stream carries
+        pool = [k for k in kt_warm if kt_warm[k][1] > 0 and (k in detect_kernels or not pipelined)]
+        dom = max(pool, key=lambda k: kt_warm[k][0] / kt_warm[k][1] / (7 if k == "resize" else 1)) if pool else "fast"      # per LAUNCH: the resize span covers seven
+        for c_ in ctxs:
+            c_.kernel_times_select(dom)
+            c_.kernel_times_reset()
     for c_ in ctxs:
         c_.redo_count(reset=True)                 # (waits for the context: the warm-up is over)
     barrier(); torch.cuda.synchronize()
@@ -393,9 +462,12 @@ def main():
     dt_own = dt                                   # this rank's own clock around the K steps; `value` uses the MAX over ranks
     dt = reduce_max(dt, dev, world)
 
-    kt = batch.pooled_kernel_times()
+    kt = batch.pooled_kernel_times() if full else None
     redo_pairs = sum(c_.redo_count(reset=True) for c_ in ctxs)
     results = batch.results()
+    assert allrec is not None and allrec.shape[0] == world * B
+    if args.dump_outputs and rank == 0:           # the last timed step's outputs, before any other step runs on the contexts
+        dump_outputs(args.dump_outputs, batch, allrec.cpu().numpy(), args.max_kps)
     timeline = None
     if args.timeline > 0 and world == 1:
         nt_ = min(args.timeline, 14, plan_steps - total_steps)
@@ -417,14 +489,13 @@ def main():
     mean_track = float(np.mean([r.tracked_feats_from_last_frame for r in results]))
     ts_mean = {k: round(float(np.mean([r.track_stats[i] for r in results])), 1) for i, k in enumerate(TS_NAMES)}
     dist_info = dist_audit(allrec, batch.rec, world, rank, local_rank, dev, own_ms_per_step=1e3 * dt_own / args.steps, own_enqueue_ms_per_step=1e3 * t_enqueue / args.steps)
-    assert allrec is not None and allrec.shape[0] == world * B
     if args.dump_records:      # tests/test_gpu_parity.py: every rank's own records and what the all-gather handed it
         np.savez(args.dump_records + ".rank%d.npz" % rank, local=batch.rec.cpu().numpy(), gathered=allrec.cpu().numpy(), rank=rank, world=world,
                  own=np.frombuffer(b"".join(bytes(r) for r in results), np.uint8).reshape(B, -1))
 
-    if rank == 0:
-        pairs = world * B * args.steps
-        value = pairs / dt
+    def full_report(value):
+        """--full, rank 0: the fields of the line besides `value` and what it was measured on -- the roofline and per-kernel
+        table of this run's HIP events, then the legs, each after the timed region."""
         lw, lh = [], []
         if detect_fast_orb:       # FAST+ORB works on the x1/2 octave images (S1:80-83), not on ORB's x1/1.2 levels
             for o in range(n_octaves):
@@ -554,21 +625,7 @@ def main():
                                      "note": "same kernel, same launch shape, %d launches with one context alone on the GPU (HIP events, after the timed region)" % calls}
         except Exception as e:
             roofline["exclusive"] = {"error": str(e)}
-        line = {
-            "metric": "stereo pairs/sec @%d×%d" % (W, H), "value": round(value, 2), "unit": "stereo pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/f64", "data": "synthetic",
-            "config": {"workload": "%s: %dx%d synthetic stereo streams, %s, orb_nfeats %d (~%d kps/image in octave 0 after NMS), BF match, BF track, robust GN; %d independent streams per GPU in %d contexts on separate HIP streams, one frame per stream per step"
-                                   % (args.workload, W, H, "FAST+ORB on %d x1/2 octaves" % n_octaves if detect_fast_orb else "ORB x 8 levels", args.orb_nfeats, int(mean_kps), B, NC),
-                       "lanes_per_gpu": B, "contexts_per_gpu": NC, "lanes_per_context": Bc, "schedule": args.schedule if NC > 1 else "single stream", "detect_ahead": bool(args.detect_ahead),
-                       "sequence": "%d trajectories x %d frames per rank (scene '%s'), stream s = trajectory s %% %d from frame %d * (s // %d) on: %d consecutive DISTINCT frames per stream over warm-up + timed steps, none seen twice"
-                                   % (T, F, args.scene, T, PHASE_STRIDE, T, total_steps),
-                       "frames_per_trajectory": F, "distinct_frames_per_stream": min(total_steps, F), "render_s": round(t_render, 1),
-                       "parallelism": "streams sharded across %d GPU(s), result all-gather per step" % world},
-            "timed_region_s": round(dt, 4),
-            "host_enqueue_ms_per_step": round(1e3 * t_enqueue / args.steps, 4),
-            "fast_redo_rate": round(redo_pairs / float(max(1, args.steps * 2 * B * (n_octaves if detect_fast_orb else 8))), 6),
-            "fast_redo_note": "(image, level) pairs of the timed steps whose speculative FAST threshold found too few corners and ran k_fast again at the caller's threshold (%d of %d); every frame of the run is new to its stream" % (redo_pairs, args.steps * 2 * B * (n_octaves if detect_fast_orb else 8)),
+        return {
             "long_run": long_run,
             "scene_cuts": scene_cuts,
             "other_workloads": other_workloads,
@@ -580,19 +637,46 @@ def main():
             "single_stream": single_stream,
             "path_hbm_frac": round(pair_bytes * value / 1e9 / HBM_PEAK_GBS, 5),
             "algorithmic_bytes_per_pair": int(pair_bytes),
-            "valid_last_step": "%d/%d" % (n_valid, B),
-            "mean_kps": round(mean_kps, 1), "mean_matches": round(mean_match, 1), "mean_tracked": round(mean_track, 1),
-            "scene": args.scene,
-            "track_funnel_mean": ts_mean,
-            "track_funnel_note": "svo_result.track_stats of the last timed step, mean over this rank's streams: previous-frame pairings that pass the descriptor threshold on both sides -> survive the joint collision filter (S4:145-160) -> are inliers of the left / right F-matrix RANSAC (1.0 px, S4:202, 237; hyp_* = hypotheses visited before the 0.99-confidence stop) -> of both -> pass the L/R consistency check (S4:282) = tracked",
             "other_scene": other_scene,
-            "dist": dist_info,
-            "env": {k: os.environ.get(k) for k in ("GPU_MAX_HW_QUEUES", "SVO_TIMELINE", "SVO_DEBUG_MODE", "SVO_REST_PRIO", "HIP_FORCE_DEV_KERNARG") if os.environ.get(k) is not None},
             "timeline": timeline,
             "kernels_ms_per_context_step": {k: round(v["ms_per_step"], 4) for k, v in per_kernel_warm.items()},
             "legs_s": legs_s,
             "kernels_ms_note": "all kernels: HIP-event spans of the %d warm-up steps; roofline kernel: spans of the timed region" % args.warmup,
         }
+
+    if rank == 0:
+        pairs = world * B * args.steps
+        value = pairs / dt
+        if pooled:
+            sequence = ("%d trajectories x %d frames per rank (scene '%s'), stream s = slot s // %d of trajectory s %% %d plays frame (s // %d) + f(step), f walking 0 .. %d and back: "
+                        "the streams of a trajectory move in lockstep one frame apart, no two read the same frame in a step, every stream sees consecutive poses" % (T, F, args.scene, T, T, T, POOL_SWING - 1))
+        else:
+            sequence = ("%d trajectories x %d frames per rank (scene '%s'), stream s = trajectory s %% %d from frame %d * (s // %d) on: %d consecutive DISTINCT frames per stream over warm-up + timed steps, none seen twice"
+                        % (T, F, args.scene, T, PHASE_STRIDE, T, total_steps))
+        line = {
+            "metric": "stereo pairs/sec @%d×%d" % (W, H), "value": round(value, 2), "unit": "stereo pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/f64", "data": "synthetic",
+            "config": {"workload": "%s: %dx%d synthetic stereo streams, %s, orb_nfeats %d (~%d kps/image in octave 0 after NMS), BF match, BF track, robust GN; %d independent streams per GPU in %d contexts on separate HIP streams, one frame per stream per step"
+                                   % (args.workload, W, H, "FAST+ORB on %d x1/2 octaves" % n_octaves if detect_fast_orb else "ORB x 8 levels", args.orb_nfeats, int(mean_kps), B, NC),
+                       "lanes_per_gpu": B, "contexts_per_gpu": NC, "lanes_per_context": Bc, "schedule": args.schedule if NC > 1 else "single stream", "detect_ahead": bool(args.detect_ahead),
+                       "sequence": sequence,
+                       "frames_per_trajectory": F, "distinct_frames_per_stream": min(total_steps, POOL_SWING if pooled else F), "render_s": round(t_render, 1),
+                       "parallelism": "streams sharded across %d GPU(s), result all-gather per step" % world},
+            "timed_region_s": round(dt, 4),
+            "host_enqueue_ms_per_step": round(1e3 * t_enqueue / args.steps, 4),
+            "fast_redo_rate": round(redo_pairs / float(max(1, args.steps * 2 * B * (n_octaves if detect_fast_orb else 8))), 6),
+            "fast_redo_note": "(image, level) pairs of the timed steps whose speculative FAST threshold found too few corners and ran k_fast again at the caller's threshold (%d of %d)%s" % (redo_pairs, args.steps * 2 * B * (n_octaves if detect_fast_orb else 8), "" if pooled else "; every frame of the run is new to its stream"),
+            "valid_last_step": "%d/%d" % (n_valid, B),
+            "mean_kps": round(mean_kps, 1), "mean_matches": round(mean_match, 1), "mean_tracked": round(mean_track, 1),
+            "scene": args.scene,
+            "track_funnel_mean": ts_mean,
+            "track_funnel_note": "svo_result.track_stats of the last timed step, mean over this rank's streams: previous-frame pairings that pass the descriptor threshold on both sides -> survive the joint collision filter (S4:145-160) -> are inliers of the left / right F-matrix RANSAC (1.0 px, S4:202, 237; hyp_* = hypotheses visited before the 0.99-confidence stop) -> of both -> pass the L/R consistency check (S4:282) = tracked",
+            "dist": dist_info,
+            "env": {k: os.environ.get(k) for k in ("GPU_MAX_HW_QUEUES", "SVO_TIMELINE", "SVO_DEBUG_MODE", "SVO_REST_PRIO", "HIP_FORCE_DEV_KERNARG") if os.environ.get(k) is not None},
+        }
+        if full:
+            line.update(full_report(value))
         print(json.dumps(line))
     batch.close()
     if world > 1:
@@ -837,7 +921,7 @@ def other_workloads_leg(args):
     import subprocess
     out = {}
     for wl, extra in (("config3", ["--lanes", "192", "--contexts", "2"]), ("config5", ["--lanes", "64", "--contexts", "2"])):
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "40", "--warmup", "6", "--cpu-frames", "12", "--long-steps", "0", "--host-fed-steps", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", wl, "--steps", "40", "--warmup", "6", "--cpu-frames", "12", "--long-steps", "0", "--host-fed-steps", "0",
                "--single-stream", "0", "--relief-lanes", "0", "--cut-steps", "0", "--other-workloads", "0", "--exclusive", "1"] + extra
         try:
             pr = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -1,7 +1,11 @@
-"""CPU checks of bench.py's host-side helpers that need no GPU: the sweep of the in-kernel launch timeline (SVO_TIMELINE=1, `--timeline`)."""
+"""CPU checks of bench.py's host-side helpers that need no GPU: the sweep of the in-kernel launch timeline (SVO_TIMELINE=1, `--timeline`),
+the frame schedules and the --dump-outputs writer."""
+import os
+
 import numpy as np
 
 import bench
+from stereo_vo_amd.abi import Result, dmatch_dtype, index_pair_dtype, keypoint_dtype
 
 
 class _FakeCtx:
@@ -52,3 +56,76 @@ def test_frames_needed_and_lane_frame_never_repeat_a_frame():
         seen = [bench.lane_frame(lane, i, T, F) for i in range(steps)]
         assert len(set(seen)) == steps and all(j == lane % T for j, _ in seen)
         assert all(b[1] == a[1] + 1 for a, b in zip(seen, seen[1:]))            # consecutive frames of one trajectory
+
+
+def test_plain_run_pool_never_shows_two_streams_one_frame_and_keeps_poses_consecutive():
+    """The plain run's pool: a size that does not depend on the number of steps; at every step the 192 streams read 192 different
+    frames of it (no stream reads a frame another one reads in the same step), and every stream moves one frame per step."""
+    T, B = 8, 192
+    F = bench.pool_frames(B, T)
+    assert F == B // T - 1 + bench.POOL_SWING
+    prev = None
+    for i in range(3 * bench.POOL_SWING):
+        now = [bench.pool_frame(lane, i, T) for lane in range(B)]
+        assert len(set(now)) == B and all(0 <= t < F and j == lane % T for lane, (j, t) in enumerate(now))
+        if prev is not None:
+            assert all(abs(a[1] - b[1]) == 1 for a, b in zip(prev, now))
+        prev = now
+
+
+class _ListsCtx:
+    """what hip.Context's list getters return for one lane: n keypoints per side, n // 2 pairings, n // 4 tracked pairs"""
+    def __init__(self, n):
+        self.n = n
+
+    def keypoints(self, lane, which, side, octave):
+        assert all(type(v) is int for v in (lane, which, side, octave))         # what ctypes converts
+        k = np.zeros(self.n, keypoint_dtype)
+        k["x"] = np.arange(self.n) + 0.25 + lane; k["y"] = side + 0.5; k["octave"] = octave
+        return k, np.full((self.n, 32), 200 + side, np.uint8)
+
+    def matches(self, lane, which, octave):
+        m = np.zeros(self.n // 2, dmatch_dtype)
+        m["queryIdx"] = np.arange(self.n // 2); m["distance"] = 7.0
+        return m
+
+    def tracked(self, lane, octave):
+        return np.zeros(self.n // 4, index_pair_dtype)
+
+    def residuals(self, lane):
+        return np.linspace(0.0, 1.0, self.n // 4)
+
+
+class _Batch:
+    def __init__(self, B, n):
+        self.B, self.ctx = B, _ListsCtx(n)
+
+    def lane(self, g):
+        return self.ctx, g
+
+
+def test_dump_outputs_writes_every_record_field_and_a_fixed_sample_of_lists(tmp_path):
+    B = 24
+    recs = (Result * B)()
+    for g in range(B):
+        recs[g].outPose[0] = 0.125 * g; recs[g].valid = g % 2; recs[g].n_octaves = 1; recs[g].track_stats[7] = g
+    raw = np.frombuffer(bytes(recs), np.uint8).reshape(B, -1)
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    n1 = bench.dump_outputs(d1, _Batch(B, 40), raw, 4096)
+    n2 = bench.dump_outputs(d2, _Batch(B, 40), raw, 4096)
+    names = sorted(os.listdir(d1))
+    assert names == sorted(os.listdir(d2)) and n1 == n2 and n1 < 64 << 20
+    arrs = {f[:-4]: np.load(os.path.join(d1, f)) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert arrs["result_outPose"].shape == (B, 6) and arrs["result_outPose"][5, 0] == 0.625
+    assert list(arrs["result_valid"]) == [g % 2 for g in range(B)] and arrs["result_track_stats"][9, 7] == 9
+    lanes = sorted({int(f[4:7]) for f in arrs if f.startswith("lane")})
+    assert len(lanes) == bench.DUMP_LANES and all(0 <= g < B for g in lanes)
+    g = lanes[0]
+    k = arrs["lane%03d_o0_keypoints_right" % g]
+    assert k.shape == (40, 7) and k[3, 0] == 3.25 + g and k[0, 1] == 1.5
+    assert arrs["lane%03d_o0_descriptors_left" % g].shape == (40, 32) and arrs["lane%03d_o0_descriptors_left" % g].max() == 200
+    assert arrs["lane%03d_o0_pairings" % g].shape == (20, 4) and arrs["lane%03d_o0_tracked" % g].shape == (10, 2)
+    assert arrs["lane%03d_residuals" % g].shape == (10,)
+    for f in names:
+        assert np.array_equal(np.load(os.path.join(d1, f)), np.load(os.path.join(d2, f)))

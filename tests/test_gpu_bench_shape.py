@@ -8,6 +8,8 @@ train splits all depend on lane count x image size; no smaller test exercises th
 test_bench_two_ranks_*: `bench.py --gpus 2` under torch.distributed.run with both ranks on device 0 (this box has one
 GPU): sharding, event ordering around the all-gather, MAX-time reduction and the gather itself on REAL result records.
 RCCL refuses two ranks on one device, so the collective backend is gloo there; the 8-GPU driver run uses nccl.
+
+test_plain_bench_* / test_full_bench_*: what a plain run prints and writes (--dump-outputs), and that --full still carries the rest.
 """
 import os
 import subprocess
@@ -145,6 +147,44 @@ def test_bench_launches_its_own_ranks_when_started_plainly(tmp_path):
     import torch
     if torch.cuda.device_count() < 2:
         assert pr.returncode == 2 and "refusing" in pr.stderr and not [l for l in pr.stdout.splitlines() if l.startswith("{")]
+
+
+SMALL = ["--gpus", "1", "--warmup", "2", "--lanes", "16", "--contexts", "2", "--width", "640", "--height", "480", "--orb-nfeats", "500"]
+
+
+def _bench_line(args):
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, capture_output=True, text=True, timeout=420)
+    assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-2000:]
+    import json
+    return json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: K timed steps (more than the pool's 62-step period), the headline fields and none that
+    take runs of their own; --dump-outputs of a second run with the same arguments writes the same arrays."""
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [_bench_line(SMALL + ["--steps", "70", "--dump-outputs", d]) for d in dirs]
+    for line in lines:
+        assert line["steps"] == 70 and line["warmup"] == 2 and line["unit"] == "stereo pairs/s" and line["higher_is_better"] is True and line["dtype"]
+        assert abs(line["ms_per_step"] * 70 / 1e3 - line["timed_region_s"]) < 1e-3 and abs(line["value"] - 16 / (line["ms_per_step"] / 1e3)) < 1e-3 * line["value"]
+        assert not set(line) & {"roofline", "cpu_baseline", "parity_probe", "long_run", "scene_cuts", "kernels_ms_per_context_step", "legs_s"}
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "result_outPose.npy" in names
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert np.load(os.path.join(dirs[0], "result_valid.npy")).sum() >= 14
+    kps = [f for f in names if f.endswith("_keypoints_left.npy")]
+    assert len(kps) == 8 and all(np.load(os.path.join(dirs[0], f)).shape[0] > 100 for f in kps)
+
+
+def test_full_bench_still_carries_the_roofline_and_the_parity_probe():
+    line = _bench_line(SMALL + ["--full", "--steps", "4", "--frames", "12", "--cpu-frames", "6", "--long-steps", "0", "--host-fed-steps", "0", "--single-stream", "0",
+                                "--relief-lanes", "0", "--cut-steps", "0", "--other-workloads", "0"])
+    assert line["steps"] == 4 and line["roofline"]["avg_launch_ms"] > 0 and line["kernels_ms_per_context_step"]
+    pp = line["parity_probe"]
+    assert pp["frames"] == 6 and pp["lists_bit_exact"] and pp["flags_equal"] and pp["final_state_of_timed_run_ok"]
+    assert line["cpu_baseline"]["value"] > 0 and "cpu_baseline_and_parity_probe" in line["legs_s"]
 
 
 def test_host_fed_path_64_lanes_matches_oracle():

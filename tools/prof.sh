@@ -9,7 +9,7 @@
 #             PARITY_ENV="NAME=VALUE" runs it under that environment, PARITY_K="expr" replaces the -k expression
 #   tests     the whole GPU suite (pytest -m gpu)
 #   bench     a short bench line (40 timed steps, 12-frame parity probe, no side legs)
-#   default   bench.py as the driver calls it (--gpus 1 --steps 20 --warmup 5: every leg, several minutes)
+#   default   the full bench line (--gpus 1 --steps 20 --warmup 5 --full: every leg, several minutes)
 #   stats3    rocprofv3 --kernel-trace --stats of the benchmarked shape (2 x 96 lanes since round 6; the files keep the `3ctx` tag of rounds 2-5), steady state
 #   stats1    the same with one context of 64 lanes alone (exclusive kernel times)
 #   stats_ss  one stream alone (tools/single_stream_bench.py)
@@ -23,7 +23,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 tag=${1:-prof}; shift
 mkdir -p $O
-SIDE="--cpu-frames 0 --long-steps 0 --host-fed-steps 0 --single-stream 0 --exclusive 0 --cut-steps 0 --other-workloads 0 --relief-lanes 0"
+SIDE="--full --cpu-frames 0 --long-steps 0 --host-fed-steps 0 --single-stream 0 --exclusive 0 --cut-steps 0 --other-workloads 0 --relief-lanes 0"
 PB="--steps 10 --warmup 3 $SIDE"
 
 line_summary() {   # bench json -> a few lines on stdout
@@ -65,10 +65,10 @@ for step in "$@"; do
     ( cd $R; time timeout 1800 python -m pytest tests -m gpu -q ) > $O/${tag}_tests.log 2>&1
     echo "tests rc=$?" >> $O/${tag}_tests.log; tail -8 $O/${tag}_tests.log; grep -E "^E  |^FAILED" $O/${tag}_tests.log | head -30 ;;
   bench)
-    ( cd $R; time timeout 600 python bench.py --steps 40 --warmup 6 --cpu-frames 12 --long-steps 0 --host-fed-steps 0 --single-stream 0 --relief-lanes 0 --cut-steps 0 --other-workloads 0 --frames 210 $BENCH_ARGS ) > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+    ( cd $R; time timeout 600 python bench.py --full --steps 40 --warmup 6 --cpu-frames 12 --long-steps 0 --host-fed-steps 0 --single-stream 0 --relief-lanes 0 --cut-steps 0 --other-workloads 0 --frames 210 $BENCH_ARGS ) > $O/${tag}_bench.json 2> $O/${tag}_bench.err
     line_summary $O/${tag}_bench.json; tail -3 $O/${tag}_bench.err ;;
   default)
-    ( cd $R; time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 $BENCH_ARGS ) > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
+    ( cd $R; time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full $BENCH_ARGS ) > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
     line_summary $O/${tag}_bench_default.json; tail -3 $O/${tag}_bench_default.err ;;
   stats3)
     stats 3ctx 3 13 python $R/bench.py $PB --frames 176 $BENCH_ARGS

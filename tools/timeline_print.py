@@ -1,4 +1,4 @@
-"""print the `timeline` block of a bench line (bench.py --timeline N): python tools/timeline_print.py <bench.json>"""
+"""print the `timeline` block of a bench line (bench.py --full --timeline N): python tools/timeline_print.py <bench.json>"""
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 t = d.get("timeline") or {}
