@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
     const int sx0 = xi[dx0] & ~15, sy0 = yi[dy0];                      // window origin (block-uniform)
     if (tid < RZ_W) {
         const int x = min(dx0 + tid, d.w - 1), rx = xi[x] - sx0;
-        xw[tid] = (uint32_t)xf[x];                                                                 // dot2 weights: a0 | a1 << 16
+        xw[tid] = (uint32_t)xf[x] << 4;                                                            // dot2 weights times 16: a0 << 4 | a1 << 20 (a0, a1 <= 2048: each half <= 32768)
         xr[tid] = (uint32_t)rx;
     } else if (tid < RZ_W + RZ_H) {
         const int y = min(dy0 + tid - RZ_W, d.h - 1);
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
     for (int k = 0; k < 4; k++) {
         const uint32_t o = xr[gx + k] - rx0;                            // 0 .. 5 (< 7: both taps inside the window)
         wx[k] = xw[gx + k];
-        sel[k] = 0x0c010c00u + o * 0x00010001u;                         // bytes (o, o + 1) of the 8-byte window -> u16 pair
+        sel[k] = 0x010c000cu + o * 0x01000100u;                         // bytes (o, o + 1) of the 8-byte window -> the HIGH bytes of a u16 pair (pixel << 8)
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -288,8 +288,10 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
             const uint32_t top = __builtin_amdgcn_udot2(__builtin_bit_cast(rz_u16x2, t0), __builtin_bit_cast(rz_u16x2, wx[k]), 0u, false);
             const uint32_t bot = __builtin_amdgcn_udot2(__builtin_bit_cast(rz_u16x2, t1), __builtin_bit_cast(rz_u16x2, wx[k]), 0u, false);
             // cv::resize's uchar VResizeLinear (oracle v7): the row sums lose 4 bits, each product is cut to quarter grey levels, then one rounding:
-            // ((b0 * (top >> 4)) >> 16) + ((b1 * (bot >> 4)) >> 16) + 2.  The two high halves come out of ONE v_perm, their sum + 2 out of one v_sad_u16
-            const uint32_t m0 = __umul24(top >> 4, wy0), m1 = __umul24(bot >> 4, wy1);
+            // ((b0 * (top >> 4)) >> 16) + ((b1 * (bot >> 4)) >> 16) + 2.  The two high halves come out of ONE v_perm, their sum + 2 out of one v_sad_u16.
+            // With the pixels at << 8 and the weights at << 4 the dot product delivers 4096 * sum exactly (sum <= 255 * 2048: below 2^31), so
+            // sum >> 4 is its high word -- which the multiply's SDWA operand select reads for free (v_mul_u32_u24_sdwa ... src0_sel:WORD_1), no shift
+            const uint32_t m0 = __umul24(top >> 16, wy0), m1 = __umul24(bot >> 16, wy1);
             v[k] = __builtin_amdgcn_sad_u16(__builtin_amdgcn_perm(m1, m0, 0x07060302u), 0u, 2u);       // <= 1022; >> 2 below, two at a time
         }
         const rz_u16x2 p01 = __builtin_bit_cast(rz_u16x2, v[0] | (v[1] << 16)) >> 2, p23 = __builtin_bit_cast(rz_u16x2, v[2] | (v[3] << 16)) >> 2;
@@ -355,20 +357,22 @@ __device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(
 // caller scales the threshold the same way).  A half of the result is nonzero when its position passes.
 __device__ __forceinline__ uint32_t quick_half(uint32_t c, uint32_t n, uint32_t e, uint32_t s, uint32_t w, u16x2 t2)
 {
-    const u16x2 cc = as_u16x2(c), hi = __builtin_elementwise_add_sat(cc, t2), lo = __builtin_elementwise_sub_sat(cc, t2);
+    const u16x2 cc = as_u16x2(c);
     const u16x2 N = as_u16x2(n), E = as_u16x2(e), S = as_u16x2(s), W = as_u16x2(w);
     // "two adjacent compass points bright" == (N or S bright) and (E or W bright): any N/S point is adjacent to any E/W point
     //   bright  <=>  min(max(N, S), max(E, W)) > c + t        dark  <=>  max(min(N, S), min(E, W)) < c - t
     const u16x2 b = __builtin_elementwise_min(__builtin_elementwise_max(N, S), __builtin_elementwise_max(E, W));
     const u16x2 d = __builtin_elementwise_max(__builtin_elementwise_min(N, S), __builtin_elementwise_min(E, W));
-    return as_u32(__builtin_elementwise_sub_sat(b, hi) | __builtin_elementwise_sub_sat(lo, d));
+    // b > c + t  <=>  sat(b - c) > t  and  c - t > d  <=>  sat(c - d) > t (unsigned saturation; both forms fail alike when c + t passes
+    // 65535 or c < t), so ONE comparison against t serves both polarities: four packed operations after b and d instead of five
+    return as_u32(__builtin_elementwise_sub_sat(__builtin_elementwise_max(__builtin_elementwise_sub_sat(b, cc), __builtin_elementwise_sub_sat(cc, d)), t2));
 }
 
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 
 // FAST-9 score of the pixel at byte offset `off` of the LDS window: the largest t for which it is still a corner
 // = max over the 16 arcs of 9 contiguous circle pixels of the min one-sided difference, minus 1; 0 when that is
-// not above th.  Both polarities ride in the two halves of one register, v[i] = (p_i - c, c - p_i), so one min
+// not above th.  Both polarities ride in the two halves of one register, v[i] = (p_i, -p_i) with (-c, c) added at the end, so one min
 // network serves both.  The 16 circular 9-windows come from block prefix/suffix minima (van Herk): with the circle
 // cut into [0,8) and [8,16), window [i, i+8] = suffix_i of one block + prefix_i of the other: 28 + 16 + 15 packed ops.
 __device__ __forceinline__ int fast_score_lds(const uint8_t* win, int off, int th)
@@ -388,8 +392,9 @@ __device__ __forceinline__ int fast_score_lds(const uint8_t* win, int off, int t
 #undef FO
     const i16x2 K = { (short)(-c), (short)c };
     i16x2 v[16];
+    // (p, -p) alone: min and max commute with adding a constant, so (-c, c) is added ONCE, to the network's result (|values| <= 255 before, <= 510 after)
 #pragma unroll
-    for (int i = 0; i < 16; i++) v[i] = __builtin_bit_cast(i16x2, __mul24(p[i], -65535)) + K;      // (p, -p) + (-c, c)
+    for (int i = 0; i < 16; i++) v[i] = __builtin_bit_cast(i16x2, __mul24(p[i], -65535));
     i16x2 s0[8], s1[8], p0[8], p1[8];       // suffix / prefix minima of the blocks [0,8) and [8,16)
     s0[7] = v[7]; s1[7] = v[15]; p0[0] = v[0]; p1[0] = v[8];
 #pragma unroll
@@ -401,6 +406,7 @@ __device__ __forceinline__ int fast_score_lds(const uint8_t* win, int off, int t
     for (int i = 1; i < 8; i++) m = __builtin_elementwise_max(m, __builtin_elementwise_min(s0[i], p1[i]));      // [i, i+8]
 #pragma unroll
     for (int i = 0; i < 8; i++) m = __builtin_elementwise_max(m, __builtin_elementwise_min(s1[i], p0[i]));      // [8+i, 16+i]
+    m += K;
     const int best = max((int)m.x, (int)m.y);
     return best > th ? best - 1 : 0;
 }
@@ -530,13 +536,19 @@ __device__ __forceinline__ void fast_compute(const DevCtx& c, uint8_t* tile, uin
         // "half nonzero" -> 0 / 1 by ONE v_pk_min_u16 per register, written as asm: left to itself hipcc turns min(x, 1) on
         // packed halves into two 16-bit compares, two selects and a v_perm (80 instructions per thread instead of 16)
         const uint32_t one2 = 0x00010001u;
+        // rows from the last to the first, m = (m << 1) | f: row g ends at bits g and 16 + g.  One v_lshl_or_b32 per update, as asm too:
+        // the plain C form is re-associated into separate shifts and v_or3_b32
         uint32_t me = 0, mo = 0;
 #pragma unroll
-        for (int g = 0; g < FT_ROWS; g++) {
+        for (int g = FT_ROWS - 1; g >= 0; g--) {
             uint32_t fe, fo;
             asm("v_pk_min_u16 %0, %1, %2" : "=v"(fe) : "v"(pe[g]), "s"(one2));
             asm("v_pk_min_u16 %0, %1, %2" : "=v"(fo) : "v"(po[g]), "s"(one2));
-            me |= fe << g; mo |= fo << g;                                  // positions 0, 2 from pe's halves; 1, 3 from po's
+            if (g == FT_ROWS - 1) { me = fe; mo = fo; }
+            else {
+                asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(me) : "v"(me), "v"(fe));      // positions 0, 2 from pe's halves
+                asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(mo) : "v"(mo), "v"(fo));      // positions 1, 3 from po's
+            }
         }
         uint32_t m = me | (mo << 8);
         const int cnt = __popc(m), inc = wave_inclusive_scan(cnt);

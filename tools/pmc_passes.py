@@ -14,7 +14,7 @@ The launches of the first `--skip-steps` steps are dropped (un-speculated FAST t
   lds_conflict_frac = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE
 Writes gpurun_out/<tag>_pmc.json.   Usage: python tools/pmc_passes.py <tag> [bench.py arguments ...]
 """
-import collections, csv, glob, json, os, subprocess, sys
+import collections, csv, glob, json, os, subprocess, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _kname import kname
@@ -75,7 +75,9 @@ for a in extra:
         res["workload"] = a
 allc, launches = collections.defaultdict(dict), {}
 for name, counters in PASSES.items():
+    t0 = time.time()
     avg, ln = run_pass(name, counters)
+    print("pass %s: %d kernels in %.0f s" % (name, len(avg), time.time() - t0), file=sys.stderr, flush=True)      # a sign of life per pass: the whole run takes minutes
     launches.update(ln)
     for k, d in avg.items():
         allc[k].update(d)
