@@ -84,7 +84,27 @@ typedef struct svo_config {
 typedef struct svo_image {
     const uint8_t* data;
     int32_t w, h;
-    int64_t stride;         /* bytes between rows */
+    int64_t stride;         /* bytes between rows, >= w * channels (1 grey, 3 with SVO_FLAG_BGR_IMAGES); svo_process refuses a
+                               smaller one with SVO_ERR_ARG.  Any value from there on and any byte alignment of `data` are
+                               accepted: a crop of a larger frame, a side-by-side stereo frame (stride 2 w, right = left + w),
+                               odd widths held contiguously.
+                               READ CONTRACT of a device frame (SVO_FLAG_DEVICE_IMAGES).  Without a rectify map, BGR or
+                               svo_use_graphs the kernels read the frame IN PLACE, level 0 is never copied.  Every byte of
+                               [data, data + h * stride) must be readable device memory, the padding behind the last row
+                               included (k_resize fetches whole 16-byte pieces of a row up to its stride when the stride is a
+                               multiple of 16; what the padding holds never reaches a result).  Nothing outside that range is
+                               read and nothing of the caller's is ever written: k_fast, k_harris, k_describe, k_half and
+                               k_prepare stay inside the w x h pixels.  The kernels address the frame with 32-bit byte offsets,
+                               so h * stride must not exceed 2^31 - 1: svo_process refuses a larger span with SVO_ERR_ARG.
+                               Both refusals happen before anything is enqueued and leave a text in svo_last_error.
+                               CONSEQUENCE for sub-images: the range is h * stride bytes from `data`, not from the parent frame's
+                               first byte.  For the right half of a side-by-side frame it ends w bytes behind the parent's last
+                               row, for a crop at column x of the parent's bottom rows x bytes behind it -- and with a stride that
+                               is a multiple of 16 k_resize does fetch there (the 16-byte pieces of the last source rows up to
+                               data + h * stride).  A parent frame that is the very tail of its allocation therefore needs that
+                               many readable bytes behind it (at most one stride); hipMalloc's page granularity usually provides
+                               them, a sub-allocator that packs frames back to back up to the end of a mapping does not.
+                               All images of one call share w, h and stride. */
 } svo_image;
 
 typedef struct svo_frame {  /* one lane's rectified stereo pair (request_data.stereo_imgs, H:208) */
@@ -97,7 +117,7 @@ void svo_params_defaults(svo_params* p);          /* reference defaults, north-s
 int  svo_create(const svo_config* cfg, svo_ctx** out);
 void svo_destroy(svo_ctx* ctx);
 const char* svo_strerror(int status);
-const char* svo_last_error(const svo_ctx* ctx);   /* text of the last HIP failure */
+const char* svo_last_error(const svo_ctx* ctx);   /* text of the last HIP failure or refusal; svo_process clears it on entry */
 
 /* loadParamsFromConfigFile (H:554-663): stores the record, then resetFASTThreshold / resetORBThreshold.  The reference has no
  * keypoint cap (stage2_detect.cpp:461-464); a request that this context's lists cannot hold (orb_nfeats against

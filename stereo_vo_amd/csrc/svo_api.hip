@@ -921,6 +921,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
 {
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();                               // svo_last_error speaks of THIS call: a refusal below that sets no text must not inherit an earlier one
     // svo_record_after_post arms ONE call: the next one that runs the detector's post-processing.  Whatever way that call leaves --
     // an argument check, SVO_ERR_STATE, a failed launch -- the event is recorded behind what was enqueued (possibly nothing) and
     // disarmed, so that a waiter is released and a later, unrelated call cannot record it at the wrong point.
@@ -959,15 +960,34 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
             const svo_frame& f = frames[l];
             if (!f.left.data || !f.right.data || f.left.w != w || f.left.h != h || f.right.w != w || f.right.h != h) return SVO_ERR_ARG;
         }
-        int rc = ensure_geometry(ctx, w, h); if (rc) return rc;
         const int ch = (flags & SVO_FLAG_BGR_IMAGES) ? 3 : 1;
+        // the read contract of svo_image.stride (svo_hip.h): rows may not overlap, and the kernels that read a device frame in place
+        // address it with 32-bit byte offsets from its base.  Refused here, before anything is enqueued.
+        for (int l = 0; l < d.n_lanes; l++)
+            for (int s = 0; s < 2; s++) {
+                const svo_image& im = s ? frames[l].right : frames[l].left;
+                char msg[200];
+                if (w < 1 || h < 1) {
+                    snprintf(msg, sizeof(msg), "image size %d x %d: both must be positive", w, h);
+                    ctx->last_error = msg; return SVO_ERR_ARG;
+                }
+                if (im.stride < (int64_t)w * ch) {
+                    snprintf(msg, sizeof(msg), "lane %d %s image: stride %lld is smaller than a row (%d px x %d B)", l, s ? "right" : "left", (long long)im.stride, w, ch);
+                    ctx->last_error = msg; return SVO_ERR_ARG;
+                }
+                if ((flags & SVO_FLAG_DEVICE_IMAGES) && im.stride > (int64_t)INT32_MAX / h) {
+                    snprintf(msg, sizeof(msg), "lane %d %s image: h * stride = %d x %lld exceeds the 2^31 - 1 bytes a device frame may span", l, s ? "right" : "left", h, (long long)im.stride);
+                    ctx->last_error = msg; return SVO_ERR_ARG;
+                }
+            }
+        int rc = ensure_geometry(ctx, w, h); if (rc) return rc;
         prepare = ch == 3 || ctx->n_maps > 0;
         if (ctx->n_maps > 0 && (ctx->map_w != w || ctx->map_h != h)) return SVO_ERR_ARG;
         const int ipitch = ctx->img0_pitch_internal;
         if (flags & SVO_FLAG_DEVICE_IMAGES) {
             const long long stride = frames[0].left.stride;
             for (int l = 0; l < d.n_lanes; l++) {
-                if (frames[l].left.stride != stride || frames[l].right.stride != stride) return SVO_ERR_ARG;
+                if (frames[l].left.stride != stride || frames[l].right.stride != stride) { ctx->last_error = "device frames of one call must share one stride"; return SVO_ERR_ARG; }
                 ptrs[2 * l] = frames[l].left.data; ptrs[2 * l + 1] = frames[l].right.data;
             }
             d.img0_pitch = (int)stride;

@@ -1,0 +1,154 @@
+"""Whole frames full of ties, saturated pixels and scores on the FAST threshold (tests/image_content.py) through the HIP path
+against the CPU oracle.
+
+On the golden sequence, the synthetic world and white noise no two raw keypoints share a Harris response and no descriptor
+repeats, so the rules that make a parallel kernel differ from the oracle's sequential walk -- the whole score bin of the K-th key
+(retainBest), (response desc, position asc), the grid and adaptive NMS orders, (score desc, raster asc) of the FAST+ORB NMS, the
+first minimum in the matchers, the 1-to-1 rule, the tracker's collision rule -- are never decided there.  Here hundreds of them are,
+on every frame: the test asserts so from the oracle's own output before it compares anything."""
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from stereo_vo_amd import hip
+from stereo_vo_amd.abi import StereoCamera, north_star_params, DM_FAST_ORB
+from stereo_vo_amd.synth import SyntheticStereoWorld
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import image_content as IC                                      # noqa: E402
+from test_gpu_parity import assert_same_frame, O                # noqa: E402
+from test_gpu_frame_layouts import assert_same_octaves, check_pyramid_and_raw, make_frames    # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+# (match_method, ifm_method, enable_robust_1to1_match, nmsMethod): every (matcher, tracker) combination with the 1-to-1 rule on and the
+# grid NMS and with the rule off and the adaptive NMS, and one more set per combination: every value of every parameter meets
+# every content (and every value of every other parameter) at least once
+PARAM_SETS = [(mm, ifm, one, nms) for mm, ifm in itertools.product((0, 1), (0, 1)) for one, nms in ((1, 0), (0, 1))] + \
+             [(0, 0, 1, 1), (1, 1, 0, 0), (0, 1, 1, 1), (1, 0, 0, 0)]
+
+
+def sequence(name, w, h, n=3):
+    return make_frames(name, w, h, n, seed=1)
+
+
+def fast_corner_sequence(name, w, h, n=3):
+    """The same moving sequence rendered 1.2 x larger and brought to w x h by the oracle's resize (what level 1 of the ORB pyramid
+    is): perfect blocks are plateaus of equal FAST scores, which the strict 3x3 NMS removes altogether -- at full resolution and at
+    every x1/2 octave of the FAST+ORB mode -- while their resampled edges carry hundreds of corners, still in a few repeated shapes"""
+    return [tuple(O().resize(x, w, h) for x in pr) for pr in make_frames(name, (w * 6 + 4) // 5, (h * 6 + 4) // 5, n, seed=1)]
+
+
+def assert_frame_has_ties(name, img, nfe):
+    """from the oracle alone: the floors of tests/test_image_content_cpu.py hold for the frame about to be compared"""
+    k, d = O().orb_detect(img, int(1.5 * nfe), 8, 20)
+    if name in IC.TIE_CONTENTS:
+        assert IC.tied_responses(k) >= IC.TIE_FLOOR, (name, IC.tied_responses(k))
+    if name in ("periodic", "checker"):
+        assert IC.duplicate_descriptors(d) > 0, name
+    return k, d
+
+
+def floors_hold(name, t, side):
+    """where the tie floors are asserted: on every image compared, except that a rolled mirror image is no longer symmetric about
+    the centre the pyramid resamples around -- its ties are those of the generator's own output, the left image of frame 0"""
+    return name != "mirror" or (t == 0 and side == 0)
+
+
+def check_debug_lists(monkeypatch, name, w, h, nfe, pair, max_kps):
+    """debug mode 9 on host frames: pyramid and raw keypoint list (check_pyramid_and_raw), the oracle's list first held to the floors"""
+    def oracle_list(lane, side, img):
+        return assert_frame_has_ties(name, img, nfe) if floors_hold(name, 0, side) else O().orb_detect(img, int(1.5 * nfe), 8, 20)
+    check_pyramid_and_raw(monkeypatch, w, h, nfe, [pair], lambda c: c.process_host([pair], hip.RUN_DETECT), name, max_kps=max_kps, max_cand=1 << 17, oracle_list=oracle_list)
+
+
+def run_param_sets(name, w, h, nfe, frames, max_kps, sets):
+    cam = StereoCamera.simple(400.0 * w / 640.0, w / 2.0, h / 2.0, 0.12, w, h)
+    for mm, ifm, one, nms in sets:
+        p = north_star_params(hip.default_params(), orb_nfeats=nfe)
+        p.match_method = mm; p.ifm_method = ifm; p.enable_robust_1to1_match = one; p.nmsMethod = nms
+        p.ifm_win_w = 20; p.ifm_win_h = 30
+        ctx = hip.Context(n_lanes=1, max_w=w, max_h=h, max_kps=max_kps, max_cand=1 << 17)
+        ctx.set_params(p); ctx.set_camera(cam)
+        orc = O().Oracle(p)
+        for t, (L, R) in enumerate(frames):
+            ctx.process_host([(L, R)])
+            ro = orc.process(L, R, cam)
+            tag = "%s %dx%d match %d ifm %d 1to1 %d nms %d t=%d" % (name, w, h, mm, ifm, one, nms, t)
+            assert_same_frame(ctx, 0, orc, ctx.result(0), ro, tag)
+            assert ctx.status_word(0) == 0, (tag, ctx.status_word(0))
+            assert (ctx.matches_row_index(0, 0) == orc.matches_row_index(0)).all(), (tag, "row index of the pairings")
+            assert ro.detected_left[0] > 100, (tag, "the oracle's frame is all but empty")
+        ctx.close()
+
+
+@pytest.mark.parametrize("name", sorted(IC.CONTENTS))
+def test_structured_content_matches_oracle(monkeypatch, name):
+    w, h, nfe = 640, 480, 750
+    frames = sequence(name, w, h)
+    for t, pair in enumerate(frames):              # every frame compared below is a tie-heavy one, by the oracle's own output
+        for side, img in enumerate(pair):
+            if floors_hold(name, t, side):
+                assert_frame_has_ties(name, img, nfe)
+    check_debug_lists(monkeypatch, name, w, h, nfe, frames[0], 2048)
+    run_param_sets(name, w, h, nfe, frames, 2048, PARAM_SETS)
+
+
+def test_periodic_content_full_size_matches_oracle(monkeypatch):
+    """1280x960, 2000 requested: about 86 000 candidates in level 0 and a kept list of 1330 for K = 1304 (the CPU guard)"""
+    w, h, nfe = 1280, 960, 2000
+    frames = sequence("periodic", w, h)
+    check_debug_lists(monkeypatch, "periodic", w, h, nfe, frames[0], 4096)
+    run_param_sets("periodic", w, h, nfe, frames, 4096, [(0, 0, 1, 0), (1, 1, 0, 1), (1, 0, 1, 1), (0, 1, 0, 0)])
+
+
+@pytest.mark.parametrize("name", sorted(IC.CONTENTS))
+@pytest.mark.parametrize("noct,nms", [(1, 0), (2, 1), (2, 0), (1, 1)])
+def test_structured_content_fast_orb_matches_oracle(name, noct, nms):
+    """FAST+ORB: every FAST corner of every x1/2 octave goes through the NMS in (score desc, raster asc) order, grid and adaptive,
+    lists per octave, on the resampled sequences (fast_corner_sequence): by the oracle alone every content then has hundreds of
+    corners in every octave of every frame -- asserted below, so that no case compares an empty list with an empty list"""
+    w, h, nfe = 640, 480, 600
+    frames = fast_corner_sequence(name, w, h)
+    cam = StereoCamera.simple(400.0, w / 2.0, h / 2.0, 0.12, w, h)
+    p = north_star_params(hip.default_params(), orb_nfeats=nfe)
+    p.detect_method = DM_FAST_ORB; p.nOctaves = noct; p.nmsMethod = nms
+    ctx = hip.Context(n_lanes=1, max_w=w, max_h=h, max_kps=4096, max_cand=1 << 17, max_octaves=noct)
+    ctx.set_params(p); ctx.set_camera(cam)
+    orc = O().Oracle(p)
+    for t, (L, R) in enumerate(frames):
+        ctx.process_host([(L, R)])
+        r, ro = ctx.result(0), orc.process(L, R, cam)
+        tag = "%s fast+orb octaves %d nms %d t=%d" % (name, noct, nms, t)
+        assert ctx.status_word(0) == 0, (tag, ctx.status_word(0))
+        assert_same_octaves(ctx, 0, orc, r, ro, noct, tag)
+        for o in range(noct):                               # from the oracle's own result (observed there: 236 .. 1200)
+            assert ro.detected_left[o] > 100 and ro.detected_right[o] > 100, (tag, o, ro.detected_left[o], ro.detected_right[o])
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ["periodic", "mirror"])
+def test_tie_heavy_lane_beside_an_ordinary_lane(name):
+    """two lanes of one context: tie-heavy content in one, the synthetic world in the other; each against its own oracle"""
+    import torch
+    w, h, nfe = 640, 480, 750
+    frames = sequence(name, w, h)
+    world = SyntheticStereoWorld(w, h, 400.0, 0.12, seed=17, n_frames=3, device=torch.device("cpu"))
+    cam = world.camera()
+    p = north_star_params(hip.default_params(), orb_nfeats=nfe)
+    ctx = hip.Context(n_lanes=2, max_w=w, max_h=h, max_kps=2048, max_cand=1 << 17)
+    ctx.set_params(p); ctx.set_camera(cam)
+    orcs = [O().Oracle(p), O().Oracle(p)]
+    assert_frame_has_ties(name, frames[0][0], nfe)
+    for t in range(3):
+        pairs = [frames[t], tuple(x.numpy() for x in world.render(t))]
+        ctx.process_host(pairs)
+        for lane in range(2):
+            ro = orcs[lane].process(pairs[lane][0], pairs[lane][1], cam)
+            assert_same_frame(ctx, lane, orcs[lane], ctx.result(lane), ro, "%s beside the world: lane=%d t=%d" % (name, lane, t))
+            assert ctx.status_word(lane) == 0
+    assert ro.valid and ro.tracked_feats_from_last_frame > 50          # (the ordinary lane: the tie-heavy neighbour did not disturb it)
+    ctx.close()

@@ -1115,10 +1115,16 @@ def test_random_parameter_sets_match_oracle(seed):
     """Parameter combinations nobody wrote a dedicated test for: every documented key of the path (SURVEY.md 8b "Config keys")
     drawn at random in ORB mode -- pyramid depth, feature count, NMS on / off / adaptive and its cell size, FAST threshold,
     response floor, both stereo matchers with and without the 1-to-1 rule, both trackers, RANSAC on / off, robust kernel on /
-    off, iteration limits, warm start, match IDs -- four frames each, every list bit-exact, poses within tolerance."""
+    off, iteration limits, warm start, match IDs -- four frames each, every list bit-exact, poses within tolerance.  Image
+    sources: the synthetic world and, for the seeds with seed % 4 == 3 (the 417x311 ones), windows of the reference's photograph."""
     rng = np.random.RandomState(1000 + seed)
     w, h = [(640, 480), (512, 384), (800, 600), (417, 311)][seed % 4]
-    world = SyntheticStereoWorld(w + (-w) % 8, h + (-h) % 8, 400.0 * w / 640.0, 0.12, seed=100 + seed, n_frames=4)
+    photo = None
+    if seed % 4 == 3:         # a quarter of the seeds see a photograph instead: moving 417x311 windows of the reference's 800x600 stereo pair
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_pair_800x600.npz"))
+        photo, px0, py0 = (g["left"], g["right"]), 100 + (17 * seed) % 250, 80 + (11 * seed) % 180
+    else:
+        world = SyntheticStereoWorld(w + (-w) % 8, h + (-h) % 8, 400.0 * w / 640.0, 0.12, seed=100 + seed, n_frames=4)
     cam = StereoCamera.simple(400.0 * w / 640.0, w / 2.0, h / 2.0, 0.12, w, h)
     p = north_star_params(hip.default_params(), orb_nfeats=int(rng.choice([60, 200, 500, 900])))
     p.orb_nlevels = int(rng.choice([1, 2, 3, 5, 8]))
@@ -1151,7 +1157,10 @@ def test_random_parameter_sets_match_oracle(seed):
     ctx.set_params(p); ctx.set_camera(cam)
     orc = O().Oracle(p)
     for t in range(4):
-        L, R = [np.ascontiguousarray(x.numpy()[:h, :w]) for x in world.render(t)]
+        if photo is not None:
+            L, R = [np.ascontiguousarray(x[py0 + 2 * t:py0 + 2 * t + h, px0 + 4 * t:px0 + 4 * t + w]) for x in photo]
+        else:
+            L, R = [np.ascontiguousarray(x.numpy()[:h, :w]) for x in world.render(t)]
         ctx.process_host([(L, R)])
         r, ro = ctx.result(0), orc.process(L, R, cam)
         assert_same_frame(ctx, 0, orc, r, ro, "%s t=%d" % (tag, t))
