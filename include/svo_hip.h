@@ -165,6 +165,17 @@ int svo_reset(svo_ctx* ctx, int lane);
 /* processNewImagePair for every lane (P:41-385): ENQUEUES the whole frame on the context's stream and
  * returns; frames[lane] for lane in [0,n_lanes).  Nothing is copied back until svo_wait/svo_get_*. */
 int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
+/* smSAD (svo_params.match_method = SVO_SM_SAD, S3:185-419) and ifmSAD (ifm_method = SVO_IFM_SAD, S4:435-738) compare the 8 x 8 image
+ * windows around two keypoints (rso::compute_SAD8).  Stage 2 is the only stage that reads images, so it gathers the window of every
+ * final keypoint -- from the call on in which either selector is in force; a context that never selects them allocates and launches
+ * nothing.  A frame has windows only if THIS library detected it under such parameters.  Features that came through
+ * svo_put_features(_oct), svo_load_state or svo_import_frame have none: hand-over records and state files do not carry windows (the
+ * reference's state format holds no images either, C:475-543), and neither does a frame detected while no SAD method was selected.
+ * A call that runs a SAD stage on a frame without windows is refused with SVO_ERR_STATE and a text in svo_last_error BEFORE anything is
+ * enqueued: the lists and the lane state stay as they were.  When it is the PREVIOUS frame that lacks them (a stream that switches
+ * to ifmSAD) and the call would have shifted, the refusal is remembered: the lane's next shifting call forgets that frame, i.e. it is
+ * processed as the lane's first frame (voecFirstIteration; the match-ID counter runs on), and the stream is tracked with ifmSAD from the frame after.
+ * SVO_IFM_OPTICAL_FLOW, KLT and FASTER stay SVO_ERR_UNSUPPORTED. */
 /* block until every enqueued frame has finished */
 int svo_wait(svo_ctx* ctx);
 /* Host-fed frames (the reference's contract: P:100-120 takes host images per call).  Uploads go through a ring of two

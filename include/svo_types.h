@@ -52,8 +52,8 @@ enum { SVO_IFM_DESC_BF = 0, SVO_IFM_DESC_WIN = 1, SVO_IFM_SAD = 2, SVO_IFM_OPTIC
 
 /* The INI keys / struct fields that parameterise the path (H:266-508, H:554-663), one flat record.
  * Field names are the reference's. Defaults: svo_params_defaults() (S2:44-58, S3:46-57, C:69-82, S1:27-30),
- * except that the selectors default to the north-star configuration (ORB + BF + BF), because the
- * reference's own defaults select variants that are out of scope. */
+ * except that the selectors default to the north-star configuration (ORB + BF + BF): the reference's own defaults are
+ * dmFASTER (out of scope), smSAD (SVO_SM_SAD, supported) and none for the tracker. */
 typedef struct svo_params {
     /* RECTIFY */
     int32_t nOctaves;
@@ -83,13 +83,16 @@ typedef struct svo_params {
     int32_t bad_tracking_th;
     int32_t use_previous_pose_as_initial;
     int32_t use_custom_initial_pose;
-    int32_t _pad0;
+    int32_t sad_max_distance;     /* MATCH group (H:458, kept here so that every offset of the record stays): smSAD's largest SAD of two 8 x 8
+                                     windows that still counts as a match (S3:201, 334).  0 = the reference's default 200 (S3:48);
+                                     negative = no threshold (the reference's unsigned wrap of a negative INI value) */
     double  kernel_param;
     double  min_mod_out_vector;
     double  residual_threshold;
     /* GENERAL */
     int32_t vo_use_matches_ids;
-    int32_t _pad1;
+    int32_t ifm_sad_max_distance; /* IF-MATCH group (H:297): ifmSAD's MAX_SAD, per side (S4:448, 573, 577).  0 = 200 (the group has no
+                                     constructor default, common.cpp:84; H:297 says "~200"); negative = no threshold (uint32_t wrap) */
 } svo_params;
 
 /* TStereoOdometryResult (H:235-264) without the variable-length members, which have their own getters. */

@@ -44,9 +44,9 @@ class Params(C.Structure):
         ("ifm_method", C.c_int32), ("ifm_win_w", C.c_int32), ("ifm_win_h", C.c_int32), ("filter_fund_matrix", C.c_int32),
         ("use_robust_kernel", C.c_int32), ("max_iters", C.c_int32), ("initial_max_iters", C.c_int32),
         ("max_incr_cost", C.c_int32), ("bad_tracking_th", C.c_int32), ("use_previous_pose_as_initial", C.c_int32),
-        ("use_custom_initial_pose", C.c_int32), ("_pad0", C.c_int32),
+        ("use_custom_initial_pose", C.c_int32), ("sad_max_distance", C.c_int32),
         ("kernel_param", C.c_double), ("min_mod_out_vector", C.c_double), ("residual_threshold", C.c_double),
-        ("vo_use_matches_ids", C.c_int32), ("_pad1", C.c_int32),
+        ("vo_use_matches_ids", C.c_int32), ("ifm_sad_max_distance", C.c_int32),
     ]
 
     def copy(self):

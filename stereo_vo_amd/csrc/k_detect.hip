@@ -80,7 +80,7 @@ hipError_t svo_upload_tables()
 // ------------------------------------------------------------------------------------------------------------
 struct ImgPtrs { const uint8_t* p[2 * SVO_MAX_LANES]; };
 
-__global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags)
+__global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask drop_prev)
 {
     SVO_TL_SCOPE(c, TL_BEGIN, (flags & SVO_RUN_DETECT) ? 0 : 1);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -120,6 +120,9 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags)
             }
             s.m_error = SVO_VOEC_NONE;                                                 // P:95
             s.has_cur = 1;                                                             // P:100
+            // (a lane whose previous frame cannot serve the tracker the parameters now select -- ifmSAD and no patches gathered for it,
+            // svo_hip.h -- starts over from this frame: all zero outside that case)
+            if ((drop_prev.w[t >> 6] >> (t & 63)) & 1ull) s.has_prev = 0;
             const int cur = 1 - s.prev_slot;
             for (int o = 0; o < c.oct_cap; o++) {
                 const int vl = t * c.oct_cap + o;
@@ -1342,6 +1345,37 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// K5b: the "patch descriptor" of the SAD matchers (smSAD S3:301-317, ifmSAD S4:570-588).  rso::compute_SAD8 only ever compares the
+// 8 x 8 windows [x-3, x+4] x [y-3, y+4] at (int)pt.x, (int)pt.y of two keypoints, so the 64 bytes of every final keypoint's window
+// are gathered here, while stage 2 still has the octave image (level 0 in ORB mode, the x1/2 image of lv[] in FAST+ORB mode), and
+// stages 3-4 need no image.  Eight lanes per keypoint, one row of eight bytes each (the row-sorted list keeps the rows of
+// neighbouring keypoints near each other); a block's 32 patches are 2 KB in one piece.  A keypoint that fails the border rule of
+// S3:290-293 (on the float coordinates, as there) gets a flag and no patch: nothing is read outside the image.
+// ------------------------------------------------------------------------------------------------------------
+typedef unsigned long long sad_row_t __attribute__((aligned(1)));      // a window row starts at any byte
+__global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
+{
+    SVO_TL_SCOPE(c, TL_DESCRIBE, 2);
+    const int vs = blockIdx.y, vl = vs >> 1, side = vs & 1, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap;
+    if (oct >= c.n_oct) return;
+    const int cur = 1 - c.lane[lane_id].prev_slot;
+    const int n = c.n_kps[feat_cnt_idx(vl, cur, side)];
+    const int i = blockIdx.x * 32 + (threadIdx.x >> 3), r = threadIdx.x & 7;
+    if (i >= n) return;
+    const long long fo = feat_base(c, vl, cur, side) + i;
+    const svo_keypoint k = c.kps[fo];
+    const int W = c.ow[oct], H = c.oh[oct];
+    const bool border = k.x < 3.0f || k.y < 3.0f || k.x > (float)(W - 5) || k.y > (float)(H - 5);       // S3:290-293, max_pt = (W-4-1, H-4-1)
+    if (r == 0) c.sad_flag[fo] = border ? 1 : 0;
+    if (border) return;
+    int pitch;
+    const uint8_t* img = level_ptr(c, lane_id * 2 + side, c.fast_orb ? oct : 0, pitch);
+    const int x = (int)k.x, y = (int)k.y;                               // TPixelCoord(pt.x, pt.y): 3 <= x <= W-5, 3 <= y <= H-5
+    const unsigned long long v = *(const sad_row_t*)(img + (long long)(y - 3 + r) * pitch + (x - 3));
+    *(unsigned long long*)(c.sad_patch + fo * 64 + r * 8) = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // K6: the reference's own post-processing of the detector output, one 1024-thread block per image:
 //   m_non_max_sup (stage2_detect.cpp:296-370): visit in (response desc, index asc) order, greedy grid occupancy;
 //   m_update_indexes(order=true) (stage2_detect.cpp:65-130): re-sort by (pt.y asc, rank asc).
@@ -2014,7 +2048,7 @@ void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st)
 // ------------------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------------------
-void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, hipStream_t st)
+void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, const LaneMask& drop_prev, hipStream_t st)
 {
     ImgPtrs ip;
     for (int i = 0; i < 2 * SVO_MAX_LANES; i++) ip.p[i] = (ptrs && i < c.n_img) ? ptrs[i] : nullptr;
@@ -2024,7 +2058,7 @@ void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned fl
         const size_t n16 = (size_t)c.n_lanes * c.oct_cap * 3 * c.max_kps / 4;
         blocks = std::max(blocks, (int)std::min<size_t>((n16 + 1023) / 1024, 2048));
     }
-    hipLaunchKernelGGL(k_begin_frame, dim3(blocks), dim3(256), 0, st, c, ip, flags);
+    hipLaunchKernelGGL(k_begin_frame, dim3(blocks), dim3(256), 0, st, c, ip, flags, drop_prev);
 }
 
 void launch_resize(const DevCtx& c, int level, hipStream_t st)
@@ -2067,6 +2101,14 @@ void launch_describe(const DevCtx& c, int pre, hipStream_t st)
     if (tl < 0) { const char* e = getenv("SVO_DESC_TL"); tl = (e && atoi(e) == 0) ? 0 : 1; }       // default: operands in LDS (0.204 -> 0.198 ms at 64 lanes, profiles/r04i); SVO_DESC_TL=0 keeps them in registers
     if (tl) hipLaunchKernelGGL((k_describe<4, true>), dim3((unsigned)((long long)gx * img8)), dim3(256), 0, st, c, make_fastdiv((uint32_t)gx), (pre && !c.fast_orb) ? 1 : 0, kpw);
     else hipLaunchKernelGGL((k_describe<4, false>), dim3((unsigned)((long long)gx * img8)), dim3(256), 0, st, c, make_fastdiv((uint32_t)gx), (pre && !c.fast_orb) ? 1 : 0, kpw);
+}
+
+// the final lists hold at most n_slots keypoints in ORB mode (all levels feed one list) and one octave's share of max_kps otherwise
+void launch_sad_patch(const DevCtx& c, hipStream_t st)
+{
+    const int n = c.fast_orb ? c.max_kps : std::min(c.n_slots, c.max_kps);
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_sad_patch, dim3((n + 31) / 32, c.n_lanes * c.oct_cap * 2), dim3(256), 0, st, c);
 }
 
 #define FO_PMAX 2048     // chunk size of k_fastorb_nms (LDS: 45 B per entry)

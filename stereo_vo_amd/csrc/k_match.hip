@@ -394,13 +394,33 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
 // One 256-thread block per lane-octave.  The reference's sequential assignment (first claimant, or best claimant with
 // enable_robust_1to1_match) is order-independent once written as a minimum over the claimants of a right feature.
 // ------------------------------------------------------------------------------------------------------------
+// SAD = true is smSAD, the same loop (S3:185-419) on the 8 x 8 windows k_sad_patch gathered: the distance is rso::compute_SAD8's sum of
+// 64 absolute differences (sixteen v_sad_u8 on four 16-byte loads, the left window in 16 registers for the whole candidate loop), a
+// pair with a keypoint too close to the border for a window is skipped before the distance (S3:289-295), and a distance is 14 bits
+// (64 * 255 = 16320), so left_pick is min_idx << 14 | min_1 (13 bits of index: max_kps <= 8192).  sad_max_ratio has no effect either.
+// (A template KERNEL, not a shared device function called from two kernels: k_match_lr_rbr<false> then compiles to the instructions
+// k_match_lr_rbr had before the parameter existed; through an inlined body the Hamming form came out ten instructions longer.)
+__device__ __forceinline__ unsigned sad64(const uint4 (&q)[4], const uint4* t)
+{
+    unsigned d = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = t[k];
+        d = __builtin_amdgcn_sad_u8(q[k].x, v.x, d); d = __builtin_amdgcn_sad_u8(q[k].y, v.y, d);
+        d = __builtin_amdgcn_sad_u8(q[k].z, v.z, d); d = __builtin_amdgcn_sad_u8(q[k].w, v.w, d);
+    }
+    return d;
+}
+
+template <bool SAD>
 __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, double max_y_diff, double minimum_response, int max_distance)
 {
-    SVO_TL_SCOPE(c, TL_LR_FILTER, 1);
+    constexpr int DB = SAD ? 14 : 8;                     // bits of a distance in left_pick
+    SVO_TL_SCOPE(c, TL_LR_FILTER, SAD ? 2 : 1);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* right_best = (unsigned*)smem;              // max_kps: per right feature, min over its claimants
-    unsigned* left_pick = right_best + c.max_kps;        // max_kps: per left feature (min_idx << 8 | min_1) or ~0
+    unsigned* left_pick = right_best + c.max_kps;        // max_kps: per left feature (min_idx << DB | min_1) or ~0
     int* scan = (int*)(left_pick + c.max_kps);           // 32
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
     if (oct >= c.n_oct) return;
@@ -409,6 +429,8 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
     const int nl = c.n_kps[feat_cnt_idx(vl, cur, 0)], nr = c.n_kps[feat_cnt_idx(vl, cur, 1)];
     const svo_keypoint* kl = c.kps + feat_base(c, vl, cur, 0), *kr = c.kps + feat_base(c, vl, cur, 1);
     const uint8_t* dl = c.desc + feat_base(c, vl, cur, 0) * 32, *dr = c.desc + feat_base(c, vl, cur, 1) * 32;
+    const uint8_t* pl = SAD ? c.sad_patch + feat_base(c, vl, cur, 0) * 64 : nullptr, *pr = SAD ? c.sad_patch + feat_base(c, vl, cur, 1) * 64 : nullptr;
+    const uint8_t* bl = SAD ? c.sad_flag + feat_base(c, vl, cur, 0) : nullptr, *br = SAD ? c.sad_flag + feat_base(c, vl, cur, 1) : nullptr;
     const int* idxL = c.row_index + (long long)feat_cnt_idx(vl, cur, 0) * c.max_h, *idxR = c.row_index + (long long)feat_cnt_idx(vl, cur, 1) * c.max_h;
     svo_dmatch* out = c.matches + match_base(c, vl, cur);
     const int W = c.ow[oct], H = c.oh[oct];
@@ -424,20 +446,31 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
         if (!(idxL[y] <= iL && iL < idxL[y + 1])) continue;                     // S3:253, 265 (empty / wrapped ranges)
         const int mrr = y - d_round, xrr = y + d_round;
         const int R0 = idxR[mrr > 0 ? mrr : 0], R1 = idxR[xrr < H - 1 ? xrr : H - 1];   // S3:254-256
-        const ulonglong2 qa = ((const ulonglong2*)(dl + (long long)iL * 32))[0], qb = ((const ulonglong2*)(dl + (long long)iL * 32))[1];
+        ulonglong2 qa = make_ulonglong2(0, 0), qb = qa; uint4 qp[4] = {};
+        if constexpr (SAD) {
+            if (bl[iL]) continue;                                               // S3:289-295: no pair of this keypoint reaches the distance
+#pragma unroll
+            for (int k = 0; k < 4; k++) qp[k] = ((const uint4*)(pl + (long long)iL * 64))[k];
+        } else { qa = ((const ulonglong2*)(dl + (long long)iL * 32))[0]; qb = ((const ulonglong2*)(dl + (long long)iL * 32))[1]; }
         unsigned min_1 = 0xFFFFFFFFu; int min_idx = -1;
         for (int iR = R0; iR < R1; iR++) {                                      // S3:274 (R1 <= R0: no candidates)
             const svo_keypoint fR = kr[iR];
             if ((double)fL.response < minimum_response || (double)fR.response < minimum_response) continue;   // S3:279
             const int disparity = (int)(fL.x - fR.x);                           // S3:283
             if (disparity < 1 || disparity > max_disparity) continue;
-            const ulonglong2 ta = ((const ulonglong2*)(dr + (long long)iR * 32))[0], tb = ((const ulonglong2*)(dr + (long long)iR * 32))[1];
-            const unsigned dist = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // uint8_t accumulator (S3:321-331)
+            unsigned dist;
+            if constexpr (SAD) {
+                if (br[iR]) continue;                                           // S3:289-295
+                dist = sad64(qp, (const uint4*)(pr + (long long)iR * 64));      // S3:309-313
+            } else {
+                const ulonglong2 ta = ((const ulonglong2*)(dr + (long long)iR * 32))[0], tb = ((const ulonglong2*)(dr + (long long)iR * 32))[1];
+                dist = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // uint8_t accumulator (S3:321-331)
+            }
             if ((int)dist > max_distance) continue;                             // S3:334
             if (dist < min_1) { min_1 = dist; min_idx = iR; }                   // S3:338-343 (first minimum)
         }
         if (min_idx >= 0) {
-            left_pick[iL] = ((unsigned)min_idx << 8) | min_1;
+            left_pick[iL] = ((unsigned)min_idx << DB) | min_1;
             // S3:359-387: best claimant (robust) or first claimant wins the right feature
             atomicMin(&right_best[min_idx], one_to_one ? ((min_1 << 16) | (unsigned)iL) : (unsigned)iL);
         }
@@ -448,10 +481,10 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
     for (int it = 0; it < n_iter; it++) {
         const int i = it * blockDim.x + tid;
         int keep = 0; unsigned pk = 0xFFFFFFFFu;
-        if (i < nl && (pk = left_pick[i]) != 0xFFFFFFFFu) keep = (int)(right_best[pk >> 8] & 0xFFFFu) == i;
+        if (i < nl && (pk = left_pick[i]) != 0xFFFFFFFFu) keep = (int)(right_best[pk >> DB] & 0xFFFFu) == i;
         int tot;
         const int off = block_exclusive_scan(keep, scan, &tot);
-        if (keep) { svo_dmatch d; d.queryIdx = i; d.trainIdx = (int)(pk >> 8); d.imgIdx = -1; d.distance = (float)(pk & 0xFFu); out[m_total + off] = d; }   // DMatch(i, fr, d): S3:404
+        if (keep) { svo_dmatch d; d.queryIdx = i; d.trainIdx = (int)(pk >> DB); d.imgIdx = -1; d.distance = (float)(pk & ((1u << DB) - 1u)); out[m_total + off] = d; }   // DMatch(i, fr, d): S3:404
         m_total += tot;
         __syncthreads();
     }
@@ -487,9 +520,14 @@ __device__ __forceinline__ int rs_first_bound(int n) { return rs_is_lmeds(n) ? S
 // of rows [y - WIN_W, y + WIN_W]; a current pairing keeps its best claimant (first on ties).  Survivors are listed in
 // ascending current index and handed to the same RANSAC kernels as the brute-force tracker.
 // ------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_H)
+// SAD = true is ifmSAD, the same loop with use_SAD: the windows keep a patch away from the border (S4:489-490, 525, 552-555), a candidate
+// needs sad_l <= MAX_SAD (previous-left against current-left window) and then sad_r <= MAX_SAD (the right ones), and the best is the
+// smallest sad_l + sad_r (<= 32640, 15 bits), strict "<" from UINT32_MAX (S4:570-588).  Deviation: the reference never checks that the
+// PREVIOUS keypoints' own windows lie inside the image; a pairing with a flagged keypoint on either frame is skipped here.
+template <bool SAD>
+__global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_H, unsigned MAX_SAD)
 {
-    SVO_TL_SCOPE(c, TL_TRK_FILTER, 1);
+    SVO_TL_SCOPE(c, TL_TRK_FILTER, SAD ? 2 : 1);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* cur_best = (unsigned*)smem;                // max_kps: (dist << 16 | pi) min over claimants
@@ -506,7 +544,15 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
     const uint8_t* pdl = c.desc + feat_base(c, vl, prev, 0) * 32, *cdl = c.desc + feat_base(c, vl, cur, 0) * 32;
     const int* ri_p = c.mrow_index + (long long)(vl * 2 + prev) * (c.max_h + 1), *ri_c = c.mrow_index + (long long)(vl * 2 + cur) * (c.max_h + 1);
     const int W = c.ow[oct], H = c.oh[oct];
-    const int awx = W - 1, awy = H - 1;                                          // S4:489-490 (descriptor variant)
+    const int awx = SAD ? W - 1 - 4 : W - 1, awy = SAD ? H - 1 - 4 : H - 1;      // S4:489-490
+    constexpr int LO = SAD ? 3 : 0;                                              // PATCHSIZE_L (S4:525, 552, 554)
+    const uint8_t* ppl = nullptr, *ppr = nullptr, *cpl = nullptr, *cpr = nullptr, *pbl = nullptr, *pbr = nullptr, *cbl = nullptr, *cbr = nullptr;
+    if constexpr (SAD) {
+        ppl = c.sad_patch + feat_base(c, vl, prev, 0) * 64; ppr = c.sad_patch + feat_base(c, vl, prev, 1) * 64;
+        cpl = c.sad_patch + feat_base(c, vl, cur, 0) * 64; cpr = c.sad_patch + feat_base(c, vl, cur, 1) * 64;
+        pbl = c.sad_flag + feat_base(c, vl, prev, 0); pbr = c.sad_flag + feat_base(c, vl, prev, 1);
+        cbl = c.sad_flag + feat_base(c, vl, cur, 0); cbr = c.sad_flag + feat_base(c, vl, cur, 1);
+    }
     for (int i = tid; i < ncm; i += blockDim.x) cur_best[i] = 0xFFFFFFFFu;
     __syncthreads();
     for (int pi = tid; pi < npm; pi += blockDim.x) {
@@ -514,18 +560,33 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
         const int y = (int)ceilf(pl.y);                                          // the row iteration whose range [ri[y], ri[y+1]) holds pi
         if (y < 0 || y >= H - 1) continue;                                       // S4:514
         if (!(ri_p[y] <= pi && pi < ri_p[y + 1])) continue;
-        const int wy_min = (y - WIN_W) > 0 ? (y - WIN_W) : 0, wy_max = awy < (y + WIN_W) ? awy : (y + WIN_W);   // S4:525-526
+        const int wy_min = (y - WIN_W) > LO ? (y - WIN_W) : LO, wy_max = awy < (y + WIN_W) ? awy : (y + WIN_W);   // S4:525-526
         const int c0 = ri_c[wy_min], c1 = ri_c[wy_max + 1];                      // S4:529-530
         const int a = (int)(pl.x - (float)WIN_H), b = (int)(pl.x + (float)WIN_H), cc = (int)(pr.x - (float)WIN_H), d = (int)(pr.x + (float)WIN_H);
-        const int wxl0 = a > 0 ? a : 0, wxl1 = awx < b ? awx : b, wxr0 = cc > 0 ? cc : 0, wxr1 = awx < d ? awx : d;   // S4:552-555
-        const ulonglong2 qa = ((const ulonglong2*)(pdl + (long long)pm[pi].queryIdx * 32))[0], qb = ((const ulonglong2*)(pdl + (long long)pm[pi].queryIdx * 32))[1];
-        int best_c = -1; unsigned best_orb = 255;                                // S4:543-545
+        const int wxl0 = a > LO ? a : LO, wxl1 = awx < b ? awx : b, wxr0 = cc > LO ? cc : LO, wxr1 = awx < d ? awx : d;   // S4:552-555
+        ulonglong2 qa = make_ulonglong2(0, 0), qb = qa; uint4 ql[4] = {}, qr[4] = {};
+        if constexpr (SAD) {
+            if (pbl[pm[pi].queryIdx] || pbr[pm[pi].trainIdx]) continue;          // (deviation: see above)
+#pragma unroll
+            for (int k = 0; k < 4; k++) { ql[k] = ((const uint4*)(ppl + (long long)pm[pi].queryIdx * 64))[k]; qr[k] = ((const uint4*)(ppr + (long long)pm[pi].trainIdx * 64))[k]; }
+        } else { qa = ((const ulonglong2*)(pdl + (long long)pm[pi].queryIdx * 32))[0]; qb = ((const ulonglong2*)(pdl + (long long)pm[pi].queryIdx * 32))[1]; }
+        int best_c = -1; unsigned best_orb = SAD ? 0xFFFFFFFFu : 255u;           // S4:543-545
         for (int ci = c0; ci < c1; ci++) {
             const svo_dmatch mc = cm[ci];
             const svo_keypoint fl = ckl[mc.queryIdx], fr = ckr[mc.trainIdx];
             if (fl.x < (float)wxl0 || fl.x > (float)wxl1 || fr.x < (float)wxr0 || fr.x > (float)wxr1) continue;   // S4:567
-            const ulonglong2 ta = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[0], tb = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[1];
-            const unsigned orb_l = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // S4:596-609
+            unsigned orb_l;
+            if constexpr (SAD) {
+                if (cbl[mc.queryIdx] || cbr[mc.trainIdx]) continue;
+                const unsigned sad_l = sad64(ql, (const uint4*)(cpl + (long long)mc.queryIdx * 64));      // S4:572-574
+                if (sad_l > MAX_SAD) continue;
+                const unsigned sad_r = sad64(qr, (const uint4*)(cpr + (long long)mc.trainIdx * 64));      // S4:576-578
+                if (sad_r > MAX_SAD) continue;
+                orb_l = sad_l + sad_r;                                           // S4:580
+            } else {
+                const ulonglong2 ta = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[0], tb = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[1];
+                orb_l = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // S4:596-609
+            }
             if (orb_l < best_orb) { best_orb = orb_l; best_c = ci; }             // S4:614-618
         }
         if (best_c >= 0) atomicMin(&cur_best[best_c], (best_orb << 16) | (unsigned)pi);   // S4:622-636
@@ -2063,7 +2124,9 @@ hipError_t configure_match(int max_kps)
     if (max_kps <= 4096) return hipSuccess;
     hipError_t e = svo_raise_dyn_smem((const void*)k_track_filter<32>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)32 * 256 * 5);
     if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_match_lr_rbr, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
+    e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<false>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
+    if (e != hipSuccess) return e;
+    e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<true>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
     return e;
 }
 
@@ -2114,11 +2177,20 @@ void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, 
 void launch_match_lr_rbr(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st)
 {
     const size_t sm = sizeof(unsigned) * 2 * c.max_kps + sizeof(int) * 32;
-    hipLaunchKernelGGL(k_match_lr_rbr, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c, one_to_one, max_y_diff, minimum_response, max_distance);
+    hipLaunchKernelGGL(k_match_lr_rbr<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c, one_to_one, max_y_diff, minimum_response, max_distance);
+}
+void launch_match_lr_sad(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st)
+{
+    const size_t sm = sizeof(unsigned) * 2 * c.max_kps + sizeof(int) * 32;
+    hipLaunchKernelGGL(k_match_lr_rbr<true>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c, one_to_one, max_y_diff, minimum_response, max_distance);
+}
+void launch_track_sad(const DevCtx& c, int win_w, int win_h, unsigned max_sad, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_track_win<true>, dim3(c.n_lanes * c.oct_cap), dim3(256), sizeof(unsigned) * c.max_kps + sizeof(int) * 40, st, c, win_w, win_h, max_sad);
 }
 void launch_track_win(const DevCtx& c, int win_w, int win_h, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_track_win, dim3(c.n_lanes * c.oct_cap), dim3(256), sizeof(unsigned) * c.max_kps + sizeof(int) * 40, st, c, win_w, win_h);      // (40: the sample schedule at its end uses scan[33..36])
+    hipLaunchKernelGGL(k_track_win<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), sizeof(unsigned) * c.max_kps + sizeof(int) * 40, st, c, win_w, win_h, 0u);      // (40: the sample schedule at its end uses scan[33..36])
 }
 void launch_match_ids(const DevCtx& c, unsigned flags, hipStream_t st)
 {

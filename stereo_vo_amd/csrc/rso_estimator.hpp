@@ -91,7 +91,10 @@ public:
         std::vector<size_t> stereo_matches;
         TStereoOdometryResult() : num_it(0), num_it_final(0), valid(false), error_code(voecNone), tracked_feats_from_last_KF(0), tracked_feats_from_last_frame(0) {}
     };
-    // the seven parameter groups (H:266-508) collapse into the flat record whose fields carry the reference's names
+    // the seven parameter groups (H:266-508) collapse into the flat record whose fields carry the reference's names; the two groups
+    // that both have a sad_max_distance keep them apart: params.sad_max_distance is params_lr_match's (H:458, smSAD),
+    // params.ifm_sad_max_distance is params_if_match's (H:297, ifmSAD).  match_method = SVO_SM_SAD and ifm_method = SVO_IFM_SAD,
+    // the reference's own default matcher, go through like every other selector
     svo_params params;
 
     explicit CStereoOdometryEstimator(int max_w = 1280, int max_h = 960, int device = 0, int max_octaves = 4) : m_ctx(NULL), m_verbose_level(1) {

@@ -19,10 +19,11 @@
 #define HIPCHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e); return SVO_ERR_HIP; } } while (0)
 
 enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, KT_LR_FILTER, KT_HAM_TRK, KT_TRK_FILTER,
-       KT_RANSAC_HYP, KT_RANSAC_CNT, KT_TRK_FINAL, KT_GN, KT_RANSAC_HYP1, KT_RANSAC_CNT1, KT_RANSAC_HYP2, KT_RANSAC_CNT2, KT_COUNT };
+       KT_RANSAC_HYP, KT_RANSAC_CNT, KT_TRK_FINAL, KT_GN, KT_RANSAC_HYP1, KT_RANSAC_CNT1, KT_RANSAC_HYP2, KT_RANSAC_CNT2,
+       KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD, KT_COUNT };
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
-    "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2" };
+    "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -92,6 +93,11 @@ struct svo_ctx {
     // svo_get_values: device packing buffer and its page-locked host mirror
     uint8_t* d_vals; uint8_t* h_vals; size_t vals_bytes;
     uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
+    // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
+    // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
+    // such frame yet" (the kernels then read nothing).  The device decides the prev/cur shift (the recovery rule of P:86-95 needs
+    // m_error), so the previous frame after a shift is known to have patches only when both candidates for it had them.
+    std::vector<uint8_t> sad_cur, sad_prev, sad_drop;  // sad_drop: the lane's next shift forgets its previous frame (svo_hip.h)
     bool imported_pending;                             // svo_import_frame ran since the last svo_process
     int sampler_nmax;                                  // > 0: holds a reference on the shared sampler table of (device, sampler_nmax)
     hipEvent_t post_event;                             // svo_record_after_post: armed for the next call that runs the detector's post-processing
@@ -346,6 +352,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->imported_pending = false; ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr;
+    ctx->sad_cur.assign((size_t)cfg->n_lanes, 1); ctx->sad_prev.assign((size_t)cfg->n_lanes, 1); ctx->sad_drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
@@ -436,6 +443,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     HIPCHECK(dev_alloc(ctx, &d.results, (size_t)L));
     HIPCHECK(dev_alloc(ctx, &d.status, (size_t)L));
     HIPCHECK(dev_alloc(ctx, &d.det_status, (size_t)L)); d.det_ahead = 0;
+    d.sad_patch = nullptr; d.sad_flag = nullptr;
     d.bf_dist = nullptr;
     { const char* dm = getenv("SVO_DEBUG_MODE"); d.debug_mode = dm ? atoi(dm) : 0; }
     if (svo_ab_form_requested(d.debug_mode) && !svo_ab_kernels_built()) {
@@ -622,6 +630,7 @@ extern "C" int svo_reset(svo_ctx* ctx, int lane)
             HIPCHECK(hipMemset(ctx->dc.n_ids + (size_t)l * OC * 2, 0, (size_t)OC * 2 * sizeof(int)));
             HIPCHECK(hipMemset(ctx->dc.results + l, 0, sizeof(svo_result)));
             HIPCHECK(hipMemset(ctx->dc.fast_th_dyn + (size_t)2 * l * SVO_MAX_LEVELS, 0, (size_t)2 * SVO_MAX_LEVELS * sizeof(uint32_t)));   // a fresh estimator speculates nothing
+            ctx->sad_cur[l] = ctx->sad_prev[l] = 1; ctx->sad_drop[l] = 0;                       // no frames: nothing a SAD stage could miss
         }
     return SVO_OK;
 }
@@ -932,8 +941,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     // P:54-76: invalid selectors are hard errors; the variants outside the hot path are refused explicitly
     if (p.detect_method < 0 || p.detect_method > 3 || p.match_method < 0 || p.match_method > 2 || p.ifm_method < 0 || p.ifm_method > 3) return SVO_ERR_ARG;
     if ((flags & SVO_RUN_DETECT) && p.detect_method != SVO_DM_ORB && p.detect_method != SVO_DM_FAST_ORB) return SVO_ERR_UNSUPPORTED;   // KLT / FASTER: out of scope
-    if ((flags & SVO_RUN_MATCH) && p.match_method != SVO_SM_DESC_BF && p.match_method != SVO_SM_DESC_RBR) return SVO_ERR_UNSUPPORTED;   // smSAD: out of scope
-    if ((flags & SVO_RUN_TRACK) && p.ifm_method != SVO_IFM_DESC_BF && p.ifm_method != SVO_IFM_DESC_WIN) return SVO_ERR_UNSUPPORTED;      // ifmSAD / optical flow: out of scope
+    if ((flags & SVO_RUN_TRACK) && p.ifm_method == SVO_IFM_OPTICAL_FLOW) return SVO_ERR_UNSUPPORTED;                                   // optical flow: out of scope
     if (p.non_maximal_suppression && p.nmsMethod != SVO_NMS_STANDARD && p.nmsMethod != SVO_NMS_ADAPTIVE) return SVO_ERR_ARG;          // S2:608
     if (p.min_distance < 2) return SVO_ERR_ARG;            // cell size 0 divides by zero in the reference (S2:331-332)
     // SVO_FLAG_DETECT_AHEAD: a detect call that leaves lane state and records alone (it may overlap stages 3-5 of the frame before),
@@ -1034,7 +1042,43 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     // capturing thread and would invalidate the capture (the adaptive NMS after the FAST+ORB detector has such a buffer)
     if ((flags & SVO_RUN_DETECT) && d.fast_orb && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
         HIPCHECK(dev_alloc(ctx, &ctx->d_anms, (size_t)3 * d.n_img * ctx->cand_total_alloc));
-    const bool graph_ok = ctx->use_graphs && !prepare && !ctx->cfg.kernel_times && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
+    // smSAD / ifmSAD: the window buffer exists from the first call made while either is selected (a context that never selects
+    // them allocates and launches nothing), and a SAD stage on a frame whose windows were never gathered is refused here
+    const bool sad_m = p.match_method == SVO_SM_SAD, sad_t = p.ifm_method == SVO_IFM_SAD, sad_any = sad_m || sad_t;
+    if (sad_any && !d.sad_patch) {
+        const size_t nk = (size_t)d.n_lanes * d.oct_cap * 4 * d.max_kps;
+        HIPCHECK(dev_alloc(ctx, &d.sad_flag, nk));
+        HIPCHECK(dev_alloc(ctx, &d.sad_patch, nk * 64));
+    }
+    const bool runs_post = (flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST));
+    LaneMask drop_prev; memset(&drop_prev, 0, sizeof(drop_prev)); bool any_drop = false;
+    {
+        const bool shifts = !(flags & SVO_FLAG_NO_SHIFT) && !(ahead && (flags & SVO_RUN_DETECT)), repeat = (flags & SVO_FLAG_REPEAT) != 0;
+        std::vector<uint8_t> cur = ctx->sad_cur, prev = ctx->sad_prev, drop = ctx->sad_drop;
+        int bad_lane = -1; bool bad_prev = false;
+        for (int l = 0; l < d.n_lanes; l++) {
+            if (shifts) {
+                if (drop[l]) { drop_prev.w[l >> 6] |= 1ull << (l & 63); any_drop = true; prev[l] = 1; drop[l] = 0; }
+                else if (!repeat) prev[l] = prev[l] && cur[l];
+                cur[l] = 0;                                  // an empty list until the post-processing has run
+            }
+            if (runs_post) cur[l] = sad_any ? 1 : 0;
+            if (bad_lane < 0 && (flags & SVO_RUN_MATCH) && sad_m && !cur[l]) bad_lane = l;
+            if (bad_lane < 0 && (flags & SVO_RUN_TRACK) && sad_t && !(cur[l] && prev[l])) { bad_lane = l; bad_prev = cur[l] != 0; }
+        }
+        if (bad_lane >= 0) {
+            char msg[320];
+            snprintf(msg, sizeof(msg), "lane %d: %s selects SAD but the 8 x 8 windows of its %s frame were never gathered (features put, loaded or imported, "
+                     "or detected while no SAD method was selected)%s", bad_lane, bad_prev ? "ifm_method" : (((flags & SVO_RUN_MATCH) && sad_m) ? "match_method" : "ifm_method"),
+                     bad_prev ? "previous" : "current", (bad_prev && shifts && !repeat) ? ": this frame is refused, the next one starts the lane's track afresh" : "");
+            ctx->last_error = msg;
+            // the frame before cannot be tracked from with SAD, and its image is gone: the next frame of such a lane forgets it
+            if (bad_prev && shifts && !repeat) for (int l = 0; l < d.n_lanes; l++) if (!ctx->sad_prev[l] || !ctx->sad_cur[l]) ctx->sad_drop[l] = 1;
+            return SVO_ERR_STATE;
+        }
+        ctx->sad_cur = cur; ctx->sad_prev = prev; ctx->sad_drop = drop;
+    }
+    const bool graph_ok = ctx->use_graphs && !prepare && !ctx->cfg.kernel_times && !any_drop && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
     const uint32_t gflags = flags & ~(uint32_t)(SVO_FLAG_DEVICE_IMAGES | SVO_FLAG_PINNED_IMAGES);
     const int gslot = (flags & SVO_RUN_DETECT) ? ctx->det_slot : -1;
     if (graph_ok) {
@@ -1051,7 +1095,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     }
     struct CaptureGuard { hipStream_t st; bool* on; ~CaptureGuard() { if (*on) { hipGraph_t g = nullptr; hipStreamEndCapture(st, &g); if (g) hipGraphDestroy(g); *on = false; } } } guard{ st, &capturing };
     d.det_ahead = (ahead && (flags & SVO_RUN_DETECT)) ? 1 : 0;
-    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, (flags & SVO_RUN_DETECT) ? ptrs : nullptr, flags, st); if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); } }
+    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, (flags & SVO_RUN_DETECT) ? ptrs : nullptr, flags, drop_prev, st); if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); } }
     // the detector's per-image scratch has had its last reader: the armed event (svo_record_after_post) goes here
     auto after_post = [&]() -> hipError_t {
         if (!ctx->post_event || capturing) return hipSuccess;
@@ -1097,7 +1141,9 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
             { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
         }
     }
-    if ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST))) HIPCHECK(after_post());
+    // the final keypoint lists exist: the windows of the SAD matchers, while the octave images are still this frame's
+    if (runs_post && sad_any) { Span s(ctx, KT_SAD_PATCH); launch_sad_patch(d, st); }
+    if (runs_post) HIPCHECK(after_post());
     const int nsplit = hamming_splits(ctx);
     if (flags & SVO_RUN_MATCH) {
         Section sec("_stg3"), sec2("stg3.find_pairings");                           // S3:64, 77
@@ -1105,15 +1151,21 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         if (p.match_method == SVO_SM_DESC_BF) {
             { Span s(ctx, KT_HAM_LR); launch_hamming(d, 0, nsplit, st); }
             { Span s(ctx, KT_LR_FILTER); launch_match_lr_filter(d, p.enable_robust_1to1_match, p.max_y_diff, st); }
-        } else {                                                // smDescRbR (stage3_match_left_right.cpp:185-419)
+        } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
             const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
             Span s(ctx, KT_LR_FILTER);
             launch_match_lr_rbr(d, p.enable_robust_1to1_match, p.max_y_diff, minresp, (int)(size_t)p.orb_max_distance, st);
+        } else {                                                // smSAD: the same loop on the gathered windows
+            const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
+            // size_t(sad_max_distance) (S3:201): 0 = the reference's default 200 (S3:48), negative = no threshold (a SAD is <= 16320)
+            const int max_sad = p.sad_max_distance == 0 ? 200 : (p.sad_max_distance < 0 ? INT32_MAX : p.sad_max_distance);
+            Span s(ctx, KT_LR_SAD);
+            launch_match_lr_sad(d, p.enable_robust_1to1_match, p.max_y_diff, minresp, max_sad, st);
         }
     }
     if (flags & SVO_RUN_TRACK) {
         Section sec("_stg4"), sec2("stg4.track");                                    // S4:76, 457
-        const int win = p.ifm_method == SVO_IFM_DESC_WIN;
+        const int win = p.ifm_method == SVO_IFM_DESC_WIN || p.ifm_method == SVO_IFM_SAD;
         // The chunks of the RANSAC's sample schedule (set before the tracker kernels: phase 0 of the schedule rides in them).  A handful of
         // lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
         // there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
@@ -1125,8 +1177,11 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         if (!win) {
             { Span s(ctx, KT_HAM_TRK); launch_hamming(d, 1, nsplit, st); }
             { Span s(ctx, KT_TRK_FILTER); launch_track_filter(d, st); }
-        } else {                                                // ifmDescWin (stage4_match_consecutive.cpp:435-738)
+        } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
             Span s(ctx, KT_TRK_FILTER); launch_track_win(d, p.ifm_win_w, p.ifm_win_h, st);
+        } else {                                                // ifmSAD: uint32_t MAX_SAD (S4:448); 0 = "~200" (H:297), negative wraps to no threshold
+            const unsigned max_sad = p.ifm_sad_max_distance == 0 ? 200u : (unsigned)p.ifm_sad_max_distance;
+            Span s(ctx, KT_TRK_SAD); launch_track_sad(d, p.ifm_win_w, p.ifm_win_h, max_sad, st);
         }
         // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
         // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
@@ -1407,6 +1462,7 @@ extern "C" int svo_put_features_oct(svo_ctx* ctx, int lane, int which, int side,
     const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
     if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.kps + base, kps, sizeof(svo_keypoint) * n, hipMemcpyHostToDevice));
     if (n > 0 && desc) HIPCHECK(hipMemcpy(ctx->dc.desc + base * 32, desc, (size_t)32 * n, hipMemcpyHostToDevice));
+    (which ? ctx->sad_prev : ctx->sad_cur)[lane] = 0;                      // caller features come without an image: no windows for smSAD / ifmSAD
     HIPCHECK(hipMemcpy(ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, &n, sizeof(int), hipMemcpyHostToDevice));
     if (which == 0) {                                                      // result.detected_feats[octave] (P:171-176)
         int32_t* cnt = side ? ctx->dc.results[lane].detected_right : ctx->dc.results[lane].detected_left;
@@ -1566,6 +1622,7 @@ extern "C" int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes
     note_stream(ctx);
     launch_import_frame(ctx->dc, (const uint8_t*)dev_blob, ctx->stream);
     ctx->imported_pending = true;
+    for (int l = 0; l < ctx->cfg.n_lanes; l++) ctx->sad_prev[l] = 0;       // the record carries no windows (svo_hip.h)
     mark_stream(ctx);
     HIPCHECK(hipGetLastError());
     return SVO_OK;

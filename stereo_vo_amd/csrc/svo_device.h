@@ -6,6 +6,7 @@
 //   lvl_pos/resp [n_img][raw_cap]              per-level winners (level-segmented, quota[l] slots each)
 //   raw_kps/raw_desc [n_img][raw_cap]          cv::ORB output stand-in before the reference's own NMS
 //   kps/desc   [n_lanes][2 slots][2 sides][max_kps]   final row-sorted features; slot = current/previous frame
+//   sad_patch/sad_flag   the same index space, 64 B / 1 B per keypoint: 8 x 8 windows for smSAD / ifmSAD, only once those are selected
 //   matches    [n_lanes][2 slots][max_kps]     left-right pairings (cv::DMatch records)
 //   ...        per-lane scratch of stages 4 and 5, lane state, result records
 // n_img = 2 * n_lanes; image index = lane * 2 + side.
@@ -189,6 +190,9 @@ struct DevCtx {
     LaneState* lane;
     svo_result* results;
     uint32_t* status;         // [n_lanes]
+    // the SAD matchers' patch descriptors (k_sad_patch): nullptr until svo_params select smSAD or ifmSAD for the first time
+    uint8_t* sad_patch;       // same index space as desc, 64 bytes each: the 8 x 8 window of every final keypoint, rows top to bottom
+    uint8_t* sad_flag;        // same index space as kps: 1 = too close to the border for a window (S3:290-293), no patch
     uint32_t* det_status;     // [n_lanes] capacity bits raised by a detect call that runs ahead (SVO_FLAG_DETECT_AHEAD): folded into status / the record by its post call
     int det_ahead;            // 1 while launching the kernels of such a call: k_fast / k_select raise their bits in det_status
     int rest_prio;            // SVO_REST_PRIO (0..3, default in svo_create): wave priority the per-lane latency chains of stages 3-5 run at (SVO_LATENCY_CHAIN)

@@ -1,8 +1,8 @@
 // svo_ini.cpp -- loadParamsFromConfigFile (libstereo-odometry/include/libstereo-odometry.h:551-672) for the flat svo_params
 // record: the reference reads its seven parameter groups from seven named sections of an MRPT INI file; this is the same
 // key list, the same "keep the current value when the key is absent" rule and the same quirk (`if_match_method` falls back
-// to 0, not to the current value, H:611).  Keys of groups that are not on the path (KLT, SAD, GUI, file output) are accepted
-// and ignored, as a file written for the reference carries them.
+// to 0, not to the current value, H:611).  Keys of groups that are not on the path (KLT, GUI, file output) and sad_max_ratio, which
+// has no effect in the reference either (S3:347-349), are accepted and ignored, as a file written for the reference carries them.
 //
 // File grammar = what mrpt::utils::CConfigFile (MRPT 1.x, a SimpleIni front end; not vendored in the reference, not in this
 // image) accepts for such files: `[section]` headers, `key = value` lines, whole-line comments starting with ';' or '#',
@@ -105,6 +105,7 @@ extern "C" int svo_params_load_ini(const char* path, const char* const sections[
         p->orb_min_th = r.read_int("orb_min_th", p->orb_min_th);
         p->orb_max_th = r.read_int("orb_max_th", p->orb_max_th);
         p->orb_max_distance = r.read_double("orb_max_distance", p->orb_max_distance);
+        p->sad_max_distance = r.read_int("sad_max_distance", p->sad_max_distance);            // H:599 (0 = the default 200, svo_types.h)
     }
     if (on(3)) {                                                                               // IF-MATCH  H:607-623
         Reader r{ ini, lower(sections[3]) };
@@ -112,6 +113,7 @@ extern "C" int svo_params_load_ini(const char* path, const char* const sections[
         p->filter_fund_matrix = r.read_bool("filter_fund_matrix", p->filter_fund_matrix);
         p->ifm_win_h = r.read_int("window_height", p->ifm_win_h);
         p->ifm_win_w = r.read_int("window_width", p->ifm_win_w);
+        p->ifm_sad_max_distance = r.read_int("sad_max_distance", p->ifm_sad_max_distance);    // H:619
         // params_if_match.orb_max_distance (H:622) is "unused by now" (H:301): no field
     }
     if (on(4)) {                                                                               // LEAST_SQUARES H:625-643

@@ -43,11 +43,13 @@ size_t handover_record_bytes(const DevCtx& c);
 void launch_export_frame(const DevCtx& c, uint8_t* blob, hipStream_t st);
 void launch_import_frame(const DevCtx& c, const uint8_t* blob, hipStream_t st);
 void launch_pack_values(const DevCtx& c, int lane, int which, int octave, uint8_t* dst, hipStream_t st);
-void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, hipStream_t st);
+struct LaneMask { unsigned long long w[(SVO_MAX_LANES + 63) / 64]; };      // one bit per lane
+void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, const LaneMask& drop_prev, hipStream_t st);
 void launch_resize(const DevCtx& c, int level, hipStream_t st);
 void launch_fast(const DevCtx& c, hipStream_t st);
 void launch_select(const DevCtx& c, hipStream_t st);
 void launch_describe(const DevCtx& c, int pre, hipStream_t st);
+void launch_sad_patch(const DevCtx& c, hipStream_t st);       // needs DevCtx.sad_patch / sad_flag (allocated when a SAD selector is first in force)
 hipError_t configure_nms_rowsort(const DevCtx& c);
 size_t nms_rowsort_scratch_bytes(const DevCtx& c);
 void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, hipStream_t st);
@@ -62,6 +64,8 @@ void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st);
 void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, hipStream_t st);
 void launch_match_lr_rbr(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
 void launch_track_win(const DevCtx& c, int win_w, int win_h, hipStream_t st);
+void launch_match_lr_sad(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
+void launch_track_sad(const DevCtx& c, int win_w, int win_h, unsigned max_sad, hipStream_t st);
 void launch_match_ids(const DevCtx& c, unsigned flags, hipStream_t st);
 void launch_hamming_plain(const uint8_t* q, int nq, const uint8_t* t, int nt, unsigned* out, int nsplit, hipStream_t st);
 hipError_t configure_gauss_newton(int pmax);
