@@ -711,7 +711,8 @@ __global__ void __launch_bounds__(FT_NT) k_fast_redo(DevCtx c)
 // and keep the best quota.  One 512-thread block per (image, level).
 // ------------------------------------------------------------------------------------------------------------
 // SEL_MAX = capacity of the 2 * quota list of a level (template parameter: 2048 in the usual configurations, 4096 for contexts
-// with max_kps > 4096); the LDS tie list holds 2 * SEL_MAX u32 entries aliasing the u64 key array
+// with max_kps > 4096, 8192 for max_kps = 16384: 96 KB of LDS in k_select, 128 KB + 8 KB in k_select_sort); the LDS tie list
+// holds 2 * SEL_MAX u32 entries aliasing the u64 key array
 
 __device__ __forceinline__ float harris_at(const uint8_t* img, int pitch, int x, int y)
 {
@@ -1381,7 +1382,7 @@ __global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
 //   m_update_indexes(order=true) (stage2_detect.cpp:65-130): re-sort by (pt.y asc, rank asc).
 // Writes the final keypoints + descriptors of the lane's current slot.
 // ------------------------------------------------------------------------------------------------------------
-// NI = keys per thread: 4 (lists up to 4096) or 8 (up to 8192)
+// NI = keys per thread: 4 (lists up to 4096), 8 (up to 8192) or 16 (up to 16384)
 template <int NI>
 __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int min_distance, int NS_MAX, int pre, uint8_t* big)
 {
@@ -1583,7 +1584,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
         }
         __syncthreads();
         if (c.debug_mode == 26) return;
-        grid_nms_block<NI>(n, gly, cellxy, hkey, hval, NS_HASH, state, flag);
+        grid_nms_block<(NI > 8 ? 0 : NI)>(n, gly, cellxy, hkey, hval, NS_HASH, state, flag);      // sixteen keys per thread: the form without the register cache
         if (c.debug_mode == 23) return;
         // survivors in rank order, at most num_out_points of them (S2:342)
         for (int base = 0; base < n && nacc < num_out_points; base += blockDim.x) {
@@ -2078,15 +2079,18 @@ void launch_fast(const DevCtx& c, hipStream_t st)
 
 void launch_select(const DevCtx& c, hipStream_t st)
 {
-    const bool big = c.sel_max > 2048;
-    if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
+    const bool big = c.sel_max > 2048, wide = c.sel_max > 4096;
+    if (wide) hipLaunchKernelGGL(k_select<8192>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
+    else if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
     else hipLaunchKernelGGL(k_select<2048>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
     // the pairs whose speculated FAST threshold was too high (normally none: both launches retire at once)
     hipLaunchKernelGGL(k_fast_redo, dim3(4096), dim3(FT_NT), 0, st, c);
-    if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
+    if (wide) hipLaunchKernelGGL(k_select<8192>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
+    else if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
     else hipLaunchKernelGGL(k_select<2048>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
     hipLaunchKernelGGL(k_harris, dim3(c.n_img, c.sel_max / 256, c.n_levels), dim3(256), 0, st, c);
-    if (big) hipLaunchKernelGGL(k_select_sort<4096>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)4096 * 16, st, c);
+    if (wide) hipLaunchKernelGGL(k_select_sort<8192>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)8192 * 16, st, c);
+    else if (big) hipLaunchKernelGGL(k_select_sort<4096>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)4096 * 16, st, c);
     else hipLaunchKernelGGL(k_select_sort<2048>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)2048 * 16, st, c);
 }
 
@@ -2122,6 +2126,8 @@ static int nms_pmax(const DevCtx& c)
 static size_t nms_rowsort_smem(int pmax) { return pmax > 4096 ? (size_t)pmax * 3 + 16 + 4 * 40 : (size_t)pmax * (8 + 8 + 8 + 4 + 2 + 1) + 16 + 4 * 40; }
 static size_t fastorb_nms_smem(int pmax, int accmax) { return (size_t)pmax * (8 + 16 + 16 + 4 + 1) + (size_t)accmax * 4 + 4 * (256 + 32 + 8) + 16; }
 
+int nms_rowsort_items(const DevCtx& c) { const int pmax = nms_pmax(c); return pmax > 8192 ? 16 : (pmax > 4096 ? 8 : 4); }      // the instantiation launch_nms_rowsort picks
+
 size_t nms_rowsort_scratch_bytes(const DevCtx& c)          // global scratch of k_nms_rowsort for lists above 4096 keys (0: everything fits LDS)
 {
     const int pmax = nms_pmax(c);
@@ -2137,8 +2143,10 @@ hipError_t configure_nms_rowsort(const DevCtx& c)
     if (e != hipSuccess) return e;
     e = svo_raise_dyn_smem((const void*)k_select_sort<4096>, 4096 * 16);
     if (e != hipSuccess) return e;
+    if (c.sel_max > 4096) { e = svo_raise_dyn_smem((const void*)k_select_sort<8192>, 8192 * 16); if (e != hipSuccess) return e; }
     const int pmax = nms_pmax(c);
-    if (pmax > 8192) return hipErrorInvalidValue;
+    if (pmax > 16384) return hipErrorInvalidValue;
+    if (pmax > 8192) { e = svo_raise_dyn_smem((const void*)k_nms_rowsort<16>, nms_rowsort_smem(16384)); if (e != hipSuccess) return e; }
     e = svo_raise_dyn_smem((const void*)k_nms_rowsort<8>, nms_rowsort_smem(8192));
     if (e != hipSuccess) return e;
     return svo_raise_dyn_smem((const void*)k_nms_rowsort<4>, nms_rowsort_smem(pmax > 4096 ? 4096 : pmax));
@@ -2152,7 +2160,8 @@ void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, 
     static int nt_knob = -1;
     if (nt_knob < 0) { const char* e = getenv("SVO_NMS_NT"); nt_knob = e ? atoi(e) : 0; }
     const int nt = (pmax <= 2048 && nt_knob == 512) ? 512 : 1024;
-    if (pmax > 4096) hipLaunchKernelGGL(k_nms_rowsort<8>, dim3(c.n_img, c.n_oct), dim3(1024), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, c.big_scratch);
+    if (pmax > 8192) hipLaunchKernelGGL(k_nms_rowsort<16>, dim3(c.n_img, c.n_oct), dim3(1024), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, c.big_scratch);
+    else if (pmax > 4096) hipLaunchKernelGGL(k_nms_rowsort<8>, dim3(c.n_img, c.n_oct), dim3(1024), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, c.big_scratch);
     else hipLaunchKernelGGL(k_nms_rowsort<4>, dim3(c.n_img, c.n_oct), dim3(nt), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, (uint8_t*)nullptr);
 }
 

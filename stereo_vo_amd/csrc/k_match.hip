@@ -75,6 +75,10 @@ __device__ __forceinline__ hm_v4i hm_expand16(uint32_t bits, uint32_t base)
     return r;
 }
 
+// WIDE = true (contexts with max_kps = 16384, k_hamming_wide): 8192 * ham leaves 13 bits for the train index, so the tile origin is not added
+// to D itself.  With u = D + 2^20 = row + 8192 * ham of the tile's minimum (row < 32), u + (u & ~8191) + j0 = (row + j0) + 16384 * ham is the
+// same key with 14 index bits -- three integer instructions per tile and query set, the minimum over the tiles as before.
+template <bool WIDE>
 __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nsplit)
 {
     __shared__ __attribute__((aligned(16))) hm_v4i tileA[2][16 * 32];          // [buffer][k-step * 64 + ((half * 32 + row) ^ k-step)]
@@ -150,7 +154,7 @@ __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nspl
         }
         if (j0 + 32 > j_end) {                                     // ragged last tile: rows past the end can never win
 #pragma unroll
-            for (int v = 0; v < 16; v++) { const bool in = j0 + tc0[v] < j_end; acc0[v] = in ? acc0[v] : 0x3FFFFFFF; acc1[v] = in ? acc1[v] : 0x3FFFFFFF; }
+            for (int v = 0; v < 16; v++) { const bool in = j0 + tc0[v] < j_end; acc0[v] = in ? acc0[v] : (WIDE ? 0x1FFFFFFF : 0x3FFFFFFF); acc1[v] = in ? acc1[v] : (WIDE ? 0x1FFFFFFF : 0x3FFFFFFF); }      // (WIDE: the key built from it below stays under 2^31)
         }
         auto min3 = [](int a, int b, int c) -> int { return min(min(a, b), c); };        // v_min3_i32
         auto min16 = [&](const hm_v16i& a) -> int {
@@ -158,8 +162,14 @@ __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nspl
             const int t3 = min3(a[9], a[10], a[11]), t4 = min3(a[12], a[13], a[14]);
             return min(min3(t0, t1, a[15]), min3(t2, t3, t4));
         };
-        best[0] = min(best[0], min16(acc0) + j0);
-        best[1] = min(best[1], min16(acc1) + j0);
+        if constexpr (WIDE) {
+            const int u0 = min16(acc0) + (1 << 20), u1 = min16(acc1) + (1 << 20);
+            best[0] = min(best[0], u0 + (u0 & ~8191) + j0);
+            best[1] = min(best[1], u1 + (u1 & ~8191) + j0);
+        } else {
+            best[0] = min(best[0], min16(acc0) + j0);
+            best[1] = min(best[1], min16(acc1) + j0);
+        }
         if (more) stage(buf ^ 1, nxt);
     }
     // ---- per query column: min over the two lane halves; D -> (distance << 16 | index) ----
@@ -169,8 +179,8 @@ __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nspl
         m = min(m, __shfl_xor(m, 32, 64));
         const int q = (int)blockIdx.y * HM_QB + wid * 64 + st * 32 + col;
         if (half == 0 && q < nq && m < 0x30000000) {
-            const unsigned u = (unsigned)(m + (1 << 20));
-            const unsigned packed = ((u >> 13) << 16) | (u & 8191u);
+            const unsigned u = WIDE ? (unsigned)m : (unsigned)(m + (1 << 20));
+            const unsigned packed = WIDE ? (((u >> 14) << 16) | (u & 16383u)) : (((u >> 13) << 16) | (u & 8191u));
             unsigned* out = (unsigned*)c.bf_idx + ((long long)vl * 3 + (mode ? 1 + side : 0)) * c.max_kps + q;
             if (nsplit > 1) atomicMin(out, packed); else *out = packed;
         }
@@ -180,7 +190,8 @@ __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nspl
 // (a build capped at 128 VGPRs = 4 waves per SIMD instead of 3 pays one 16-byte spill reloaded per train tile: 50.5 against 45.4 us
 // per launch at 64 lanes, profiles/r04f -- dropped)
 #ifdef SVO_AB_KERNELS      // an A/B anchor, not a product form (svo_kernels.h): compiled into libsvo_hip_ab.so only
-__global__ void __launch_bounds__(256) k_hamming(DevCtx c, int mode, int nsplit) { hamming_body(c, mode, nsplit); }
+__global__ void __launch_bounds__(256) k_hamming(DevCtx c, int mode, int nsplit) { hamming_body<false>(c, mode, nsplit); }
+__global__ void __launch_bounds__(256) k_hamming_wide(DevCtx c, int mode, int nsplit) { hamming_body<true>(c, mode, nsplit); }
 #endif
 
 // ---- the same brute force on gfx950's block-scaled FP4 matrix path (round 4) ------------------------------------------------
@@ -194,9 +205,14 @@ __global__ void __launch_bounds__(256) k_hamming(DevCtx c, int mode, int nsplit)
 // form spends four VALU instructions per nibble.  Operand element (lane, nibble n) meets element (lane', nibble n) of the other
 // operand for lanes of the same k-block (lane / 32): query and train rows are expanded by the same code, so the order of the bits
 // inside a k-block does not matter.
+// WIDE = true: train lists of up to 16384 rows (contexts with max_kps = 16384).  The accumulator is the same: index / 8192 now reaches
+// [0, 2), still below the step of 2 between two distances, so D orders by (distance, index) as before, and |D| < 512 with 13 fraction
+// bits is 22 significant bits, inside f32's 24.  Only the unpacking differs: floor(D) is 2 ham - 256 or 2 ham - 255, so the index is
+// taken from D - (2 ham - 256), exact like every step before it.  WIDE = false is the kernel as it was (max_kps <= 8192).
 typedef int hm_v8i __attribute__((ext_vector_type(8)));
 typedef float hm_v16f __attribute__((ext_vector_type(16)));
 
+template <bool WIDE>
 __global__ void __launch_bounds__(256) k_hamming_f4(DevCtx c, int mode, int nsplit)
 {
     SVO_TL_SCOPE(c, TL_HAMMING, mode);
@@ -309,7 +325,7 @@ __global__ void __launch_bounds__(256) k_hamming_f4(DevCtx c, int mode, int nspl
         const int q = (int)blockIdx.y * HM_QB + wid * 64 + st * 32 + col;
         if (kb == 0 && q < nq && m < 1.0e8f) {
             const float fl = floorf(m);
-            const unsigned ham = (unsigned)((int)fl + 256) >> 1, idx = (unsigned)(int)((m - fl) * 8192.0f);
+            const unsigned ham = (unsigned)((int)fl + 256) >> 1, idx = (unsigned)(int)((m - (WIDE ? (float)(2 * (int)ham - 256) : fl)) * 8192.0f);
             const unsigned packed = (ham << 16) | idx;
             unsigned* out = (unsigned*)c.bf_idx + ((long long)vl * 3 + (mode ? 1 + side : 0)) * c.max_kps + q;
             if (nsplit > 1) atomicMin(out, packed); else *out = packed;
@@ -397,7 +413,7 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
 // SAD = true is smSAD, the same loop (S3:185-419) on the 8 x 8 windows k_sad_patch gathered: the distance is rso::compute_SAD8's sum of
 // 64 absolute differences (sixteen v_sad_u8 on four 16-byte loads, the left window in 16 registers for the whole candidate loop), a
 // pair with a keypoint too close to the border for a window is skipped before the distance (S3:289-295), and a distance is 14 bits
-// (64 * 255 = 16320), so left_pick is min_idx << 14 | min_1 (13 bits of index: max_kps <= 8192).  sad_max_ratio has no effect either.
+// (64 * 255 = 16320), so left_pick is min_idx << 14 | min_1 (14 bits of index at max_kps = 16384: 28 bits, and never the empty mark ~0).  sad_max_ratio has no effect either.
 // (A template KERNEL, not a shared device function called from two kernels: k_match_lr_rbr<false> then compiles to the instructions
 // k_match_lr_rbr had before the parameter existed; through an inlined body the Hamming form came out ten instructions longer.)
 __device__ __forceinline__ unsigned sad64(const uint4 (&q)[4], const uint4* t)
@@ -631,7 +647,7 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
 // minima live in LDS.  (One wave walking 64 entries at a time took 70 us; the rounds take a few.)
 // Also gathers the pixel pairs for the two RANSACs (S4:181-189, 216-224).
 // ------------------------------------------------------------------------------------------------------------
-// TF_ITEMS x 256 threads >= max_kps: 16 (lists up to 4096) or 32
+// TF_ITEMS x 256 threads >= max_kps: 16 (lists up to 4096), 32 (up to 8192) or 64 (up to 16384)
 template <int TF_ITEMS>
 __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
 {
@@ -657,16 +673,22 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
     // a thread's candidates k = tid + 256 j: (train indices, state).  Up to 16 per thread they live in registers; the 32 of a max_kps = 8192
     // context spilled there (512 VGPRs + 1.4 KB of scratch per thread, hipcc's report): those live in LDS behind the tables above
     unsigned tlr_r[TF_ITEMS <= 16 ? TF_ITEMS : 1]; unsigned char st_r[TF_ITEMS <= 16 ? TF_ITEMS : 1];
-    unsigned* tlr_s = takenR + c.max_kps / 32; unsigned char* st_s = (unsigned char*)(tlr_s + (TF_ITEMS <= 16 ? 0 : TF_ITEMS * 256));
+    // The 64 of a max_kps = 16384 context do not fit there either (the two tables alone are 128 KB of the CU's 160): that form keeps the
+    // states in LDS and reads the train indices from the matcher's result words in global memory (bf_idx, what the others copy at the
+    // start; nothing writes them during this kernel) whenever it needs them -- only for k < npm, where a state can be other than 0.
+    constexpr bool TF_REREAD = TF_ITEMS > 32;
+    unsigned* tlr_s = takenR + c.max_kps / 32; unsigned char* st_s = (unsigned char*)(tlr_s + ((TF_ITEMS <= 16 || TF_REREAD) ? 0 : TF_ITEMS * 256));
     auto TLR = [&](int j) -> unsigned& { if constexpr (TF_ITEMS <= 16) return tlr_r[j]; else return tlr_s[j * 256 + tid]; };
     auto ST = [&](int j) -> unsigned char& { if constexpr (TF_ITEMS <= 16) return st_r[j]; else return st_s[j * 256 + tid]; };
+    auto TLRV = [&](int j) -> unsigned { if constexpr (TF_REREAD) { const int k = tid + 256 * j; return (gL[k] & 0xFFFFu) | (gR[k] << 16); } else return TLR(j); };
 #pragma unroll
     for (int j = 0; j < TF_ITEMS; j++) {
         const int k = tid + 256 * j;
-        TLR(j) = 0; ST(j) = 0;
+        if constexpr (!TF_REREAD) TLR(j) = 0;
+        ST(j) = 0;
         if (k < npm) {
             const unsigned a = gL[k], b = gR[k];
-            TLR(j) = (a & 0xFFFFu) | (b << 16);                                   // tl | tr << 16
+            if constexpr (!TF_REREAD) TLR(j) = (a & 0xFFFFu) | (b << 16);         // tl | tr << 16
             ST(j) = ((float)(a >> 16) > (float)c.orb_th || (float)(b >> 16) > (float)c.orb_th) ? 0 : 2;      // S4:149
             if ((int)(a & 0xFFFFu) >= ncm || (int)(b & 0xFFFFu) >= ncm) { ST(j) = 0; atomicOr(&c.status[lane_id], SVO_ST_INTERNAL); }   // no match was written for k: never the case on a sound frame
         }
@@ -692,12 +714,12 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < TF_ITEMS; j++)
-            if (j < n_items && ST(j) == 2) { atomicMin(&firstL[TLR(j) & 0xFFFFu], (unsigned)(tid + 256 * j)); atomicMin(&firstR[TLR(j) >> 16], (unsigned)(tid + 256 * j)); }
+            if (j < n_items && ST(j) == 2) { atomicMin(&firstL[TLRV(j) & 0xFFFFu], (unsigned)(tid + 256 * j)); atomicMin(&firstR[TLRV(j) >> 16], (unsigned)(tid + 256 * j)); }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < TF_ITEMS; j++)
             if (j < n_items && ST(j) == 2) {
-                const unsigned k = (unsigned)(tid + 256 * j), tl = TLR(j) & 0xFFFFu, tr = TLR(j) >> 16;
+                const unsigned k = (unsigned)(tid + 256 * j), tl = TLRV(j) & 0xFFFFu, tr = TLRV(j) >> 16;
                 if (firstL[tl] == k && firstR[tr] == k) { ST(j) = 1; atomicOr(&takenL[tl >> 5], 1u << (tl & 31)); atomicOr(&takenR[tr >> 5], 1u << (tr & 31)); }
             }
         __syncthreads();
@@ -705,7 +727,7 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
 #pragma unroll
         for (int j = 0; j < TF_ITEMS; j++)
             if (j < n_items && ST(j) == 2) {
-                const unsigned tl = TLR(j) & 0xFFFFu, tr = TLR(j) >> 16;
+                const unsigned tl = TLRV(j) & 0xFFFFu, tr = TLRV(j) >> 16;
                 if (((takenL[tl >> 5] >> (tl & 31)) & 1u) || ((takenR[tr >> 5] >> (tr & 31)) & 1u)) ST(j) = 0; else und = true;
             }
         if (und) s_und = 1;
@@ -729,7 +751,7 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
         const int off = block_exclusive_scan(keep, scan, &tot);
         if (keep) {
             const int o = nk + off, k = tid + 256 * j;
-            const int tl = (int)(TLR(j) & 0xFFFFu), tr = (int)(TLR(j) >> 16);
+            const int tl = (int)(TLRV(j) & 0xFFFFu), tr = (int)(TLRV(j) >> 16);
             kq[o] = k;
             const svo_dmatch mp = pm[k];
             const svo_keypoint a = pkl[mp.queryIdx], b = ckl[cm[tl].queryIdx];
@@ -2122,12 +2144,21 @@ __global__ void __launch_bounds__(256) k_match_ids(DevCtx c, unsigned flags)
 hipError_t configure_match(int max_kps)
 {
     if (max_kps <= 4096) return hipSuccess;
-    hipError_t e = svo_raise_dyn_smem((const void*)k_track_filter<32>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)32 * 256 * 5);
+    hipError_t e = hipSuccess;
+    if (max_kps <= 8192) e = svo_raise_dyn_smem((const void*)k_track_filter<32>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)32 * 256 * 5);
     if (e != hipSuccess) return e;
     e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<false>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
     if (e != hipSuccess) return e;
     e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<true>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
-    return e;
+    if (e != hipSuccess || max_kps <= 8192) return e;
+    // 16384 entries: the one-array kernels pass 64 KB too, and the joint filter runs its third form (states in LDS, 148 KB with the tables)
+    e = svo_raise_dyn_smem((const void*)k_track_filter<64>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)64 * 256);
+    if (e != hipSuccess) return e;
+    e = svo_raise_dyn_smem((const void*)k_match_lr_filter, sizeof(unsigned) * max_kps + sizeof(int) * 32);
+    if (e != hipSuccess) return e;
+    e = svo_raise_dyn_smem((const void*)k_track_win<false>, sizeof(unsigned) * max_kps + sizeof(int) * 40);
+    if (e != hipSuccess) return e;
+    return svo_raise_dyn_smem((const void*)k_track_win<true>, sizeof(unsigned) * max_kps + sizeof(int) * 40);
 }
 
 // Which kernel forms this library holds: the product forms always; the A/B anchors (the int8 matcher SVO_HAM_FP4=0, the RANSAC count forms
@@ -2161,11 +2192,14 @@ void launch_hamming(const DevCtx& c, int mode, int nsplit, hipStream_t st)
     // (the int8 form reads the paired descriptors from a list laid out by a kernel of its own; the FP4 form gathers through the pairing lists)
     if (!hamming_fp4()) {
         if (mode) hipLaunchKernelGGL(k_gather_mdesc, dim3((c.max_kps * 8 + 255) / 256, c.n_lanes * c.oct_cap, 4), dim3(256), 0, st, c);
-        hipLaunchKernelGGL(k_hamming, grid, dim3(256), 0, st, c, mode, nsplit);
+        if (c.max_kps > 8192) hipLaunchKernelGGL(k_hamming_wide, grid, dim3(256), 0, st, c, mode, nsplit);
+        else hipLaunchKernelGGL(k_hamming, grid, dim3(256), 0, st, c, mode, nsplit);
         return;
     }
 #endif
-    hipLaunchKernelGGL(k_hamming_f4, grid, dim3(256), 0, st, c, mode, nsplit);       // (svo_create refuses SVO_HAM_FP4=0 in a library without the A/B forms)
+    // (svo_create refuses SVO_HAM_FP4=0 in a library without the A/B forms)
+    if (c.max_kps > 8192) hipLaunchKernelGGL(k_hamming_f4<true>, grid, dim3(256), 0, st, c, mode, nsplit);
+    else hipLaunchKernelGGL(k_hamming_f4<false>, grid, dim3(256), 0, st, c, mode, nsplit);
 }
 
 void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, hipStream_t st)
@@ -2199,7 +2233,8 @@ void launch_match_ids(const DevCtx& c, unsigned flags, hipStream_t st)
 void launch_track_filter(const DevCtx& c, hipStream_t st)
 {
     const size_t sm = (size_t)(c.max_kps / 32) * 2 * sizeof(unsigned) + (size_t)c.max_kps * 2 * sizeof(unsigned);
-    if (c.max_kps > 4096) hipLaunchKernelGGL(k_track_filter<32>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm + (size_t)32 * 256 * 5, st, c);      // + the per-thread candidates (4 + 1 bytes each) in LDS
+    if (c.max_kps > 8192) hipLaunchKernelGGL(k_track_filter<64>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm + (size_t)64 * 256, st, c);          // + the states (1 byte each) in LDS
+    else if (c.max_kps > 4096) hipLaunchKernelGGL(k_track_filter<32>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm + (size_t)32 * 256 * 5, st, c);      // + the per-thread candidates (4 + 1 bytes each) in LDS
     else hipLaunchKernelGGL(k_track_filter<16>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c);
 }
 void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st)

@@ -20,10 +20,14 @@
 
 enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, KT_LR_FILTER, KT_HAM_TRK, KT_TRK_FILTER,
        KT_RANSAC_HYP, KT_RANSAC_CNT, KT_TRK_FINAL, KT_GN, KT_RANSAC_HYP1, KT_RANSAC_CNT1, KT_RANSAC_HYP2, KT_RANSAC_CNT2,
-       KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD, KT_COUNT };
+       KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD,
+       // the instantiations that only a 16384-entry context launches, under names of their own (a context with max_kps <= 8192 never counts a call here)
+       KT_SELECT_8192, KT_NMS_16, KT_HAM_LR_WIDE, KT_HAM_TRK_WIDE, KT_TRK_FILTER_64, KT_COUNT };
+static_assert(KT_COUNT <= 32, "kt_mask is one 32-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
-    "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad" };
+    "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
+    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -255,7 +259,7 @@ static long long pyramid_bytes(int w, int h, int nlevels)
 // cv::RNG from the seed RANSACPointSetRegistrator::run uses, (uint64)-1 -- state = (uint32)state * 4164903690 + (state >> 32), output
 // (uint32)state --, rng.uniform(0, n) = next() % n, a draw that repeats an index of the same attempt is drawn again (getSubset); the
 // collinearity rejection depends on the data and stays on the device.  The attempts depend on the point count n alone: tabulated once per
-// process and nmax on the host (~0.1 s, 18 KB per n: 84 MB at max_kps 4096) and uploaded ONCE per (device, nmax) -- three contexts of a
+// process and nmax on the host (~0.1 s, 18 KB per n: 84 MB at max_kps 4096, about 310 MB at 16384) and uploaded ONCE per (device, nmax) -- three contexts of a
 // batch used to hold three copies -- together with the generator's state at the end of every row, from which the device
 // continues the stream when a lane needs more attempts than its row holds (rs_schedule_block).  The host mutex covers the maps only,
 // not the upload of another device's copy.
@@ -339,7 +343,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     if (!cfg || !out) return SVO_ERR_ARG;
     *out = nullptr;
     if (cfg->n_lanes < 1 || cfg->n_lanes > SVO_MAX_LANES || cfg->max_w < 64 || cfg->max_h < 64) return SVO_ERR_ARG;
-    if (cfg->max_kps < 64 || cfg->max_kps > 8192 || (cfg->max_kps & (cfg->max_kps - 1))) return SVO_ERR_ARG;   // above 4096 the NMS / GN kernels keep their sort and hash arrays in global scratch
+    if (cfg->max_kps < 64 || cfg->max_kps > 16384 || (cfg->max_kps & (cfg->max_kps - 1))) return SVO_ERR_ARG;   // above 4096 the NMS / GN kernels keep their sort and hash arrays in global scratch
     if ((long long)cfg->max_w * cfg->max_h >= (1 << 24)) return SVO_ERR_UNSUPPORTED;      // position packs into 24 bits
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return SVO_ERR_NO_DEVICE;
@@ -389,7 +393,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     d.redo_list = d.redo_flag + (size_t)NI * SVO_MAX_LEVELS; d.redo_n = d.redo_list + (size_t)NI * SVO_MAX_LEVELS;
     HIPCHECK(dev_alloc(ctx, &d.lvl_pos, (size_t)NI * ctx->raw_cap_alloc));
     HIPCHECK(dev_alloc(ctx, &d.lvl_resp, (size_t)NI * ctx->raw_cap_alloc));
-    d.sel_max = MK > 4096 ? 2 * SVO_SEL_MAX : SVO_SEL_MAX;
+    d.sel_max = MK > 8192 ? 4 * SVO_SEL_MAX : (MK > 4096 ? 2 * SVO_SEL_MAX : SVO_SEL_MAX);
     HIPCHECK(dev_alloc(ctx, &d.sel_keys, (size_t)NI * SVO_MAX_LEVELS * d.sel_max));
     HIPCHECK(dev_alloc(ctx, &d.sel_resp, (size_t)NI * SVO_MAX_LEVELS * d.sel_max));
     d.big_scratch = nullptr; d.gn_scratch = nullptr;
@@ -509,11 +513,11 @@ static int params_fit(svo_ctx* ctx, const svo_params& p)
     const int nfe = p.non_maximal_suppression ? (int)(size_t)(1.5 * (double)(size_t)p.orb_nfeats) : p.orb_nfeats;       // S2:461-464
     int nlev = p.orb_nlevels < 1 ? 1 : p.orb_nlevels;
     if (nlev > SVO_MAX_LEVELS) return SVO_OK;                                  // refused as unsupported by the first frame
-    if (nfe > MK) { snprintf(msg, sizeof(msg), "orb_nfeats %d asks the detector for %d keypoints, svo_config.max_kps is %d (largest supported: 8192)", p.orb_nfeats, nfe, MK); ctx->last_error = msg; return SVO_ERR_CAPACITY; }
+    if (nfe > MK) { snprintf(msg, sizeof(msg), "orb_nfeats %d asks the detector for %d keypoints, svo_config.max_kps is %d (largest supported: 16384)", p.orb_nfeats, nfe, MK); ctx->last_error = msg; return SVO_ERR_CAPACITY; }
     int quota[SVO_MAX_LEVELS];
     level_quota(nfe, nlev, quota);
     for (int l = 0; l < nlev; l++)
-        if (2 * quota[l] > ctx->dc.sel_max) { snprintf(msg, sizeof(msg), "level %d ranks 2 x %d corners, the selection list of this context holds %d (max_kps > 4096 doubles it)", l, quota[l], ctx->dc.sel_max); ctx->last_error = msg; return SVO_ERR_CAPACITY; }
+        if (2 * quota[l] > ctx->dc.sel_max) { snprintf(msg, sizeof(msg), "level %d ranks 2 x %d corners, the selection list of this context holds %d (2048; 4096 with max_kps 8192, 8192 with max_kps 16384)", l, quota[l], ctx->dc.sel_max); ctx->last_error = msg; return SVO_ERR_CAPACITY; }
     return SVO_OK;
 }
 
@@ -737,7 +741,7 @@ static int ensure_geometry(svo_ctx* ctx, int w, int h)
             rtab.insert(rtab.end(), yi.begin(), yi.end()); rtab.insert(rtab.end(), yf.begin(), yf.end());
             rt_off += 2 * (g.w + g.h);
         }
-        if (!fast_orb && 2 * g.quota > d.sel_max) return SVO_ERR_CAPACITY;         // k_select's list capacity (2048, 4096 with max_kps > 4096)
+        if (!fast_orb && 2 * g.quota > d.sel_max) return SVO_ERR_CAPACITY;         // k_select's list capacity (2048, 4096 with max_kps 8192, 8192 with max_kps 16384)
         if (fast_orb && g.quota > d.max_kps) return SVO_ERR_CAPACITY;               // one octave's list must fit max_kps
     }
     for (int l = nlev; l < SVO_MAX_LEVELS; l++) { memset(&d.lv[l], 0, sizeof(LevelGeom)); d.lv[l].tile_off = tile_off; d.lv[l].slot_off = slot_off; }
@@ -1095,6 +1099,10 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     }
     struct CaptureGuard { hipStream_t st; bool* on; ~CaptureGuard() { if (*on) { hipGraph_t g = nullptr; hipStreamEndCapture(st, &g); if (g) hipGraphDestroy(g); *on = false; } } } guard{ st, &capturing };
     d.det_ahead = (ahead && (flags & SVO_RUN_DETECT)) ? 1 : 0;
+    // kernel_times: the instantiations of a 16384-entry context are counted under their own names (kt_names)
+    const bool wide = d.max_kps > 8192;
+    const int kt_select = d.sel_max > 4096 ? KT_SELECT_8192 : KT_SELECT;
+    auto kt_nms = [&]() -> int { return nms_rowsort_items(d) > 8 ? KT_NMS_16 : KT_NMS; };
     { Span s(ctx, KT_BEGIN); launch_begin_frame(d, (flags & SVO_RUN_DETECT) ? ptrs : nullptr, flags, drop_prev, st); if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); } }
     // the detector's per-image scratch has had its last reader: the armed event (svo_record_after_post) goes here
     auto after_post = [&]() -> hipError_t {
@@ -1112,21 +1120,21 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
                 Span s(ctx, KT_SELECT); launch_fastorb_anms(d, ctx->d_anms, st);
             } else { Span s(ctx, KT_SELECT); launch_fastorb_nms(d, p.non_maximal_suppression, p.min_distance, st); }
             { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
-            if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, KT_NMS); launch_nms_rowsort(d, p.non_maximal_suppression ? 0 : 3, p.min_distance, 0, st); }   // 0: the NMS ran above; 3: none, raster order
+            if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, p.non_maximal_suppression ? 0 : 3, p.min_distance, 0, st); }   // 0: the NMS ran above; 3: none, raster order
         } else {                // stage2_detect.cpp:458-497
             { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_resize(d, l, st); }
             { Span s(ctx, KT_FAST); launch_fast(d, st); }
             const bool split_early = (flags & SVO_FLAG_DETECT_NO_POST) && (flags & SVO_FLAG_DETECT_SPLIT_AT_SELECT);
-            if (!split_early) { Span s(ctx, KT_SELECT); launch_select(d, st); }
+            if (!split_early) { Span s(ctx, kt_select); launch_select(d, st); }
             // The reference's NMS needs positions and responses only, so it runs BEFORE orientation + description and only
             // its survivors are described (debug mode 9 keeps the detector's order: describe everything, then NMS --
             // that is what svo_debug_get_raw_keypoints shows)
             const int nms_mode = p.non_maximal_suppression ? (p.nmsMethod == SVO_NMS_ADAPTIVE ? 2 : 1) : 0;
             if (d.debug_mode == 9) {
                 { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
-                if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, KT_NMS); launch_nms_rowsort(d, nms_mode, p.min_distance, 0, st); }
+                if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 0, st); }
             } else if (!(flags & SVO_FLAG_DETECT_NO_POST)) {
-                { Span s(ctx, KT_NMS); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
+                { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
                 { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
             }
         }
@@ -1134,10 +1142,10 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         if (!ctx->geom_ready) return SVO_ERR_STATE;
         Section sec("_stg2");
         const int nms_mode = p.non_maximal_suppression ? (p.nmsMethod == SVO_NMS_ADAPTIVE ? 2 : 1) : 0;
-        if ((flags & SVO_FLAG_DETECT_SPLIT_AT_SELECT) && !d.fast_orb) { Span s(ctx, KT_SELECT); launch_select(d, st); }
-        if (d.fast_orb || d.debug_mode == 9) { Span s(ctx, KT_NMS); launch_nms_rowsort(d, d.fast_orb ? (p.non_maximal_suppression ? 0 : 3) : nms_mode, p.min_distance, 0, st); }
+        if ((flags & SVO_FLAG_DETECT_SPLIT_AT_SELECT) && !d.fast_orb) { Span s(ctx, kt_select); launch_select(d, st); }
+        if (d.fast_orb || d.debug_mode == 9) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, d.fast_orb ? (p.non_maximal_suppression ? 0 : 3) : nms_mode, p.min_distance, 0, st); }
         else {
-            { Span s(ctx, KT_NMS); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
+            { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
             { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
         }
     }
@@ -1149,7 +1157,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         Section sec("_stg3"), sec2("stg3.find_pairings");                           // S3:64, 77
         // (the brute-force result words were set to all ones by k_begin_frame)
         if (p.match_method == SVO_SM_DESC_BF) {
-            { Span s(ctx, KT_HAM_LR); launch_hamming(d, 0, nsplit, st); }
+            { Span s(ctx, wide ? KT_HAM_LR_WIDE : KT_HAM_LR); launch_hamming(d, 0, nsplit, st); }
             { Span s(ctx, KT_LR_FILTER); launch_match_lr_filter(d, p.enable_robust_1to1_match, p.max_y_diff, st); }
         } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
             const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
@@ -1175,8 +1183,8 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
             d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
         }
         if (!win) {
-            { Span s(ctx, KT_HAM_TRK); launch_hamming(d, 1, nsplit, st); }
-            { Span s(ctx, KT_TRK_FILTER); launch_track_filter(d, st); }
+            { Span s(ctx, wide ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, 1, nsplit, st); }
+            { Span s(ctx, wide ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
         } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
             Span s(ctx, KT_TRK_FILTER); launch_track_win(d, p.ifm_win_w, p.ifm_win_h, st);
         } else {                                                // ifmSAD: uint32_t MAX_SAD (S4:448); 0 = "~200" (H:297), negative wraps to no threshold

@@ -52,6 +52,7 @@ void launch_describe(const DevCtx& c, int pre, hipStream_t st);
 void launch_sad_patch(const DevCtx& c, hipStream_t st);       // needs DevCtx.sad_patch / sad_flag (allocated when a SAD selector is first in force)
 hipError_t configure_nms_rowsort(const DevCtx& c);
 size_t nms_rowsort_scratch_bytes(const DevCtx& c);
+int nms_rowsort_items(const DevCtx& c);           // keys per thread of the k_nms_rowsort instantiation this geometry launches: 4, 8 or 16
 void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, hipStream_t st);
 void launch_half(const DevCtx& c, int level, hipStream_t st);
 void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st);     // scratch3: 3 x n_img x cand_total words
