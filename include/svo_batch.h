@@ -77,6 +77,7 @@ int  svo_batch_contexts(const svo_batch* b);
 svo_ctx* svo_batch_context(svo_batch* b, int k);
 int  svo_batch_set_params(svo_batch* b, const svo_params* p);   /* every context (loadParamsFromConfigFile, H:554-663) */
 int  svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam);   /* global lane index, -1 = every stream */
+int  svo_batch_set_klt_win(svo_batch* b, int klt_win);          /* every context (svo_hip.h: dmFASTER's KLT_win, 1 .. 15) */
 /* Where every step leaves the result records: caller-owned DEVICE memory of svo_batch_lanes() * sizeof(svo_result) bytes, in
  * lane order (lane = context * lanes_per_context + lane_in_context) -- e.g. this rank's slot of an all-gather buffer.
  * NULL: a buffer of the batch's own (svo_batch_results reads it). */
@@ -110,6 +111,7 @@ svo_ctx* svo_fpstream_context(svo_fpstream* f, int k);          /* borrowed */
 svo_ctx* svo_fpstream_last_owner(svo_fpstream* f);              /* the context that ran the frame pushed last (NULL before the first) */
 int  svo_fpstream_set_params(svo_fpstream* f, const svo_params* p);
 int  svo_fpstream_set_camera(svo_fpstream* f, int lane, const svo_stereo_camera* cam);
+int  svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win);    /* every context */
 /* the next frame of the stream(s): frames[lane]; flags as for svo_batch_step.  Enqueues and returns; the frame's result records
  * (n_lanes of them) land in the owner context -- svo_get_result(s) on svo_fpstream_last_owner waits for them. */
 int  svo_fpstream_push(svo_fpstream* f, const svo_frame* frames, uint32_t flags);

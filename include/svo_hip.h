@@ -75,9 +75,12 @@ typedef struct svo_config {
     int32_t max_kps;        /* capacity of every keypoint / pairing list per octave (power of two, <= 16384; above 4096 the NMS and
                                Gauss-Newton kernels keep their sort / hash arrays in global memory instead of LDS: slower per lane.
                                16384 ranks up to 2 x 4096 corners per ORB level and holds a sampler table of about 310 MB per device) */
-    int32_t max_cand;       /* capacity of the per-level FAST candidate list at level 0 (scaled by area above) */
+    int32_t max_cand;       /* capacity of the per-level FAST candidate list at level 0 (scaled by area above).  dmFASTER keeps EVERY
+                               FAST-12 corner as a candidate (no score, no 3 x 3 suppression) and is dense on noisy content -- 24 % of
+                               the pixels of a smoothed random texture at threshold 20 -- so size it by the image there, not by the
+                               feature count: beyond it SVO_ST_CAND_OVERFLOW (status bit 1) is raised and the list is cut */
     int32_t kernel_times;   /* 1: bracket every kernel with HIP events (svo_kernel_times) */
-    int32_t max_octaves;    /* 1..4: octave lists per lane (params_rectify.nOctaves of the FAST+ORB mode); 1 suffices for ORB */
+    int32_t max_octaves;    /* 1..4: octave lists per lane (params_rectify.nOctaves of the FAST+ORB and FASTER modes); 1 suffices for ORB */
     void*   stream;         /* hipStream_t to run on; NULL = the context creates its own */
 } svo_config;
 
@@ -135,6 +138,15 @@ int svo_set_fast_threshold(svo_ctx* ctx, int v);  /* setFASTThreshold, clamped (
 int svo_set_orb_threshold(svo_ctx* ctx, int v);   /* setORBThreshold, clamped (H:538) */
 int svo_get_fast_threshold(const svo_ctx* ctx);
 int svo_get_orb_threshold(const svo_ctx* ctx);
+/* TDetectParams::KLT_win (H:561-587, default 4 at S2:47): dmFASTER ranks its corners by CImage::KLT_response over the
+ * (2 KLT_win + 1)^2 window around each.  The layout of svo_params is frozen, so the value belongs to the context, like the two
+ * thresholds above; every lane shares it.  1 .. 15; anything else is SVO_ERR_ARG and the value in force stays.  May be changed
+ * between frames under the rule of svo_set_params (it is an argument of the launches that follow; captured graphs are dropped). */
+int svo_set_klt_win(svo_ctx* ctx, int klt_win);
+int svo_get_klt_win(const svo_ctx* ctx);
+/* the INI half: reads `KLT_win` from the DETECT section of a file written for the reference.  *klt_win keeps its value when the
+ * section or the key is absent (an empty or NULL section name reads nothing); SVO_ERR_ARG when the file cannot be opened.  Host only. */
+int svo_klt_win_load_ini(const char* path, const char* detect_section, int32_t* klt_win);
 /* Switch the HIP stream that later svo_process / svo_copy_results_async calls enqueue on (NULL: the context's own).
  * Ordering between work already enqueued on the old stream and work on the new one is the caller's business (events):
  * this is what lets a caller run stage 2 of one context on a normal-priority stream and stages 3-5 of another on a
@@ -176,7 +188,15 @@ int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
  * enqueued: the lists and the lane state stay as they were.  When it is the PREVIOUS frame that lacks them (a stream that switches
  * to ifmSAD) and the call would have shifted, the refusal is remembered: the lane's next shifting call forgets that frame, i.e. it is
  * processed as the lane's first frame (voecFirstIteration; the match-ID counter runs on), and the stream is tracked with ifmSAD from the frame after.
- * SVO_IFM_OPTICAL_FLOW, KLT and FASTER stay SVO_ERR_UNSUPPORTED. */
+ * dmFASTER (detect_method = SVO_DM_FASTER, the reference's default, S2:519-576): FAST-12 corners of every x1/2 octave at the constant
+ * svo_params.initial_FAST_threshold (0 .. 255, SVO_ERR_ARG otherwise; svo_set_fast_threshold does not touch it: the reference only moves
+ * it under update_dyn_thresholds, which processNewImagePair never passes), each with its KLT response (KLT_win above), then the grid NMS
+ * and the row sort of the FAST+ORB path -- one list per octave, keypoint records (x, y, size 0, angle -1, response, octave 0,
+ * class_id -1), all-zero descriptor rows.  It computes no descriptors, so only the SAD stages can follow it: SVO_RUN_MATCH with another
+ * match_method or SVO_RUN_TRACK with ifm_method 0 / 1 is SVO_ERR_STATE, and nmsMethod = SVO_NMS_ADAPTIVE under it SVO_ERR_UNSUPPORTED,
+ * each with a text and before anything is enqueued.  target_feats_per_pixel and minimum_KLT_response have no effect on any output of the
+ * reference's path and are accepted and ignored by the INI loader.
+ * SVO_IFM_OPTICAL_FLOW and SVO_DM_KLT stay SVO_ERR_UNSUPPORTED. */
 /* block until every enqueued frame has finished */
 int svo_wait(svo_ctx* ctx);
 /* Host-fed frames (the reference's contract: P:100-120 takes host images per call).  Uploads go through a ring of two

@@ -53,7 +53,9 @@ enum { SVO_IFM_DESC_BF = 0, SVO_IFM_DESC_WIN = 1, SVO_IFM_SAD = 2, SVO_IFM_OPTIC
 /* The INI keys / struct fields that parameterise the path (H:266-508, H:554-663), one flat record.
  * Field names are the reference's. Defaults: svo_params_defaults() (S2:44-58, S3:46-57, C:69-82, S1:27-30),
  * except that the selectors default to the north-star configuration (ORB + BF + BF): the reference's own defaults are
- * dmFASTER (out of scope), smSAD (SVO_SM_SAD, supported) and none for the tracker. */
+ * dmFASTER (SVO_DM_FASTER, supported on the SAD path: svo_hip.h; its KLT_win lives on the context, svo_set_klt_win, because this
+ * record's layout is frozen), smSAD (SVO_SM_SAD, supported) and none for the tracker.  Not built: SVO_DM_KLT, SVO_IFM_OPTICAL_FLOW,
+ * the adaptive NMS under dmFASTER and the dynamic FAST threshold of update_dyn_thresholds. */
 typedef struct svo_params {
     /* RECTIFY */
     int32_t nOctaves;

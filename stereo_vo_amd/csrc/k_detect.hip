@@ -2047,6 +2047,304 @@ void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// dmFASTER (stage2_detect.cpp:519-576): FAST-12 corners of every x1/2 octave image at ONE constant threshold, ranked by
+// CImage::KLT_response -- no score, no 3 x 3 suppression, no descriptors.  One workgroup per (image, tile of FK_W x FK_H
+// positions); the tile and a halo of max(3, KLT_win + 1) pixels are staged in LDS once, clamped to the image (a pixel outside
+// it is never used: the segment test runs on [3, w-3) x [3, h-3) and a corner closer than KLT_win + 1 to the border has
+// response 0, S2:565), the segment test appends the tile's corners to an LDS list, and the SAME window then serves the
+// (2 KLT_win + 1)^2 gradient sums of each corner -- fused because the alternative is 4 x 81 global gathers per corner.
+// Published: 64-bit keys ord32(response) << 32 | (0xFFFFFFFF - raster position), one global atomic per tile; their descending
+// order is the reference's NMS order (response desc, detector index asc: the detector emits in raster order), so the raw
+// list needs no sort and the order inside a tile's range does not matter.
+// Level 0 is read in place with byte loads: any stride, any alignment (svo_hip.h, the read contract of svo_image.stride).
+// ------------------------------------------------------------------------------------------------------------
+#define FK_W SVO_FK_W
+#define FK_H SVO_FK_H
+#define FK_NT 256
+#define FK_HALO_MAX 16                      // KLT_win <= 15 (svo_set_klt_win)
+#define FK_LW (FK_W + 2 * FK_HALO_MAX)      // 96: LDS window pitch
+#define FK_LH (FK_H + 2 * FK_HALO_MAX)
+static_assert(FK_LW % 4 == 0 && FK_LW <= 128 && FK_W == 64 && FK_NT == 256 && FK_W * FK_H <= 65536, "k_faster's thread mapping: 32 threads x 4 bytes per window row, one thread per column and four rows per pass, 16-bit list entries");
+
+__device__ __forceinline__ bool faster_run12(uint32_t m)      // 12 contiguous set bits in the cyclic 16-bit mask
+{
+    const uint32_t mm = m | (m << 16);
+    const uint32_t x2 = mm & (mm >> 1), x4 = x2 & (x2 >> 2), x8 = x4 & (x4 >> 4), x12 = x8 & (x4 >> 8);
+    return (x12 & 0xFFFFu) != 0u;
+}
+#define FKO(dx, dy) ((dy) * FK_LW + (dx))
+__device__ __forceinline__ bool faster_is_corner(const uint8_t* p, int th)
+{
+    const int c0 = p[0], hi = c0 + th, lo = c0 - th;
+    // an arc of 12 leaves out 4 contiguous circle pixels, i.e. exactly one of the four cardinal ones
+    const int pn = p[FKO(0, -3)], pe = p[FKO(3, 0)], ps = p[FKO(0, 3)], pw = p[FKO(-3, 0)];
+    const int nb = (pn > hi) + (pe > hi) + (ps > hi) + (pw > hi), nd = (pn < lo) + (pe < lo) + (ps < lo) + (pw < lo);
+    if (nb < 3 && nd < 3) return false;
+    constexpr int off[16] = { FKO(0, -3), FKO(1, -3), FKO(2, -2), FKO(3, -1), FKO(3, 0), FKO(3, 1), FKO(2, 2), FKO(1, 3),
+                              FKO(0, 3), FKO(-1, 3), FKO(-2, 2), FKO(-3, 1), FKO(-3, 0), FKO(-3, -1), FKO(-2, -2), FKO(-1, -3) };
+    uint32_t b = 0, d = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) { const int v = p[off[i]]; b |= (uint32_t)(v > hi) << i; d |= (uint32_t)(v < lo) << i; }
+    return faster_run12(b) || faster_run12(d);
+}
+#undef FKO
+
+// CImage::KLT_response on the LDS window (p = the corner): the smaller eigenvalue of the gradient matrix over
+// [x-win, x+win] x [y-win, y+win], central differences, int32 sums, then float, one IEEE operation per operator
+__device__ __forceinline__ float faster_klt_response(const uint8_t* p, int win)
+{
+    int gxx = 0, gxy = 0, gyy = 0;
+    for (int v = -win; v <= win; v++) {
+        const uint8_t* r = p + v * FK_LW;
+        int left = r[-win - 1], mid = r[-win];
+        for (int u = -win; u <= win; u++) {
+            const int right = r[u + 1];
+            const int dx = right - left, dy = (int)r[u + FK_LW] - (int)r[u - FK_LW];
+            gxx += dx * dx; gxy += dx * dy; gyy += dy * dy;
+            left = mid; mid = right;
+        }
+    }
+    const int side = 2 * win + 1;
+    const float K = 0.5f / (float)(side * side);
+    const float Gxx = (float)gxx * K, Gxy = (float)gxy * K, Gyy = (float)gyy * K;
+    const float t = Gxx + Gyy;
+    const float de = Gxx * Gyy - Gxy * Gxy;
+    const float rad = t * t - 4.0f * de;
+    return 0.5f * (t - sqrtf(rad < 0.0f ? 0.0f : rad));      // (the clamp: rad comes out negative for near-isotropic windows)
+}
+
+__global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* cand64, int th, int win)
+{
+    SVO_TL_SCOPE(c, TL_FAST, 2);
+    __shared__ __attribute__((aligned(16))) uint8_t tile[FK_LH * FK_LW];
+    __shared__ unsigned short list[FK_W * FK_H];
+    __shared__ unsigned s_n, s_base;
+    const int tid = threadIdx.x;
+    const int img = (int)fastdiv(blockIdx.x, c.div_tiles), tile_id = (int)blockIdx.x - img * c.n_tiles;
+    if (img >= c.n_img) return;
+    const uint4 e = c.fast_tiles[tile_id];                  // x0 | y0 << 16, w | h << 16, level | pitch << 8, level offset in the pyramid
+    const int level = (int)(e.z & 0xFFu), gw = (int)(e.y & 0xFFFFu), gh = (int)(e.y >> 16), x0 = (int)(e.x & 0xFFFFu), y0 = (int)(e.x >> 16);
+    const uint8_t* src = level == 0 ? c.img0[img] : c.pyr + (long long)img * c.pyr_bytes + e.w;
+    const int pitch = level == 0 ? c.img0_pitch : (int)(e.z >> 8);
+    const int halo = max(3, win + 1), lw = FK_W + 2 * halo, lh = FK_H + 2 * halo;
+    if (tid == 0) s_n = 0;
+    // window byte (r, q) = pixel (x0 - halo + q, y0 - halo + r); outside the image: 0, never used
+    {
+        const int q4 = (tid & 31) * 4, gx = x0 - halo + q4;
+        if (q4 < lw)
+            for (int r = tid >> 5; r < lh; r += FK_NT / 32) {
+                const int gy = y0 - halo + r;
+                uint32_t v = 0;
+                if (gy >= 0 && gy < gh) {
+                    const uint8_t* row = src + (size_t)gy * (size_t)pitch;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) if (gx + k >= 0 && gx + k < gw) v |= (uint32_t)row[gx + k] << (8 * k);
+                }
+                *(uint32_t*)(tile + r * FK_LW + q4) = v;
+            }
+    }
+    __syncthreads();
+    // segment test: one column per thread, rows tid / 64 + 4 k (a wave's trip count is uniform: the ballots need every lane)
+    const int lx = tid & 63, x = x0 + lx;
+#pragma unroll 2
+    for (int k = 0; k < FK_H / 4; k++) {
+        const int ly = (tid >> 6) + 4 * k, y = y0 + ly;
+        const bool is = x < gw - 3 && y < gh - 3 && faster_is_corner(tile + (ly + halo) * FK_LW + lx + halo, th);
+        const unsigned long long m = __ballot(is);
+        if (m) {
+            unsigned b0 = 0;
+            const int leader = __ffsll((long long)m) - 1;
+            if ((tid & 63) == leader) b0 = atomicAdd(&s_n, (unsigned)__popcll(m));
+            b0 = __shfl(b0, leader, 64);
+            if (is) list[b0 + __popcll(m & ((1ull << (tid & 63)) - 1ull))] = (unsigned short)(ly * FK_W + lx);
+        }
+    }
+    __syncthreads();
+    const unsigned n = s_n;
+    if (n == 0) return;
+    const LevelGeom& g = c.lv[level];
+    if (tid == 0) s_base = atomicAdd(&c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE], n);
+    __syncthreads();
+    const unsigned gbase = s_base;
+    unsigned long long* dst = cand64 + (long long)img * c.cand_total + g.cand_off;
+    for (unsigned i = tid; i < n; i += FK_NT) {
+        const int ent = list[i], cy = ent / FK_W, cx = ent % FK_W, px = x0 + cx, py = y0 + cy;
+        float resp = 0.0f;                                               // S2:565: no response this close to the border
+        if (px >= win + 1 && py >= win + 1 && px < gw - win - 1 && py < gh - win - 1) resp = faster_klt_response(tile + (cy + halo) * FK_LW + cx + halo, win);
+        if (gbase + i < (unsigned)g.cand_cap) dst[gbase + i] = ((unsigned long long)ord32(resp) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(py * gw + px));
+        else raise_detect_status(c, img >> 1, SVO_ST_CAND_OVERFLOW);
+    }
+}
+
+// dmFASTER: the grid NMS of k_fastorb_nms over the 64-bit (response, raster position) keys -- the same chunked radix select (eight
+// byte passes instead of four), the same cell hash, the same cap min(kps_to_detect, quota, ACC_MAX).  Survivors go to the
+// level-segmented raw keypoint array as the records m_convert_featureList_to_keypointList makes of them (S2:31-42: pt and
+// response into a default cv::KeyPoint -- size 0, angle -1, octave 0, class_id -1) with all-zero descriptor rows; k_nms_rowsort
+// in its FAST+ORB mode then row-sorts them into the final lists.  Without NMS every corner is kept (S2:613-614), as many as the
+// octave's slots hold.
+__global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 4);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int NS_HASH = 4 * NS_MAX;
+    unsigned long long* keys = (unsigned long long*)smem;                  // NS_MAX
+    unsigned long long* sh64 = keys + NS_MAX;                              // 2: prefix of the radix select
+    uint32_t* hkey = (uint32_t*)(sh64 + 2);                                // 4*NS_MAX
+    uint32_t* hval = hkey + NS_HASH;                                       // 4*NS_MAX
+    uint32_t* cellxy = hval + NS_HASH;                                     // NS_MAX
+    uint32_t* acc_cells = cellxy + NS_MAX;                                 // ACC_MAX: cell keys of everything accepted so far
+    unsigned* hist = acc_cells + ACC_MAX;                                  // 256
+    int* scan = (int*)(hist + 256);                                        // 32
+    int* flag = scan + 32;
+    unsigned* sh = (unsigned*)(flag + 1);                                  // s_need, s_sel
+    unsigned char* state = (unsigned char*)(sh + 4);                       // NS_MAX
+    const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    const LevelGeom& g = c.lv[level];
+    unsigned nc = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
+    if (nc > (unsigned)g.cand_cap) nc = g.cand_cap;
+    const int cap = do_nms ? min(min(c.kps_to_detect[level], g.quota), ACC_MAX) : min(g.quota, ACC_MAX);
+    if (!do_nms && nc > (unsigned)cap && tid == 0) raise_detect_status(c, img >> 1, SVO_ST_KPS_OVERFLOW);
+    const unsigned long long* ck = cand64 + (long long)img * c.cand_total + g.cand_off;
+    const unsigned cell = (unsigned)((double)min_distance / 2.0);
+    const float inv = 1.0f / (float)cell;
+    const unsigned glx = (unsigned)(1 + (float)g.w * inv), gly = (unsigned)(1 + (float)g.h * inv);
+    auto slot_of_key = [&](uint32_t key) {                                 // find-or-insert
+        uint32_t h = nms_hash_slot(key, NS_HASH);
+        for (;;) {
+            const uint32_t old = atomicCAS(&hkey[h], 0xFFFFFFFFu, key);
+            if (old == 0xFFFFFFFFu || old == key) return h;
+            h = (h + 1) & (uint32_t)(NS_HASH - 1);
+        }
+    };
+    int nacc = 0;
+    unsigned long long upper = ~0ull;         // keys >= upper are already consumed (no key is all ones: that response would be a NaN)
+    unsigned remaining = nc;
+    while (remaining > 0 && nacc < cap) {
+        const unsigned K = min(remaining, (unsigned)NS_MAX);
+        // ---- the K largest keys below `upper` (radix select on the unique keys) ----
+        unsigned long long prefix = 0, mask = 0; unsigned need = K;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            for (int i = tid; i < 256; i += blockDim.x) hist[i] = 0;
+            __syncthreads();
+            for (unsigned i = tid; i < nc; i += blockDim.x) { const unsigned long long k = ck[i]; if (k < upper && (k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u); }
+            __syncthreads();
+            const int mine = tid < 256 ? (int)hist[255 - tid] : 0;
+            int tot;
+            const int before = block_exclusive_scan(mine, scan, &tot);
+            if (tid < 256 && (unsigned)before < need && need <= (unsigned)(before + mine)) { sh64[0] = prefix | ((unsigned long long)(255 - tid) << shift); sh[1] = need - (unsigned)before; }
+            __syncthreads();
+            prefix = sh64[0]; need = sh[1]; mask |= 255ull << shift;
+            __syncthreads();
+        }
+        const unsigned long long cutoff = prefix;
+        if (tid == 0) sh[2] = 0;
+        for (int i = tid; i < NS_MAX; i += blockDim.x) keys[i] = 0;
+        __syncthreads();
+        for (unsigned base = 0; base < nc; base += blockDim.x) {
+            const unsigned i = base + tid;
+            unsigned long long k = 0;
+            const bool take = i < nc && (k = ck[i]) >= cutoff && k < upper;
+            const unsigned long long m = __ballot(take);
+            if (m) {
+                unsigned b0 = 0;
+                const int leader = __ffsll((long long)m) - 1;
+                if ((tid & 63) == leader) b0 = atomicAdd(&sh[2], (unsigned)__popcll(m));
+                b0 = __shfl(b0, leader, 64);
+                const unsigned slot = b0 + __popcll(m & ((1ull << (tid & 63)) - 1ull));
+                if (take && slot < (unsigned)NS_MAX) keys[slot] = k;
+            }
+        }
+        __syncthreads();
+        int P = 64; while (P < (int)K) P <<= 1;
+        bitonic_sort_lds<true>(keys, P);                                   // rank order of this chunk
+        if (do_nms) {
+            // ---- re-seed the hash with the accepted cells, then the chunk's representatives ----
+            for (int i = tid; i < NS_HASH; i += blockDim.x) { hkey[i] = 0xFFFFFFFFu; hval[i] = 0xFFFFFFFFu; }
+            __syncthreads();
+            for (int i = tid; i < nacc; i += blockDim.x) hval[slot_of_key(acc_cells[i])] = FO_ACCEPTED;
+            __syncthreads();
+            for (int i = tid; i < (int)K; i += blockDim.x) {
+                const uint32_t pos = 0xFFFFFFFFu - (uint32_t)keys[i];
+                const float fx = (float)(pos % (uint32_t)g.w), fy = (float)(pos / (uint32_t)g.w);
+                const size_t ux = (size_t)(fx * inv), uy = (size_t)(fy * inv);
+                const uint32_t cxy = (ux < glx && uy < gly) ? (((uint32_t)ux << 16) | (uint32_t)uy) : 0xFFFFFFFFu;
+                cellxy[i] = cxy;
+                if (cxy != 0xFFFFFFFFu) {
+                    const uint32_t h = slot_of_key((cxy >> 16) * gly + (cxy & 0xFFFFu));
+                    if (hval[h] != FO_ACCEPTED) atomicMin(&hval[h], (uint32_t)i);      // markers are only written before this phase
+                }
+            }
+            __syncthreads();
+            for (int i = tid; i < (int)K; i += blockDim.x) {
+                const uint32_t cxy = cellxy[i];
+                unsigned char st = 0;
+                if (cxy != 0xFFFFFFFFu && nms_lookup(hkey, hval, NS_HASH, (cxy >> 16) * gly + (cxy & 0xFFFFu)) == (uint32_t)i) st = SVO_NMS_UNDECIDED;
+                state[i] = st;                                             // non-representatives and already-accepted cells: rejected
+            }
+            __syncthreads();
+            for (;;) {
+                if (tid == 0) *flag = 0;
+                __syncthreads();
+                bool pending = false;
+                for (int i = tid; i < (int)K; i += blockDim.x) {
+                    if (((volatile unsigned char*)state)[i] != SVO_NMS_UNDECIDED) continue;
+                    const uint32_t cxy = cellxy[i];
+                    const int sx = (int)(cxy >> 16), sy = (int)(cxy & 0xFFFFu);
+                    bool any_acc = false, any_und = false;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int cx = sx + (q == 0) - (q == 1), cy = sy + (q == 2) - (q == 3);
+                        if (cx < 0 || cy < 0 || cy >= (int)gly) continue;
+                        const uint32_t j = nms_lookup(hkey, hval, NS_HASH, (uint32_t)cx * gly + (uint32_t)cy);
+                        if (j == FO_ACCEPTED) any_acc = true;
+                        else if (j < (uint32_t)i) { const unsigned char sj = ((volatile unsigned char*)state)[j]; any_acc |= sj == 1; any_und |= sj == SVO_NMS_UNDECIDED; }
+                    }
+                    if (any_acc) ((volatile unsigned char*)state)[i] = 0;
+                    else if (!any_und) ((volatile unsigned char*)state)[i] = 1;
+                    else pending = true;
+                }
+                if (pending) *flag = 1;
+                __syncthreads();
+                const int again = *flag;
+                __syncthreads();
+                if (!again) break;
+            }
+        } else {
+            for (int i = tid; i < (int)K; i += blockDim.x) state[i] = 1;
+            __syncthreads();
+        }
+        // ---- emit the chunk's survivors in rank order, up to the cap, and remember their cells ----
+        int chunk_acc = 0;
+        for (int base = 0; base < (int)K && nacc + chunk_acc < cap; base += blockDim.x) {
+            const int i = base + tid;
+            const int keep = (i < (int)K && state[i] == 1) ? 1 : 0;
+            int tot;
+            const int off = block_exclusive_scan(keep, scan, &tot);
+            const int o_idx = nacc + chunk_acc + off;
+            if (keep && o_idx < cap) {
+                const unsigned long long k = keys[i];
+                const long long o = (long long)img * c.raw_cap + g.slot_off + o_idx;
+                const uint32_t pos = 0xFFFFFFFFu - (uint32_t)k;
+                svo_keypoint kp;
+                kp.x = (float)(pos % (uint32_t)g.w); kp.y = (float)(pos / (uint32_t)g.w); kp.size = 0.0f; kp.angle = -1.0f;
+                kp.response = inv_ord32((uint32_t)(k >> 32)); kp.octave = 0; kp.class_id = -1;
+                c.raw_kps[o] = kp;
+                uint4* dd = (uint4*)(c.raw_desc + o * 32);
+                dd[0] = make_uint4(0, 0, 0, 0); dd[1] = make_uint4(0, 0, 0, 0);
+                if (do_nms) { const uint32_t cxy = cellxy[i]; acc_cells[o_idx] = (cxy >> 16) * gly + (cxy & 0xFFFFu); }
+            }
+            chunk_acc += tot;
+            __syncthreads();
+        }
+        nacc = min(nacc + chunk_acc, cap);
+        upper = cutoff;
+        remaining -= K;
+        __syncthreads();
+    }
+    if (tid == 0) c.lvl_n[img * SVO_MAX_LEVELS + level] = nacc;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------------------
 void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, const LaneMask& drop_prev, hipStream_t st)
@@ -2174,4 +2472,18 @@ void launch_half(const DevCtx& c, int level, hipStream_t st)
 void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream_t st)
 {
     hipLaunchKernelGGL(k_fastorb_nms, dim3(c.n_levels, c.n_img), dim3(1024), fastorb_nms_smem(FO_PMAX, c.max_kps), st, c, min_distance, do_nms, FO_PMAX, c.max_kps);
+}
+
+void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st)
+{
+    if (c.n_tiles <= 0) return;
+    hipLaunchKernelGGL(k_faster, dim3((unsigned)((long long)c.n_tiles * c.n_img)), dim3(FK_NT), 0, st, c, cand64, fast_th, klt_win);
+}
+
+static size_t faster_nms_smem(int pmax, int accmax) { return fastorb_nms_smem(pmax, accmax) + 16; }       // + the 64-bit prefix words
+hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, faster_nms_smem(FO_PMAX, c.max_kps)); }
+
+void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), faster_nms_smem(FO_PMAX, c.max_kps), st, c, cand64, min_distance, do_nms, FO_PMAX, c.max_kps);
 }

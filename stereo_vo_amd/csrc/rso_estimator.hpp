@@ -96,6 +96,9 @@ public:
     // params.ifm_sad_max_distance is params_if_match's (H:297, ifmSAD).  match_method = SVO_SM_SAD and ifm_method = SVO_IFM_SAD,
     // the reference's own default matcher, go through like every other selector
     svo_params params;
+    // ... and the one field of TDetectParams the frozen record has no room for: KLT_win (H:561-587, default 4 at S2:47), the window
+    // of dmFASTER's KLT response; it lives on the context (svo_set_klt_win) and is pushed with the record by applyParams
+    struct TDetectParams { int KLT_win; TDetectParams() : KLT_win(4) {} } params_detect;
 
     explicit CStereoOdometryEstimator(int max_w = 1280, int max_h = 960, int device = 0, int max_octaves = 4) : m_ctx(NULL), m_verbose_level(1) {
         svo_params_defaults(&params);
@@ -109,7 +112,7 @@ public:
     CStereoOdometryEstimator& operator=(const CStereoOdometryEstimator&) = delete;
 
     /** loadParamsFromConfigFile's effect (H:554-663): push `params`, then reset both dynamic thresholds */
-    void applyParams() { check(svo_set_params(m_ctx, &params), "svo_set_params"); }
+    void applyParams() { check(svo_set_params(m_ctx, &params), "svo_set_params"); check(svo_set_klt_win(m_ctx, params_detect.KLT_win), "svo_set_klt_win"); }
     /** Loads configuration from an INI file from its name (H:665-672); sections in the order RECTIFY, DETECT, MATCH, IF-MATCH,
       * LEAST_SQUARES, GUI, GENERAL (H:551-553), an empty name skips the group */
     void loadParamsFromConfigFileName(const std::string& fileName, const std::vector<std::string>& sections) {
@@ -117,6 +120,7 @@ public:
         const char* names[7];
         for (int i = 0; i < 7; i++) names[i] = sections[i].c_str();
         check(svo_params_load_ini(fileName.c_str(), names, &params), "svo_params_load_ini");
+        { int32_t w = params_detect.KLT_win; check(svo_klt_win_load_ini(fileName.c_str(), names[1], &w), "svo_klt_win_load_ini"); params_detect.KLT_win = w; }
         applyParams();                                                                   // resetFASTThreshold / resetORBThreshold, H:662-663
     }
     void setVerbosityLevel(int level) { m_verbose_level = level; }                       // H:527

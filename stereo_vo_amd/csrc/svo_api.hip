@@ -22,12 +22,14 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        KT_RANSAC_HYP, KT_RANSAC_CNT, KT_TRK_FINAL, KT_GN, KT_RANSAC_HYP1, KT_RANSAC_CNT1, KT_RANSAC_HYP2, KT_RANSAC_CNT2,
        KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD,
        // the instantiations that only a 16384-entry context launches, under names of their own (a context with max_kps <= 8192 never counts a call here)
-       KT_SELECT_8192, KT_NMS_16, KT_HAM_LR_WIDE, KT_HAM_TRK_WIDE, KT_TRK_FILTER_64, KT_COUNT };
+       KT_SELECT_8192, KT_NMS_16, KT_HAM_LR_WIDE, KT_HAM_TRK_WIDE, KT_TRK_FILTER_64,
+       // dmFASTER (only a context that selects it counts a call here)
+       KT_FASTER, KT_FASTER_NMS, KT_COUNT };
 static_assert(KT_COUNT <= 32, "kt_mask is one 32-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
-    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64" };
+    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64", "faster", "faster_nms" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -72,6 +74,7 @@ struct svo_ctx {
     svo_config cfg;
     svo_params params;
     int fast_th, orb_th;
+    int klt_win;                                       // TDetectParams::KLT_win (S2:47): the window of dmFASTER's response, (2 klt_win + 1)^2 pixels
     hipStream_t stream, stream0; bool own_stream;      // stream0: the stream the context was created with / owns
     DevCtx dc;
     bool geom_ready; int geom_w, geom_h, geom_nfe, geom_nlevels, geom_method, geom_noct;
@@ -97,6 +100,7 @@ struct svo_ctx {
     // svo_get_values: device packing buffer and its page-locked host mirror
     uint8_t* d_vals; uint8_t* h_vals; size_t vals_bytes;
     uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
+    unsigned long long* d_cand64;                      // dmFASTER's 64-bit candidate keys (n_img x cand_total), allocated by the first svo_process made while it is selected
     // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
     // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
     // such frame yet" (the kernels then read nothing).  The device decides the prev/cur shift (the recovery rule of P:86-95 needs
@@ -351,6 +355,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->cfg = *cfg;
     svo_params_defaults(&ctx->params);
     ctx->fast_th = 20; ctx->orb_th = 60;                  // common.cpp:35-36
+    ctx->klt_win = 4; ctx->d_cand64 = nullptr;            // stage2_detect.cpp:47
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
@@ -496,7 +501,7 @@ void level_quota(int nfeatures, int nlevels, int* q);
 // size -- pyramid and candidate buffers -- is still checked by the first svo_process.)
 static int params_fit(svo_ctx* ctx, const svo_params& p)
 {
-    const bool fast_orb = p.detect_method == SVO_DM_FAST_ORB;
+    const bool fast_orb = p.detect_method == SVO_DM_FAST_ORB || p.detect_method == SVO_DM_FASTER;      // one list per x1/2 octave
     if (p.detect_method != SVO_DM_ORB && !fast_orb) return SVO_OK;          // refused as unsupported by svo_process
     char msg[256];
     const int MK = ctx->dc.max_kps;
@@ -552,6 +557,18 @@ extern "C" int svo_set_orb_threshold(svo_ctx* ctx, int v)
 }
 extern "C" int svo_get_fast_threshold(const svo_ctx* ctx) { return ctx ? ctx->fast_th : SVO_ERR_ARG; }
 extern "C" int svo_get_orb_threshold(const svo_ctx* ctx) { return ctx ? ctx->orb_th : SVO_ERR_ARG; }
+// TDetectParams::KLT_win: svo_params has no room for it (its layout is frozen), so it lives on the context like the two thresholds.
+// A kernel argument of the launches that follow: like svo_set_params it needs no synchronisation, only the captured graphs go.
+extern "C" int svo_set_klt_win(svo_ctx* ctx, int v)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    if (v < 1 || v > 15) { char msg[96]; snprintf(msg, sizeof(msg), "KLT_win %d: 1 .. 15 are supported", v); ctx->last_error = msg; return SVO_ERR_ARG; }
+    if (v != ctx->klt_win) drop_graphs(ctx);
+    ctx->klt_win = v;
+    return SVO_OK;
+}
+extern "C" int svo_get_klt_win(const svo_ctx* ctx) { return ctx ? ctx->klt_win : SVO_ERR_ARG; }
 
 extern "C" int svo_set_stream(svo_ctx* ctx, void* stream)
 {
@@ -678,7 +695,9 @@ static void drop_graphs(svo_ctx* ctx)
 static int ensure_geometry(svo_ctx* ctx, int w, int h)
 {
     const svo_params& p = ctx->params;
-    const bool fast_orb = p.detect_method == SVO_DM_FAST_ORB;
+    // dmFAST_ORB and dmFASTER both work on the x1/2 octave pyramid and keep one list per octave (S2:502-515, 519-576): same geometry,
+    // except that dmFASTER's detector tiles start 3 pixels from the border
+    const bool faster = p.detect_method == SVO_DM_FASTER, fast_orb = p.detect_method == SVO_DM_FAST_ORB || faster;
     const int nfe = p.non_maximal_suppression ? (int)(size_t)(1.5 * (double)(size_t)p.orb_nfeats) : p.orb_nfeats;   // stage2_detect.cpp:461-464
     // stage1_rectify.cpp:80: one octave for dmORB (cv::ORB builds its own x1/1.2 pyramid), params_rectify.nOctaves otherwise
     const int noct = fast_orb ? (p.nOctaves < 1 ? 1 : p.nOctaves) : 1;
@@ -719,9 +738,10 @@ static int ensure_geometry(svo_ctx* ctx, int w, int h)
         LevelGeom& g = d.lv[l];
         g.w = lw[l]; g.h = lh[l]; g.pitch = align_up(lw[l], 64); g.scale = sc[l];
         g.offset = off; if (l >= 1) off += (long long)g.pitch * g.h;
-        const int iw = g.w - 2 * SVO_EDGE, ih = g.h - 2 * SVO_EDGE;
+        const int edge = faster ? 3 : SVO_EDGE, tw = faster ? SVO_FK_W : SVO_FT_W, th = faster ? SVO_FK_H : SVO_FT_H;
+        const int iw = g.w - 2 * edge, ih = g.h - 2 * edge;
         const bool live = iw > 0 && ih > 0 && quota[l] > 0;
-        g.tiles_x = live ? (iw + SVO_FT_W - 1) / SVO_FT_W : 0; g.tiles_y = live ? (ih + SVO_FT_H - 1) / SVO_FT_H : 0;
+        g.tiles_x = live ? (iw + tw - 1) / tw : 0; g.tiles_y = live ? (ih + th - 1) / th : 0;
         g.tile_off = tile_off; tile_off += g.tiles_x * g.tiles_y;
         g.quota = live ? quota[l] : 0; g.slot_off = slot_off; slot_off += g.quota;
         long long cc = (long long)ctx->cfg.max_cand * ((long long)g.w * g.h) / ((long long)lw[0] * lh[0]);
@@ -752,20 +772,22 @@ static int ensure_geometry(svo_ctx* ctx, int w, int h)
     d.n_tiles = tile_off; d.n_slots = slot_off; d.cand_total = ctx->cand_total_alloc;
     d.div_tiles = make_fastdiv((uint32_t)(tile_off > 0 ? tile_off : 1));
     if (!rtab.empty()) HIPCHECK(hipMemcpy(d.rtab, rtab.data(), rtab.size() * sizeof(int), hipMemcpyHostToDevice));
-    {   // k_fast's tile table (same for every image and frame of this geometry)
+    {   // k_fast's / k_faster's tile table (same for every image and frame of this geometry)
+        const int edge = faster ? 3 : SVO_EDGE, tw = faster ? SVO_FK_W : SVO_FT_W, th = faster ? SVO_FK_H : SVO_FT_H;
         if (tile_off > ctx->tile_tab_alloc) return SVO_ERR_CAPACITY;
         std::vector<uint4> tt((size_t)tile_off);
         for (int l = 0; l < nlev; l++) {
             const LevelGeom& g = d.lv[l];
             for (int t = 0; t < g.tiles_x * g.tiles_y; t++) {
                 const int by = t / g.tiles_x, bx = t - by * g.tiles_x;
-                tt[(size_t)g.tile_off + t] = make_uint4((uint32_t)(SVO_EDGE + bx * SVO_FT_W) | ((uint32_t)(SVO_EDGE + by * SVO_FT_H) << 16), (uint32_t)g.w | ((uint32_t)g.h << 16),
+                tt[(size_t)g.tile_off + t] = make_uint4((uint32_t)(edge + bx * tw) | ((uint32_t)(edge + by * th) << 16), (uint32_t)g.w | ((uint32_t)g.h << 16),
                                                         (uint32_t)l | ((uint32_t)g.pitch << 8), (uint32_t)g.offset);
             }
         }
         if (!tt.empty()) HIPCHECK(hipMemcpy((void*)d.fast_tiles, tt.data(), tt.size() * sizeof(uint4), hipMemcpyHostToDevice));
     }
     HIPCHECK(configure_nms_rowsort(d));
+    if (faster) HIPCHECK(configure_faster_nms(d));
     ctx->geom_ready = true; ctx->geom_w = w; ctx->geom_h = h; ctx->geom_nfe = nfe_key; ctx->geom_nlevels = nlev;
     ctx->geom_method = p.detect_method; ctx->geom_noct = noct;
     return SVO_OK;
@@ -944,10 +966,23 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     const svo_params& p = ctx->params;
     // P:54-76: invalid selectors are hard errors; the variants outside the hot path are refused explicitly
     if (p.detect_method < 0 || p.detect_method > 3 || p.match_method < 0 || p.match_method > 2 || p.ifm_method < 0 || p.ifm_method > 3) return SVO_ERR_ARG;
-    if ((flags & SVO_RUN_DETECT) && p.detect_method != SVO_DM_ORB && p.detect_method != SVO_DM_FAST_ORB) return SVO_ERR_UNSUPPORTED;   // KLT / FASTER: out of scope
+    if ((flags & SVO_RUN_DETECT) && p.detect_method == SVO_DM_KLT) return SVO_ERR_UNSUPPORTED;                                         // dmKLT: out of scope
     if ((flags & SVO_RUN_TRACK) && p.ifm_method == SVO_IFM_OPTICAL_FLOW) return SVO_ERR_UNSUPPORTED;                                   // optical flow: out of scope
     if (p.non_maximal_suppression && p.nmsMethod != SVO_NMS_STANDARD && p.nmsMethod != SVO_NMS_ADAPTIVE) return SVO_ERR_ARG;          // S2:608
     if (p.min_distance < 2) return SVO_ERR_ARG;            // cell size 0 divides by zero in the reference (S2:331-332)
+    // dmFASTER (S2:519-576) produces keypoints without descriptors: only the SAD stages can consume its lists
+    const bool faster = p.detect_method == SVO_DM_FASTER;
+    if (faster) {
+        if ((flags & SVO_RUN_MATCH) && p.match_method != SVO_SM_SAD) { ctx->last_error = "dmFASTER computes no descriptors: stage 3 needs match_method = smSAD"; return SVO_ERR_STATE; }
+        if ((flags & SVO_RUN_TRACK) && p.ifm_method != SVO_IFM_SAD) { ctx->last_error = "dmFASTER computes no descriptors: stage 4 needs ifm_method = ifmSAD"; return SVO_ERR_STATE; }
+        if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {
+            ctx->last_error = "the adaptive NMS is not built for dmFASTER: use nmsMethod = nmsmStandard"; return SVO_ERR_UNSUPPORTED;
+        }
+        if ((flags & SVO_RUN_DETECT) && (p.initial_FAST_threshold < 0 || p.initial_FAST_threshold > 255)) {
+            char msg[128]; snprintf(msg, sizeof(msg), "initial_FAST_threshold %d: dmFASTER takes 0 .. 255", p.initial_FAST_threshold);
+            ctx->last_error = msg; return SVO_ERR_ARG;
+        }
+    }
     // SVO_FLAG_DETECT_AHEAD: a detect call that leaves lane state and records alone (it may overlap stages 3-5 of the frame before),
     // or the post call that completes it (and therefore runs the shift itself)
     const bool ahead = (flags & SVO_FLAG_DETECT_AHEAD) != 0;
@@ -1044,8 +1079,9 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     // ~30 kernel launches of a frame become one graph launch (what bounds ONE stream is launch latency, not the kernels)
     // every lazily allocated buffer a frame may need exists BEFORE a capture begins: hipMalloc / hipMemset are refused on a
     // capturing thread and would invalidate the capture (the adaptive NMS after the FAST+ORB detector has such a buffer)
-    if ((flags & SVO_RUN_DETECT) && d.fast_orb && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
+    if ((flags & SVO_RUN_DETECT) && d.fast_orb && !faster && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
         HIPCHECK(dev_alloc(ctx, &ctx->d_anms, (size_t)3 * d.n_img * ctx->cand_total_alloc));
+    if ((flags & SVO_RUN_DETECT) && faster && !ctx->d_cand64) HIPCHECK(dev_alloc(ctx, &ctx->d_cand64, (size_t)d.n_img * ctx->cand_total_alloc));
     // smSAD / ifmSAD: the window buffer exists from the first call made while either is selected (a context that never selects
     // them allocates and launches nothing), and a SAD stage on a frame whose windows were never gathered is refused here
     const bool sad_m = p.match_method == SVO_SM_SAD, sad_t = p.ifm_method == SVO_IFM_SAD, sad_any = sad_m || sad_t;
@@ -1113,7 +1149,13 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     };
     if (flags & SVO_RUN_DETECT) {
         Section sec("_stg2");                                                        // S2:392, 670
-        if (d.fast_orb) {       // stage2_detect.cpp:502-515 on the x1/2 octave pyramid
+        if (faster) {           // stage2_detect.cpp:519-576: FAST-12 at the constant initial_FAST_threshold (m_threshold never moves: processNewImagePair
+                                // passes no update_dyn_thresholds), KLT response, grid NMS, row sort; svo_set_fast_threshold has no part in it
+            { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
+            { Span s(ctx, KT_FASTER); launch_faster(d, ctx->d_cand64, p.initial_FAST_threshold, ctx->klt_win, st); }
+            { Span s(ctx, KT_FASTER_NMS); launch_faster_nms(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, st); }
+            if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, p.non_maximal_suppression ? 0 : 3, p.min_distance, 0, st); }
+        } else if (d.fast_orb) {       // stage2_detect.cpp:502-515 on the x1/2 octave pyramid
             { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
             { Span s(ctx, KT_FAST); launch_fast(d, st); }
             if (p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {      // S2:599-606 on the FAST detector's output

@@ -157,6 +157,13 @@ extern "C" int svo_batch_set_params(svo_batch* b, const svo_params* p)
     return SVO_OK;
 }
 
+extern "C" int svo_batch_set_klt_win(svo_batch* b, int klt_win)
+{
+    if (!b) return SVO_ERR_ARG;
+    for (svo_ctx* c : b->ctx) BSVO(b, c, svo_set_klt_win(c, klt_win));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam)
 {
     if (!b || !cam || lane < -1 || lane >= b->B) return SVO_ERR_ARG;
@@ -346,6 +353,13 @@ extern "C" int svo_fpstream_set_params(svo_fpstream* f, const svo_params* p)
 {
     if (!f || !p) return SVO_ERR_ARG;
     for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_params(c, p));
+    return SVO_OK;
+}
+
+extern "C" int svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win)
+{
+    if (!f) return SVO_ERR_ARG;
+    for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_klt_win(c, klt_win));
     return SVO_OK;
 }
 

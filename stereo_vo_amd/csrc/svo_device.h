@@ -29,6 +29,8 @@
 #define SVO_SEL_MAX 2048     // >= 2 * quota[0]: corners per (image, level) ranked by their Harris response
 #define SVO_FT_W 62          // k_fast tile (interior pixels; 64x64 score window with the NMS halo)
 #define SVO_FT_H 62
+#define SVO_FK_W 64          // k_faster tile (dmFASTER: the tiling starts 3 pixels from the border, not SVO_EDGE)
+#define SVO_FK_H 32
 #define SVO_CNT_STRIDE 32          // u32 stride between hot atomic counters = one 128-byte cache line each
 #define SVO_RS_ATT 1152             // tabulated attempts of cv::findFundamentalMat's sampler per point count n (1000 samples + room for rejected attempts)
 #define SVO_RS_SMALL_N 64           // ... below this many points 11008 of them: enough for 1000 samples and getSubset's 10000 attempts on the last
@@ -97,7 +99,7 @@ struct DevCtx {
     int oct_cap, n_oct;       // allocated / active octaves
     int ow[SVO_MAX_OCTAVES], oh[SVO_MAX_OCTAVES];      // octave image sizes
     int kps_to_detect[SVO_MAX_OCTAVES];                // stage2_detect.cpp:404-407
-    int fast_orb;             // 1: detect_method == dmFAST_ORB (levels of lv[] are the octave images, keypoint size 7)
+    int fast_orb;             // 1: detect_method == dmFAST_ORB or dmFASTER (levels of lv[] are the x1/2 octave images, one list per octave)
     int max_h;                // row-index table pitch
     int img0_pitch;
     int max_kps, raw_cap, cand_total, n_tiles, n_slots;

@@ -135,3 +135,17 @@ extern "C" int svo_params_load_ini(const char* path, const char* const sections[
     }
     return SVO_OK;
 }
+
+// TDetectParams::KLT_win (H:561-587 reads it with the DETECT group; S2:47 defaults it to 4).  svo_params cannot grow, so the key has a
+// loader of its own: *klt_win keeps its value when the section or the key is absent; follow it with svo_set_klt_win.
+extern "C" int svo_klt_win_load_ini(const char* path, const char* detect_section, int32_t* klt_win)
+{
+    if (!path || !klt_win) return SVO_ERR_ARG;
+    Ini ini;
+    if (!parse_ini(path, ini)) return SVO_ERR_ARG;
+    if (detect_section && detect_section[0]) {
+        Reader r{ ini, lower(detect_section) };
+        *klt_win = r.read_int("KLT_win", *klt_win);
+    }
+    return SVO_OK;
+}

@@ -21,7 +21,7 @@ FLAG_REPEAT, FLAG_NO_SHIFT, FLAG_DEVICE_IMAGES, FLAG_BGR_IMAGES, FLAG_DETECT_NO_
 EXPORTS = [
     "svo_config_defaults", "svo_params_defaults", "svo_create", "svo_destroy", "svo_strerror", "svo_last_error",
     "svo_set_params", "svo_get_params", "svo_params_load_ini", "svo_set_fast_threshold", "svo_set_orb_threshold", "svo_get_fast_threshold",
-    "svo_get_orb_threshold", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
+    "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
@@ -35,10 +35,10 @@ EXPORTS = [
 
 BATCH_EXPORTS = [
     "svo_batch_abi_sizes", "svo_batch_config_defaults", "svo_batch_create", "svo_batch_create_sized", "svo_batch_destroy", "svo_batch_last_error", "svo_batch_lanes", "svo_batch_contexts",
-    "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step",
+    "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_klt_win", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step",
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
-    "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_push", "svo_fpstream_synchronize",
+    "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
 ]
 
 
@@ -115,6 +115,15 @@ def load_params_ini(path, sections, p: Params = None) -> Params:
     if rc != 0:
         raise SvoError("svo_params_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
     return p
+
+
+def load_klt_win_ini(path, detect_section, klt_win=4) -> int:
+    """TDetectParams::KLT_win from the DETECT section of the reference's INI file; `klt_win` when the section or key is absent"""
+    v = C.c_int32(int(klt_win))
+    rc = lib().svo_klt_win_load_ini(str(path).encode(), detect_section.encode() if detect_section else None, C.byref(v))
+    if rc != 0:
+        raise SvoError("svo_klt_win_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
+    return int(v.value)
 
 
 def _vp(a):
@@ -196,6 +205,13 @@ class Context:
 
     def fast_threshold(self):
         return self.L.svo_get_fast_threshold(self.h)
+
+    def set_klt_win(self, v):
+        """dmFASTER's KLT_win (1 .. 15, default 4): the response window is (2 v + 1)^2 pixels"""
+        self._ck(self.L.svo_set_klt_win(self.h, int(v)), "svo_set_klt_win")
+
+    def klt_win(self):
+        return self.L.svo_get_klt_win(self.h)
 
     def orb_threshold(self):
         return self.L.svo_get_orb_threshold(self.h)

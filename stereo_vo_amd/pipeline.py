@@ -79,6 +79,10 @@ class StreamBatch:
             raise hip.SvoError("%s: %s" % (what, self._err(rc)))
         return rc
 
+    def set_klt_win(self, v):
+        """dmFASTER's KLT_win on every context (svo_batch_set_klt_win)"""
+        self._ck(self.L.svo_batch_set_klt_win(self.h, int(v)), "svo_batch_set_klt_win")
+
     def step(self, ptrs, stride=None, pinned_host=False):
         """Enqueue one frame of every lane.  ptrs[lane] = (left, right) addresses of 8-bit grey images of the batch's
         size -- device memory, or page-locked host memory with pinned_host=True (the upload then runs on each context's
