@@ -109,6 +109,9 @@ const char* svo_fpstream_last_error(const svo_fpstream* f);
 int  svo_fpstream_contexts(const svo_fpstream* f);
 svo_ctx* svo_fpstream_context(svo_fpstream* f, int k);          /* borrowed */
 svo_ctx* svo_fpstream_last_owner(svo_fpstream* f);              /* the context that ran the frame pushed last (NULL before the first) */
+/* every context; also in mid-stream.  The first parameters that select smSAD or ifmSAD make the hand-over records carry the 8 x 8
+ * windows (svo_hip.h): the stream waits for its contexts, reallocates its records and, if a frame has been pushed, has the last owner
+ * export again.  (Before the first frame -- the usual place -- that is a reallocation and nothing else.) */
 int  svo_fpstream_set_params(svo_fpstream* f, const svo_params* p);
 int  svo_fpstream_set_camera(svo_fpstream* f, int lane, const svo_stereo_camera* cam);
 int  svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win);    /* every context */

@@ -181,9 +181,10 @@ int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
 /* smSAD (svo_params.match_method = SVO_SM_SAD, S3:185-419) and ifmSAD (ifm_method = SVO_IFM_SAD, S4:435-738) compare the 8 x 8 image
  * windows around two keypoints (rso::compute_SAD8).  Stage 2 is the only stage that reads images, so it gathers the window of every
  * final keypoint -- from the call on in which either selector is in force; a context that never selects them allocates and launches
- * nothing.  A frame has windows only if THIS library detected it under such parameters.  Features that came through
- * svo_put_features(_oct), svo_load_state or svo_import_frame have none: hand-over records and state files do not carry windows (the
- * reference's state format holds no images either, C:475-543), and neither does a frame detected while no SAD method was selected.
+ * nothing.  A frame has windows only if THIS library detected it under such parameters, in this context or in the one whose hand-over
+ * record brought it (svo_import_frame below: the records of a context that has selected a SAD method carry the windows).  Features that
+ * came through svo_put_features(_oct) or svo_load_state have none: state files do not carry windows (the reference's state format holds
+ * no images either, C:475-543), and neither does a frame detected while no SAD method was selected.
  * A call that runs a SAD stage on a frame without windows is refused with SVO_ERR_STATE and a text in svo_last_error BEFORE anything is
  * enqueued: the lists and the lane state stay as they were.  When it is the PREVIOUS frame that lacks them (a stream that switches
  * to ifmSAD) and the call would have shifted, the refusal is remembered: the lane's next shifting call forgets that frame, i.e. it is
@@ -293,7 +294,20 @@ int svo_projected_coords(svo_ctx* ctx, const svo_dmatch* pre_matches, int n_pre,
  * The record is one flat DEVICE buffer of svo_handover_bytes() bytes (all lanes): hand it over device-to-device, or with
  * ncclSend / ncclRecv between GPUs.  Both calls only enqueue on the context's stream; ordering between the two
  * contexts' streams is the caller's (an event, or the send/recv pair).  The run equals the sequential one list for
- * list and pose for pose: nothing is dropped, not even the warm start. */
+ * list and pose for pose: nothing is dropped, not even the warm start.
+ * Two kinds of record.  A context that has never selected smSAD or ifmSAD writes layout version 2: lists, row tables, inherited members.
+ * From the first svo_set_params that selects either -- and for the rest of its life -- a context CARRIES WINDOWS: its records are version
+ * 3, the same sections followed by the border flags and the 8 x 8 windows of the exported frame's keypoints (2 * max_kps * 65 bytes more
+ * per lane and octave), so that frame-parallel runs work under the SAD matchers, dmFASTER's only ones.  svo_handover_bytes() answers for
+ * the context's kind at the time of the call: query it AFTER svo_set_params, and again after a later svo_set_params that selects SAD for
+ * the first time (svo_fpstream_set_params does).  The buffer of a context that carries windows must be 16-byte aligned (SVO_ERR_ARG).
+ * Which records a context takes: one that carries no windows takes version 2 only; one that does takes version 3 and version 2 (then
+ * `bytes` may be the smaller size), and also a version 3 record whose frame had no windows gathered.  A frame that arrives without
+ * windows is enough for a descriptor tracker (smSAD + ifmDescBF / ifmDescWin).  Under ifmSAD it cannot be tracked from: the lane then
+ * starts afresh at the importer's frame (voecFirstIteration; the match-ID counter runs on) -- where the sequential path's refusal rule
+ * above arrives one frame later -- and THE PARAMETERS IN FORCE AT THE IMPORT decide that, not those of the svo_process call after it.
+ * Anything else -- a version 3 record handed to a context that carries no windows, other list capacities, lanes or octaves, a buffer too
+ * short for its records -- is another layout: nothing is copied, status bit 4 is raised for the lane. */
 size_t svo_handover_bytes(const svo_ctx* ctx);
 int svo_export_frame(svo_ctx* ctx, void* dev_blob, size_t bytes);
 int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes);

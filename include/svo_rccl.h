@@ -48,7 +48,7 @@ int svo_group_allgather_inplace(svo_group* g, int rank, void* dev_table, size_t 
 int svo_group_comm_count(const svo_group* g, int rank);
 int svo_group_comm_device(const svo_group* g, int rank);
 
-/* (2) hand-over record of svo_export_frame / svo_import_frame between two ranks; bytes = svo_handover_bytes(ctx) */
+/* (2) hand-over record of svo_export_frame / svo_import_frame between two ranks; bytes = svo_handover_bytes(ctx), queried after svo_set_params (svo_hip.h) */
 int svo_group_send_frame(svo_group* g, int rank, int to_rank, const void* dev_blob, size_t bytes, void* stream);
 int svo_group_recv_frame(svo_group* g, int rank, int from_rank, void* dev_blob, size_t bytes, void* stream);
 

@@ -116,7 +116,7 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask d
         LaneState& s = c.lane[t];
         if (do_shift) {
             if (!repeat && s.m_error != SVO_VOEC_BAD_TRACKING && s.m_error != SVO_VOEC_BAD_COND_NUMBER) {
-                if (s.has_cur) { s.prev_slot = 1 - s.prev_slot; s.has_prev = 1; }     // m_prev_imgpair = m_current_imgpair (P:86-89)
+                if (s.has_cur) { s.prev_slot = 1 - s.prev_slot; s.has_prev = 1; s.prev_no_win = 0; }     // m_prev_imgpair = m_current_imgpair (P:86-89)
             }
             s.m_error = SVO_VOEC_NONE;                                                 // P:95
             s.has_cur = 1;                                                             // P:100

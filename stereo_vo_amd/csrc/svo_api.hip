@@ -23,13 +23,16 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD,
        // the instantiations that only a 16384-entry context launches, under names of their own (a context with max_kps <= 8192 never counts a call here)
        KT_SELECT_8192, KT_NMS_16, KT_HAM_LR_WIDE, KT_HAM_TRK_WIDE, KT_TRK_FILTER_64,
+       // svo_export_frame / svo_import_frame: the kernels of a context that carries no SAD windows, then those of one that does
+       KT_EXPORT, KT_IMPORT, KT_EXPORT_WIN, KT_IMPORT_WIN,
        // dmFASTER (only a context that selects it counts a call here)
        KT_FASTER, KT_FASTER_NMS, KT_COUNT };
 static_assert(KT_COUNT <= 32, "kt_mask is one 32-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
-    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64", "faster", "faster_nms" };
+    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
+    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -77,7 +80,8 @@ struct svo_ctx {
     int klt_win;                                       // TDetectParams::KLT_win (S2:47): the window of dmFASTER's response, (2 klt_win + 1)^2 pixels
     hipStream_t stream, stream0; bool own_stream;      // stream0: the stream the context was created with / owns
     DevCtx dc;
-    bool geom_ready; int geom_w, geom_h, geom_nfe, geom_nlevels, geom_method, geom_noct;
+    bool geom_ready, geom_once;                        // geom_once: DevCtx has held a frame's geometry (svo_set_params clears geom_ready only; the lists of the last frame keep theirs)
+    int geom_w, geom_h, geom_nfe, geom_nlevels, geom_method, geom_noct;
     int raw_cap_alloc;
     uint8_t* d_img0; int img0_pitch_internal;
     // host-fed frames (process_new_image_pair.cpp:100-120 hands over host images): a ring of two device level-0 buffers
@@ -121,6 +125,7 @@ struct svo_ctx {
 };
 
 static void drop_graphs(svo_ctx* ctx);
+static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
 static void sampler_table_release(int device, int nmax);
 static void note_stream(svo_ctx* ctx)
@@ -357,7 +362,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->fast_th = 20; ctx->orb_th = 60;                  // common.cpp:35-36
     ctx->klt_win = 4; ctx->d_cand64 = nullptr;            // stage2_detect.cpp:47
     ctx->sampler_nmax = 0;
-    ctx->geom_ready = false;
+    ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->imported_pending = false; ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr;
@@ -452,7 +457,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     HIPCHECK(dev_alloc(ctx, &d.results, (size_t)L));
     HIPCHECK(dev_alloc(ctx, &d.status, (size_t)L));
     HIPCHECK(dev_alloc(ctx, &d.det_status, (size_t)L)); d.det_ahead = 0;
-    d.sad_patch = nullptr; d.sad_flag = nullptr;
+    d.sad_patch = nullptr; d.sad_flag = nullptr; d.carry_win = 0;
     d.bf_dist = nullptr;
     { const char* dm = getenv("SVO_DEBUG_MODE"); d.debug_mode = dm ? atoi(dm) : 0; }
     if (svo_ab_form_requested(d.debug_mode) && !svo_ab_kernels_built()) {
@@ -532,6 +537,9 @@ extern "C" int svo_set_params(svo_ctx* ctx, const svo_params* p)
     if (!ctx || !p) return SVO_ERR_ARG;
     { const int rc = params_fit(ctx, *p); if (rc) return rc; }
     ctx->params = *p;
+    // a context that has once selected a SAD method hands its frames over with their 8 x 8 windows (k_handover.hip, version 3), for good:
+    // svo_handover_bytes grows here and never shrinks again
+    if (p->match_method == SVO_SM_SAD || p->ifm_method == SVO_IFM_SAD) ctx->dc.carry_win = 1;
     ctx->fast_th = p->initial_FAST_threshold;            // resetFASTThreshold (H:532, 661)
     ctx->orb_th = (int)p->orb_max_distance;              // resetORBThreshold (H:539, 662)
     ctx->geom_ready = false;
@@ -788,7 +796,7 @@ static int ensure_geometry(svo_ctx* ctx, int w, int h)
     }
     HIPCHECK(configure_nms_rowsort(d));
     if (faster) HIPCHECK(configure_faster_nms(d));
-    ctx->geom_ready = true; ctx->geom_w = w; ctx->geom_h = h; ctx->geom_nfe = nfe_key; ctx->geom_nlevels = nlev;
+    ctx->geom_ready = true; ctx->geom_once = true; ctx->geom_w = w; ctx->geom_h = h; ctx->geom_nfe = nfe_key; ctx->geom_nlevels = nlev;
     ctx->geom_method = p.detect_method; ctx->geom_noct = noct;
     return SVO_OK;
 }
@@ -1085,11 +1093,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     // smSAD / ifmSAD: the window buffer exists from the first call made while either is selected (a context that never selects
     // them allocates and launches nothing), and a SAD stage on a frame whose windows were never gathered is refused here
     const bool sad_m = p.match_method == SVO_SM_SAD, sad_t = p.ifm_method == SVO_IFM_SAD, sad_any = sad_m || sad_t;
-    if (sad_any && !d.sad_patch) {
-        const size_t nk = (size_t)d.n_lanes * d.oct_cap * 4 * d.max_kps;
-        HIPCHECK(dev_alloc(ctx, &d.sad_flag, nk));
-        HIPCHECK(dev_alloc(ctx, &d.sad_patch, nk * 64));
-    }
+    if (sad_any) { const int rc_sad = ensure_sad_buffers(ctx); if (rc_sad) return rc_sad; }
     const bool runs_post = (flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST));
     LaneMask drop_prev; memset(&drop_prev, 0, sizeof(drop_prev)); bool any_drop = false;
     {
@@ -1653,13 +1657,29 @@ extern "C" size_t svo_handover_bytes(const svo_ctx* ctx)
 {
     return ctx ? handover_record_bytes(ctx->dc) * (size_t)ctx->dc.n_lanes * (size_t)ctx->dc.oct_cap : 0;
 }
+// the window buffers of the SAD matchers, from the first call that may need them (never while a stream captures: hipMalloc is refused there)
+static int ensure_sad_buffers(svo_ctx* ctx)
+{
+    DevCtx& d = ctx->dc;
+    if (d.sad_patch) return SVO_OK;
+    const size_t nk = (size_t)d.n_lanes * d.oct_cap * 4 * d.max_kps;
+    HIPCHECK(dev_alloc(ctx, &d.sad_flag, nk));
+    HIPCHECK(dev_alloc(ctx, &d.sad_patch, nk * 64));
+    return SVO_OK;
+}
 extern "C" int svo_export_frame(svo_ctx* ctx, void* dev_blob, size_t bytes)
 {
     if (ctx) use_device(ctx);
     if (!ctx || !dev_blob || bytes < svo_handover_bytes(ctx)) return SVO_ERR_ARG;
-    if (!ctx->geom_ready) return SVO_ERR_STATE;
+    if (ctx->dc.carry_win && ((uintptr_t)dev_blob & 15)) { ctx->last_error = "a hand-over record with windows is copied in 16-byte pieces: the buffer must be 16-byte aligned"; return SVO_ERR_ARG; }
+    if (!ctx->geom_once) return SVO_ERR_STATE;            // (new parameters since the last frame do not unmake its lists: svo_fpstream_set_params exports again in mid-stream)
     note_stream(ctx);
-    launch_export_frame(ctx->dc, (uint8_t*)dev_blob, ctx->stream);
+    LaneMask win_cur, win_prev; memset(&win_cur, 0, sizeof(win_cur)); memset(&win_prev, 0, sizeof(win_prev));
+    for (int l = 0; l < ctx->cfg.n_lanes; l++) {
+        if (ctx->sad_cur[l]) win_cur.w[l >> 6] |= 1ull << (l & 63);
+        if (ctx->sad_prev[l] && !ctx->sad_drop[l]) win_prev.w[l >> 6] |= 1ull << (l & 63);
+    }
+    { Span s(ctx, ctx->dc.carry_win ? KT_EXPORT_WIN : KT_EXPORT); launch_export_frame(ctx->dc, (uint8_t*)dev_blob, win_cur, win_prev, ctx->stream); }
     mark_stream(ctx);
     HIPCHECK(hipGetLastError());
     return SVO_OK;
@@ -1667,12 +1687,19 @@ extern "C" int svo_export_frame(svo_ctx* ctx, void* dev_blob, size_t bytes)
 extern "C" int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || !dev_blob || bytes < svo_handover_bytes(ctx)) return SVO_ERR_ARG;
+    // (a context that carries windows also takes the shorter records of one that does not: the kernel is told the buffer's size)
+    if (!ctx || !dev_blob || bytes < handover_record_bytes(ctx->dc, false) * (size_t)ctx->dc.n_lanes * (size_t)ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (!ctx->dc.carry_win && bytes < svo_handover_bytes(ctx)) return SVO_ERR_ARG;
+    if (ctx->dc.carry_win && ((uintptr_t)dev_blob & 15)) { ctx->last_error = "a hand-over record with windows is copied in 16-byte pieces: the buffer must be 16-byte aligned"; return SVO_ERR_ARG; }
     if (!ctx->geom_ready) return SVO_ERR_STATE;
+    if (ctx->dc.carry_win) { const int rc = ensure_sad_buffers(ctx); if (rc) return rc; }
     note_stream(ctx);
-    launch_import_frame(ctx->dc, (const uint8_t*)dev_blob, ctx->stream);
+    const int need_windows = ctx->params.ifm_method == SVO_IFM_SAD ? 1 : 0;
+    { Span s(ctx, ctx->dc.carry_win ? KT_IMPORT_WIN : KT_IMPORT); launch_import_frame(ctx->dc, (const uint8_t*)dev_blob, bytes, need_windows, ctx->stream); }
     ctx->imported_pending = true;
-    for (int l = 0; l < ctx->cfg.n_lanes; l++) ctx->sad_prev[l] = 0;       // the record carries no windows (svo_hip.h)
+    // a record without windows leaves none behind; one with them brings them, and where it does not (an older kind of record, a frame
+    // whose windows were never gathered) the device has already made the lane start afresh if the tracker in force is ifmSAD
+    for (int l = 0; l < ctx->cfg.n_lanes; l++) { ctx->sad_prev[l] = ctx->dc.carry_win ? 1 : 0; if (ctx->dc.carry_win) ctx->sad_drop[l] = 0; }
     mark_stream(ctx);
     HIPCHECK(hipGetLastError());
     return SVO_OK;

@@ -353,6 +353,23 @@ extern "C" int svo_fpstream_set_params(svo_fpstream* f, const svo_params* p)
 {
     if (!f || !p) return SVO_ERR_ARG;
     for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_params(c, p));
+    // a stream that now selects smSAD or ifmSAD hands its frames over with their windows: larger records (svo_hip.h).  Before the first
+    // frame that is a reallocation; in mid-stream the last owner also exports again, so that the next push finds a record of the new kind.
+    const size_t nbytes = svo_handover_bytes(f->ctx[0]);
+    if (nbytes != f->nbytes) {
+        BHIP(f, hipSetDevice(f->cfg.device));
+        for (svo_ctx* c : f->ctx) BSVO(f, c, svo_wait(c));
+        for (uint8_t*& b : f->blob) {
+            if (b) { BHIP(f, hipFree(b)); b = nullptr; }
+            BHIP(f, hipMalloc((void**)&b, nbytes)); BHIP(f, hipMemset(b, 0, nbytes));
+        }
+        f->nbytes = nbytes;
+        if (f->t > 0) {
+            const int g = (int)((f->t - 1) % f->G);
+            BSVO(f, f->ctx[(size_t)g], svo_export_frame(f->ctx[(size_t)g], f->blob[(size_t)g], f->nbytes));
+            BHIP(f, hipEventRecord(f->exported[(size_t)g], f->st[(size_t)g]));
+        }
+    }
     return SVO_OK;
 }
 

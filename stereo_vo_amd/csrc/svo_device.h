@@ -87,7 +87,7 @@ struct LaneState {
     int last_match_id;    // m_last_match_ID (H:741)
     int last_kf_max_id;   // m_last_kf_max_id (H:738; uninitialised in the reference, 0 here)
     int num_tracked_last_kf;   // m_num_tracked_pairs_from_last_kf (S4:743-751)
-    int pad;
+    int prev_no_win;      // the previous frame came in through a hand-over record without the SAD matchers' windows (k_handover.hip); cleared by the next shift
 };
 
 // Octaves: in the FAST+ORB mode (stage2_detect.cpp:502-515) the reference works on nOctaves x1/2 images per eye and
@@ -203,7 +203,7 @@ struct DevCtx {
     // (TlScope below): (time in, time out) on the device-wide 100 MHz wall clock.
     struct TlRec* tl;
     int tl_step;              // frame counter of the context (host side: advanced by every call that runs the detector)
-    int tl_pad;
+    int carry_win;            // the context's hand-over records carry the SAD windows (version 3): from the first svo_set_params that selects smSAD or ifmSAD, for good
 };
 
 struct TlRec { unsigned long long t0, t1; };

@@ -39,11 +39,12 @@ struct PrepArgs {
 };
 void launch_prepare(const PrepArgs& a, int n_img, hipStream_t st);
 // frame hand-over between contexts (k_handover.hip)
-size_t handover_record_bytes(const DevCtx& c);
-void launch_export_frame(const DevCtx& c, uint8_t* blob, hipStream_t st);
-void launch_import_frame(const DevCtx& c, const uint8_t* blob, hipStream_t st);
-void launch_pack_values(const DevCtx& c, int lane, int which, int octave, uint8_t* dst, hipStream_t st);
 struct LaneMask { unsigned long long w[(SVO_MAX_LANES + 63) / 64]; };      // one bit per lane
+size_t handover_record_bytes(const DevCtx& c);                  // of the context's kind (DevCtx.carry_win)
+size_t handover_record_bytes(const DevCtx& c, bool windows);    // version 2 (false) / version 3 with the SAD windows (true)
+void launch_export_frame(const DevCtx& c, uint8_t* blob, const LaneMask& win_cur, const LaneMask& win_prev, hipStream_t st);
+void launch_import_frame(const DevCtx& c, const uint8_t* blob, size_t blob_bytes, int need_windows, hipStream_t st);
+void launch_pack_values(const DevCtx& c, int lane, int which, int octave, uint8_t* dst, hipStream_t st);
 void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned flags, const LaneMask& drop_prev, hipStream_t st);
 void launch_resize(const DevCtx& c, int level, hipStream_t st);
 void launch_fast(const DevCtx& c, hipStream_t st);

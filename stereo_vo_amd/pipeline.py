@@ -194,6 +194,11 @@ class FrameParallelStream:
             raise hip.SvoError("%s: %s [%s]" % (what, self.L.svo_strerror(rc).decode(), le.decode() if le else ""))
         return rc
 
+    def set_params(self, params):
+        """New parameters for every context, also in mid-stream.  Selecting smSAD or ifmSAD for the first time makes the
+        hand-over records carry the 8 x 8 windows: the stream re-reads svo_handover_bytes and reallocates its records."""
+        self._ck(self.L.svo_fpstream_set_params(self.h, C.byref(params)), "svo_fpstream_set_params")
+
     def push(self, ptrs, stride=None):
         """Enqueue the next frame (ptrs[lane] = (left, right) device addresses).  Returns the context that owns it."""
         fr = _frames(ptrs, self.W, self.H, self.W if stride is None else stride)
