@@ -1730,29 +1730,65 @@ __global__ void __launch_bounds__(256) k_half(DevCtx c, int level)
     *(uint32_t*)(dst + (long long)y * d.pitch + x4) = out;
 }
 
-// FAST+ORB: the reference's grid NMS (m_non_max_sup, S2:296-370, cap kps_to_detect[octave]) applied to ALL FAST corners
-// of one (image, octave) in (score desc, raster position asc) order -- exactly the descending order of the unique
-// candidate keys.  The corners are consumed in chunks of the NS_MAX largest remaining keys (radix select, bitonic sort,
-// block-parallel NMS).  Between chunks only the ACCEPTED cells survive (a compact list re-seeds the hash with the
-// marker FO_ACCEPTED, which every later candidate sees as "accepted, lower rank"); a cell whose representative was
-// rejected needs no memory: whatever rejected it still rejects every later candidate of that cell.
-// Survivors go to the level-segmented arrays that k_describe reads (describing only survivors gives the same
-// descriptors as the reference's describe-then-suppress order).
+// The reference's grid NMS (m_non_max_sup, S2:296-370, cap kps_to_detect[octave]) applied to ALL corners of one (image, octave) in
+// the descending order of their unique candidate keys, for both detectors that work on the x1/2 octaves:
+//   FAST+ORB  32-bit keys score << 24 | (0xFFFFFF - raster position) from k_fast: (score desc, raster position asc).  Survivors go
+//             to the level-segmented arrays that k_describe reads (describing only survivors gives the same descriptors as the
+//             reference's describe-then-suppress order).
+//   dmFASTER  64-bit keys ord32(response) << 32 | (0xFFFFFFFF - raster position) from k_faster.  Survivors go to the level-segmented
+//             raw keypoint array as the records m_convert_featureList_to_keypointList makes of them (S2:31-42: pt and response into
+//             a default cv::KeyPoint -- size 0, angle -1, octave 0, class_id -1) with all-zero descriptor rows.
+// k_nms_rowsort in its FAST+ORB mode then row-sorts either into the final lists.  Without NMS every corner is kept (S2:613-614), as
+// many as the octave's slots hold.  The corners are consumed in chunks of the NS_MAX largest remaining keys (radix select, one byte
+// pass per key byte; bitonic sort; block-parallel NMS as in grid_nms_block, svo_device.h).  Between chunks only the ACCEPTED cells
+// survive (a compact list re-seeds the hash with the marker FO_ACCEPTED, which every later candidate sees as "accepted, lower rank"); a
+// cell whose representative was rejected needs no memory: whatever rejected it still rejects every later candidate of that cell.
+// Hash bound, NOT guarded: a chunk's hash of 4 * NS_MAX = 8192 slots receives the nacc <= cap - 1 accepted cells plus up to NS_MAX = 2048
+// new cells of the chunk, and neither the find-or-insert nor nms_lookup has a probe limit: once nacc + (new cells) reaches 8192 no slot
+// is empty and the look-up of an absent neighbour cell never ends.  cap = min(kps_to_detect, quota, max_kps) <= 6144 rules that out; a
+// context with max_kps > 6144 and such a cap can spin on an image that really yields more than 6144 survivors in one octave.
 #define FO_ACCEPTED 0xFFFFFFFEu
-__global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
+struct FastOrbKeys {
+    typedef uint32_t Key;
+    static __device__ __forceinline__ uint32_t pos_of(Key k) { return 0xFFFFFFu - (k & 0xFFFFFFu); }
+    static __device__ __forceinline__ void emit(const DevCtx& c, long long o, Key k, uint32_t gw)
+    {
+        const uint32_t pos = pos_of(k);
+        c.lvl_pos[o] = (pos % gw) | ((pos / gw) << 16);                    // x | y << 16
+        c.lvl_resp[o] = (float)(k >> 24);                                  // cv::FAST response = score
+    }
+};
+struct FasterKeys {
+    typedef unsigned long long Key;
+    static __device__ __forceinline__ uint32_t pos_of(Key k) { return 0xFFFFFFFFu - (uint32_t)k; }
+    static __device__ __forceinline__ void emit(const DevCtx& c, long long o, Key k, uint32_t gw)
+    {
+        const uint32_t pos = pos_of(k);
+        svo_keypoint kp;
+        kp.x = (float)(pos % gw); kp.y = (float)(pos / gw); kp.size = 0.0f; kp.angle = -1.0f;
+        kp.response = inv_ord32((uint32_t)(k >> 32)); kp.octave = 0; kp.class_id = -1;
+        c.raw_kps[o] = kp;
+        uint4* dd = (uint4*)(c.raw_desc + o * 32);
+        dd[0] = make_uint4(0, 0, 0, 0); dd[1] = make_uint4(0, 0, 0, 0);
+    }
+};
+
+template <class T>
+__device__ __forceinline__ void chunked_grid_nms(const DevCtx& c, unsigned char* smem, const typename T::Key* cand, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
 {
-    SVO_TL_SCOPE(c, TL_NMS, 2);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    typedef typename T::Key Key;
+    constexpr int PW = sizeof(Key) > 4 ? 2 : 0;                            // 64-bit keys: two LDS words of their own for the select's prefix
     const int NS_HASH = 4 * NS_MAX;
     unsigned long long* keys = (unsigned long long*)smem;                  // NS_MAX
-    uint32_t* hkey = (uint32_t*)(keys + NS_MAX);                           // 4*NS_MAX
+    uint32_t* hkey = (uint32_t*)(keys + NS_MAX + PW);                      // 4*NS_MAX
     uint32_t* hval = hkey + NS_HASH;                                       // 4*NS_MAX
     uint32_t* cellxy = hval + NS_HASH;                                     // NS_MAX
     uint32_t* acc_cells = cellxy + NS_MAX;                                 // ACC_MAX: cell keys of everything accepted so far
     unsigned* hist = acc_cells + ACC_MAX;                                  // 256
     int* scan = (int*)(hist + 256);                                        // 32
     int* flag = scan + 32;
-    unsigned* sh = (unsigned*)(flag + 1);                                  // s_prefix, s_need, s_sel
+    unsigned* sh = (unsigned*)(flag + 1);                                  // s_need, s_sel, the prefix of 32-bit keys
+    Key* s_prefix = PW ? (Key*)(keys + NS_MAX) : (Key*)(sh + 2);
     unsigned char* state = (unsigned char*)(sh + 4);                       // NS_MAX
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     const LevelGeom& g = c.lv[level];
@@ -1761,7 +1797,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance
     // quota = slots reserved for this octave; the reference's cap kps_to_detect belongs to its NMS (S2:342), without NMS every corner stays
     const int cap = do_nms ? min(min(c.kps_to_detect[level], g.quota), ACC_MAX) : min(g.quota, ACC_MAX);
     if (!do_nms && nc > (unsigned)cap && tid == 0) raise_detect_status(c, img >> 1, SVO_ST_KPS_OVERFLOW);
-    const uint32_t* ck = c.cand_keys + (long long)img * c.cand_total + g.cand_off;
+    const Key* ck = cand + (long long)img * c.cand_total + g.cand_off;
     const unsigned cell = (unsigned)((double)min_distance / 2.0);
     const float inv = 1.0f / (float)cell;
     const unsigned glx = (unsigned)(1 + (float)g.w * inv), gly = (unsigned)(1 + (float)g.h * inv);
@@ -1774,42 +1810,29 @@ __global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance
         }
     };
     int nacc = 0;
-    uint32_t upper = 0xFFFFFFFFu;             // keys >= upper are already consumed
+    Key upper = ~(Key)0;                      // keys >= upper are already consumed (no key is all ones: score 255 at pixel 0 / a NaN response)
     unsigned remaining = nc;
     while (remaining > 0 && nacc < cap) {
         const unsigned K = min(remaining, (unsigned)NS_MAX);
         // ---- the K largest keys below `upper` (radix select on the unique keys) ----
-        unsigned prefix = 0, mask = 0, need = K;
-        for (int shift = 24; shift >= 0; shift -= 8) {
+        Key prefix = 0, mask = 0; unsigned need = K;
+        for (int shift = 8 * (int)sizeof(Key) - 8; shift >= 0; shift -= 8) {
             for (int i = tid; i < 256; i += blockDim.x) hist[i] = 0;
             __syncthreads();
-            for (unsigned i = tid; i < nc; i += blockDim.x) { const uint32_t k = ck[i]; if (k < upper && (k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u); }
+            for (unsigned i = tid; i < nc; i += blockDim.x) { const Key k = ck[i]; if (k < upper && (k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u); }
             __syncthreads();
-            const int mine = tid < 256 ? (int)hist[255 - tid] : 0;
-            int tot;
-            const int before = block_exclusive_scan(mine, scan, &tot);
-            if (tid < 256 && (unsigned)before < need && need <= (unsigned)(before + mine)) { sh[0] = prefix | ((unsigned)(255 - tid) << shift); sh[1] = need - (unsigned)before; }
-            __syncthreads();
-            prefix = sh[0]; need = sh[1]; mask |= 255u << shift;
-            __syncthreads();
+            radix_pick_bin(hist, shift, scan, s_prefix, &sh[0], prefix, need, mask);
         }
-        const uint32_t cutoff = prefix;
-        if (tid == 0) sh[2] = 0;
+        const Key cutoff = prefix;
+        if (tid == 0) sh[1] = 0;
         for (int i = tid; i < NS_MAX; i += blockDim.x) keys[i] = 0;
         __syncthreads();
         for (unsigned base = 0; base < nc; base += blockDim.x) {
             const unsigned i = base + tid;
-            uint32_t k = 0;
+            Key k = 0;
             const bool take = i < nc && (k = ck[i]) >= cutoff && k < upper;
-            const unsigned long long m = __ballot(take);
-            if (m) {
-                unsigned b0 = 0;
-                const int leader = __ffsll((long long)m) - 1;
-                if ((tid & 63) == leader) b0 = atomicAdd(&sh[2], (unsigned)__popcll(m));
-                b0 = __shfl(b0, leader, 64);
-                const unsigned slot = b0 + __popcll(m & ((1ull << (tid & 63)) - 1ull));
-                if (take && slot < (unsigned)NS_MAX) keys[slot] = (unsigned long long)k;
-            }
+            const unsigned slot = wave_append_slot(take, &sh[1]);
+            if (take && slot < (unsigned)NS_MAX) keys[slot] = (unsigned long long)k;
         }
         __syncthreads();
         int P = 64; while (P < (int)K) P <<= 1;
@@ -1821,7 +1844,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance
             for (int i = tid; i < nacc; i += blockDim.x) hval[slot_of_key(acc_cells[i])] = FO_ACCEPTED;
             __syncthreads();
             for (int i = tid; i < (int)K; i += blockDim.x) {
-                const uint32_t pos = 0xFFFFFFu - ((uint32_t)keys[i] & 0xFFFFFFu);
+                const uint32_t pos = T::pos_of((Key)keys[i]);
                 const float fx = (float)(pos % (uint32_t)g.w), fy = (float)(pos / (uint32_t)g.w);
                 const size_t ux = (size_t)(fx * inv), uy = (size_t)(fy * inv);
                 const uint32_t cxy = (ux < glx && uy < gly) ? (((uint32_t)ux << 16) | (uint32_t)uy) : 0xFFFFFFFFu;
@@ -1879,11 +1902,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance
             const int off = block_exclusive_scan(keep, scan, &tot);
             const int o_idx = nacc + chunk_acc + off;
             if (keep && o_idx < cap) {
-                const uint32_t k = (uint32_t)keys[i];
-                const long long o = (long long)img * c.raw_cap + g.slot_off + o_idx;
-                const uint32_t pos = 0xFFFFFFu - (k & 0xFFFFFFu);
-                c.lvl_pos[o] = (pos % (uint32_t)g.w) | ((pos / (uint32_t)g.w) << 16);                      // x | y << 16
-                c.lvl_resp[o] = (float)(k >> 24);                          // cv::FAST response = score
+                T::emit(c, (long long)img * c.raw_cap + g.slot_off + o_idx, (Key)keys[i], (uint32_t)g.w);
                 if (do_nms) { const uint32_t cxy = cellxy[i]; acc_cells[o_idx] = (cxy >> 16) * gly + (cxy & 0xFFFFu); }
             }
             chunk_acc += tot;
@@ -1895,6 +1914,20 @@ __global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance
         __syncthreads();
     }
     if (tid == 0) c.lvl_n[img * SVO_MAX_LEVELS + level] = nacc;
+}
+
+__global__ void __launch_bounds__(1024) k_fastorb_nms(DevCtx c, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 2);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    chunked_grid_nms<FastOrbKeys>(c, smem, c.cand_keys, min_distance, do_nms, NS_MAX, ACC_MAX);
+}
+
+__global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 4);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    chunked_grid_nms<FasterKeys>(c, smem, cand64, min_distance, do_nms, NS_MAX, ACC_MAX);
 }
 
 // FAST+ORB with nmsmAdaptive (stage2_detect.cpp:599-606 applies m_adaptive_non_max_sup, S2:141-215, to whatever the
@@ -1990,13 +2023,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_anms(DevCtx c, uint32_t* by_sc
         __syncthreads();
         for (unsigned i = tid; i < nc; i += 1024) { const uint32_t r = rad[i]; if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u); }
         __syncthreads();
-        const int mine = tid < 256 ? (int)hist[255 - tid] : 0;
-        int tot;
-        const int before = block_exclusive_scan(mine, scan, &tot);
-        if (tid < 256 && (unsigned)before < need && need <= (unsigned)(before + mine)) { sh[1] = prefix | ((unsigned)(255 - tid) << shift); sh[2] = need - (unsigned)before; }
-        __syncthreads();
-        prefix = sh[1]; need = sh[2]; mask |= 255u << shift;
-        __syncthreads();
+        radix_pick_bin(hist, shift, scan, &sh[1], &sh[2], prefix, need, mask);
     }
     const uint32_t rcut = prefix;          // radii > rcut are all in; `need` of the corners with radius == rcut, smallest positions first
     // among the ties, the `need` smallest positions = the `need` LARGEST inverted positions (key & 0xFFFFFF): radix select again
@@ -2006,13 +2033,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_anms(DevCtx c, uint32_t* by_sc
         __syncthreads();
         for (unsigned i = tid; i < nc; i += 1024) if (rad[i] == rcut) { const uint32_t ip = bs[i] & 0xFFFFFFu; if ((ip & m2) == p2) atomicAdd(&hist[(ip >> shift) & 255u], 1u); }
         __syncthreads();
-        const int mine = tid < 256 ? (int)hist[255 - tid] : 0;
-        int tot;
-        const int before = block_exclusive_scan(mine, scan, &tot);
-        if (tid < 256 && (unsigned)before < need2 && need2 <= (unsigned)(before + mine)) { sh[3] = p2 | ((unsigned)(255 - tid) << shift); sh[4] = need2 - (unsigned)before; }
-        __syncthreads();
-        p2 = sh[3]; need2 = sh[4]; m2 |= 255u << shift;
-        __syncthreads();
+        radix_pick_bin(hist, shift, scan, &sh[3], &sh[4], p2, need2, m2);
     }
     const uint32_t ipcut = p2;             // ties with inverted position >= ipcut are in (positions are unique)
     for (int i = tid; i < KMAX; i += 1024) keys[i] = 0;
@@ -2150,14 +2171,8 @@ __global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* 
     for (int k = 0; k < FK_H / 4; k++) {
         const int ly = (tid >> 6) + 4 * k, y = y0 + ly;
         const bool is = x < gw - 3 && y < gh - 3 && faster_is_corner(tile + (ly + halo) * FK_LW + lx + halo, th);
-        const unsigned long long m = __ballot(is);
-        if (m) {
-            unsigned b0 = 0;
-            const int leader = __ffsll((long long)m) - 1;
-            if ((tid & 63) == leader) b0 = atomicAdd(&s_n, (unsigned)__popcll(m));
-            b0 = __shfl(b0, leader, 64);
-            if (is) list[b0 + __popcll(m & ((1ull << (tid & 63)) - 1ull))] = (unsigned short)(ly * FK_W + lx);
-        }
+        const unsigned slot = wave_append_slot(is, &s_n);
+        if (is) list[slot] = (unsigned short)(ly * FK_W + lx);
     }
     __syncthreads();
     const unsigned n = s_n;
@@ -2174,174 +2189,6 @@ __global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* 
         if (gbase + i < (unsigned)g.cand_cap) dst[gbase + i] = ((unsigned long long)ord32(resp) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(py * gw + px));
         else raise_detect_status(c, img >> 1, SVO_ST_CAND_OVERFLOW);
     }
-}
-
-// dmFASTER: the grid NMS of k_fastorb_nms over the 64-bit (response, raster position) keys -- the same chunked radix select (eight
-// byte passes instead of four), the same cell hash, the same cap min(kps_to_detect, quota, ACC_MAX).  Survivors go to the
-// level-segmented raw keypoint array as the records m_convert_featureList_to_keypointList makes of them (S2:31-42: pt and
-// response into a default cv::KeyPoint -- size 0, angle -1, octave 0, class_id -1) with all-zero descriptor rows; k_nms_rowsort
-// in its FAST+ORB mode then row-sorts them into the final lists.  Without NMS every corner is kept (S2:613-614), as many as the
-// octave's slots hold.
-__global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
-{
-    SVO_TL_SCOPE(c, TL_NMS, 4);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int NS_HASH = 4 * NS_MAX;
-    unsigned long long* keys = (unsigned long long*)smem;                  // NS_MAX
-    unsigned long long* sh64 = keys + NS_MAX;                              // 2: prefix of the radix select
-    uint32_t* hkey = (uint32_t*)(sh64 + 2);                                // 4*NS_MAX
-    uint32_t* hval = hkey + NS_HASH;                                       // 4*NS_MAX
-    uint32_t* cellxy = hval + NS_HASH;                                     // NS_MAX
-    uint32_t* acc_cells = cellxy + NS_MAX;                                 // ACC_MAX: cell keys of everything accepted so far
-    unsigned* hist = acc_cells + ACC_MAX;                                  // 256
-    int* scan = (int*)(hist + 256);                                        // 32
-    int* flag = scan + 32;
-    unsigned* sh = (unsigned*)(flag + 1);                                  // s_need, s_sel
-    unsigned char* state = (unsigned char*)(sh + 4);                       // NS_MAX
-    const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
-    const LevelGeom& g = c.lv[level];
-    unsigned nc = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
-    if (nc > (unsigned)g.cand_cap) nc = g.cand_cap;
-    const int cap = do_nms ? min(min(c.kps_to_detect[level], g.quota), ACC_MAX) : min(g.quota, ACC_MAX);
-    if (!do_nms && nc > (unsigned)cap && tid == 0) raise_detect_status(c, img >> 1, SVO_ST_KPS_OVERFLOW);
-    const unsigned long long* ck = cand64 + (long long)img * c.cand_total + g.cand_off;
-    const unsigned cell = (unsigned)((double)min_distance / 2.0);
-    const float inv = 1.0f / (float)cell;
-    const unsigned glx = (unsigned)(1 + (float)g.w * inv), gly = (unsigned)(1 + (float)g.h * inv);
-    auto slot_of_key = [&](uint32_t key) {                                 // find-or-insert
-        uint32_t h = nms_hash_slot(key, NS_HASH);
-        for (;;) {
-            const uint32_t old = atomicCAS(&hkey[h], 0xFFFFFFFFu, key);
-            if (old == 0xFFFFFFFFu || old == key) return h;
-            h = (h + 1) & (uint32_t)(NS_HASH - 1);
-        }
-    };
-    int nacc = 0;
-    unsigned long long upper = ~0ull;         // keys >= upper are already consumed (no key is all ones: that response would be a NaN)
-    unsigned remaining = nc;
-    while (remaining > 0 && nacc < cap) {
-        const unsigned K = min(remaining, (unsigned)NS_MAX);
-        // ---- the K largest keys below `upper` (radix select on the unique keys) ----
-        unsigned long long prefix = 0, mask = 0; unsigned need = K;
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            for (int i = tid; i < 256; i += blockDim.x) hist[i] = 0;
-            __syncthreads();
-            for (unsigned i = tid; i < nc; i += blockDim.x) { const unsigned long long k = ck[i]; if (k < upper && (k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u); }
-            __syncthreads();
-            const int mine = tid < 256 ? (int)hist[255 - tid] : 0;
-            int tot;
-            const int before = block_exclusive_scan(mine, scan, &tot);
-            if (tid < 256 && (unsigned)before < need && need <= (unsigned)(before + mine)) { sh64[0] = prefix | ((unsigned long long)(255 - tid) << shift); sh[1] = need - (unsigned)before; }
-            __syncthreads();
-            prefix = sh64[0]; need = sh[1]; mask |= 255ull << shift;
-            __syncthreads();
-        }
-        const unsigned long long cutoff = prefix;
-        if (tid == 0) sh[2] = 0;
-        for (int i = tid; i < NS_MAX; i += blockDim.x) keys[i] = 0;
-        __syncthreads();
-        for (unsigned base = 0; base < nc; base += blockDim.x) {
-            const unsigned i = base + tid;
-            unsigned long long k = 0;
-            const bool take = i < nc && (k = ck[i]) >= cutoff && k < upper;
-            const unsigned long long m = __ballot(take);
-            if (m) {
-                unsigned b0 = 0;
-                const int leader = __ffsll((long long)m) - 1;
-                if ((tid & 63) == leader) b0 = atomicAdd(&sh[2], (unsigned)__popcll(m));
-                b0 = __shfl(b0, leader, 64);
-                const unsigned slot = b0 + __popcll(m & ((1ull << (tid & 63)) - 1ull));
-                if (take && slot < (unsigned)NS_MAX) keys[slot] = k;
-            }
-        }
-        __syncthreads();
-        int P = 64; while (P < (int)K) P <<= 1;
-        bitonic_sort_lds<true>(keys, P);                                   // rank order of this chunk
-        if (do_nms) {
-            // ---- re-seed the hash with the accepted cells, then the chunk's representatives ----
-            for (int i = tid; i < NS_HASH; i += blockDim.x) { hkey[i] = 0xFFFFFFFFu; hval[i] = 0xFFFFFFFFu; }
-            __syncthreads();
-            for (int i = tid; i < nacc; i += blockDim.x) hval[slot_of_key(acc_cells[i])] = FO_ACCEPTED;
-            __syncthreads();
-            for (int i = tid; i < (int)K; i += blockDim.x) {
-                const uint32_t pos = 0xFFFFFFFFu - (uint32_t)keys[i];
-                const float fx = (float)(pos % (uint32_t)g.w), fy = (float)(pos / (uint32_t)g.w);
-                const size_t ux = (size_t)(fx * inv), uy = (size_t)(fy * inv);
-                const uint32_t cxy = (ux < glx && uy < gly) ? (((uint32_t)ux << 16) | (uint32_t)uy) : 0xFFFFFFFFu;
-                cellxy[i] = cxy;
-                if (cxy != 0xFFFFFFFFu) {
-                    const uint32_t h = slot_of_key((cxy >> 16) * gly + (cxy & 0xFFFFu));
-                    if (hval[h] != FO_ACCEPTED) atomicMin(&hval[h], (uint32_t)i);      // markers are only written before this phase
-                }
-            }
-            __syncthreads();
-            for (int i = tid; i < (int)K; i += blockDim.x) {
-                const uint32_t cxy = cellxy[i];
-                unsigned char st = 0;
-                if (cxy != 0xFFFFFFFFu && nms_lookup(hkey, hval, NS_HASH, (cxy >> 16) * gly + (cxy & 0xFFFFu)) == (uint32_t)i) st = SVO_NMS_UNDECIDED;
-                state[i] = st;                                             // non-representatives and already-accepted cells: rejected
-            }
-            __syncthreads();
-            for (;;) {
-                if (tid == 0) *flag = 0;
-                __syncthreads();
-                bool pending = false;
-                for (int i = tid; i < (int)K; i += blockDim.x) {
-                    if (((volatile unsigned char*)state)[i] != SVO_NMS_UNDECIDED) continue;
-                    const uint32_t cxy = cellxy[i];
-                    const int sx = (int)(cxy >> 16), sy = (int)(cxy & 0xFFFFu);
-                    bool any_acc = false, any_und = false;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int cx = sx + (q == 0) - (q == 1), cy = sy + (q == 2) - (q == 3);
-                        if (cx < 0 || cy < 0 || cy >= (int)gly) continue;
-                        const uint32_t j = nms_lookup(hkey, hval, NS_HASH, (uint32_t)cx * gly + (uint32_t)cy);
-                        if (j == FO_ACCEPTED) any_acc = true;
-                        else if (j < (uint32_t)i) { const unsigned char sj = ((volatile unsigned char*)state)[j]; any_acc |= sj == 1; any_und |= sj == SVO_NMS_UNDECIDED; }
-                    }
-                    if (any_acc) ((volatile unsigned char*)state)[i] = 0;
-                    else if (!any_und) ((volatile unsigned char*)state)[i] = 1;
-                    else pending = true;
-                }
-                if (pending) *flag = 1;
-                __syncthreads();
-                const int again = *flag;
-                __syncthreads();
-                if (!again) break;
-            }
-        } else {
-            for (int i = tid; i < (int)K; i += blockDim.x) state[i] = 1;
-            __syncthreads();
-        }
-        // ---- emit the chunk's survivors in rank order, up to the cap, and remember their cells ----
-        int chunk_acc = 0;
-        for (int base = 0; base < (int)K && nacc + chunk_acc < cap; base += blockDim.x) {
-            const int i = base + tid;
-            const int keep = (i < (int)K && state[i] == 1) ? 1 : 0;
-            int tot;
-            const int off = block_exclusive_scan(keep, scan, &tot);
-            const int o_idx = nacc + chunk_acc + off;
-            if (keep && o_idx < cap) {
-                const unsigned long long k = keys[i];
-                const long long o = (long long)img * c.raw_cap + g.slot_off + o_idx;
-                const uint32_t pos = 0xFFFFFFFFu - (uint32_t)k;
-                svo_keypoint kp;
-                kp.x = (float)(pos % (uint32_t)g.w); kp.y = (float)(pos / (uint32_t)g.w); kp.size = 0.0f; kp.angle = -1.0f;
-                kp.response = inv_ord32((uint32_t)(k >> 32)); kp.octave = 0; kp.class_id = -1;
-                c.raw_kps[o] = kp;
-                uint4* dd = (uint4*)(c.raw_desc + o * 32);
-                dd[0] = make_uint4(0, 0, 0, 0); dd[1] = make_uint4(0, 0, 0, 0);
-                if (do_nms) { const uint32_t cxy = cellxy[i]; acc_cells[o_idx] = (cxy >> 16) * gly + (cxy & 0xFFFFu); }
-            }
-            chunk_acc += tot;
-            __syncthreads();
-        }
-        nacc = min(nacc + chunk_acc, cap);
-        upper = cutoff;
-        remaining -= K;
-        __syncthreads();
-    }
-    if (tid == 0) c.lvl_n[img * SVO_MAX_LEVELS + level] = nacc;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2413,7 +2260,7 @@ void launch_sad_patch(const DevCtx& c, hipStream_t st)
     hipLaunchKernelGGL(k_sad_patch, dim3((n + 31) / 32, c.n_lanes * c.oct_cap * 2), dim3(256), 0, st, c);
 }
 
-#define FO_PMAX 2048     // chunk size of k_fastorb_nms (LDS: 45 B per entry)
+#define FO_PMAX 2048     // chunk size of k_fastorb_nms / k_faster_nms (LDS: 45 B per entry)
 static int nms_pmax(const DevCtx& c)
 {
     // keys per block: ORB mode gathers every level of an image (n_slots), FAST+ORB mode one octave's quota
@@ -2422,7 +2269,8 @@ static int nms_pmax(const DevCtx& c)
     int p = 64; while (p < n) p <<= 1; return p;
 }
 static size_t nms_rowsort_smem(int pmax) { return pmax > 4096 ? (size_t)pmax * 3 + 16 + 4 * 40 : (size_t)pmax * (8 + 8 + 8 + 4 + 2 + 1) + 16 + 4 * 40; }
-static size_t fastorb_nms_smem(int pmax, int accmax) { return (size_t)pmax * (8 + 16 + 16 + 4 + 1) + (size_t)accmax * 4 + 4 * (256 + 32 + 8) + 16; }
+// LDS of chunked_grid_nms over keys of key_bytes: 64-bit keys add the two prefix words of their radix select
+static size_t chunked_nms_smem(int pmax, int accmax, size_t key_bytes) { return (size_t)pmax * (8 + 16 + 16 + 4 + 1) + (size_t)accmax * 4 + 4 * (256 + 32 + 8) + 16 + (key_bytes > 4 ? 16 : 0); }
 
 int nms_rowsort_items(const DevCtx& c) { const int pmax = nms_pmax(c); return pmax > 8192 ? 16 : (pmax > 4096 ? 8 : 4); }      // the instantiation launch_nms_rowsort picks
 
@@ -2434,7 +2282,7 @@ size_t nms_rowsort_scratch_bytes(const DevCtx& c)          // global scratch of 
 
 hipError_t configure_nms_rowsort(const DevCtx& c)
 {
-    hipError_t e = svo_raise_dyn_smem((const void*)k_fastorb_nms, fastorb_nms_smem(FO_PMAX, c.max_kps));
+    hipError_t e = svo_raise_dyn_smem((const void*)k_fastorb_nms, chunked_nms_smem(FO_PMAX, c.max_kps, 4));
     if (e != hipSuccess) return e;
     int kmax = 64; while (kmax < c.max_kps) kmax <<= 1;
     e = svo_raise_dyn_smem((const void*)k_fastorb_anms, (size_t)kmax * 8);
@@ -2458,9 +2306,12 @@ void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, 
     static int nt_knob = -1;
     if (nt_knob < 0) { const char* e = getenv("SVO_NMS_NT"); nt_knob = e ? atoi(e) : 0; }
     const int nt = (pmax <= 2048 && nt_knob == 512) ? 512 : 1024;
-    if (pmax > 8192) hipLaunchKernelGGL(k_nms_rowsort<16>, dim3(c.n_img, c.n_oct), dim3(1024), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, c.big_scratch);
-    else if (pmax > 4096) hipLaunchKernelGGL(k_nms_rowsort<8>, dim3(c.n_img, c.n_oct), dim3(1024), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, c.big_scratch);
-    else hipLaunchKernelGGL(k_nms_rowsort<4>, dim3(c.n_img, c.n_oct), dim3(nt), nms_rowsort_smem(pmax), st, c, c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, min_distance, pmax, (pre && !c.fast_orb) ? 1 : 0, (uint8_t*)nullptr);
+    const dim3 grid(c.n_img, c.n_oct);
+    const size_t lds = nms_rowsort_smem(pmax);
+    const int mode = c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, pre_pass = (pre && !c.fast_orb) ? 1 : 0;
+    if (pmax > 8192) hipLaunchKernelGGL(k_nms_rowsort<16>, grid, dim3(1024), lds, st, c, mode, min_distance, pmax, pre_pass, c.big_scratch);
+    else if (pmax > 4096) hipLaunchKernelGGL(k_nms_rowsort<8>, grid, dim3(1024), lds, st, c, mode, min_distance, pmax, pre_pass, c.big_scratch);
+    else hipLaunchKernelGGL(k_nms_rowsort<4>, grid, dim3(nt), lds, st, c, mode, min_distance, pmax, pre_pass, (uint8_t*)nullptr);
 }
 
 void launch_half(const DevCtx& c, int level, hipStream_t st)
@@ -2471,7 +2322,7 @@ void launch_half(const DevCtx& c, int level, hipStream_t st)
 
 void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_fastorb_nms, dim3(c.n_levels, c.n_img), dim3(1024), fastorb_nms_smem(FO_PMAX, c.max_kps), st, c, min_distance, do_nms, FO_PMAX, c.max_kps);
+    hipLaunchKernelGGL(k_fastorb_nms, dim3(c.n_levels, c.n_img), dim3(1024), chunked_nms_smem(FO_PMAX, c.max_kps, 4), st, c, min_distance, do_nms, FO_PMAX, c.max_kps);
 }
 
 void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st)
@@ -2480,10 +2331,9 @@ void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int
     hipLaunchKernelGGL(k_faster, dim3((unsigned)((long long)c.n_tiles * c.n_img)), dim3(FK_NT), 0, st, c, cand64, fast_th, klt_win);
 }
 
-static size_t faster_nms_smem(int pmax, int accmax) { return fastorb_nms_smem(pmax, accmax) + 16; }       // + the 64-bit prefix words
-hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, faster_nms_smem(FO_PMAX, c.max_kps)); }
+hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, chunked_nms_smem(FO_PMAX, c.max_kps, 8)); }
 
 void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), faster_nms_smem(FO_PMAX, c.max_kps), st, c, cand64, min_distance, do_nms, FO_PMAX, c.max_kps);
+    hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), chunked_nms_smem(FO_PMAX, c.max_kps, 8), st, c, cand64, min_distance, do_nms, FO_PMAX, c.max_kps);
 }

@@ -379,6 +379,38 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* scratch, int* to
     return base + inc - v;
 }
 
+// slot of this lane's entry in an LDS / global list that whole waves append to: one atomic per wave on *counter, the lanes that `take`
+// get consecutive slots in lane order.  Every lane of the wave must call (ballot); the value is meaningless where !take.
+__device__ __forceinline__ unsigned wave_append_slot(bool take, unsigned* counter)
+{
+    const unsigned long long m = __ballot(take);
+    const int lane = threadIdx.x & 63;
+    unsigned b0 = 0;
+    if (m) {
+        const int leader = __ffsll((long long)m) - 1;
+        if (lane == leader) b0 = atomicAdd(counter, (unsigned)__popcll(m));
+        b0 = __shfl(b0, leader, 64);
+    }
+    return b0 + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// one byte pass of a DESCENDING radix select, after the caller has filled hist[256] (and passed a barrier) with byte `shift` of every
+// key that still matches (key & mask) == prefix: picks the bin that holds the need-th largest of them, broadcasts prefix | bin << shift
+// and what is still needed inside that bin through the caller's LDS words, and extends prefix / need / mask.  Called by ALL threads of a
+// block of >= 256; `scan` as for block_exclusive_scan.  hist and both words are free again on return.
+template <typename Key>
+__device__ __forceinline__ void radix_pick_bin(const unsigned* hist, int shift, int* scan, Key* s_prefix, unsigned* s_need, Key& prefix, unsigned& need, Key& mask)
+{
+    const int tid = threadIdx.x;
+    const int mine = tid < 256 ? (int)hist[255 - tid] : 0;             // bins in descending order: thread t owns bin 255 - t
+    int tot;
+    const int before = block_exclusive_scan(mine, scan, &tot);
+    if (tid < 256 && (unsigned)before < need && need <= (unsigned)(before + mine)) { *s_prefix = prefix | ((Key)(255 - tid) << shift); *s_need = need - (unsigned)before; }
+    __syncthreads();
+    prefix = *s_prefix; need = *s_need; mask |= (Key)255 << shift;
+    __syncthreads();
+}
+
 // ---- the reference's greedy grid NMS (m_non_max_sup, stage2_detect.cpp:225-283 / 296-370), exact and block-parallel ----
 // Reference: visit keypoints in response-descending rank order; accept one iff its grid cell is unmarked, then mark
 // the cell and its 4 neighbours.  Equivalent parallel form used here:

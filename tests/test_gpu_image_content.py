@@ -130,6 +130,39 @@ def test_structured_content_fast_orb_matches_oracle(name, noct, nms):
     ctx.close()
 
 
+@pytest.mark.parametrize("nfe,nms,max_kps", [(2000, 1, 4096), (1200, 1, 4096), (500, 1, 4096), (2000, 0, 8192)])
+def test_fast_orb_nms_walks_several_chunks(nfe, nms, max_kps):
+    """FAST+ORB at one octave on a 400x300 periodic frame: more than 3 x 2048 corners, so the grid NMS walks its rank order in four
+    chunks of 2048, each seeded with the cells the chunks before it accepted (min_distance 7: 2663 survive; 1447 of the first 2048
+    keys alone, 2189 of the first 4096).  The cap 2 * orb_nfeats is never reached (2000), reached inside a later chunk (1200) or
+    inside the first (500); without NMS every corner is kept, in raster order.  All of it asserted from the oracle's own output."""
+    w, h = 400, 300
+    frames = make_frames("periodic", w, h, 2, seed=1)
+    cam = StereoCamera.simple(400.0, w / 2.0, h / 2.0, 0.12, w, h)
+    p = north_star_params(hip.default_params(), orb_nfeats=nfe)
+    p.detect_method = DM_FAST_ORB; p.nOctaves = 1; p.non_maximal_suppression = nms; p.min_distance = 7
+    ctx = hip.Context(n_lanes=1, max_w=w, max_h=h, max_kps=max_kps, max_cand=1 << 15)
+    ctx.set_params(p); ctx.set_camera(cam)
+    orc = O().Oracle(p)
+    cap = 2 * nfe
+    for t, (L, R) in enumerate(frames):
+        ctx.process_host([(L, R)])
+        r, ro = ctx.result(0), orc.process(L, R, cam)
+        tag = "periodic %dx%d fast+orb nfeats %d nms %d t=%d" % (w, h, nfe, nms, t)
+        for img, kept in ((L, ro.detected_left[0]), (R, ro.detected_right[0])):
+            ncand = len(O().fast_orb_detect(img, 20)[0])
+            assert ncand > 3 * 2048, (tag, ncand)
+            if not nms:
+                assert kept == ncand, (tag, kept, ncand)
+            elif nfe == 2000:
+                assert 2048 < kept < cap, (tag, kept, cap)
+            else:
+                assert kept == cap, (tag, kept, cap)
+        assert ctx.status_word(0) == 0, (tag, ctx.status_word(0))
+        assert_same_octaves(ctx, 0, orc, r, ro, 1, tag)
+    ctx.close()
+
+
 @pytest.mark.parametrize("name", ["periodic", "mirror"])
 def test_tie_heavy_lane_beside_an_ordinary_lane(name):
     """two lanes of one context: tie-heavy content in one, the synthetic world in the other; each against its own oracle"""

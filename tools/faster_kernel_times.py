@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch HIP-event times of the dmFASTER kernels (k_faster under `faster`, k_faster_nms under `faster_nms`) beside those of `fast`,
-`select` and `describe` from a FAST+ORB run on the same frames: ONE context of `lanes` streams at 1280x960 on three x1/2 octaves,
+`select` and `describe` from a FAST+ORB run on the same frames (`select` there is k_fastorb_nms: it and k_faster_nms are the two
+instantiations of chunked_grid_nms in k_detect.hip, over 32-bit and 64-bit keys): ONE context of `lanes` streams at 1280x960 on three x1/2 octaves,
 every lane its own trajectory through one synthetic street, svo_config.kernel_times on.  Both runs share `resize` (k_half) and
 `nms_rowsort`.  Prints one JSON line (profiles/faster_kernel_times.json).  No threshold hangs on these figures: they are the
 baseline for the next change to these kernels."""
