@@ -334,6 +334,88 @@ __global__ void __launch_bounds__(256) k_hamming_f4(DevCtx c, int mode, int nspl
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Dynamic LDS: ONE description per kernel.  A layout is built from max_kps and names the arrays of the kernel's extern __shared__
+// block in their order, each with its element type and count, and the total in bytes.  The kernel walks the block by these counts
+// (array k + 1 starts where array k ends), the launcher passes total() as the launch's dynamic LDS, and configure_match raises
+// hipFuncAttributeMaxDynamicSharedMemorySize to total() where that exceeds the default 64 KB: no size of these kernels is written
+// anywhere else.  Static __shared__ members are not part of a layout.  (Counts, not byte offsets from the base: with offsets the
+// compiler rebuilt every address from the base and k_track_filter<32>, k_track_finalize and k_match_lr_rbr came out 1-23 instructions longer.)
+// The static_asserts pin the totals at the sizes where they cross 64 KB, and the CU's 160 KB at 16384.
+// ------------------------------------------------------------------------------------------------------------
+#define LDS_FN __host__ __device__ constexpr int
+struct LdsLrFilter {                                     // k_match_lr_filter
+    int max_kps;
+    LDS_FN n_right_best() const { return max_kps; }        // unsigned
+    LDS_FN n_scan() const { return 32; }                   // int: block_exclusive_scan
+    LDS_FN total() const { return 4 * (n_right_best() + n_scan()); }
+};
+struct LdsLrRbr {                                        // k_match_lr_rbr<SAD>
+    int max_kps;
+    LDS_FN n_right_best() const { return max_kps; }        // unsigned
+    LDS_FN n_left_pick() const { return max_kps; }         // unsigned
+    LDS_FN n_scan() const { return 32; }                   // int
+    LDS_FN total() const { return 4 * (n_right_best() + n_left_pick() + n_scan()); }
+};
+struct LdsTrackWin {                                     // k_track_win<SAD>
+    int max_kps;
+    LDS_FN n_cur_best() const { return max_kps; }          // unsigned
+    LDS_FN n_scan() const { return 40; }                   // int: rs_schedule_block at the kernel's end uses scan[33..36]
+    LDS_FN total() const { return 4 * (n_cur_best() + n_scan()); }
+};
+template <int TF_ITEMS>
+struct LdsTrackFilter {                                  // k_track_filter<TF_ITEMS> (its scan area is a static member)
+    int max_kps;
+    LDS_FN n_first() const { return max_kps; }             // unsigned, twice: firstL, firstR
+    LDS_FN n_taken() const { return max_kps / 32; }        // unsigned, twice: takenL, takenR, one bit per entry
+    LDS_FN n_tlr() const { return TF_ITEMS > 16 && TF_ITEMS <= 32 ? TF_ITEMS * 256 : 0; }      // unsigned: a thread's train indices (<32> only)
+    LDS_FN n_st() const { return TF_ITEMS > 16 ? TF_ITEMS * 256 : 0; }                         // unsigned char: its states (<32>, <64>)
+    LDS_FN total() const { return 4 * (2 * n_first() + 2 * n_taken() + n_tlr()) + n_st(); }
+};
+struct LdsTrackFinalize {                                // k_track_finalize
+    int max_kps;
+    LDS_FN n_in() const { return max_kps; }                // unsigned char, twice: in_l, in_r
+    LDS_FN n_scan() const { return 32; }                   // int
+    LDS_FN total() const { return 2 * n_in() + 4 * n_scan(); }
+};
+struct LdsMatchIds {                                     // k_match_ids
+    int max_kps;
+    LDS_FN n_tracked_flag() const { return max_kps; }      // unsigned char
+    LDS_FN total() const { return n_tracked_flag(); }
+};
+#undef LDS_FN
+static_assert(LdsLrFilter{16384}.total() == 65664 && LdsLrRbr{8192}.total() == 65664 && LdsLrRbr{16384}.total() == 131200 && LdsTrackWin{16384}.total() == 65696, "stereo / window-tracker LDS totals");
+static_assert(LdsTrackFilter<16>{4096}.total() == 33792 && LdsTrackFilter<32>{8192}.total() == 108544 && LdsTrackFilter<64>{16384}.total() == 151552, "joint-filter LDS totals");
+static_assert(LdsLrFilter{4096}.total() == 4 * 4096 + 128 && LdsLrRbr{4096}.total() == 8 * 4096 + 128 && LdsTrackWin{4096}.total() == 4 * 4096 + 160 && LdsTrackFinalize{4096}.total() == 2 * 4096 + 128 && LdsMatchIds{4096}.total() == 4096, "LDS formulas");
+static_assert(LdsLrFilter{16384}.total() <= 160 * 1024 && LdsLrRbr{16384}.total() <= 160 * 1024 && LdsTrackWin{16384}.total() <= 160 * 1024 && LdsTrackFilter<64>{16384}.total() <= 160 * 1024 &&
+              LdsTrackFinalize{16384}.total() <= 160 * 1024 && LdsMatchIds{16384}.total() <= 160 * 1024, "gfx950: 160 KB of LDS per CU");
+
+// 256-bit Hamming distance of two descriptors held as two 16-byte halves each
+__device__ __forceinline__ unsigned ham256(const ulonglong2& qa, const ulonglong2& qb, const ulonglong2& ta, const ulonglong2& tb)
+{
+    return (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y));
+}
+
+// matches_lr_row_index (stage3_match_left_right.cpp:425-445), the tail of both stereo kernels: ri[y] = #pairings whose left keypoint
+// has y <= y - 1 (the m_total pairings `out` are in ascending row order: binary search); ri[H] = M (documented deviation from
+// S3:443, oracle too).  Called by all threads of the block once thread-local writes of `out` are done.
+__device__ __forceinline__ void lr_row_index(const DevCtx& c, int vl, int cur, int H, const svo_keypoint* kl, const svo_dmatch* out, int m_total)
+{
+    __threadfence_block();
+    __syncthreads();
+    int* ri = c.mrow_index + (long long)(vl * 2 + cur) * (c.max_h + 1);
+    for (int y = threadIdx.x; y <= H; y += blockDim.x) {
+        int v = m_total;
+        if (y < H) {
+            int lo = 0, hi = m_total;                      // first pairing with left y > y - 1
+            const float lim = (float)(y - 1);
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (kl[out[mid].queryIdx].y <= lim) lo = mid + 1; else hi = mid; }
+            v = y == 0 ? 0 : lo;
+        }
+        ri[y] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // K8a: stage-3 filters (S3:124-175), one 1024-thread block per lane.
 //   1-to-1: per right feature keep the left with the smallest (distance, left index)   [S3:127-147]
 //   epipolar / threshold / disparity with the reference's int truncations                [S3:159-168]
@@ -344,8 +426,9 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
     SVO_TL_SCOPE(c, TL_LR_FILTER, 0);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned* right_best = (unsigned*)smem;              // max_kps
-    int* scan = (int*)(right_best + c.max_kps);          // 32
+    const LdsLrFilter lds{c.max_kps};
+    unsigned* right_best = (unsigned*)smem;
+    int* scan = (int*)(right_best + lds.n_right_best());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
     if (oct >= c.n_oct) return;
     const LaneState& ls = c.lane[lane_id];
@@ -382,24 +465,7 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
         __syncthreads();
     }
     if (tid == 0) { c.n_matches[vl * 2 + cur] = m_total; c.results[lane_id].stereo_matches[oct] = m_total; }
-    // matches_lr_row_index (stage3_match_left_right.cpp:425-445): ri[y] = #pairings whose left keypoint has y <= y - 1
-    // (pairings are in ascending row order: binary search); ri[H] = M (documented deviation from S3:443, oracle too)
-    __threadfence_block();
-    __syncthreads();
-    {
-        int* ri = c.mrow_index + (long long)(vl * 2 + cur) * (c.max_h + 1);
-        const int H = c.oh[oct];
-        for (int y = tid; y <= H; y += blockDim.x) {
-            int v = m_total;
-            if (y < H) {
-                int lo = 0, hi = m_total;                      // first pairing with left y > y - 1
-                const float lim = (float)(y - 1);
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (kl[out[mid].queryIdx].y <= lim) lo = mid + 1; else hi = mid; }
-                v = y == 0 ? 0 : lo;
-            }
-            ri[y] = v;
-        }
-    }
+    lr_row_index(c, vl, cur, c.oh[oct], kl, out, m_total);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -415,7 +481,11 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
 // pair with a keypoint too close to the border for a window is skipped before the distance (S3:289-295), and a distance is 14 bits
 // (64 * 255 = 16320), so left_pick is min_idx << 14 | min_1 (14 bits of index at max_kps = 16384: 28 bits, and never the empty mark ~0).  sad_max_ratio has no effect either.
 // (A template KERNEL, not a shared device function called from two kernels: k_match_lr_rbr<false> then compiles to the instructions
-// k_match_lr_rbr had before the parameter existed; through an inlined body the Hamming form came out ten instructions longer.)
+// k_match_lr_rbr had before the parameter existed; through an inlined body the Hamming form came out ten instructions longer.  The
+// small shared pieces are another matter: with lr_row_index, ham256, trk_write_pair and trk_publish inlined, every kernel of this file
+// has the opcode histogram it had with its own copy (profiles/match_lds_isa.json).  Two forms of them did not: a pair writer taking the
+// keypoints by reference reloads them after every store (k_track_win: 10 more VMEM instructions), and one writing both sides of a
+// survivor at once moves k_track_filter's right-hand loads above its left-hand stores (<32>: 2 more s_nop) -- so it takes one side, by value.)
 __device__ __forceinline__ unsigned sad64(const uint4 (&q)[4], const uint4* t)
 {
     unsigned d = 0;
@@ -435,9 +505,10 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
     SVO_TL_SCOPE(c, TL_LR_FILTER, SAD ? 2 : 1);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned* right_best = (unsigned*)smem;              // max_kps: per right feature, min over its claimants
-    unsigned* left_pick = right_best + c.max_kps;        // max_kps: per left feature (min_idx << DB | min_1) or ~0
-    int* scan = (int*)(left_pick + c.max_kps);           // 32
+    const LdsLrRbr lds{c.max_kps};
+    unsigned* right_best = (unsigned*)smem;                         // per right feature, min over its claimants
+    unsigned* left_pick = right_best + lds.n_right_best();            // per left feature (min_idx << DB | min_1) or ~0
+    int* scan = (int*)(left_pick + lds.n_left_pick());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
     if (oct >= c.n_oct) return;
     const LaneState& ls = c.lane[lane_id];
@@ -480,7 +551,7 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
                 dist = sad64(qp, (const uint4*)(pr + (long long)iR * 64));      // S3:309-313
             } else {
                 const ulonglong2 ta = ((const ulonglong2*)(dr + (long long)iR * 32))[0], tb = ((const ulonglong2*)(dr + (long long)iR * 32))[1];
-                dist = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // uint8_t accumulator (S3:321-331)
+                dist = ham256(qa, qb, ta, tb) & 0xFFu;                          // uint8_t accumulator (S3:321-331)
             }
             if ((int)dist > max_distance) continue;                             // S3:334
             if (dist < min_1) { min_1 = dist; min_idx = iR; }                   // S3:338-343 (first minimum)
@@ -505,21 +576,7 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
         __syncthreads();
     }
     if (tid == 0) { c.n_matches[vl * 2 + cur] = m_total; c.results[lane_id].stereo_matches[oct] = m_total; }
-    __threadfence_block();
-    __syncthreads();
-    {
-        int* ri = c.mrow_index + (long long)(vl * 2 + cur) * (c.max_h + 1);
-        for (int y = tid; y <= H; y += blockDim.x) {
-            int v = m_total;
-            if (y < H) {
-                int lo = 0, hi = m_total;
-                const float lim = (float)(y - 1);
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (kl[out[mid].queryIdx].y <= lim) lo = mid + 1; else hi = mid; }
-                v = y == 0 ? 0 : lo;
-            }
-            ri[y] = v;
-        }
-    }
+    lr_row_index(c, vl, cur, H, kl, out, m_total);
 }
 
 // (defined with the RANSAC kernels below) phase 0 of the sample schedule runs at the end of the tracker kernels: same block shape, one launch less
@@ -528,6 +585,27 @@ __device__ __forceinline__ void rs_schedule_block(const DevCtx& c, int vl, int p
 // budget of SVO_LMEDS_ITERS samples from the same generator, every model of every one of them ranked by its median error (k_track_finalize).
 __device__ __forceinline__ bool rs_is_lmeds(int n) { return n >= 8 && n <= SVO_LMEDS_MAX_N; }
 __device__ __forceinline__ int rs_first_bound(int n) { return rs_is_lmeds(n) ? SVO_LMEDS_ITERS : SVO_RANSAC_HYP; }      // rs_bound before any count
+
+// The trackers' hand-over to the RANSAC, shared by k_track_win and k_track_filter.  Survivor o of a lane-octave, one side (called for
+// the left images, then for the right ones): its point pair previous -> current, four floats (S4:181-189, 216-224).
+__device__ __forceinline__ void trk_write_pair(float* pts, int o, const svo_keypoint prev, const svo_keypoint cur)
+{
+    pts[o * 4] = prev.x; pts[o * 4 + 1] = prev.y; pts[o * 4 + 2] = cur.x; pts[o * 4 + 3] = cur.y;
+}
+// ... and the publication once all n survivors are written, by ALL threads of the 256-thread block: the two pass-through counters
+// (n_threshold is read by thread 0 alone), the list length, the RANSAC's first budget and floors, then phase 0 of the sample schedule
+// (`scan`: 40 ints of LDS).
+__device__ __forceinline__ void trk_publish(const DevCtx& c, int vl, int lane_id, const int& n_threshold, int n, int* scan)
+{
+    if (threadIdx.x == 0) {
+        atomicAdd(&c.results[lane_id].track_stats[SVO_TS_THRESHOLD], n_threshold); atomicAdd(&c.results[lane_id].track_stats[SVO_TS_COLLISION], n);
+        c.trk_nk[vl] = n;
+        c.rs_bound[vl * 2] = c.rs_bound[vl * 2 + 1] = rs_first_bound(n);
+        c.rs_floor[vl * 4] = c.rs_floor[vl * 4 + 1] = c.rs_floor[vl * 4 + 2] = c.rs_floor[vl * 4 + 3] = 6;
+    }
+    __syncthreads();                                                       // the point pairs are written: the sampler's collinearity test reads them
+    rs_schedule_block(c, vl, 0, n, scan);
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // K8c: ifmDescWin -- window tracker (stage4_match_consecutive.cpp:435-738) with its quirks kept (appendix A #12):
@@ -546,8 +624,9 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
     SVO_TL_SCOPE(c, TL_TRK_FILTER, SAD ? 2 : 1);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned* cur_best = (unsigned*)smem;                // max_kps: (dist << 16 | pi) min over claimants
-    int* scan = (int*)(cur_best + c.max_kps);
+    const LdsTrackWin lds{c.max_kps};
+    unsigned* cur_best = (unsigned*)smem;                           // (dist << 16 | pi) min over claimants
+    int* scan = (int*)(cur_best + lds.n_cur_best());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
     if (oct >= c.n_oct) return;
     const LaneState& ls = c.lane[lane_id];
@@ -601,7 +680,7 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
                 orb_l = sad_l + sad_r;                                           // S4:580
             } else {
                 const ulonglong2 ta = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[0], tb = ((const ulonglong2*)(cdl + (long long)mc.queryIdx * 32))[1];
-                orb_l = (unsigned)(__popcll(qa.x ^ ta.x) + __popcll(qa.y ^ ta.y) + __popcll(qb.x ^ tb.x) + __popcll(qb.y ^ tb.y)) & 0xFFu;   // S4:596-609
+                orb_l = ham256(qa, qb, ta, tb) & 0xFFu;                          // uint8_t accumulator (S4:596-609)
             }
             if (orb_l < best_orb) { best_orb = orb_l; best_c = ci; }             // S4:614-618
         }
@@ -622,17 +701,14 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
         if (keep) {
             const int pi = (int)(v & 0xFFFFu), o = np_total + off;
             kq[o] = pi; cq[o] = i;
-            const svo_keypoint a = pkl[pm[pi].queryIdx], b = ckl[cm[i].queryIdx], e = pkr[pm[pi].trainIdx], f = ckr[cm[i].trainIdx];
-            ptsL[o * 4] = a.x; ptsL[o * 4 + 1] = a.y; ptsL[o * 4 + 2] = b.x; ptsL[o * 4 + 3] = b.y;
-            ptsR[o * 4] = e.x; ptsR[o * 4 + 1] = e.y; ptsR[o * 4 + 2] = f.x; ptsR[o * 4 + 3] = f.y;
+            const svo_keypoint a = pkl[pm[pi].queryIdx], b = ckl[cm[i].queryIdx], e = pkr[pm[pi].trainIdx], f = ckr[cm[i].trainIdx];      // (all four loads first)
+            trk_write_pair(ptsL, o, a, b);
+            trk_write_pair(ptsR, o, e, f);
         }
         np_total += tot;
         __syncthreads();
     }
-    if (tid == 0) { atomicAdd(&c.results[lane_id].track_stats[SVO_TS_THRESHOLD], np_total); atomicAdd(&c.results[lane_id].track_stats[SVO_TS_COLLISION], np_total); }
-    if (tid == 0) { c.trk_nk[vl] = np_total; c.rs_bound[vl * 2] = c.rs_bound[vl * 2 + 1] = rs_first_bound(np_total); c.rs_floor[vl * 4] = c.rs_floor[vl * 4 + 1] = c.rs_floor[vl * 4 + 2] = c.rs_floor[vl * 4 + 3] = 6; }
-    __syncthreads();                                                       // the point pairs are written: the sampler's collinearity test reads them
-    rs_schedule_block(c, vl, 0, np_total, scan);
+    trk_publish(c, vl, lane_id, np_total, np_total, scan);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -654,10 +730,11 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
     SVO_TL_SCOPE(c, TL_TRK_FILTER, 0);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned* firstL = (unsigned*)smem;                    // max_kps: smallest undecided k claiming left train index i
-    unsigned* firstR = firstL + c.max_kps;                 // max_kps
-    unsigned* takenL = firstR + c.max_kps;                 // max_kps / 32 bits
-    unsigned* takenR = takenL + c.max_kps / 32;
+    const LdsTrackFilter<TF_ITEMS> lds{c.max_kps};
+    unsigned* firstL = (unsigned*)smem;                      // smallest undecided k claiming left train index i
+    unsigned* firstR = firstL + lds.n_first();
+    unsigned* takenL = firstR + lds.n_first();                 // one bit per train index
+    unsigned* takenR = takenL + lds.n_taken();
     __shared__ int scan[40];
     __shared__ int s_und, s_th;
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, tid = threadIdx.x;
@@ -677,7 +754,7 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
     // states in LDS and reads the train indices from the matcher's result words in global memory (bf_idx, what the others copy at the
     // start; nothing writes them during this kernel) whenever it needs them -- only for k < npm, where a state can be other than 0.
     constexpr bool TF_REREAD = TF_ITEMS > 32;
-    unsigned* tlr_s = takenR + c.max_kps / 32; unsigned char* st_s = (unsigned char*)(tlr_s + ((TF_ITEMS <= 16 || TF_REREAD) ? 0 : TF_ITEMS * 256));
+    unsigned* tlr_s = takenR + lds.n_taken(); unsigned char* st_s = (unsigned char*)(tlr_s + lds.n_tlr());
     auto TLR = [&](int j) -> unsigned& { if constexpr (TF_ITEMS <= 16) return tlr_r[j]; else return tlr_s[j * 256 + tid]; };
     auto ST = [&](int j) -> unsigned char& { if constexpr (TF_ITEMS <= 16) return st_r[j]; else return st_s[j * 256 + tid]; };
     auto TLRV = [&](int j) -> unsigned { if constexpr (TF_REREAD) { const int k = tid + 256 * j; return (gL[k] & 0xFFFFu) | (gR[k] << 16); } else return TLR(j); };
@@ -754,18 +831,13 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
             const int tl = (int)(TLRV(j) & 0xFFFFu), tr = (int)(TLRV(j) >> 16);
             kq[o] = k;
             const svo_dmatch mp = pm[k];
-            const svo_keypoint a = pkl[mp.queryIdx], b = ckl[cm[tl].queryIdx];
-            ptsL[o * 4] = a.x; ptsL[o * 4 + 1] = a.y; ptsL[o * 4 + 2] = b.x; ptsL[o * 4 + 3] = b.y;
-            const svo_keypoint e = pkr[mp.trainIdx], f = ckr[cm[tr].trainIdx];
-            ptsR[o * 4] = e.x; ptsR[o * 4 + 1] = e.y; ptsR[o * 4 + 2] = f.x; ptsR[o * 4 + 3] = f.y;
+            trk_write_pair(ptsL, o, pkl[mp.queryIdx], ckl[cm[tl].queryIdx]);
+            trk_write_pair(ptsR, o, pkr[mp.trainIdx], ckr[cm[tr].trainIdx]);
         }
         nk += tot;
         __syncthreads();
     }
-    if (tid == 0) { atomicAdd(&c.results[lane_id].track_stats[SVO_TS_THRESHOLD], s_th); atomicAdd(&c.results[lane_id].track_stats[SVO_TS_COLLISION], nk); }
-    if (tid == 0) { c.trk_nk[vl] = nk; c.rs_bound[vl * 2] = c.rs_bound[vl * 2 + 1] = rs_first_bound(nk); c.rs_floor[vl * 4] = c.rs_floor[vl * 4 + 1] = c.rs_floor[vl * 4 + 2] = c.rs_floor[vl * 4 + 3] = 6; }
-    __syncthreads();                                                       // the point pairs are written: the sampler's collinearity test reads them
-    rs_schedule_block(c, vl, 0, nk, scan);
+    trk_publish(c, vl, lane_id, s_th, nk, scan);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1830,9 +1902,10 @@ __global__ void __launch_bounds__(256) k_track_finalize(DevCtx c, int win_mode, 
     SVO_TL_SCOPE(c, TL_TRK_FINAL, 0);
     SVO_LATENCY_CHAIN(c);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* in_l = smem;                         // max_kps
-    unsigned char* in_r = in_l + c.max_kps;             // max_kps
-    int* scan = (int*)(in_r + c.max_kps);               // 32
+    const LdsTrackFinalize lds{c.max_kps};
+    unsigned char* in_l = smem;
+    unsigned char* in_r = in_l + lds.n_in();
+    int* scan = (int*)(in_r + lds.n_in());
     __shared__ int s_best[2], s_cnt[2], s_vis[2], s_both;
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
     if (oct >= c.n_oct) return;
@@ -2079,7 +2152,7 @@ __global__ void __launch_bounds__(256) k_match_ids(DevCtx c, unsigned flags)
     __shared__ int scan[32];
     __shared__ int s_next, s_kf;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* tracked_flag = smem;                  // max_kps
+    unsigned char* tracked_flag = smem;                  // LdsMatchIds: the block's only array
     const int lane_id = blockIdx.x, tid = threadIdx.x;
     LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
@@ -2140,25 +2213,32 @@ __global__ void __launch_bounds__(256) k_match_ids(DevCtx c, unsigned flags)
 // ------------------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------------------
-// contexts with max_kps > 4096 need more than the default 64 KB of dynamic LDS in some of the per-lane kernels
+// k_track_filter<TF_ITEMS>: TF_ITEMS x 256 threads >= max_kps.  The instantiation a context launches, with its dynamic LDS.
+struct TrackFilterForm { void (*kernel)(DevCtx); int lds; };
+static TrackFilterForm track_filter_form(int max_kps)
+{
+    if (max_kps > 8192) return { k_track_filter<64>, LdsTrackFilter<64>{max_kps}.total() };
+    if (max_kps > 4096) return { k_track_filter<32>, LdsTrackFilter<32>{max_kps}.total() };
+    return { k_track_filter<16>, LdsTrackFilter<16>{max_kps}.total() };
+}
+// Every kernel with dynamic LDS that a context of max_kps entries launches: the ones whose layout exceeds the default 64 KB are raised
+// to their total (none up to 4096; the two k_match_lr_rbr and k_track_filter<32> at 8192; at 16384 the two k_match_lr_rbr,
+// k_track_filter<64>, k_match_lr_filter and the two k_track_win).
 hipError_t configure_match(int max_kps)
 {
-    if (max_kps <= 4096) return hipSuccess;
-    hipError_t e = hipSuccess;
-    if (max_kps <= 8192) e = svo_raise_dyn_smem((const void*)k_track_filter<32>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)32 * 256 * 5);
-    if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<false>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
-    if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_match_lr_rbr<true>, sizeof(unsigned) * 2 * max_kps + sizeof(int) * 32);
-    if (e != hipSuccess || max_kps <= 8192) return e;
-    // 16384 entries: the one-array kernels pass 64 KB too, and the joint filter runs its third form (states in LDS, 148 KB with the tables)
-    e = svo_raise_dyn_smem((const void*)k_track_filter<64>, (size_t)(max_kps / 32) * 8 + (size_t)max_kps * 8 + (size_t)64 * 256);
-    if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_match_lr_filter, sizeof(unsigned) * max_kps + sizeof(int) * 32);
-    if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_track_win<false>, sizeof(unsigned) * max_kps + sizeof(int) * 40);
-    if (e != hipSuccess) return e;
-    return svo_raise_dyn_smem((const void*)k_track_win<true>, sizeof(unsigned) * max_kps + sizeof(int) * 40);
+    const struct { const void* kernel; int lds; } uses[] = {
+        { (const void*)k_match_lr_rbr<false>, LdsLrRbr{max_kps}.total() }, { (const void*)k_match_lr_rbr<true>, LdsLrRbr{max_kps}.total() },
+        { (const void*)track_filter_form(max_kps).kernel, track_filter_form(max_kps).lds },
+        { (const void*)k_match_lr_filter, LdsLrFilter{max_kps}.total() },
+        { (const void*)k_track_win<false>, LdsTrackWin{max_kps}.total() }, { (const void*)k_track_win<true>, LdsTrackWin{max_kps}.total() },
+        { (const void*)k_track_finalize, LdsTrackFinalize{max_kps}.total() }, { (const void*)k_match_ids, LdsMatchIds{max_kps}.total() },
+    };
+    for (const auto& u : uses) {
+        if (u.lds <= 64 * 1024) continue;
+        const hipError_t e = svo_raise_dyn_smem(u.kernel, u.lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // Which kernel forms this library holds: the product forms always; the A/B anchors (the int8 matcher SVO_HAM_FP4=0, the RANSAC count forms
@@ -2204,38 +2284,24 @@ void launch_hamming(const DevCtx& c, int mode, int nsplit, hipStream_t st)
 
 void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, hipStream_t st)
 {
-    const size_t sm = sizeof(unsigned) * c.max_kps + sizeof(int) * 32;
-    hipLaunchKernelGGL(k_match_lr_filter, dim3(c.n_lanes * c.oct_cap), dim3(1024), sm, st, c, one_to_one, max_y_diff);
+    hipLaunchKernelGGL(k_match_lr_filter, dim3(c.n_lanes * c.oct_cap), dim3(1024), LdsLrFilter{c.max_kps}.total(), st, c, one_to_one, max_y_diff);
 }
-
-void launch_match_lr_rbr(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st)
+void launch_match_lr_rbr(const DevCtx& c, bool sad, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st)
 {
-    const size_t sm = sizeof(unsigned) * 2 * c.max_kps + sizeof(int) * 32;
-    hipLaunchKernelGGL(k_match_lr_rbr<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c, one_to_one, max_y_diff, minimum_response, max_distance);
+    hipLaunchKernelGGL(sad ? k_match_lr_rbr<true> : k_match_lr_rbr<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), LdsLrRbr{c.max_kps}.total(), st, c, one_to_one, max_y_diff, minimum_response, max_distance);
 }
-void launch_match_lr_sad(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st)
+void launch_track_win(const DevCtx& c, bool sad, int win_w, int win_h, unsigned max_sad, hipStream_t st)
 {
-    const size_t sm = sizeof(unsigned) * 2 * c.max_kps + sizeof(int) * 32;
-    hipLaunchKernelGGL(k_match_lr_rbr<true>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c, one_to_one, max_y_diff, minimum_response, max_distance);
-}
-void launch_track_sad(const DevCtx& c, int win_w, int win_h, unsigned max_sad, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_track_win<true>, dim3(c.n_lanes * c.oct_cap), dim3(256), sizeof(unsigned) * c.max_kps + sizeof(int) * 40, st, c, win_w, win_h, max_sad);
-}
-void launch_track_win(const DevCtx& c, int win_w, int win_h, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_track_win<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), sizeof(unsigned) * c.max_kps + sizeof(int) * 40, st, c, win_w, win_h, 0u);      // (40: the sample schedule at its end uses scan[33..36])
+    hipLaunchKernelGGL(sad ? k_track_win<true> : k_track_win<false>, dim3(c.n_lanes * c.oct_cap), dim3(256), LdsTrackWin{c.max_kps}.total(), st, c, win_w, win_h, max_sad);
 }
 void launch_match_ids(const DevCtx& c, unsigned flags, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_match_ids, dim3(c.n_lanes), dim3(256), (size_t)c.max_kps, st, c, flags);
+    hipLaunchKernelGGL(k_match_ids, dim3(c.n_lanes), dim3(256), LdsMatchIds{c.max_kps}.total(), st, c, flags);
 }
 void launch_track_filter(const DevCtx& c, hipStream_t st)
 {
-    const size_t sm = (size_t)(c.max_kps / 32) * 2 * sizeof(unsigned) + (size_t)c.max_kps * 2 * sizeof(unsigned);
-    if (c.max_kps > 8192) hipLaunchKernelGGL(k_track_filter<64>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm + (size_t)64 * 256, st, c);          // + the states (1 byte each) in LDS
-    else if (c.max_kps > 4096) hipLaunchKernelGGL(k_track_filter<32>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm + (size_t)32 * 256 * 5, st, c);      // + the per-thread candidates (4 + 1 bytes each) in LDS
-    else hipLaunchKernelGGL(k_track_filter<16>, dim3(c.n_lanes * c.oct_cap), dim3(256), sm, st, c);
+    const TrackFilterForm f = track_filter_form(c.max_kps);
+    hipLaunchKernelGGL(f.kernel, dim3(c.n_lanes * c.oct_cap), dim3(256), f.lds, st, c);
 }
 void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st)
 {
@@ -2279,7 +2345,7 @@ void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st)
 void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, hipStream_t st)
 {
     const bool fold = c.oct_cap == 1;
-    hipLaunchKernelGGL(k_track_finalize, dim3(c.n_lanes * c.oct_cap), dim3(256), (size_t)c.max_kps * 2 + sizeof(int) * 32, st, c, win_mode, fold ? bad_tracking_th : -1);
+    hipLaunchKernelGGL(k_track_finalize, dim3(c.n_lanes * c.oct_cap), dim3(256), LdsTrackFinalize{c.max_kps}.total(), st, c, win_mode, fold ? bad_tracking_th : -1);
     if (!fold) hipLaunchKernelGGL(k_track_gate, dim3((c.n_lanes + 63) / 64), dim3(64), 0, st, c, bad_tracking_th);
 }
 
@@ -2306,7 +2372,7 @@ __global__ void __launch_bounds__(256) k_hamming_plain(const uint8_t* qd, int nq
 #pragma unroll 4
         for (int j = 0; j < jn; j++) {
             const ulonglong2 a = ((const ulonglong2*)tile)[j * 2], b = ((const ulonglong2*)tile)[j * 2 + 1];
-            const unsigned d = __popcll(q0 ^ a.x) + __popcll(q1 ^ a.y) + __popcll(q2 ^ b.x) + __popcll(q3 ^ b.y);
+            const unsigned d = ham256(make_ulonglong2(q0, q1), make_ulonglong2(q2, q3), a, b);
             best = min(best, (d << 16) | (unsigned)(j0 + j));
         }
     }

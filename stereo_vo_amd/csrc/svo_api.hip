@@ -1208,13 +1208,13 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
             const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
             Span s(ctx, KT_LR_FILTER);
-            launch_match_lr_rbr(d, p.enable_robust_1to1_match, p.max_y_diff, minresp, (int)(size_t)p.orb_max_distance, st);
+            launch_match_lr_rbr(d, false, p.enable_robust_1to1_match, p.max_y_diff, minresp, (int)(size_t)p.orb_max_distance, st);
         } else {                                                // smSAD: the same loop on the gathered windows
             const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
             // size_t(sad_max_distance) (S3:201): 0 = the reference's default 200 (S3:48), negative = no threshold (a SAD is <= 16320)
             const int max_sad = p.sad_max_distance == 0 ? 200 : (p.sad_max_distance < 0 ? INT32_MAX : p.sad_max_distance);
             Span s(ctx, KT_LR_SAD);
-            launch_match_lr_sad(d, p.enable_robust_1to1_match, p.max_y_diff, minresp, max_sad, st);
+            launch_match_lr_rbr(d, true, p.enable_robust_1to1_match, p.max_y_diff, minresp, max_sad, st);
         }
     }
     if (flags & SVO_RUN_TRACK) {
@@ -1232,10 +1232,10 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
             { Span s(ctx, wide ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, 1, nsplit, st); }
             { Span s(ctx, wide ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
         } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
-            Span s(ctx, KT_TRK_FILTER); launch_track_win(d, p.ifm_win_w, p.ifm_win_h, st);
+            Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
         } else {                                                // ifmSAD: uint32_t MAX_SAD (S4:448); 0 = "~200" (H:297), negative wraps to no threshold
             const unsigned max_sad = p.ifm_sad_max_distance == 0 ? 200u : (unsigned)p.ifm_sad_max_distance;
-            Span s(ctx, KT_TRK_SAD); launch_track_sad(d, p.ifm_win_w, p.ifm_win_h, max_sad, st);
+            Span s(ctx, KT_TRK_SAD); launch_track_win(d, true, p.ifm_win_w, p.ifm_win_h, max_sad, st);
         }
         // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
         // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far

@@ -68,10 +68,9 @@ void launch_track_filter(const DevCtx& c, hipStream_t st);
 void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st);
 void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st);
 void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, hipStream_t st);
-void launch_match_lr_rbr(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
-void launch_track_win(const DevCtx& c, int win_w, int win_h, hipStream_t st);
-void launch_match_lr_sad(const DevCtx& c, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
-void launch_track_sad(const DevCtx& c, int win_w, int win_h, unsigned max_sad, hipStream_t st);
+// sad = false: smDescRbR / ifmDescWin on the descriptors; sad = true: smSAD / ifmSAD on the windows of launch_sad_patch (max_sad: ifmSAD's threshold)
+void launch_match_lr_rbr(const DevCtx& c, bool sad, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
+void launch_track_win(const DevCtx& c, bool sad, int win_w, int win_h, unsigned max_sad, hipStream_t st);
 void launch_match_ids(const DevCtx& c, unsigned flags, hipStream_t st);
 void launch_hamming_plain(const uint8_t* q, int nq, const uint8_t* t, int nt, unsigned* out, int nsplit, hipStream_t st);
 hipError_t configure_gauss_newton(int pmax);
