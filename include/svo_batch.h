@@ -89,6 +89,15 @@ int  svo_batch_switch_results_buffer(svo_batch* b, void* dev_records, size_t byt
 /* processNewImagePair for every stream: frames[lane], lane in [0, svo_batch_lanes).  `flags`: SVO_FLAG_DEVICE_IMAGES,
  * SVO_FLAG_PINNED_IMAGES or neither (pageable host images), | SVO_FLAG_BGR_IMAGES.  ENQUEUES and returns. */
 int  svo_batch_step(svo_batch* b, const svo_frame* frames, uint32_t flags);
+/* The same for the streams that HAVE a frame in this step: active holds ceil(svo_batch_lanes / 64) words, bit (lane & 63) of word
+ * lane >> 6 in the GLOBAL lane order of frames[]; NULL = every stream (svo_batch_step is that case).  For a stream whose bit is
+ * clear the step is as if it had not been made (svo_process_lanes in svo_hip.h: no shift, no zero-motion frame, record and lists as
+ * they were; frames[lane] is not read and may hold NULL pointers).  Each context gets its slice of the mask in every call of its
+ * frame (detect, post, stages 3-5).  A context none of whose streams is selected gets no kernel launch in the step; its records,
+ * unchanged, are still copied into the step's records buffer and its place in the event chain is kept, so svo_batch_wait_on_stream,
+ * svo_batch_hold_for_event and svo_batch_switch_results_buffer behave as in any other step.  A bit at or above svo_batch_lanes is
+ * SVO_ERR_ARG before anything is enqueued. */
+int  svo_batch_step_lanes(svo_batch* b, const svo_frame* frames, uint32_t flags, const uint64_t* active);
 /* make the caller's hipStream_t wait for the last step's work of every context (e.g. before an all-gather of the records) */
 int  svo_batch_wait_on_stream(svo_batch* b, void* stream);
 /* the NEXT step's result copies -- and nothing ahead of them in that step -- wait for this hipEvent_t (e.g. the all-gather that

@@ -178,6 +178,33 @@ int svo_reset(svo_ctx* ctx, int lane);
 /* processNewImagePair for every lane (P:41-385): ENQUEUES the whole frame on the context's stream and
  * returns; frames[lane] for lane in [0,n_lanes).  Nothing is copied back until svo_wait/svo_get_*. */
 int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
+/* svo_process for the lanes whose bit is set: bit l & 63 of active[l >> 6] selects lane l.  Cameras do not tick in lockstep -- frames
+ * are dropped, streams start late, end early or run at other rates -- and one estimator is only ever called when ITS camera has a
+ * frame (H:732-831: all state is per instance).  For every lane whose bit is CLEAR the call is AS IF IT HAD NOT BEEN MADE: nothing that a
+ * getter, a later frame, a hand-over record or a state file can observe changes -- the result record, both slots' keypoint /
+ * descriptor / pairing / ID lists with their counts and row-index tables, the tracked list, residuals and outliers, the lane state
+ * (iteration counter, m_error, which slot is the previous frame, the match-ID counters), the status word, the speculative FAST
+ * thresholds of its two images, its gathered SAD windows and the host-side record of which of its frames have them.  No shift, no
+ * zero-motion frame, no match IDs consumed.  Only per-frame scratch (pyramid, candidate lists, matcher and RANSAC tables) may be
+ * rewritten.  For every lane whose bit is SET the call is exactly svo_process; with every bit set it IS svo_process, launch for launch.
+ *   - frames[l] of an idle lane is not read and may hold NULL pointers; it is neither copied nor uploaded.  An active lane with NULL
+ *     data is SVO_ERR_ARG, and the active lanes must agree on w / h (and on the stride of device frames).
+ *   - a bit at or above n_lanes: SVO_ERR_ARG, with a text.  active == NULL: SVO_ERR_ARG.  Like every refusal of svo_process these disarm
+ *     an event armed by svo_record_after_post, if the flags are those of a call that would have consumed it.
+ *   - no bit set: SVO_OK; nothing is enqueued, no state moves (an armed event stays armed), svo_last_error is empty.
+ *   - svo_import_frame writes every lane.  The first-frame rule of the match IDs that follows an import applies to each lane at ITS
+ *     first call after the import: a lane that sits that call out keeps it for its own next frame.
+ *   - ONE MASK PER FRAME.  The calls that continue a frame -- the SVO_RUN_DETECT_POST call of a SVO_FLAG_DETECT_NO_POST detect call
+ *     (with or without SVO_FLAG_DETECT_AHEAD), and stages run with SVO_FLAG_NO_SHIFT -- must carry the mask of the call that began it
+ *     (the last call that ran the detector or the shift; svo_process counts as all lanes).  Another mask is SVO_ERR_STATE with a text,
+ *     before anything is enqueued.
+ *   - a SAD stage on a frame whose windows were never gathered (below) is looked for in the active lanes only, and a lane whose
+ *     previous frame is to be forgotten forgets it at ITS next active frame.
+ *   - svo_use_graphs: a call with an idle lane runs as plain launches (the mask is a kernel argument); calls with every lane active go
+ *     on replaying.
+ * The grids stay whole: an idle lane's workgroups leave at once.  A context that is mostly idle therefore still pays for launching
+ * them ("Idle lanes"). */
+int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t active[2]);
 /* smSAD (svo_params.match_method = SVO_SM_SAD, S3:185-419) and ifmSAD (ifm_method = SVO_IFM_SAD, S4:435-738) compare the 8 x 8 image
  * windows around two keypoints (rso::compute_SAD8).  Stage 2 is the only stage that reads images, so it gathers the window of every
  * final keypoint -- from the call on in which either selector is in force; a context that never selects them allocates and launches
@@ -343,6 +370,9 @@ int svo_hamming_match(svo_ctx* ctx, const uint8_t* query, int nq, const uint8_t*
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
 int svo_debug_get_status_word(svo_ctx* ctx, int lane, uint32_t* w);   /* capacity-overflow bits */
+/* svo_use_graphs bookkeeping: graphs this context holds (one per distinct captured call) and calls served by replaying one since
+ * svo_create; either pointer may be NULL.  A call that runs as plain launches moves neither. */
+int svo_debug_get_graph_count(svo_ctx* ctx, uint32_t* captured, uint32_t* replayed);
 /* 1 when the reference's profiler sections (CTimeLogger names: "processNewImagePair", "_stg1" .. "_stg5", "stg3.find_pairings",
  * "stg4.track") are being emitted as roctx ranges around the enqueue of each stage: SVO_ROCTX=1 in the environment, or a rocprofv3
  * session (it sets ROCP_TOOL_LIBRARIES); the roctx library is looked up with dlopen, never linked. */

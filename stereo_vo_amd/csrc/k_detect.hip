@@ -99,9 +99,11 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask d
     // SVO_FLAG_DETECT_AHEAD: a detect call that may overlap stages 3-5 of the frame before it -- it initialises the detector's
     // per-image scratch and nothing else; its post call (SVO_RUN_DETECT_POST with the same flag) does the lane part below
     const bool ahead = flags & SVO_FLAG_DETECT_AHEAD, ahead_post = ahead && !detect;
+    // (one thread per image, per (image, level) and per lane here, not one block: an idle lane's threads skip their part; the fill
+    // above may stay whole, bf_idx is scratch)
     if (detect) {
-        if (t < c.n_img) { c.img0[t] = ptrs.p[t]; c.raw_n[t] = 0; }
-        if (t < c.n_img * SVO_MAX_LEVELS) {
+        if (t < c.n_img && !lane_idle(c, t >> 1)) { c.img0[t] = ptrs.p[t]; c.raw_n[t] = 0; }
+        if (t < c.n_img * SVO_MAX_LEVELS && !lane_idle(c, (t / SVO_MAX_LEVELS) >> 1)) {
             c.cand_cnt[t * SVO_CNT_STRIDE] = 0; c.lvl_n[t] = 0;
             // this frame's FAST threshold per (image, level): the speculated one when there is one (ORB mode only; debug
             // mode 12 switches the speculation off), never below the caller's threshold
@@ -110,9 +112,9 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask d
             c.redo_flag[t] = 0;
         }
         if (t == 0) *c.redo_n = 0;
-        if (ahead && t < c.n_lanes) c.det_status[t] = 0;
+        if (ahead && t < c.n_lanes && !lane_idle(c, t)) c.det_status[t] = 0;
     }
-    if (t < c.n_lanes && !(ahead && detect)) {
+    if (t < c.n_lanes && !(ahead && detect) && !lane_idle(c, t)) {
         LaneState& s = c.lane[t];
         if (do_shift) {
             if (!repeat && s.m_error != SVO_VOEC_BAD_TRACKING && s.m_error != SVO_VOEC_BAD_COND_NUMBER) {
@@ -216,7 +218,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
     const uint32_t slot = blockIdx.x >> 3;
     const uint32_t work = c.debug_mode == 8 ? blockIdx.x : (((slot / RZ_CHUNK) * 8 + (blockIdx.x & 7)) * RZ_CHUNK + slot % RZ_CHUNK);
     const int img = (int)fastdiv(work, div_img);
-    if (img >= c.n_img) return;
+    if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const int tt = (int)work - img * per_img, tby = (int)fastdiv((uint32_t)tt, div_ntx), tbx = tt - tby * ntx;
     const int dx0 = tbx * RZ_W, dy0 = tby * RZ_H;
     int spitch; const uint8_t* src = level_ptr(c, img, level - 1, spitch);
@@ -661,7 +663,7 @@ __global__ void __launch_bounds__(FT_NT) __attribute__((amdgpu_waves_per_eu(8, 8
     const uint32_t slot = blockIdx.x >> 3;
     const uint32_t work = c.debug_mode == 8 ? blockIdx.x : (((slot / FT_CHUNK) * 8 + (blockIdx.x & 7)) * FT_CHUNK + slot % FT_CHUNK);
     const int img = (int)fastdiv(work, c.div_tiles), tile_id = (int)work - img * c.n_tiles;
-    if (img >= c.n_img) return;
+    if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const uint4 e = c.fast_tiles[tile_id];                  // x0 | y0 << 16, w | h << 16, level | pitch << 8, level offset in the pyramid
     const uint4 tha = ((const uint4*)(c.fast_th_used + img * SVO_MAX_LEVELS))[0], thb = ((const uint4*)(c.fast_th_used + img * SVO_MAX_LEVELS))[1];
     const uint8_t* base0 = c.img0[img];
@@ -924,6 +926,7 @@ __global__ void __launch_bounds__(512) k_select(DevCtx c, int redo_pass)
     // image index fastest: consecutive workgroups go to consecutive XCDs, so with the level fastest every level-0 block
     // (the heavy ones) landed on the same XCD
     const int level = blockIdx.y, img = blockIdx.x, tid = threadIdx.x;
+    if (lane_idle(c, img >> 1)) return;
     const int K = select_block<SEL_MAX>(c, redo_pass, img, level, keys, sel, hist, scan_s, sv);
     if (K <= 0) return;
     // hand the K winners to k_harris: one CU gathering 868 x 9 scattered rows was bound by its own outstanding-request
@@ -938,6 +941,7 @@ __global__ void __launch_bounds__(256) k_harris(DevCtx c)
 {
     SVO_TL_SCOPE(c, TL_HARRIS, 0);
     const int img = blockIdx.x, level = blockIdx.z, i = blockIdx.y * 256 + threadIdx.x;
+    if (lane_idle(c, img >> 1)) return;
     const LevelGeom& g = c.lv[level];
     const int K = g.quota > 0 ? c.sel_n[img * SVO_MAX_LEVELS + level] : 0;
     if ((int)(blockIdx.y * 256) >= K) return;
@@ -1053,7 +1057,7 @@ __global__ void __launch_bounds__(512) k_select_sort(DevCtx c)
     __shared__ int cnt[SS_NB], off[SS_NB], scan_s[32];
     __shared__ unsigned sv[4];
     const int level = blockIdx.y, img = blockIdx.x, tid = threadIdx.x;
-    if (c.lv[level].quota <= 0) return;
+    if (c.lv[level].quota <= 0 || lane_idle(c, img >> 1)) return;
     const int K = c.sel_n[img * SVO_MAX_LEVELS + level];
     if (K <= 0) return;                                      // lvl_n was zeroed by k_select
     const unsigned long long* gk = c.sel_resp + ((long long)img * SVO_MAX_LEVELS + level) * c.sel_max;
@@ -1145,6 +1149,11 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
     __shared__ uint32_t s_disc_m[SVO_DISC_E], s_disc_x[SVO_DISC_E];
     static_assert(NW * 64 == SVO_BRIEF_NPAIRS && NW * 64 == SVO_DISC_E, "one table entry per thread");
     __shared__ __attribute__((aligned(16))) uint4 s_gh[TL ? 3 * 64 : 1], s_gv[TL ? 3 * 64 : 1];
+    // an idle lane's blocks (svo_process_lanes) leave ahead of the tables and the barrier: the test needs the block's image only
+    if (c.idle.w[0] | c.idle.w[1]) {
+        const int img_b = c.debug_mode == 8 ? (int)(blockIdx.x / gx_div.d) : (int)(fastdiv(blockIdx.x >> 3, gx_div) * 8 + (blockIdx.x & 7));
+        if (img_b < c.n_img && lane_idle(c, img_b >> 1)) return;
+    }
     s_pat[threadIdx.x] = g_brief_patf[threadIdx.x]; s_disc_m[threadIdx.x] = g_disc_m[threadIdx.x]; s_disc_x[threadIdx.x] = g_disc_x[threadIdx.x];
     if (TL && threadIdx.x < 3 * 64) { s_gh[threadIdx.x] = g_blur_gh[threadIdx.x]; s_gv[threadIdx.x] = g_blur_gv[threadIdx.x]; }
     __syncthreads();                                         // the only block barrier: before any wave can leave
@@ -1358,7 +1367,7 @@ __global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
 {
     SVO_TL_SCOPE(c, TL_DESCRIBE, 2);
     const int vs = blockIdx.y, vl = vs >> 1, side = vs & 1, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap;
-    if (oct >= c.n_oct) return;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
     const int cur = 1 - c.lane[lane_id].prev_slot;
     const int n = c.n_kps[feat_cnt_idx(vl, cur, side)];
     const int i = blockIdx.x * 32 + (threadIdx.x >> 3), r = threadIdx.x & 7;
@@ -1395,6 +1404,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int NS_HASH = 2 * NS_MAX;
     const int img = blockIdx.x, oct = blockIdx.y, lane_id = img >> 1, side = img & 1, tid = threadIdx.x;
+    if (lane_idle(c, lane_id)) return;
     const bool raster = do_nms == 3;          // FAST + ORB with the NMS switched off: every corner, in cv::FAST's raster order
     if (raster) do_nms = 0;
     unsigned char* wide = big ? big + ((size_t)img * c.oct_cap + oct) * ((size_t)NS_MAX * 28) : smem;
@@ -1717,6 +1727,7 @@ __global__ void __launch_bounds__(256) k_half(DevCtx c, int level)
 {
     SVO_TL_SCOPE(c, TL_RESIZE, level);
     const int img = blockIdx.z;
+    if (lane_idle(c, img >> 1)) return;
     const LevelGeom& d = c.lv[level];
     const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
     if (x4 >= d.w || y >= d.h) return;
@@ -1791,6 +1802,7 @@ __device__ __forceinline__ void chunked_grid_nms(const DevCtx& c, unsigned char*
     Key* s_prefix = PW ? (Key*)(keys + NS_MAX) : (Key*)(sh + 2);
     unsigned char* state = (unsigned char*)(sh + 4);                       // NS_MAX
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    if (lane_idle(c, img >> 1)) return;
     const LevelGeom& g = c.lv[level];
     unsigned nc = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
     if (nc > (unsigned)g.cand_cap) nc = g.cand_cap;
@@ -1950,6 +1962,7 @@ __global__ void __launch_bounds__(1024) k_fastorb_anms(DevCtx c, uint32_t* by_sc
     __shared__ int scan[40];
     __shared__ unsigned sh[8];
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    if (lane_idle(c, img >> 1)) return;
     const LevelGeom& g = c.lv[level];
     unsigned nc = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
     if (nc > (unsigned)g.cand_cap) nc = g.cand_cap;
@@ -2142,7 +2155,7 @@ __global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* 
     __shared__ unsigned s_n, s_base;
     const int tid = threadIdx.x;
     const int img = (int)fastdiv(blockIdx.x, c.div_tiles), tile_id = (int)blockIdx.x - img * c.n_tiles;
-    if (img >= c.n_img) return;
+    if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const uint4 e = c.fast_tiles[tile_id];                  // x0 | y0 << 16, w | h << 16, level | pitch << 8, level offset in the pyramid
     const int level = (int)(e.z & 0xFFu), gw = (int)(e.y & 0xFFFFu), gh = (int)(e.y >> 16), x0 = (int)(e.x & 0xFFFFu), y0 = (int)(e.x >> 16);
     const uint8_t* src = level == 0 ? c.img0[img] : c.pyr + (long long)img * c.pyr_bytes + e.w;

@@ -443,6 +443,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int PM = P.pmax, LC = PM < GN_LCAP ? PM : GN_LCAP;
     const int lane_id = blockIdx.x, tid = threadIdx.x;
+    if (lane_idle(c, lane_id)) return;
     int* scan = (int*)(smem + (size_t)LC * 30);
     GnShared& sh = *(GnShared*)(scan + 40);
     LaneState& ls = c.lane[lane_id];

@@ -70,7 +70,6 @@ __device__ __forceinline__ void copy_vec16(const void* src, void* dst, size_t nb
     const size_t rest = (nbytes - 16 * n16) / 4;
     if ((size_t)t < rest) ((uint32_t*)dst)[4 * n16 + t] = ((const uint32_t*)src)[4 * n16 + t];
 }
-__device__ __forceinline__ bool lane_bit(const LaneMask& m, int lane) { return (m.w[lane >> 6] >> (lane & 63)) & 1ull; }
 
 // grid (n_vl, parts): block (vl, part) copies a share of the lane-octave's lists.  WIN = false is the kernel of a context that
 // carries no windows (8 parts, dword copies, version 2); WIN = true adds the window sections and copies in 16-byte pieces.

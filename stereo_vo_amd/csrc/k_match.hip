@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(256) k_gather_mdesc(DevCtx c)
 {
     // blockIdx.z: bit 0 = side, bit 1 = 0 previous / 1 current slot; 8 threads per descriptor (one dword each)
     const int vl = blockIdx.y, lane_id = vl / c.oct_cap;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const LaneState& ls = c.lane[lane_id];
     if (!ls.has_prev) return;
     const int side = blockIdx.z & 1, slot = (blockIdx.z & 2) ? 1 - ls.prev_slot : ls.prev_slot;
@@ -86,7 +86,7 @@ __device__ __forceinline__ void hamming_body(const DevCtx& c, int mode, int nspl
     // fastest they sit at the END of the dispatch order.  (With the query block fastest, live and dead workgroups
     // alternate, the dispatcher hands them to the two halves of each XCD in turn, and half the CUs idle: measured 2x.)
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int side = mode ? (blockIdx.z / nsplit) : 0, split = blockIdx.z % nsplit;
     const LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(256) k_hamming_f4(DevCtx c, int mode, int nspl
     __shared__ __attribute__((aligned(16))) hm_v4i tileA[2][8 * 32];           // [buffer][(2 s + kb) * 32 + (row ^ (2 s + kb))]: MFMA s, k-block kb
     __shared__ uint32_t lut[256];                                             // byte of TRAIN bits -> 8 nibbles (bit 1 -> +1 = 0x2, bit 0 -> -1 = 0xA); a query byte goes in complemented
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int side = mode ? (blockIdx.z / nsplit) : 0, split = blockIdx.z % nsplit;
     const LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
@@ -430,7 +430,7 @@ __global__ void __launch_bounds__(1024) k_match_lr_filter(DevCtx c, int one_to_o
     unsigned* right_best = (unsigned*)smem;
     int* scan = (int*)(right_best + lds.n_right_best());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
-    if (oct >= c.n_oct) return;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
     const LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot;
     const int nl = c.n_kps[feat_cnt_idx(vl, cur, 0)], nr = c.n_kps[feat_cnt_idx(vl, cur, 1)];
@@ -510,7 +510,7 @@ __global__ void __launch_bounds__(256) k_match_lr_rbr(DevCtx c, int one_to_one, 
     unsigned* left_pick = right_best + lds.n_right_best();            // per left feature (min_idx << DB | min_1) or ~0
     int* scan = (int*)(left_pick + lds.n_left_pick());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
-    if (oct >= c.n_oct) return;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
     const LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot;
     const int nl = c.n_kps[feat_cnt_idx(vl, cur, 0)], nr = c.n_kps[feat_cnt_idx(vl, cur, 1)];
@@ -628,7 +628,7 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
     unsigned* cur_best = (unsigned*)smem;                           // (dist << 16 | pi) min over claimants
     int* scan = (int*)(cur_best + lds.n_cur_best());
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
-    if (oct >= c.n_oct) return;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
     const LaneState& ls = c.lane[lane_id];
     if (!ls.has_prev) { if (tid == 0) c.trk_nk[vl] = 0; return; }
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
@@ -738,7 +738,7 @@ __global__ void __launch_bounds__(256) k_track_filter(DevCtx c)
     __shared__ int scan[40];
     __shared__ int s_und, s_th;
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, tid = threadIdx.x;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const LaneState& ls = c.lane[lane_id];
     if (!ls.has_prev) { if (tid == 0) c.trk_nk[vl] = 0; return; }
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
@@ -1053,7 +1053,7 @@ __global__ void __launch_bounds__(256) k_ransac_schedule(DevCtx c, int phase)
     SVO_LATENCY_CHAIN(c);
     __shared__ int scan[40];
     const int vl = blockIdx.x;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     rs_schedule_block(c, vl, phase, c.trk_nk[vl], scan);
 }
 
@@ -1313,7 +1313,7 @@ __global__ void __launch_bounds__(256) k_ransac_hyp(DevCtx c, int chunk)
     __shared__ int nm_s[16];
     const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
     const int h = RS_CHUNK_BEGIN(chunk) + blockIdx.x * 16 + grp, side = blockIdx.y, vl = blockIdx.z;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int n = c.trk_nk[vl];
     if (n < 8) return;                  // (exactly seven pairs: findFundamentalMat's direct path, see k_track_finalize)
     // rs_bound is stable while this kernel runs (only k_ransac_count lowers it, and the previous chunk's has finished): what
@@ -1466,7 +1466,7 @@ __global__ void __launch_bounds__(64) k_ransac_hyp_thread(DevCtx c, int chunk)
     SVO_TL_SCOPE(c, TL_RS_HYP, chunk);
     SVO_LATENCY_CHAIN(c);
     const int h = RS_CHUNK_BEGIN(chunk) + blockIdx.x * 64 + threadIdx.x, side = blockIdx.y, vl = blockIdx.z;
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int n = c.trk_nk[vl];
     if (n < 8) return;                  // (exactly seven pairs: findFundamentalMat's direct path, see k_track_finalize)
     const int gen = min(chunk ? min(RS_CHUNK_END(chunk), c.rs_bound[vl * 2 + side]) : RS_CHUNK_END(chunk), c.rs_sched[vl * SVO_RS_ST + 2 + side]);      // (... and no further than the schedule's samples)
@@ -1583,7 +1583,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma(DevCtx c, int chunk)
     SVO_LATENCY_CHAIN(c);
     __shared__ int cnt_s[16];
     const int side = blockIdx.y, vl = blockIdx.z, h0 = 3 * RS_CHUNK_BEGIN(chunk) + blockIdx.x * 16, tid = threadIdx.x;      // first SLOT of the block
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int n = c.trk_nk[vl];
     if (n <= SVO_LMEDS_MAX_N) return;   // (exactly seven pairs: findFundamentalMat's direct path; eight to fourteen: LMedS ranks medians, not counts -- see k_track_finalize)
     if (h0 >= RS_SLOT_END(chunk)) return;
@@ -1688,7 +1688,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma16(DevCtx c, int chunk
     __shared__ double ops[(RC16_SUPER / 16) * 256];            // per tile of 16 pairs: B1 | B2 | phi[0..3] | phi[4..7], each [k][j]
     const int sblk = blockIdx.x / nsplit, split = blockIdx.x % nsplit;                                          // the splits of a group are neighbours in dispatch order
     const int side = blockIdx.y, vl = blockIdx.z, h0 = 3 * RS_CHUNK_BEGIN(chunk) + sblk * 64, tid = threadIdx.x;     // first SLOT of the block
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int n = c.trk_nk[vl];
     if (n <= SVO_LMEDS_MAX_N) return;   // (exactly seven pairs: findFundamentalMat's direct path; eight to fourteen: LMedS ranks medians, not counts -- see k_track_finalize)
     if (h0 >= RS_SLOT_END(chunk)) return;
@@ -1850,7 +1850,7 @@ __global__ void __launch_bounds__(256) k_ransac_count(DevCtx c, int chunk)
     SVO_LATENCY_CHAIN(c);
     __shared__ int cnt_s[RC_HB];
     const int side = blockIdx.y, vl = blockIdx.z, h0 = 3 * RS_CHUNK_BEGIN(chunk) + blockIdx.x * RC_HB, tid = threadIdx.x;      // first SLOT of the block
-    if (vl % c.oct_cap >= c.n_oct) return;
+    if (vl % c.oct_cap >= c.n_oct || lane_idle(c, vl / c.oct_cap)) return;
     const int n = c.trk_nk[vl];
     if (n <= SVO_LMEDS_MAX_N) return;   // (exactly seven pairs: findFundamentalMat's direct path; eight to fourteen: LMedS ranks medians, not counts -- see k_track_finalize)
     if (h0 >= RS_SLOT_END(chunk)) return;
@@ -1908,7 +1908,7 @@ __global__ void __launch_bounds__(256) k_track_finalize(DevCtx c, int win_mode, 
     int* scan = (int*)(in_r + lds.n_in());
     __shared__ int s_best[2], s_cnt[2], s_vis[2], s_both;
     const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, tid = threadIdx.x;
-    if (oct >= c.n_oct) return;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
     LaneState& ls = c.lane[lane_id];
     if (!ls.has_prev) {
         if (tid == 0) { c.n_tracked[vl] = 0; if (gate_th >= 0) { svo_result& res = c.results[lane_id]; res.error_code = SVO_VOEC_FIRST_ITERATION; res.valid = 0; } }       // P:348-352
@@ -2128,7 +2128,7 @@ __global__ void k_track_gate(DevCtx c, int bad_tracking_th)
 {
     SVO_TL_SCOPE(c, TL_TRK_FINAL, 1);
     const int lane_id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane_id >= c.n_lanes) return;
+    if (lane_id >= c.n_lanes || lane_idle(c, lane_id)) return;          // (one thread per lane)
     LaneState& ls = c.lane[lane_id];
     svo_result& res = c.results[lane_id];
     if (!ls.has_prev) { res.error_code = SVO_VOEC_FIRST_ITERATION; res.valid = 0; return; }
@@ -2154,6 +2154,7 @@ __global__ void __launch_bounds__(256) k_match_ids(DevCtx c, unsigned flags)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* tracked_flag = smem;                  // LdsMatchIds: the block's only array
     const int lane_id = blockIdx.x, tid = threadIdx.x;
+    if (lane_idle(c, lane_id)) return;
     LaneState& ls = c.lane[lane_id];
     const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
     int next_id = ls.last_match_id, kf_max = ls.last_kf_max_id;

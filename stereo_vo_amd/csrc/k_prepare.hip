@@ -20,6 +20,7 @@ __device__ __forceinline__ int grey_at(const uint8_t* p, int channels)
 __global__ void __launch_bounds__(256) k_prepare(PrepArgs a)
 {
     const int img = blockIdx.z;
+    if (lane_bit(a.idle, img >> 1)) return;          // the lane sits this call out (svo_process_lanes): its source pointers are not even valid
     const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x4 >= a.w || y >= a.h) return;
     const uint8_t* src = a.src[img];

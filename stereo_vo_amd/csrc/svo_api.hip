@@ -110,12 +110,15 @@ struct svo_ctx {
     // such frame yet" (the kernels then read nothing).  The device decides the prev/cur shift (the recovery rule of P:86-95 needs
     // m_error), so the previous frame after a shift is known to have patches only when both candidates for it had them.
     std::vector<uint8_t> sad_cur, sad_prev, sad_drop;  // sad_drop: the lane's next shift forgets its previous frame (svo_hip.h)
-    bool imported_pending;                             // svo_import_frame ran since the last svo_process
+    LaneMask imported;                                 // lanes that svo_import_frame has written and that have not had a svo_process call since (an idle lane keeps its bit)
+    // svo_process_lanes: the active mask of the call that began the frame in flight.  The later calls of a multi-call frame (the post
+    // call of a detect call, stages run with SVO_FLAG_NO_SHIFT) must carry the same one.
+    LaneMask frame_active; bool frame_active_set;
     int sampler_nmax;                                  // > 0: holds a reference on the shared sampler table of (device, sampler_nmax)
     hipEvent_t post_event;                             // svo_record_after_post: armed for the next call that runs the detector's post-processing
     // svo_use_graphs: the kernel sequence of a frame captured once per (flags, ring slot, thresholds) and replayed
     struct GraphEntry { uint32_t flags; int slot, fast_th, orb_th; hipGraphExec_t exec; };
-    std::vector<GraphEntry> graphs; bool use_graphs;
+    std::vector<GraphEntry> graphs; bool use_graphs; unsigned graph_replays;      // graph_replays: calls served by an earlier capture (svo_debug_get_graph_count)
     // every stream that has had work of this context enqueued since the last full synchronisation (svo_set_stream), each with
     // a context-owned event recorded behind the last work enqueued on it.  Synchronising waits on the EVENTS, never on the
     // foreign stream handles: a caller may synchronise and destroy its own stream and switch back with svo_set_stream(NULL);
@@ -125,6 +128,7 @@ struct svo_ctx {
 };
 
 static void drop_graphs(svo_ctx* ctx);
+static inline bool lane_in(const LaneMask& m, int l) { return ((m.w[l >> 6] >> (l & 63)) & 1ull) != 0; }
 static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
 static void sampler_table_release(int device, int nmax);
@@ -365,7 +369,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
-    ctx->imported_pending = false; ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr;
+    memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr;
     ctx->sad_cur.assign((size_t)cfg->n_lanes, 1); ctx->sad_prev.assign((size_t)cfg->n_lanes, 1); ctx->sad_drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
@@ -891,16 +895,19 @@ static int ensure_upload(svo_ctx* ctx)
 // page-locked (SVO_FLAG_PINNED_IMAGES): the call returns while the copy is in flight and the caller keeps the images
 // valid until svo_wait_upload / svo_wait.  Pageable images are first copied into the context's own page-locked
 // staging slot (that is the cost of "borrowed for the duration of the call", P:111-120), then uploaded the same way.
-static int upload_frames(svo_ctx* ctx, const svo_frame* frames, int w, int h, bool pinned, hipStream_t st, const uint8_t** ptrs)
+// idle: lanes that sit the call out (svo_process_lanes) -- their images are neither copied nor uploaded, frames[l] is not read
+static int upload_frames(svo_ctx* ctx, const svo_frame* frames, int w, int h, bool pinned, hipStream_t st, const uint8_t** ptrs, const LaneMask& idle)
 {
+    auto is_idle = [&](int l) { return lane_in(idle, l); };
+    const bool partial = (idle.w[0] | idle.w[1]) != 0;
     int rc = ensure_upload(ctx); if (rc) return rc;
     const int L = ctx->cfg.n_lanes, ipitch = ctx->img0_pitch_internal, slot = ctx->up_slot;
     const size_t img_bytes = (size_t)ipitch * ctx->cfg.max_h;
     uint8_t* dbase = ctx->d_img0_ring[slot];
     // the slot's previous frame must be through stage 2 (the only stage that reads level 0) before it is overwritten
     if (ctx->ev_det_valid[slot]) HIPCHECK(hipStreamWaitEvent(ctx->s_copy, ctx->ev_det[slot], 0));
-    const uint8_t* src0 = frames[0].left.data;
-    bool contiguous = (w == ipitch) && (h == ctx->cfg.max_h);
+    const uint8_t* src0 = partial ? nullptr : frames[0].left.data;
+    bool contiguous = !partial && (w == ipitch) && (h == ctx->cfg.max_h);
     for (int l = 0; l < L && contiguous; l++)
         for (int sd = 0; sd < 2; sd++) {
             const svo_image& im = sd ? frames[l].right : frames[l].left;
@@ -910,6 +917,7 @@ static int upload_frames(svo_ctx* ctx, const svo_frame* frames, int w, int h, bo
         if (contiguous) HIPCHECK(hipMemcpyAsync(dbase, src0, img_bytes * 2 * L, hipMemcpyHostToDevice, ctx->s_copy));       // [lane][side][h][w] in one piece
         else for (int l = 0; l < L; l++)
             for (int sd = 0; sd < 2; sd++) {
+                if (is_idle(l)) continue;
                 const svo_image& im = sd ? frames[l].right : frames[l].left;
                 HIPCHECK(hipMemcpy2DAsync(dbase + (size_t)(2 * l + sd) * img_bytes, ipitch, im.data, (size_t)im.stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->s_copy));
             }
@@ -918,13 +926,14 @@ static int upload_frames(svo_ctx* ctx, const svo_frame* frames, int w, int h, bo
         if (ctx->ev_h2d_valid[slot]) HIPCHECK(hipEventSynchronize(ctx->ev_h2d[slot]));          // the staging slot's last upload has left it
         for (int l = 0; l < L; l++)
             for (int sd = 0; sd < 2; sd++) {
+                if (is_idle(l)) continue;
                 const svo_image& im = sd ? frames[l].right : frames[l].left;
                 uint8_t* hs = ctx->h_stage[slot] + (size_t)(2 * l + sd) * img_bytes;
                 if (im.stride == (int64_t)ipitch && w == ipitch) memcpy(hs, im.data, (size_t)ipitch * h);
                 else for (int y = 0; y < h; y++) memcpy(hs + (size_t)y * ipitch, im.data + (size_t)y * im.stride, (size_t)w);
             }
-        if (h == ctx->cfg.max_h) HIPCHECK(hipMemcpyAsync(dbase, ctx->h_stage[slot], img_bytes * 2 * L, hipMemcpyHostToDevice, ctx->s_copy));
-        else for (int i = 0; i < 2 * L; i++) HIPCHECK(hipMemcpyAsync(dbase + (size_t)i * img_bytes, ctx->h_stage[slot] + (size_t)i * img_bytes, (size_t)ipitch * h, hipMemcpyHostToDevice, ctx->s_copy));
+        if (h == ctx->cfg.max_h && !partial) HIPCHECK(hipMemcpyAsync(dbase, ctx->h_stage[slot], img_bytes * 2 * L, hipMemcpyHostToDevice, ctx->s_copy));
+        else for (int i = 0; i < 2 * L; i++) if (!is_idle(i >> 1)) HIPCHECK(hipMemcpyAsync(dbase + (size_t)i * img_bytes, ctx->h_stage[slot] + (size_t)i * img_bytes, (size_t)ipitch * h, hipMemcpyHostToDevice, ctx->s_copy));
     }
     HIPCHECK(hipEventRecord(ctx->ev_h2d[slot], ctx->s_copy)); ctx->ev_h2d_valid[slot] = true;
     HIPCHECK(hipStreamWaitEvent(st, ctx->ev_h2d[slot], 0));
@@ -960,17 +969,33 @@ extern "C" int svo_host_register(void* p, size_t bytes) { return (p && bytes && 
 extern "C" int svo_host_unregister(void* p) { return (p && hipHostUnregister(p) == hipSuccess) ? SVO_OK : SVO_ERR_HIP; }
 
 // ---- processNewImagePair ---------------------------------------------------------------------------------
-extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags)
+// The body of svo_process (lanes == NULL: every lane) and svo_process_lanes (one bit per lane that takes part).
+static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, const svo_frame* frames, uint32_t flags)
 {
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();                               // svo_last_error speaks of THIS call: a refusal below that sets no text must not inherit an earlier one
+    // the mask first, without leaving: who is active, who sits out, and whether the mask itself is acceptable
+    LaneMask active, idle; bool bad_mask = masked && !lanes; unsigned long long bad_word = 0; int bad_wd = 0;
+    for (int wd = 0; wd < 2; wd++) {
+        const int n = ctx->cfg.n_lanes - wd * 64 < 0 ? 0 : (ctx->cfg.n_lanes - wd * 64 > 64 ? 64 : ctx->cfg.n_lanes - wd * 64);
+        const unsigned long long all = n == 64 ? ~0ull : ((1ull << n) - 1ull), a = lanes ? (unsigned long long)lanes[wd] : all;
+        if ((a & ~all) && !bad_mask) { bad_mask = true; bad_word = a; bad_wd = wd; }
+        active.w[wd] = a & all; idle.w[wd] = all & ~a;
+    }
+    const bool partial = (idle.w[0] | idle.w[1]) != 0, nobody = !bad_mask && (active.w[0] | active.w[1]) == 0;
+    auto is_idle = [&](int l) { return lane_in(idle, l); };
     // svo_record_after_post arms ONE call: the next one that runs the detector's post-processing.  Whatever way that call leaves --
-    // an argument check, SVO_ERR_STATE, a failed launch -- the event is recorded behind what was enqueued (possibly nothing) and
-    // disarmed, so that a waiter is released and a later, unrelated call cannot record it at the wrong point.
+    // an argument check (the mask's included), SVO_ERR_STATE, a failed launch -- the event is recorded behind what was enqueued
+    // (possibly nothing) and disarmed, so that a waiter is released and a later, unrelated call cannot record it at the wrong point
+    // (ADVICE r04).  A call in which nobody takes part is no call: it leaves the event armed.
     struct PostDisarm { svo_ctx* c; bool consumes; ~PostDisarm() { if (consumes && c->post_event) { hipStreamCaptureStatus cs = hipStreamCaptureStatusNone; hipStreamIsCapturing(c->stream, &cs);
                                                                     if (cs == hipStreamCaptureStatusNone) hipEventRecord(c->post_event, c->stream); c->post_event = nullptr; } } }
-        post_disarm{ ctx, (flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST)) };
+        post_disarm{ ctx, !nobody && ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST))) };
+    if (bad_mask) {
+        char msg[160];
+        if (!lanes) snprintf(msg, sizeof(msg), "active == NULL");
+        else snprintf(msg, sizeof(msg), "active[%d] = %016llx selects a lane at or above n_lanes = %d", bad_wd, bad_word, ctx->cfg.n_lanes);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    if (nobody) return SVO_OK;                              // nothing is enqueued, no state moves
     const svo_params& p = ctx->params;
     // P:54-76: invalid selectors are hard errors; the variants outside the hot path are refused explicitly
     if (p.detect_method < 0 || p.detect_method > 3 || p.match_method < 0 || p.match_method > 2 || p.ifm_method < 0 || p.ifm_method > 3) return SVO_ERR_ARG;
@@ -998,8 +1023,17 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         if (flags & SVO_RUN_DETECT) { if (!(flags & SVO_FLAG_DETECT_NO_POST) || (flags & (SVO_RUN_MATCH | SVO_RUN_TRACK | SVO_RUN_OPTIMIZE | SVO_RUN_DETECT_POST))) return SVO_ERR_ARG; }
         else if (!(flags & SVO_RUN_DETECT_POST) || (flags & SVO_FLAG_NO_SHIFT)) return SVO_ERR_ARG;
     }
-    Section sec_all("processNewImagePair");                                       // P:79, 377
     DevCtx& d = ctx->dc;
+    // the calls of one frame carry one mask: what a frame's first call (any call that is not a continuation) ran with is what its
+    // post call and its SVO_FLAG_NO_SHIFT stages must run with -- refused here, before anything is enqueued or noted
+    const bool continuation = !(flags & SVO_RUN_DETECT) && (flags & (SVO_FLAG_NO_SHIFT | SVO_RUN_DETECT_POST));
+    if (continuation && ctx->frame_active_set && memcmp(&active, &ctx->frame_active, sizeof(active)) != 0) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "active lanes %016llx:%016llx, but the frame in flight began with %016llx:%016llx: every call of a frame carries the same mask",
+                 active.w[1], active.w[0], ctx->frame_active.w[1], ctx->frame_active.w[0]);
+        ctx->last_error = msg; return SVO_ERR_STATE;
+    }
+    Section sec_all("processNewImagePair");                                       // P:79, 377
     const hipStream_t st = ctx->stream;
     note_stream(ctx);
     bool capturing = false;
@@ -1010,8 +1044,10 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     PrepArgs prep; memset(&prep, 0, sizeof(prep)); bool prepare = false;
     if (flags & SVO_RUN_DETECT) {
         if (!frames) return SVO_ERR_ARG;                    // P:81
-        const int w = frames[0].left.w, h = frames[0].left.h;
+        int l0 = 0; while (is_idle(l0)) l0++;               // the first active lane: what the others must agree with
+        const int w = frames[l0].left.w, h = frames[l0].left.h;
         for (int l = 0; l < d.n_lanes; l++) {
+            if (is_idle(l)) continue;                       // (its frames[] entry is not read: it may hold NULL pointers)
             const svo_frame& f = frames[l];
             if (!f.left.data || !f.right.data || f.left.w != w || f.left.h != h || f.right.w != w || f.right.h != h) return SVO_ERR_ARG;
         }
@@ -1020,6 +1056,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         // address it with 32-bit byte offsets from its base.  Refused here, before anything is enqueued.
         for (int l = 0; l < d.n_lanes; l++)
             for (int s = 0; s < 2; s++) {
+                if (is_idle(l)) continue;
                 const svo_image& im = s ? frames[l].right : frames[l].left;
                 char msg[200];
                 if (w < 1 || h < 1) {
@@ -1040,14 +1077,15 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         if (ctx->n_maps > 0 && (ctx->map_w != w || ctx->map_h != h)) return SVO_ERR_ARG;
         const int ipitch = ctx->img0_pitch_internal;
         if (flags & SVO_FLAG_DEVICE_IMAGES) {
-            const long long stride = frames[0].left.stride;
+            const long long stride = frames[l0].left.stride;
             for (int l = 0; l < d.n_lanes; l++) {
+                if (is_idle(l)) { ptrs[2 * l] = nullptr; ptrs[2 * l + 1] = nullptr; continue; }
                 if (frames[l].left.stride != stride || frames[l].right.stride != stride) { ctx->last_error = "device frames of one call must share one stride"; return SVO_ERR_ARG; }
                 ptrs[2 * l] = frames[l].left.data; ptrs[2 * l + 1] = frames[l].right.data;
             }
             d.img0_pitch = (int)stride;
             if (prepare) { for (int i = 0; i < 2 * d.n_lanes; i++) prep.src[i] = ptrs[i]; prep.src_stride = stride; }
-            else if (ctx->use_graphs) {
+            else if (ctx->use_graphs && !partial) {
                 // a captured frame reads fixed addresses: the images go to the ring slot first (device to device, same stream)
                 rc = ensure_upload(ctx); if (rc) return rc;
                 const int slot = ctx->up_slot; ctx->up_slot = slot ^ 1; ctx->det_slot = slot;
@@ -1060,12 +1098,13 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
                 d.img0_pitch = ipitch;
             }
         } else if (!prepare) {
-            rc = upload_frames(ctx, frames, w, h, (flags & SVO_FLAG_PINNED_IMAGES) != 0, st, ptrs); if (rc) return rc;
+            rc = upload_frames(ctx, frames, w, h, (flags & SVO_FLAG_PINNED_IMAGES) != 0, st, ptrs, idle); if (rc) return rc;
             d.img0_pitch = ipitch;
         } else {
             if (!ctx->d_src) { ctx->src_pitch = align_up(3 * ctx->cfg.max_w, 64); HIPCHECK(dev_alloc(ctx, &ctx->d_src, (size_t)2 * ctx->cfg.n_lanes * ctx->src_pitch * ctx->cfg.max_h)); }
             for (int l = 0; l < d.n_lanes; l++)
                 for (int s = 0; s < 2; s++) {
+                    if (is_idle(l)) continue;
                     const svo_image& im = s ? frames[l].right : frames[l].left;
                     uint8_t* dst = ctx->d_src + (size_t)(2 * l + s) * ctx->src_pitch * ctx->cfg.max_h;
                     HIPCHECK(hipMemcpy2DAsync(dst, ctx->src_pitch, im.data, (size_t)im.stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
@@ -1078,7 +1117,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
             d.img0_pitch = ipitch;
             prep.maps = ctx->n_maps > 0 ? (const uint2* const*)ctx->d_map_ptrs : nullptr;
             prep.dst = ctx->d_img0; prep.dst_img_stride = (long long)ipitch * ctx->cfg.max_h; prep.dst_pitch = ipitch;
-            prep.channels = ch; prep.w = w; prep.h = h;
+            prep.channels = ch; prep.w = w; prep.h = h; prep.idle = idle;
         }
     } else if (!ctx->geom_ready && (flags & (SVO_RUN_MATCH | SVO_RUN_OPTIMIZE))) return SVO_ERR_STATE;
     d.fast_th = ctx->fast_th; d.orb_th = ctx->orb_th;
@@ -1101,6 +1140,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
         std::vector<uint8_t> cur = ctx->sad_cur, prev = ctx->sad_prev, drop = ctx->sad_drop;
         int bad_lane = -1; bool bad_prev = false;
         for (int l = 0; l < d.n_lanes; l++) {
+            if (is_idle(l)) continue;                        // (sad_drop of an idle lane waits for the lane's next active frame)
             if (shifts) {
                 if (drop[l]) { drop_prev.w[l >> 6] |= 1ull << (l & 63); any_drop = true; prev[l] = 1; drop[l] = 0; }
                 else if (!repeat) prev[l] = prev[l] && cur[l];
@@ -1117,20 +1157,28 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
                      bad_prev ? "previous" : "current", (bad_prev && shifts && !repeat) ? ": this frame is refused, the next one starts the lane's track afresh" : "");
             ctx->last_error = msg;
             // the frame before cannot be tracked from with SAD, and its image is gone: the next frame of such a lane forgets it
-            if (bad_prev && shifts && !repeat) for (int l = 0; l < d.n_lanes; l++) if (!ctx->sad_prev[l] || !ctx->sad_cur[l]) ctx->sad_drop[l] = 1;
+            if (bad_prev && shifts && !repeat) for (int l = 0; l < d.n_lanes; l++) if (!is_idle(l) && (!ctx->sad_prev[l] || !ctx->sad_cur[l])) ctx->sad_drop[l] = 1;
             return SVO_ERR_STATE;
         }
         ctx->sad_cur = cur; ctx->sad_prev = prev; ctx->sad_drop = drop;
     }
-    const bool graph_ok = ctx->use_graphs && !prepare && !ctx->cfg.kernel_times && !any_drop && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
+    if (!continuation) { ctx->frame_active = active; ctx->frame_active_set = true; }
+    // the idle lanes travel in DevCtx to every launch below; outside this call the mask is all zero (the other entry points launch with it)
+    d.idle = idle;
+    struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } } idle_guard{ &d };
+    // (a call with idle lanes runs as plain launches, as one with any_drop does: the mask is a kernel argument)
+    // svo_import_frame writes every lane; the lanes of this call that it wrote and that have had no call since (all of them or none)
+    const bool imported_pending = ((ctx->imported.w[0] & active.w[0]) | (ctx->imported.w[1] & active.w[1])) != 0;
+    const bool graph_ok = ctx->use_graphs && !partial && !prepare && !ctx->cfg.kernel_times && !any_drop && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
     const uint32_t gflags = flags & ~(uint32_t)(SVO_FLAG_DEVICE_IMAGES | SVO_FLAG_PINNED_IMAGES);
     const int gslot = (flags & SVO_RUN_DETECT) ? ctx->det_slot : -1;
     if (graph_ok) {
-        const bool ids_first = p.vo_use_matches_ids && ctx->imported_pending;       // changes one kernel argument: not replayable
+        const bool ids_first = p.vo_use_matches_ids && imported_pending;            // changes one kernel argument: not replayable
         for (auto& g : ctx->graphs)
             if (!ids_first && g.flags == gflags && g.slot == gslot && g.fast_th == ctx->fast_th && g.orb_th == ctx->orb_th) {
                 HIPCHECK(hipGraphLaunch(g.exec, st));
-                ctx->imported_pending = false;
+                ctx->graph_replays++;
+                for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];
                 if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && ctx->up_ready && ctx->det_slot >= 0) { HIPCHECK(hipEventRecord(ctx->ev_det[ctx->det_slot], st)); ctx->ev_det_valid[ctx->det_slot] = true; }
                 if (ctx->post_event && ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST)))) { HIPCHECK(hipEventRecord(ctx->post_event, st)); ctx->post_event = nullptr; }
                 return SVO_OK;
@@ -1251,8 +1299,8 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     }
     // (after svo_import_frame the lane may turn out to be at its stream's FIRST frame: the first-frame ID rule of S3:172-173
     // then applies in this call although stage 3 ran in an earlier one)
-    if (p.vo_use_matches_ids && (flags & (SVO_RUN_MATCH | SVO_RUN_TRACK))) { Span s(ctx, KT_TRK_FINAL); launch_match_ids(d, flags | (ctx->imported_pending ? SVO_RUN_MATCH : 0), st); }
-    ctx->imported_pending = false;
+    if (p.vo_use_matches_ids && (flags & (SVO_RUN_MATCH | SVO_RUN_TRACK))) { Span s(ctx, KT_TRK_FINAL); launch_match_ids(d, flags | (imported_pending ? SVO_RUN_MATCH : 0), st); }
+    for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];       // (a lane that sat this call out keeps its bit for its own next call)
     if (flags & SVO_RUN_OPTIMIZE) {
         Section sec("_stg5");                                                        // S5:398, 729
         GNParams g; memset(&g, 0, sizeof(g));
@@ -1281,6 +1329,23 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
     }
     HIPCHECK(hipGetLastError());
     return SVO_OK;
+}
+
+extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();                               // svo_last_error speaks of THIS call: a refusal below that sets no text must not inherit an earlier one
+    return process_lanes_body(ctx, nullptr, false, frames, flags);
+}
+
+// svo_process for the lanes whose bit is set; for the others as if the call had not been made (svo_hip.h)
+extern "C" int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t active[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    return process_lanes_body(ctx, active, true, frames, flags);
 }
 
 extern "C" int svo_record_after_post(svo_ctx* ctx, void* event)
@@ -1696,7 +1761,7 @@ extern "C" int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes
     note_stream(ctx);
     const int need_windows = ctx->params.ifm_method == SVO_IFM_SAD ? 1 : 0;
     { Span s(ctx, ctx->dc.carry_win ? KT_IMPORT_WIN : KT_IMPORT); launch_import_frame(ctx->dc, (const uint8_t*)dev_blob, bytes, need_windows, ctx->stream); }
-    ctx->imported_pending = true;
+    for (int l = 0; l < ctx->cfg.n_lanes; l++) ctx->imported.w[l >> 6] |= 1ull << (l & 63);
     // a record without windows leaves none behind; one with them brings them, and where it does not (an older kind of record, a frame
     // whose windows were never gathered) the device has already made the lane start afresh if the tracker in force is ifmSAD
     for (int l = 0; l < ctx->cfg.n_lanes; l++) { ctx->sad_prev[l] = ctx->dc.carry_win ? 1 : 0; if (ctx->dc.carry_win) ctx->sad_drop[l] = 0; }
@@ -2032,6 +2097,14 @@ extern "C" int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, 
         HIPCHECK(hipMemcpy(ctx->dc.tl, all.data(), all.size() * sizeof(TlRec), hipMemcpyHostToDevice));
     }
     return ctx->dc.tl_step;
+}
+
+extern "C" int svo_debug_get_graph_count(svo_ctx* ctx, uint32_t* captured, uint32_t* replayed)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (captured) *captured = (uint32_t)ctx->graphs.size();
+    if (replayed) *replayed = ctx->graph_replays;
+    return SVO_OK;
 }
 
 extern "C" int svo_debug_get_status_word(svo_ctx* ctx, int lane, uint32_t* w)

@@ -188,13 +188,16 @@ extern "C" int svo_batch_switch_results_buffer(svo_batch* b, void* dev_records, 
     return SVO_OK;
 }
 
-static int batch_step_impl(svo_batch* b, const svo_frame* frames, uint32_t flags);
+static int batch_step_impl(svo_batch* b, const svo_frame* frames, uint32_t flags, const uint64_t* active);
 
-extern "C" int svo_batch_step(svo_batch* b, const svo_frame* frames, uint32_t flags)
+extern "C" int svo_batch_step(svo_batch* b, const svo_frame* frames, uint32_t flags) { return svo_batch_step_lanes(b, frames, flags, nullptr); }
+
+// active: ceil(svo_batch_lanes / 64) words, bit (lane & 63) of word lane >> 6 in GLOBAL lane order; NULL = every stream (svo_batch_step)
+extern "C" int svo_batch_step_lanes(svo_batch* b, const svo_frame* frames, uint32_t flags, const uint64_t* active)
 {
     if (!b) return SVO_ERR_ARG;
     b->step_started = false;
-    const int rc = batch_step_impl(b, frames, flags);
+    const int rc = batch_step_impl(b, frames, flags, active);
     if (rc == SVO_OK || b->step_started) b->held.clear();      // the held events belong to the step that was ENQUEUED (wholly or in part): a call refused
                                                                // before anything was enqueued (NULL frames, unknown flags) keeps them for the caller's retry
     if (rc != SVO_OK && b->step_started) {    // (an argument refused before anything was enqueued leaves the event chain intact)
@@ -207,9 +210,24 @@ extern "C" int svo_batch_step(svo_batch* b, const svo_frame* frames, uint32_t fl
     return rc;
 }
 
-static int batch_step_impl(svo_batch* b, const svo_frame* frames, uint32_t flags)
+// context k's slice of the global mask as the two words svo_process_lanes takes; returns whether any of its lanes is active
+static bool slice_mask(const svo_batch* b, const uint64_t* active, int k, uint64_t out[2])
+{
+    out[0] = out[1] = 0;
+    for (int l = 0; l < b->Bc; l++) {
+        const int g = k * b->Bc + l;
+        if (!active || ((active[g >> 6] >> (g & 63)) & 1ull)) out[l >> 6] |= 1ull << (l & 63);
+    }
+    return (out[0] | out[1]) != 0;
+}
+
+static int batch_step_impl(svo_batch* b, const svo_frame* frames, uint32_t flags, const uint64_t* active)
 {
     if (!frames || (flags & ~IMG_FLAGS)) return SVO_ERR_ARG;
+    if (active) {                                   // a bit at or above svo_batch_lanes: refused before anything is enqueued
+        const int nw = (b->B + 63) / 64, tail = b->B & 63;
+        if (tail && (active[nw - 1] >> tail)) { b->last_error = "svo_batch_step_lanes: the mask selects a stream at or above svo_batch_lanes = " + std::to_string(b->B); return SVO_ERR_ARG; }
+    }
     BHIP(b, hipSetDevice(b->cfg.ctx.device));
     const size_t rsz = sizeof(svo_result);
     const uint32_t AH = b->ahead ? (uint32_t)SVO_FLAG_DETECT_AHEAD : 0u;
@@ -220,28 +238,41 @@ static int batch_step_impl(svo_batch* b, const svo_frame* frames, uint32_t flags
         svo_ctx* c = b->ctx[(size_t)k];
         const svo_frame* pk = frames + (size_t)k * b->Bc;
         uint8_t* dst = b->rec + (size_t)k * b->Bc * rsz;
+        uint64_t am[2];
+        if (!slice_mask(b, active, k, am)) {
+            // none of this context's streams has a frame: no launch.  Its records -- unchanged -- still go to the step's records buffer
+            // (the caller may have switched buffers), behind the context's earlier work on the same stream, and the event the next
+            // step and svo_batch_wait_on_stream look at is recorded behind that copy; det_done / scratch_free keep what the context's
+            // last real step left in them, which is what its next detect call has to wait for.
+            hipStream_t s = b->pipelined ? b->s_rests[(size_t)k % b->s_rests.size()] : b->own[(size_t)k];
+            BSVO(b, c, svo_set_stream(c, b->pipelined ? s : nullptr));
+            for (hipEvent_t h : b->held) BHIP(b, hipStreamWaitEvent(s, h, 0));
+            BSVO(b, c, svo_copy_results_async(c, dst, (size_t)b->Bc * rsz));
+            BHIP(b, hipEventRecord(b->pipelined ? b->rest_done[(size_t)k] : b->done[(size_t)k], s));
+            continue;
+        }
         if (b->pipelined) {
             hipStream_t s_det = b->s_dets[(size_t)k % b->s_dets.size()], s_rest = b->s_rests[(size_t)k % b->s_rests.size()];
             if (!b->first) BHIP(b, hipStreamWaitEvent(s_det, b->ahead ? b->scratch_free[(size_t)k] : b->rest_done[(size_t)k], 0));
             BSVO(b, c, svo_set_stream(c, s_det));
-            BSVO(b, c, svo_process(c, pk, SVO_RUN_DETECT | AH | (b->ahead ? (uint32_t)SVO_FLAG_NO_SHIFT : 0u) | (b->cfg.post_mode ? (uint32_t)SVO_FLAG_DETECT_NO_POST : 0u) | (b->cfg.post_mode == 3 ? (uint32_t)SVO_FLAG_DETECT_SPLIT_AT_SELECT : 0u) | flags));
+            BSVO(b, c, svo_process_lanes(c, pk, SVO_RUN_DETECT | AH | (b->ahead ? (uint32_t)SVO_FLAG_NO_SHIFT : 0u) | (b->cfg.post_mode ? (uint32_t)SVO_FLAG_DETECT_NO_POST : 0u) | (b->cfg.post_mode == 3 ? (uint32_t)SVO_FLAG_DETECT_SPLIT_AT_SELECT : 0u) | flags, am));
             if (b->cfg.post_mode == 2) {
                 BHIP(b, hipEventRecord(b->pre_done[(size_t)k], s_det));
                 BHIP(b, hipStreamWaitEvent(b->s_post, b->pre_done[(size_t)k], 0));
                 BSVO(b, c, svo_set_stream(c, b->s_post));
-                BSVO(b, c, svo_process(c, nullptr, SVO_RUN_DETECT_POST | SVO_FLAG_NO_SHIFT));
+                BSVO(b, c, svo_process_lanes(c, nullptr, SVO_RUN_DETECT_POST | SVO_FLAG_NO_SHIFT, am));
                 BHIP(b, hipEventRecord(b->det_done[(size_t)k], b->s_post));
             } else BHIP(b, hipEventRecord(b->det_done[(size_t)k], s_det));
             BHIP(b, hipStreamWaitEvent(s_rest, b->det_done[(size_t)k], 0));
             BSVO(b, c, svo_set_stream(c, s_rest));
             if (b->ahead) BSVO(b, c, svo_record_after_post(c, b->scratch_free[(size_t)k]));
-            BSVO(b, c, svo_process(c, nullptr, REST));
+            BSVO(b, c, svo_process_lanes(c, nullptr, REST, am));
             for (hipEvent_t h : b->held) BHIP(b, hipStreamWaitEvent(s_rest, h, 0));       // only the record copy waits for a reader of the records buffer
             BSVO(b, c, svo_copy_results_async(c, dst, (size_t)b->Bc * rsz));
             BHIP(b, hipEventRecord(b->rest_done[(size_t)k], s_rest));
         } else {
             BSVO(b, c, svo_set_stream(c, nullptr));
-            BSVO(b, c, svo_process(c, pk, SVO_RUN_ALL | flags));
+            BSVO(b, c, svo_process_lanes(c, pk, SVO_RUN_ALL | flags, am));
             for (hipEvent_t h : b->held) BHIP(b, hipStreamWaitEvent(b->own[(size_t)k], h, 0));
             BSVO(b, c, svo_copy_results_async(c, dst, (size_t)b->Bc * rsz));
             BHIP(b, hipEventRecord(b->done[(size_t)k], b->own[(size_t)k]));

@@ -90,6 +90,9 @@ struct LaneState {
     int prev_no_win;      // the previous frame came in through a hand-over record without the SAD matchers' windows (k_handover.hip); cleared by the next shift
 };
 
+// one bit per lane: bit l of w[l >> 6] (kernel argument of k_begin_frame and the hand-over kernels, and DevCtx.idle)
+struct LaneMask { unsigned long long w[(SVO_MAX_LANES + 63) / 64]; };
+
 // Octaves: in the FAST+ORB mode (stage2_detect.cpp:502-515) the reference works on nOctaves x1/2 images per eye and
 // keeps one feature / pairing / track list per octave.  Every per-lane list below is therefore indexed by the
 // "lane-octave" vl = lane * oct_cap + octave (oct_cap = svo_config.max_octaves; ORB mode uses octave 0 only).
@@ -203,6 +206,8 @@ struct DevCtx {
     // (TlScope below): (time in, time out) on the device-wide 100 MHz wall clock.
     struct TlRec* tl;
     int tl_step;              // frame counter of the context (host side: advanced by every call that runs the detector)
+    LaneMask idle;            // lanes that take no part in the call being enqueued (svo_process_lanes; all zero otherwise): every kernel of a
+                              // frame leaves such a lane's blocks at once (lane_idle below), so nothing observable of the lane changes
     int carry_win;            // the context's hand-over records carry the SAD windows (version 3): from the first svo_set_params that selects smSAD or ifmSAD, for good
 };
 
@@ -254,6 +259,12 @@ struct TlScope {
 };
 #define SVO_TL_SCOPE(c, kind, aux) TlScope _tl_scope((c), (kind), (aux))
 #endif
+
+__device__ __forceinline__ bool lane_bit(const LaneMask& m, int lane) { return (m.w[lane >> 6] >> (lane & 63)) & 1ull; }
+// the lane sits this call out.  Read from the kernel arguments alone: the test goes ahead of a kernel's first access to
+// memory and of its first barrier, and is block-uniform wherever the lane comes from the block index.
+static_assert(SVO_MAX_LANES <= 128, "lane_idle selects between two mask words");
+__device__ __forceinline__ bool lane_idle(const DevCtx& c, int lane) { return (((lane & 64) ? c.idle.w[1] : c.idle.w[0]) >> (lane & 63)) & 1ull; }
 
 // where a detect-phase kernel raises a capacity bit of its lane
 __device__ __forceinline__ void raise_detect_status(const DevCtx& c, int lane, uint32_t bit)

@@ -36,10 +36,10 @@ struct PrepArgs {
     const uint2* const* maps;         // device table [n_img] of fixed-point maps (nullptr entries: no rectification), or nullptr
     uint8_t* dst; long long dst_img_stride; int dst_pitch;
     long long src_stride; int channels, w, h;
+    LaneMask idle;                    // lanes that sit the call out (DevCtx.idle): their images are neither read nor written
 };
 void launch_prepare(const PrepArgs& a, int n_img, hipStream_t st);
 // frame hand-over between contexts (k_handover.hip)
-struct LaneMask { unsigned long long w[(SVO_MAX_LANES + 63) / 64]; };      // one bit per lane
 size_t handover_record_bytes(const DevCtx& c);                  // of the context's kind (DevCtx.carry_win)
 size_t handover_record_bytes(const DevCtx& c, bool windows);    // version 2 (false) / version 3 with the SAD windows (true)
 void launch_export_frame(const DevCtx& c, uint8_t* blob, const LaneMask& win_cur, const LaneMask& win_prev, hipStream_t st);

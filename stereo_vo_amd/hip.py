@@ -21,11 +21,11 @@ FLAG_REPEAT, FLAG_NO_SHIFT, FLAG_DEVICE_IMAGES, FLAG_BGR_IMAGES, FLAG_DETECT_NO_
 EXPORTS = [
     "svo_config_defaults", "svo_params_defaults", "svo_create", "svo_destroy", "svo_strerror", "svo_last_error",
     "svo_set_params", "svo_get_params", "svo_params_load_ini", "svo_set_fast_threshold", "svo_set_orb_threshold", "svo_get_fast_threshold",
-    "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
+    "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
-    "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
+    "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
     "svo_handover_bytes", "svo_export_frame", "svo_import_frame",
@@ -35,7 +35,7 @@ EXPORTS = [
 
 BATCH_EXPORTS = [
     "svo_batch_abi_sizes", "svo_batch_config_defaults", "svo_batch_create", "svo_batch_create_sized", "svo_batch_destroy", "svo_batch_last_error", "svo_batch_lanes", "svo_batch_contexts",
-    "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_klt_win", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step",
+    "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_klt_win", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step", "svo_batch_step_lanes",
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
     "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
@@ -93,6 +93,8 @@ def lib():
             getattr(L, n).restype = None
         L.svo_batch_destroy.argtypes = [C.c_void_p]; L.svo_fpstream_destroy.argtypes = [C.c_void_p]
         L.svo_batch_create_sized.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         _LIB = L
     return _LIB
 
@@ -128,6 +130,38 @@ def load_klt_win_ini(path, detect_section, klt_win=4) -> int:
 
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def lane_mask_words(active, n_lanes):
+    """The active-lane mask of svo_process_lanes / svo_batch_step_lanes as a list of ceil(n_lanes / 64) ints: bit l & 63 of
+    word l >> 6 selects lane l.  `active`: None (every lane), an iterable of lane indices, or a bool array of n_lanes entries."""
+    n_lanes = int(n_lanes)
+    if n_lanes < 1:
+        raise ValueError("n_lanes must be positive")
+    words = [0] * ((n_lanes + 63) // 64)
+    if active is None:
+        lanes = range(n_lanes)
+    else:
+        a = np.asarray(list(active) if not isinstance(active, np.ndarray) else active)
+        if a.dtype == np.bool_:
+            if a.shape != (n_lanes,):
+                raise ValueError("a bool mask needs one entry per lane: %d, got shape %s" % (n_lanes, a.shape))
+            lanes = np.flatnonzero(a)
+        else:
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("lane indices must be integers")
+            lanes = a.reshape(-1)
+    for l in lanes:
+        l = int(l)
+        if l < 0 or l >= n_lanes:
+            raise ValueError("lane %d outside [0, %d)" % (l, n_lanes))
+        words[l >> 6] |= 1 << (l & 63)
+    return words
+
+
+def lane_mask_lanes(words, n_lanes):
+    """the lane indices a mask of lane_mask_words selects, ascending"""
+    return [l for l in range(int(n_lanes)) if (int(words[l >> 6]) >> (l & 63)) & 1]
 
 
 class Context:
@@ -220,12 +254,32 @@ class Context:
         self._ck(self.L.svo_reset(self.h, lane), "svo_reset")
 
     # -- frames ----------------------------------------------------------------------------------------
-    def process_host(self, pairs, flags=RUN_ALL):
-        """pairs: list of (left, right) uint8 numpy arrays [h, w], one per lane."""
+    def _process(self, fr, flags, words):
+        """svo_process (words None), or svo_process_lanes with the mask words of the lanes that take part (the others: as if not called)"""
+        if words is None:
+            self._ck(self.L.svo_process(self.h, fr, C.c_uint32(flags)), "svo_process")
+            return
+        w = list(words) + [0]
+        self._ck(self.L.svo_process_lanes(self.h, fr, C.c_uint32(flags), (C.c_uint64 * 2)(w[0], w[1])), "svo_process_lanes")
+
+    def _mask(self, active):
+        """`active` consumed ONCE (it may be a generator): (mask words or None, the set of lanes that sit out)"""
+        if active is None:
+            return None, set()
+        words = lane_mask_words(active, self.n_lanes)
+        return words, set(range(self.n_lanes)) - set(lane_mask_lanes(words, self.n_lanes))
+
+    def process_host(self, pairs, flags=RUN_ALL, active=None):
+        """pairs: list of (left, right) uint8 numpy arrays [h, w], one per lane.  active: None = every lane, else an iterable of lane
+        indices or a bool array; the entries of `pairs` for the other lanes are not read and may be None."""
         assert len(pairs) == self.n_lanes
         fr = (Frame * self.n_lanes)()
         keep = []
-        for i, (l, r) in enumerate(pairs):
+        words, idle = self._mask(active)
+        for i, pr in enumerate(pairs):
+            if i in idle:
+                continue
+            l, r = pr
             l = np.ascontiguousarray(l, np.uint8)
             r = np.ascontiguousarray(r, np.uint8)
             keep += [l, r]
@@ -236,26 +290,31 @@ class Context:
             fr[i].left = Image(l.ctypes.data, w, h, l.strides[0])
             fr[i].right = Image(r.ctypes.data, w, h, r.strides[0])
         self._keep = keep
-        self._ck(self.L.svo_process(self.h, fr, C.c_uint32(flags & ~FLAG_DEVICE_IMAGES)), "svo_process")
+        self._process(fr, flags & ~FLAG_DEVICE_IMAGES, words)
 
-    def process_device(self, ptr_pairs, w, h, stride, flags=RUN_ALL):
-        """ptr_pairs: list of (left_ptr, right_ptr) device addresses (e.g. torch tensor.data_ptr()), one per lane."""
+    def _ptr_frames(self, ptr_pairs, w, h, stride, active):
         assert len(ptr_pairs) == self.n_lanes
         fr = (Frame * self.n_lanes)()
-        for i, (l, r) in enumerate(ptr_pairs):
-            fr[i].left = Image(l, w, h, stride)
-            fr[i].right = Image(r, w, h, stride)
-        self._ck(self.L.svo_process(self.h, fr, C.c_uint32(flags | FLAG_DEVICE_IMAGES)), "svo_process")
+        words, idle = self._mask(active)
+        for i, pr in enumerate(ptr_pairs):
+            if i in idle:
+                continue
+            fr[i].left = Image(pr[0], w, h, stride)
+            fr[i].right = Image(pr[1], w, h, stride)
+        return fr, words
 
-    def process_pinned(self, ptr_pairs, w, h, stride, flags=RUN_ALL):
+    def process_device(self, ptr_pairs, w, h, stride, flags=RUN_ALL, active=None):
+        """ptr_pairs: list of (left_ptr, right_ptr) device addresses (e.g. torch tensor.data_ptr()), one per lane; active as for
+        process_host (entries of the other lanes may be None)."""
+        fr, words = self._ptr_frames(ptr_pairs, w, h, stride, active)
+        self._process(fr, flags | FLAG_DEVICE_IMAGES, words)
+
+    def process_pinned(self, ptr_pairs, w, h, stride, flags=RUN_ALL, active=None):
         """ptr_pairs: (left_ptr, right_ptr) PAGE-LOCKED host addresses per lane (torch pin_memory() tensors, svo_host_alloc):
-        the upload is enqueued on the context's copy stream; the buffers must stay untouched until wait_upload()."""
-        assert len(ptr_pairs) == self.n_lanes
-        fr = (Frame * self.n_lanes)()
-        for i, (l, r) in enumerate(ptr_pairs):
-            fr[i].left = Image(l, w, h, stride)
-            fr[i].right = Image(r, w, h, stride)
-        self._ck(self.L.svo_process(self.h, fr, C.c_uint32((flags | FLAG_PINNED_IMAGES) & ~FLAG_DEVICE_IMAGES)), "svo_process")
+        the upload is enqueued on the context's copy stream; the buffers must stay untouched until wait_upload().  active as for
+        process_host: the other lanes are not uploaded."""
+        fr, words = self._ptr_frames(ptr_pairs, w, h, stride, active)
+        self._process(fr, (flags | FLAG_PINNED_IMAGES) & ~FLAG_DEVICE_IMAGES, words)
 
     def handover_bytes(self):
         self.L.svo_handover_bytes.restype = C.c_size_t
@@ -310,9 +369,10 @@ class Context:
         """loadStateFromFile (common.cpp:261-350) into one lane."""
         self._ck(self.L.svo_load_state(self.h, lane, os.fsencode(path)), "svo_load_state")
 
-    def run_stages(self, flags):
-        """Run stages on data already in the context (svo_put_* / previous svo_process), no prev/cur shift."""
-        self._ck(self.L.svo_process(self.h, None, C.c_uint32((flags | FLAG_NO_SHIFT) & ~RUN_DETECT)), "svo_process")
+    def run_stages(self, flags, active=None):
+        """Run stages on data already in the context (svo_put_* / previous svo_process), no prev/cur shift.  active: the mask the
+        frame's first call ran with (process_host)."""
+        self._process(None, (flags | FLAG_NO_SHIFT) & ~RUN_DETECT, self._mask(active)[0])
 
     def wait(self):
         self._ck(self.L.svo_wait(self.h), "svo_wait")
@@ -379,6 +439,12 @@ class Context:
         a = np.zeros((16, 32, 8, 2), np.uint64)
         n = self._ck(self.L.svo_debug_timeline(self.h, _vp(a), 16 * 256, int(bool(reset))), "svo_debug_timeline")
         return n, a
+
+    def graph_count(self):
+        """(graphs captured, calls served by a replay) under use_graphs since the context was created"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self.L.svo_debug_get_graph_count(self.h, C.byref(a), C.byref(b)), "svo_debug_get_graph_count")
+        return int(a.value), int(b.value)
 
     def status_word(self, lane=0):
         w = C.c_uint32(0)

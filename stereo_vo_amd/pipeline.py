@@ -21,10 +21,20 @@ from .abi import Result
 
 def _frames(ptrs, w, h, stride):
     fr = (hip.Frame * len(ptrs))()
-    for i, (l, r) in enumerate(ptrs):
-        fr[i].left = hip.Image(l, w, h, stride)
-        fr[i].right = hip.Image(r, w, h, stride)
+    for i, pr in enumerate(ptrs):
+        if pr is None:                      # a stream that sits the step out (step(..., active=)): its entry is not read
+            continue
+        fr[i].left = hip.Image(pr[0], w, h, stride)
+        fr[i].right = hip.Image(pr[1], w, h, stride)
     return fr
+
+
+def batch_mask(active, lanes):
+    """the mask argument of svo_batch_step_lanes: ceil(lanes / 64) words in global lane order, or None for every stream"""
+    if active is None:
+        return None
+    w = hip.lane_mask_words(active, lanes)
+    return (C.c_uint64 * len(w))(*w)
 
 
 class StreamBatch:
@@ -83,14 +93,22 @@ class StreamBatch:
         """dmFASTER's KLT_win on every context (svo_batch_set_klt_win)"""
         self._ck(self.L.svo_batch_set_klt_win(self.h, int(v)), "svo_batch_set_klt_win")
 
-    def step(self, ptrs, stride=None, pinned_host=False):
+    def _step(self, fr, flags, active):
+        if active is None:
+            self._ck(self.L.svo_batch_step(self.h, fr, C.c_uint32(flags)), "svo_batch_step")
+        else:
+            self._ck(self.L.svo_batch_step_lanes(self.h, fr, C.c_uint32(flags), batch_mask(active, self.B)), "svo_batch_step_lanes")
+
+    def step(self, ptrs, stride=None, pinned_host=False, active=None):
         """Enqueue one frame of every lane.  ptrs[lane] = (left, right) addresses of 8-bit grey images of the batch's
         size -- device memory, or page-locked host memory with pinned_host=True (the upload then runs on each context's
         copy stream and overlaps the kernels of the frames before it) -- lane = context * lanes_per_context +
-        lane_in_context.  Returns at once; the result records land in self.rec (device) in lane order."""
+        lane_in_context.  Returns at once; the result records land in self.rec (device) in lane order.
+        active: None = every stream, else an iterable of global lane indices or a bool array -- the streams that have a frame in this
+        step.  For the others the step is as if it had not been made (their entries of ptrs may be None, their records stay)."""
         assert len(ptrs) == self.B
         fr = _frames(ptrs, self.W, self.H, self.W if stride is None else stride)
-        self._ck(self.L.svo_batch_step(self.h, fr, C.c_uint32(hip.FLAG_PINNED_IMAGES if pinned_host else hip.FLAG_DEVICE_IMAGES)), "svo_batch_step")
+        self._step(fr, hip.FLAG_PINNED_IMAGES if pinned_host else hip.FLAG_DEVICE_IMAGES, active)
 
     def prepare(self, ptrs, stride=None):
         """The frame table of one step built ahead of time (a few hundred ctypes structures: ~0.5 ms of Python per step otherwise, which
@@ -98,9 +116,9 @@ class StreamBatch:
         assert len(ptrs) == self.B
         return _frames(ptrs, self.W, self.H, self.W if stride is None else stride)
 
-    def step_prepared(self, fr, pinned_host=False):
+    def step_prepared(self, fr, pinned_host=False, active=None):
         """step() with a frame table from prepare()."""
-        self._ck(self.L.svo_batch_step(self.h, fr, C.c_uint32(hip.FLAG_PINNED_IMAGES if pinned_host else hip.FLAG_DEVICE_IMAGES)), "svo_batch_step")
+        self._step(fr, hip.FLAG_PINNED_IMAGES if pinned_host else hip.FLAG_DEVICE_IMAGES, active)
 
     def flip_records(self):
         """Later steps leave their records in the OTHER of two buffers (self.rec afterwards): an all-gather may still be reading the
