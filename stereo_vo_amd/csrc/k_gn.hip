@@ -7,8 +7,11 @@
 // iteration (21 of J^T J, 6 of J^T r, cost) are reduced inside each wave on the permlane-swap / DPP network and across the
 // waves through 28 doubles of LDS each (gn_wave_sums): the Jacobian block is 4T x 6 with a 6x6 output, far too thin for an
 // MFMA tile.  LDS per block: 33 KB (lists of up to 1024 tracked pairs; longer ones use DevCtx::gn_scratch).
-// The reduction order differs from the reference's sequential loop, so results agree with the oracle to rounding
-// (tests: 1e-4 rad / 1e-3 m), not bit for bit.
+// The reduction order differs from the reference's sequential loop, so results agree with the oracle to rounding, not bit for
+// bit.  What "to rounding" means is held per evaluation: from a given start, ONE m_evalRGN returns the float residuals of an
+// extended-precision reference exactly (squared and summed within 4 * 2^-52) and a step within
+// K * kappa_2(H) * 2^-52 * ||step|| of it, K = 16 times what the oracle itself reaches
+// (tests/test_gpu_stage5.py::test_single_evaluation_against_the_reference, reference in tests/stage5_ref.py).
 #include <mutex>
 #include <map>
 #include <utility>
@@ -21,8 +24,9 @@
 // between two barriers of every Gauss-Newton iteration (4.5 of the 8.3 us of an iteration were that thread: tests/dev/gn_breakdown.py).
 // An IEEE f64 division is ~10 dependent instructions and the device library's sin / cos ~100 each with their range reduction;
 // v_rcp_f64 / v_rsq_f64 plus two Newton steps are 5, and below 0.5 rad the Taylor series to x^17 / x^16 is exact to 1e-19.
-// Stage 5 is held to the oracle by a tolerance (1e-3 m / 1e-4 rad, residuals 1e-6 relative), not bit for bit: these agree with the
-// correctly rounded results to an ulp or two.
+// Stage 5 is held to rounding, not bit for bit (the single-evaluation bound in the file header: a step within
+// K * kappa_2(H) * 2^-52 of the extended-precision one, tests/test_gpu_stage5.py::test_single_evaluation_against_the_reference, whose
+// K allows for exactly this): these agree with the correctly rounded results to an ulp or two.
 __device__ __forceinline__ double gn_rcp(double a)
 {
     double r = __builtin_amdgcn_rcp(a);
@@ -121,10 +125,12 @@ __device__ int solve_sym6(const double* H, const double* g, double* x)
     double L[36];
     bool spd = dmax > 0;
     if (spd) {
+        double amp = 4.0 * DBL_EPSILON;                                      // the growth bound of chol6's pivot test (see there)
         for (int j = 0; j < 6 && spd; j++) {
             double s = H[j * 6 + j];
             for (int k = 0; k < j; k++) s -= L[j * 6 + k] * L[j * 6 + k];
-            if (!(s > 1e-13 * dmax)) { spd = false; break; }
+            if (!(s > 1e-13 * dmax) || !(s > amp * H[j * 6 + j])) { spd = false; break; }
+            amp *= H[j * 6 + j] / s;
             const double ljj = sqrt(s);
             L[j * 6 + j] = ljj;
             for (int i = j + 1; i < 6; i++) {
@@ -284,19 +290,28 @@ __device__ __forceinline__ void gn_wave_sums(const double* acc, double* out)
 // per column).  Same pivots as the L L^T form (d_j = l_jj^2), same positivity test; the solution agrees to rounding, which is
 // what stage 5's tolerance is stated in.  Returns false when a pivot is not safely positive; the caller then takes the general
 // path (solve_sym6).
+// "Safely" has two parts.  s > 1e-13 * dmax alone is not enough: a pivot d_k far below its diagonal entry H_kk is the difference of
+// two nearly equal numbers, its rounding error is of the order DBL_EPSILON * H_kk, and every later pivot inherits that error
+// multiplied by up to H_kk / d_k.  On a rank-deficient H (collinear landmarks) a genuine fifth pivot of 8.7e-9 * H_55 left a sixth
+// "pivot" of +-1e-10 * dmax that was nothing but that noise, positive or negative with the summation order, and a positive one
+// passed the first test: the step then had a component of ~2000 times its norm along the direction the pseudo-inverse cuts
+// (tests/test_gpu_stage5.py, collinear-eps0).  So a pivot must also exceed 4 * DBL_EPSILON * H_jj * prod_{k<j} H_kk / d_k, the noise
+// the columns before it can have put into it; the product is 1 ... 1e4 on ordinary frames.
 __device__ __forceinline__ bool chol6(const double* H, const double* g, double dmax, double* x)
 {
     double L[6][6], d[6], inv[6];
     bool ok = true;
+    double amp = 4.0 * DBL_EPSILON;
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         double w[6];                                                        // w[k] = L[j][k] * d[k]
         double s = H[j * 6 + j];
 #pragma unroll
         for (int k = 0; k < j; k++) { w[k] = L[j][k] * d[k]; s = __builtin_fma(-L[j][k], w[k], s); }
-        ok = ok && (s > 1e-13 * dmax);
+        ok = ok && (s > 1e-13 * dmax) && (s > amp * H[j * 6 + j]);
         d[j] = s;
         inv[j] = gn_rcp(s);
+        amp *= H[j * 6 + j] * inv[j];
 #pragma unroll
         for (int i = j + 1; i < 6; i++) {
             double t = H[i * 6 + j];

@@ -299,8 +299,9 @@ def ref_stage5(tracked, pre_m, cur_m, pre_l, pre_r, cur_l, cur_r, cam, p, W, H, 
         out = []
         for m in range(T):
             if not survivors[m]: continue
-            ul, vl, ur = float(l1l["x"][m]), float(l1l["y"][m]), float(l1r["x"][m])
-            b_d = B / (fl * (cur_ - ur) + fr * (ul - cul))
+            ul, vl, ur = np.float64(l1l["x"][m]), np.float64(l1l["y"][m]), np.float64(l1r["x"][m])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                b_d = np.float64(B) / (fl * (cur_ - ur) + fr * (ul - cul))                                    # zero disparity: inf, as in C
             out.append((b_d * fr * (ul - cul), b_d * fr * (vl - cvl), b_d * fl * fr))
         return np.array(out, np.float64)
     out_residual = []
@@ -327,7 +328,7 @@ def ref_stage5(tracked, pre_m, cur_m, pre_l, pre_r, cur_l, cur_r, cam, p, W, H, 
             g += rho_p * (J.T @ r); Hm += J.T @ J                                                            # S5:364-369: the Hessian is NOT weighted
             i += 1
         U, sv, Vt = np.linalg.svd(Hm)                                                                        # S5:375-388
-        cond = sv[0] / sv[5]
+        with np.errstate(invalid="ignore"): cond = sv[0] / sv[5]                                           # H = 0: NaN, as in C
         if np.isnan(cond): return None, cost
         return Vt.T @ ((U.T @ g) / sv), cost
 
