@@ -208,10 +208,12 @@ int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, con
 /* smSAD (svo_params.match_method = SVO_SM_SAD, S3:185-419) and ifmSAD (ifm_method = SVO_IFM_SAD, S4:435-738) compare the 8 x 8 image
  * windows around two keypoints (rso::compute_SAD8).  Stage 2 is the only stage that reads images, so it gathers the window of every
  * final keypoint -- from the call on in which either selector is in force; a context that never selects them allocates and launches
- * nothing.  A frame has windows only if THIS library detected it under such parameters, in this context or in the one whose hand-over
- * record brought it (svo_import_frame below: the records of a context that has selected a SAD method carry the windows).  Features that
- * came through svo_put_features(_oct) or svo_load_state have none: state files do not carry windows (the reference's state format holds
- * no images either, C:475-543), and neither does a frame detected while no SAD method was selected.
+ * nothing.  A frame has windows when this library detected it under such parameters -- in this context, in the one whose hand-over
+ * record brought it (svo_import_frame below: the records of a context that has selected a SAD method carry the windows), or in the one
+ * that saved it (svo_save_state below: the file's extension block carries them) -- or when svo_gather_windows (below) was given its
+ * images.  Features that came through svo_put_features(_oct) have none until then (the reference's bypass call still carries the image
+ * pair, P:100-108; here the lists and the images arrive in separate calls), and neither does a frame detected while no SAD method was
+ * selected, nor one loaded from a file that was saved without them.
  * A call that runs a SAD stage on a frame without windows is refused with SVO_ERR_STATE and a text in svo_last_error BEFORE anything is
  * enqueued: the lists and the lane state stay as they were.  When it is the PREVIOUS frame that lacks them (a stream that switches
  * to ifmSAD) and the call would have shifted, the refusal is remembered: the lane's next shifting call forgets that frame, i.e. it is
@@ -301,6 +303,39 @@ int svo_put_features_oct(svo_ctx* ctx, int lane, int which, int side, int octave
                          int img_w, int img_h);
 int svo_put_matches_oct(svo_ctx* ctx, int lane, int which, int octave, const svo_dmatch* m, int n);
 int svo_put_match_ids_oct(svo_ctx* ctx, int lane, int which, int octave, const int32_t* ids, int n);
+/* (svo_put_features(_oct) also builds the list's row table pyr_feats_index (m_update_indexes, S2:103-129) from the keypoints' rows, as
+ * stage 2 would have: the row-by-row stereo matchers smDescRbR and smSAD read it, S3:253-256.) */
+
+/* The images of a frame whose lists were put (or loaded without windows): what makes smSAD / ifmSAD work on the precomputed-data bypass.
+ * In the reference a bypass call still carries the image pair: stage 1 builds the octave images (P:100-108) and ifmSAD reads its
+ * windows from them (S4:572, 576).  Here: put the lists of a frame, then hand its images to this call.
+ *   frames   taken exactly as svo_process takes them: host frames, SVO_FLAG_PINNED_IMAGES, SVO_FLAG_DEVICE_IMAGES (read in place under the
+ *            read contract of svo_image.stride), SVO_FLAG_BGR_IMAGES, a rectify map.  Any other flag bit is SVO_ERR_ARG.
+ *   which    0: the lists of the current frame, 1: those of the previous one.
+ *   active   as in svo_process_lanes; NULL = every lane.  frames[l] of an idle lane is not read; its windows and the host-side record
+ *            of which of its frames have them stay as they were.  No bit set: SVO_OK, nothing is enqueued.
+ * In the FAST+ORB / dmFASTER geometry the call builds the x1/2 octave images (n_oct - 1 launches); in ORB mode the windows come from
+ * level 0.  ONE launch then gathers the window and the border flag of every keypoint of that slot, for every active lane, side and
+ * octave: (int)pt, rows y - 3 .. y + 4, the float border rule of S3:290-293, exactly as stage 2 gathers them for a frame it detected;
+ * nothing outside the w x h pixels is read.  A NaN coordinate is flagged.  The window buffers are allocated on first use.
+ * The call only enqueues on the context's stream and returns.  It marks the frame of every active lane as having windows and touches
+ * NOTHING ELSE: no prev/cur shift, no counters, result records, lists, row tables or status words, no match IDs; whether the
+ * context's hand-over records carry windows stays as it is.
+ * SCHEDULING.  The call overwrites the detector's per-image scratch -- the level-0 pointer table, the upload ring slot, the octave
+ * pyramid -- as a detect call does: in a pipelined schedule it TAKES A DETECT CALL'S PLACE (it may not overlap the detection or the
+ * post-processing of another frame of this context, and the next detect call must be ordered behind it).  It always runs as plain
+ * launches: it is neither captured nor replayed under svo_use_graphs.  svo_kernel_times counts its gather launch as "gather_windows".
+ * Refusals, all before anything is enqueued and with a text in svo_last_error:
+ *   SVO_ERR_ARG    which not 0 / 1; frames == NULL; a flag bit other than the three above; a mask bit at or above n_lanes; NULL data,
+ *                  disagreeing sizes, stride or span violations of an active lane, as svo_process refuses them
+ *   SVO_ERR_STATE  no geometry yet (no lists were put or loaded since the last svo_set_params); a frame size other than the one the
+ *                  lists were put with */
+int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, int which, const uint64_t active[2] /* NULL = all lanes */);
+/* the gathered windows of one list, like the other list getters (size query with cap 0; returns the list's length): win receives
+ * min(length, cap) x 64 bytes (rows top to bottom), flag as many bytes (1: too close to the border for a window, S3:290-293; the 64 bytes
+ * of such a keypoint mean nothing).  0 when the lane has no such frame; SVO_ERR_STATE with a text when that frame's windows were never
+ * gathered. */
+int svo_get_windows_oct(svo_ctx* ctx, int lane, int which, int side, int octave, uint8_t* win /* n x 64 */, uint8_t* flag /* n */, int cap);
 
 /* getProjectedCoords (H:175-182, C:415-466): pixel coordinates (uL vL uR vR, 4 floats each) that the previous
  * pairings NOT marked as tracked (tracked_first[m] == -1, C:430-431) take after the change in pose: triangulation as
@@ -344,10 +379,30 @@ int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes);
  * float and octave class_id as int per keypoint, then rows cols type and the descriptor bytes), pairings (count,
  * id count, then [id] queryIdx trainIdx distance imgIdx each); then m_reset (1 byte) and m_lastID,
  * m_num_tracked_pairs_from_last_kf, m_num_tracked_pairs_from_last_frame, m_last_match_ID, m_kf_max_match_ID as
- * 8-byte integers.  Octave-0 lists (single-octave contexts only).  svo_load_state reads what svo_save_state (and
+ * 8-byte integers.  These bytes come first and hold the octave-0 lists: old readers, the reference's included, still get octave 0;
+ * npyr is the context's octave count (C:488-489).  svo_load_state reads what svo_save_state (and
  * the reference's saveStateToFile) writes; the reference's own loader expects one more 8-byte word before
  * m_last_match_ID that its saver never writes (C:342-343 vs C:533-539) -- deviation, see SURVEY.md appendix A #18.
- * After a load both frames are present, m_error is cleared and the warm start is the identity. */
+ * After a load both frames are present, m_error is cleared and the warm start is the identity.
+ * THE EXTENSION BLOCK follows the tail directly, little-endian, no padding.  It is written only when the context works on more than
+ * one octave or at least one of the two frames has SAD windows (above); a single-octave context that never selected SAD writes the
+ * bytes it always wrote.  Byte for byte:
+ *     magic   u32  0x58455653 ("SVEX")        version  u32  1
+ *     n_oct   u32  1 .. 4                      w, h     u32 each: the octave-0 image size (the reference's file has none)
+ *     has_windows  u8 x 2: PRE, CUR (0 / 1)
+ *     for octave 1 .. n_oct - 1:  the PRE group, then the CUR group, each in the sub-layout above (left keypoints, right keypoints,
+ *                                 pairings + ids)
+ *     for frame in (PRE, CUR) with has_windows, for octave 0 .. n_oct - 1, for side in (left, right):
+ *                                 count u64 (= that list's keypoint count), count flag bytes, count x 64 window bytes (all zero where
+ *                                 the flag is set)
+ * svo_load_state: a file without the block loads into a single-octave context as it always did (image size: the last geometry, or the
+ * context's maximum).  A file with the block needs n_oct equal to the octave count the context's parameters give (SVO_ERR_ARG with both
+ * numbers otherwise, also for a file without the block offered to a multi-octave context) and w x h within max_w x max_h; per octave and
+ * slot it restores the lists, pairings, IDs and row tables, the windows and flags, and from the has_windows bytes which frames have
+ * windows: a frame saved without them loads without them and the refusal rule above applies unchanged.  A malformed file --
+ * truncated anywhere, a count above max_kps, a windows count different from its list's, a wrong magic or version, bytes behind the
+ * block -- is SVO_ERR_ARG with a text; the WHOLE file is validated before the first write to the lane, which is left as it was.
+ * (Parser and writer: stereo_vo_amd/csrc/state_format.cpp, host only; stereo_vo_amd/state_file.py reads the same layout independently.) */
 int svo_save_state(svo_ctx* ctx, int lane, const char* path);
 int svo_load_state(svo_ctx* ctx, int lane, const char* path);
 

@@ -1363,12 +1363,16 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
 // S3:290-293 (on the float coordinates, as there) gets a flag and no patch: nothing is read outside the image.
 // ------------------------------------------------------------------------------------------------------------
 typedef unsigned long long sad_row_t __attribute__((aligned(1)));      // a window row starts at any byte
-__global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
+// ANY_SLOT = false is stage 2's form (the current slot, nothing else); true takes the frame from `which` (0 current, 1 previous): the
+// form of svo_gather_windows, for lists that came without an image.  A template parameter, so that the detect path's instantiation
+// carries neither the argument nor the select (profiles/put_windows_isa.json).
+template <bool ANY_SLOT>
+__device__ __forceinline__ void sad_patch_body(const DevCtx& c, int which)
 {
-    SVO_TL_SCOPE(c, TL_DESCRIBE, 2);
     const int vs = blockIdx.y, vl = vs >> 1, side = vs & 1, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap;
     if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
-    const int cur = 1 - c.lane[lane_id].prev_slot;
+    const int prev = c.lane[lane_id].prev_slot;
+    const int cur = (ANY_SLOT && which) ? prev : 1 - prev;
     const int n = c.n_kps[feat_cnt_idx(vl, cur, side)];
     const int i = blockIdx.x * 32 + (threadIdx.x >> 3), r = threadIdx.x & 7;
     if (i >= n) return;
@@ -1376,6 +1380,7 @@ __global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
     const svo_keypoint k = c.kps[fo];
     const int W = c.ow[oct], H = c.oh[oct];
     const bool border = k.x < 3.0f || k.y < 3.0f || k.x > (float)(W - 5) || k.y > (float)(H - 5);       // S3:290-293, max_pt = (W-4-1, H-4-1)
+    if (ANY_SLOT && (k.x != k.x || k.y != k.y)) { if (r == 0) c.sad_flag[fo] = 1; return; }            // a caller's NaN passes every comparison above: no window, nothing read
     if (r == 0) c.sad_flag[fo] = border ? 1 : 0;
     if (border) return;
     int pitch;
@@ -1383,6 +1388,25 @@ __global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
     const int x = (int)k.x, y = (int)k.y;                               // TPixelCoord(pt.x, pt.y): 3 <= x <= W-5, 3 <= y <= H-5
     const unsigned long long v = *(const sad_row_t*)(img + (long long)(y - 3 + r) * pitch + (x - 3));
     *(unsigned long long*)(c.sad_patch + fo * 64 + r * 8) = v;
+}
+__global__ void __launch_bounds__(256) k_sad_patch(DevCtx c)
+{
+    SVO_TL_SCOPE(c, TL_DESCRIBE, 2);
+    sad_patch_body<false>(c, 0);
+}
+// svo_gather_windows: the same gather for a frame this library did not detect (put or loaded lists), either slot.  The list may hold
+// up to max_kps keypoints whatever the detector's quota is (the launcher sizes the grid by max_kps).
+__global__ void __launch_bounds__(256) k_sad_patch_slot(DevCtx c, int which)
+{
+    SVO_TL_SCOPE(c, TL_DESCRIBE, 3);
+    sad_patch_body<true>(c, which);
+}
+// The level-0 pointer table of the active lanes and nothing else: k_begin_frame publishes it together with the shift, the counters and
+// the result record, none of which svo_gather_windows may touch.
+__global__ void k_publish_img0(DevCtx c, ImgPtrs ptrs)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < c.n_img && !lane_idle(c, t >> 1)) c.img0[t] = ptrs.p[t];
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2271,6 +2295,19 @@ void launch_sad_patch(const DevCtx& c, hipStream_t st)
     const int n = c.fast_orb ? c.max_kps : std::min(c.n_slots, c.max_kps);
     if (n <= 0) return;
     hipLaunchKernelGGL(k_sad_patch, dim3((n + 31) / 32, c.n_lanes * c.oct_cap * 2), dim3(256), 0, st, c);
+}
+
+// svo_gather_windows: publish the level-0 pointers of the active lanes (plain launches; ptrs holds n_img entries)
+void launch_publish_img0(const DevCtx& c, const uint8_t* const* ptrs, hipStream_t st)
+{
+    ImgPtrs ip;
+    for (int i = 0; i < 2 * SVO_MAX_LANES; i++) ip.p[i] = i < c.n_img ? ptrs[i] : nullptr;
+    hipLaunchKernelGGL(k_publish_img0, dim3((c.n_img + 255) / 256), dim3(256), 0, st, c, ip);
+}
+// ... and gather the windows of slot `which` (0 current, 1 previous): a put list may be as long as max_kps in either mode
+void launch_sad_patch_slot(const DevCtx& c, int which, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_sad_patch_slot, dim3((c.max_kps + 31) / 32, c.n_lanes * c.oct_cap * 2), dim3(256), 0, st, c, which);
 }
 
 #define FO_PMAX 2048     // chunk size of k_fastorb_nms / k_faster_nms (LDS: 45 B per entry)

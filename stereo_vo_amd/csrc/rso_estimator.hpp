@@ -163,6 +163,9 @@ public:
                     check(svo_put_match_ids_oct(m_ctx, 0, 0, (int)o, ids.data(), (int)ids.size()), "svo_put_match_ids_oct");
                 }
             }
+            // a bypass call still carries the image pair (stage 1 builds the octave images, P:100-108) and ifmSAD reads its windows from
+            // them (S4:572, 576): the lists put above get theirs from the images of this request
+            if (params.ifm_method == SVO_IFM_SAD && f.left.data && f.right.data) check(svo_gather_windows(m_ctx, &f, 0, 0, NULL), "svo_gather_windows");
             check(svo_process(m_ctx, NULL, SVO_RUN_TRACK | SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT), "svo_process");
         } else {
             if (!f.left.data || !f.right.data) throw std::runtime_error("Pointer 'request_data.stereo_imgs' must be set to stereo observation data!");   // P:81

@@ -5,6 +5,7 @@
 // host synchronisation inside a frame and frames can be enqueued back to back.
 #include "svo_device.h"
 #include "svo_kernels.h"
+#include "state_format.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -26,13 +27,15 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // svo_export_frame / svo_import_frame: the kernels of a context that carries no SAD windows, then those of one that does
        KT_EXPORT, KT_IMPORT, KT_EXPORT_WIN, KT_IMPORT_WIN,
        // dmFASTER (only a context that selects it counts a call here)
-       KT_FASTER, KT_FASTER_NMS, KT_COUNT };
-static_assert(KT_COUNT <= 32, "kt_mask is one 32-bit word");
+       KT_FASTER, KT_FASTER_NMS,
+       // svo_gather_windows: the slot-selecting window gather (only a caller of that entry point counts a call here)
+       KT_GATHER_WIN, KT_COUNT };
+static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
     "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
-    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms" };
+    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -92,7 +95,7 @@ struct svo_ctx {
     std::vector<void*> allocs;
     std::string last_error;
     std::vector<TimedSpan> spans; std::vector<hipEvent_t> free_events;
-    double kt_total[KT_COUNT]; long long kt_calls[KT_COUNT]; unsigned kt_mask;
+    double kt_total[KT_COUNT]; long long kt_calls[KT_COUNT]; unsigned long long kt_mask;
     unsigned* d_ham_out; uint8_t* d_ham_q, *d_ham_t; int ham_cap_q, ham_cap_t;
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
@@ -375,7 +378,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
     for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
-    ctx->kt_mask = 0xFFFFFFFFu;
+    ctx->kt_mask = ~0ull;
     *out = ctx;                                           // so that the caller can read last_error and destroy
     HIPCHECK(hipSetDevice(cfg->device));
     if (cfg->stream) { ctx->stream = (hipStream_t)cfg->stream; ctx->own_stream = false; }
@@ -813,7 +816,7 @@ static hipEvent_t get_event(svo_ctx* ctx)
 }
 struct Span {
     svo_ctx* ctx; int id; hipEvent_t a, b; bool on; hipStream_t st;
-    Span(svo_ctx* c, int i, hipStream_t on_stream = nullptr) : ctx(c), id(i), on(c->cfg.kernel_times != 0 && ((c->kt_mask >> i) & 1u)), st(on_stream ? on_stream : c->stream) { if (on) { a = get_event(ctx); b = get_event(ctx); hipEventRecord(a, st); } }
+    Span(svo_ctx* c, int i, hipStream_t on_stream = nullptr) : ctx(c), id(i), on(c->cfg.kernel_times != 0 && ((c->kt_mask >> i) & 1ull)), st(on_stream ? on_stream : c->stream) { if (on) { a = get_event(ctx); b = get_event(ctx); hipEventRecord(a, st); } }
     ~Span() { if (on) { hipEventRecord(b, st); ctx->spans.push_back({ id, a, b }); } }
 };
 static void collect_spans(svo_ctx* ctx)
@@ -847,8 +850,8 @@ extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
 {
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
-    if (!name || !*name) { ctx->kt_mask = 0xFFFFFFFFu; return SVO_OK; }
-    for (int i = 0; i < KT_COUNT; i++) if (!strcmp(name, kt_names[i])) { ctx->kt_mask = 1u << i; return SVO_OK; }
+    if (!name || !*name) { ctx->kt_mask = ~0ull; return SVO_OK; }
+    for (int i = 0; i < KT_COUNT; i++) if (!strcmp(name, kt_names[i])) { ctx->kt_mask = 1ull << i; return SVO_OK; }
     return SVO_ERR_ARG;
 }
 
@@ -968,6 +971,107 @@ extern "C" int svo_host_free(void* p) { return (!p || hipHostFree(p) == hipSucce
 extern "C" int svo_host_register(void* p, size_t bytes) { return (p && bytes && hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) ? SVO_OK : SVO_ERR_HIP; }
 extern "C" int svo_host_unregister(void* p) { return (p && hipHostUnregister(p) == hipSuccess) ? SVO_OK : SVO_ERR_HIP; }
 
+// The frame intake of a call that reads images (svo_process with SVO_RUN_DETECT, svo_gather_windows): the checks of the read contract of
+// svo_image.stride (svo_hip.h) -- all before anything is enqueued --, the geometry, and the way of every kind of frame to the
+// level-0 addresses in ptrs[]: device frames in place, host frames through the upload ring, BGR / unrectified ones through stage 1's
+// source staging (prep is then filled and *prepare_out set: the caller launches k_prepare behind the pointer table).
+// lists_geometry: the images belong to lists that are already there (svo_gather_windows) -- their geometry is required, not made.
+static int intake_frames(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const LaneMask& idle, bool lists_geometry, hipStream_t st,
+                         const uint8_t** ptrs, PrepArgs& prep, bool* prepare_out)
+{
+    DevCtx& d = ctx->dc;
+    auto is_idle = [&](int l) { return lane_in(idle, l); };
+    const bool partial = (idle.w[0] | idle.w[1]) != 0;
+    *prepare_out = false;
+    if (!frames) return SVO_ERR_ARG;                    // P:81
+    int l0 = 0; while (is_idle(l0)) l0++;               // the first active lane: what the others must agree with
+    const int w = frames[l0].left.w, h = frames[l0].left.h;
+    for (int l = 0; l < d.n_lanes; l++) {
+        if (is_idle(l)) continue;                       // (its frames[] entry is not read: it may hold NULL pointers)
+        const svo_frame& f = frames[l];
+        if (!f.left.data || !f.right.data || f.left.w != w || f.left.h != h || f.right.w != w || f.right.h != h) return SVO_ERR_ARG;
+    }
+    const int ch = (flags & SVO_FLAG_BGR_IMAGES) ? 3 : 1;
+    // the read contract of svo_image.stride (svo_hip.h): rows may not overlap, and the kernels that read a device frame in place
+    // address it with 32-bit byte offsets from its base.  Refused here, before anything is enqueued.
+    for (int l = 0; l < d.n_lanes; l++)
+        for (int s = 0; s < 2; s++) {
+            if (is_idle(l)) continue;
+            const svo_image& im = s ? frames[l].right : frames[l].left;
+            char msg[200];
+            if (w < 1 || h < 1) {
+                snprintf(msg, sizeof(msg), "image size %d x %d: both must be positive", w, h);
+                ctx->last_error = msg; return SVO_ERR_ARG;
+            }
+            if (im.stride < (int64_t)w * ch) {
+                snprintf(msg, sizeof(msg), "lane %d %s image: stride %lld is smaller than a row (%d px x %d B)", l, s ? "right" : "left", (long long)im.stride, w, ch);
+                ctx->last_error = msg; return SVO_ERR_ARG;
+            }
+            if ((flags & SVO_FLAG_DEVICE_IMAGES) && im.stride > (int64_t)INT32_MAX / h) {
+                snprintf(msg, sizeof(msg), "lane %d %s image: h * stride = %d x %lld exceeds the 2^31 - 1 bytes a device frame may span", l, s ? "right" : "left", h, (long long)im.stride);
+                ctx->last_error = msg; return SVO_ERR_ARG;
+            }
+        }
+    int rc = SVO_OK;
+    if (!lists_geometry) { rc = ensure_geometry(ctx, w, h); if (rc) return rc; }
+    else {
+        // svo_gather_windows: the geometry is the one the lists were put (or loaded) with; the images must be of that frame size
+        if (!ctx->geom_ready) { ctx->last_error = "no geometry yet: put or load the lists first (svo_set_params clears the geometry of the lists before it)"; return SVO_ERR_STATE; }
+        if (w != ctx->geom_w || h != ctx->geom_h) {
+            char msg[160]; snprintf(msg, sizeof(msg), "frame size %d x %d, but the lists were put with %d x %d", w, h, ctx->geom_w, ctx->geom_h);
+            ctx->last_error = msg; return SVO_ERR_STATE;
+        }
+    }
+    const bool prepare = ch == 3 || ctx->n_maps > 0;
+    if (ctx->n_maps > 0 && (ctx->map_w != w || ctx->map_h != h)) return SVO_ERR_ARG;
+    const int ipitch = ctx->img0_pitch_internal;
+    if (flags & SVO_FLAG_DEVICE_IMAGES) {
+        const long long stride = frames[l0].left.stride;
+        for (int l = 0; l < d.n_lanes; l++) {
+            if (is_idle(l)) { ptrs[2 * l] = nullptr; ptrs[2 * l + 1] = nullptr; continue; }
+            if (frames[l].left.stride != stride || frames[l].right.stride != stride) { ctx->last_error = "device frames of one call must share one stride"; return SVO_ERR_ARG; }
+            ptrs[2 * l] = frames[l].left.data; ptrs[2 * l + 1] = frames[l].right.data;
+        }
+        d.img0_pitch = (int)stride;
+        if (prepare) { for (int i = 0; i < 2 * d.n_lanes; i++) prep.src[i] = ptrs[i]; prep.src_stride = stride; }
+        else if (ctx->use_graphs && !partial && !lists_geometry) {
+            // a captured frame reads fixed addresses: the images go to the ring slot first (device to device, same stream)
+            rc = ensure_upload(ctx); if (rc) return rc;
+            const int slot = ctx->up_slot; ctx->up_slot = slot ^ 1; ctx->det_slot = slot;
+            const size_t img_bytes = (size_t)ipitch * ctx->cfg.max_h;
+            for (int i = 0; i < 2 * d.n_lanes; i++) {
+                uint8_t* dst = ctx->d_img0_ring[slot] + (size_t)i * img_bytes;
+                HIPCHECK(hipMemcpy2DAsync(dst, ipitch, ptrs[i], (size_t)stride, (size_t)w, (size_t)h, hipMemcpyDeviceToDevice, st));
+                ptrs[i] = dst;
+            }
+            d.img0_pitch = ipitch;
+        }
+    } else if (!prepare) {
+        rc = upload_frames(ctx, frames, w, h, (flags & SVO_FLAG_PINNED_IMAGES) != 0, st, ptrs, idle); if (rc) return rc;
+        d.img0_pitch = ipitch;
+    } else {
+        if (!ctx->d_src) { ctx->src_pitch = align_up(3 * ctx->cfg.max_w, 64); HIPCHECK(dev_alloc(ctx, &ctx->d_src, (size_t)2 * ctx->cfg.n_lanes * ctx->src_pitch * ctx->cfg.max_h)); }
+        for (int l = 0; l < d.n_lanes; l++)
+            for (int s = 0; s < 2; s++) {
+                if (is_idle(l)) continue;
+                const svo_image& im = s ? frames[l].right : frames[l].left;
+                uint8_t* dst = ctx->d_src + (size_t)(2 * l + s) * ctx->src_pitch * ctx->cfg.max_h;
+                HIPCHECK(hipMemcpy2DAsync(dst, ctx->src_pitch, im.data, (size_t)im.stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
+                prep.src[2 * l + s] = dst;
+            }
+        prep.src_stride = ctx->src_pitch;
+    }
+    if (prepare) {       // stage 1 writes the context's own level-0 buffers; detection reads those
+        for (int i = 0; i < 2 * d.n_lanes; i++) ptrs[i] = ctx->d_img0 + (size_t)i * ipitch * ctx->cfg.max_h;
+        d.img0_pitch = ipitch;
+        prep.maps = ctx->n_maps > 0 ? (const uint2* const*)ctx->d_map_ptrs : nullptr;
+        prep.dst = ctx->d_img0; prep.dst_img_stride = (long long)ipitch * ctx->cfg.max_h; prep.dst_pitch = ipitch;
+        prep.channels = ch; prep.w = w; prep.h = h; prep.idle = idle;
+    }
+    *prepare_out = prepare;
+    return SVO_OK;
+}
+
 // ---- processNewImagePair ---------------------------------------------------------------------------------
 // The body of svo_process (lanes == NULL: every lane) and svo_process_lanes (one bit per lane that takes part).
 static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, const svo_frame* frames, uint32_t flags)
@@ -1043,82 +1147,7 @@ static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, 
     const uint8_t* ptrs[2 * SVO_MAX_LANES];
     PrepArgs prep; memset(&prep, 0, sizeof(prep)); bool prepare = false;
     if (flags & SVO_RUN_DETECT) {
-        if (!frames) return SVO_ERR_ARG;                    // P:81
-        int l0 = 0; while (is_idle(l0)) l0++;               // the first active lane: what the others must agree with
-        const int w = frames[l0].left.w, h = frames[l0].left.h;
-        for (int l = 0; l < d.n_lanes; l++) {
-            if (is_idle(l)) continue;                       // (its frames[] entry is not read: it may hold NULL pointers)
-            const svo_frame& f = frames[l];
-            if (!f.left.data || !f.right.data || f.left.w != w || f.left.h != h || f.right.w != w || f.right.h != h) return SVO_ERR_ARG;
-        }
-        const int ch = (flags & SVO_FLAG_BGR_IMAGES) ? 3 : 1;
-        // the read contract of svo_image.stride (svo_hip.h): rows may not overlap, and the kernels that read a device frame in place
-        // address it with 32-bit byte offsets from its base.  Refused here, before anything is enqueued.
-        for (int l = 0; l < d.n_lanes; l++)
-            for (int s = 0; s < 2; s++) {
-                if (is_idle(l)) continue;
-                const svo_image& im = s ? frames[l].right : frames[l].left;
-                char msg[200];
-                if (w < 1 || h < 1) {
-                    snprintf(msg, sizeof(msg), "image size %d x %d: both must be positive", w, h);
-                    ctx->last_error = msg; return SVO_ERR_ARG;
-                }
-                if (im.stride < (int64_t)w * ch) {
-                    snprintf(msg, sizeof(msg), "lane %d %s image: stride %lld is smaller than a row (%d px x %d B)", l, s ? "right" : "left", (long long)im.stride, w, ch);
-                    ctx->last_error = msg; return SVO_ERR_ARG;
-                }
-                if ((flags & SVO_FLAG_DEVICE_IMAGES) && im.stride > (int64_t)INT32_MAX / h) {
-                    snprintf(msg, sizeof(msg), "lane %d %s image: h * stride = %d x %lld exceeds the 2^31 - 1 bytes a device frame may span", l, s ? "right" : "left", h, (long long)im.stride);
-                    ctx->last_error = msg; return SVO_ERR_ARG;
-                }
-            }
-        int rc = ensure_geometry(ctx, w, h); if (rc) return rc;
-        prepare = ch == 3 || ctx->n_maps > 0;
-        if (ctx->n_maps > 0 && (ctx->map_w != w || ctx->map_h != h)) return SVO_ERR_ARG;
-        const int ipitch = ctx->img0_pitch_internal;
-        if (flags & SVO_FLAG_DEVICE_IMAGES) {
-            const long long stride = frames[l0].left.stride;
-            for (int l = 0; l < d.n_lanes; l++) {
-                if (is_idle(l)) { ptrs[2 * l] = nullptr; ptrs[2 * l + 1] = nullptr; continue; }
-                if (frames[l].left.stride != stride || frames[l].right.stride != stride) { ctx->last_error = "device frames of one call must share one stride"; return SVO_ERR_ARG; }
-                ptrs[2 * l] = frames[l].left.data; ptrs[2 * l + 1] = frames[l].right.data;
-            }
-            d.img0_pitch = (int)stride;
-            if (prepare) { for (int i = 0; i < 2 * d.n_lanes; i++) prep.src[i] = ptrs[i]; prep.src_stride = stride; }
-            else if (ctx->use_graphs && !partial) {
-                // a captured frame reads fixed addresses: the images go to the ring slot first (device to device, same stream)
-                rc = ensure_upload(ctx); if (rc) return rc;
-                const int slot = ctx->up_slot; ctx->up_slot = slot ^ 1; ctx->det_slot = slot;
-                const size_t img_bytes = (size_t)ipitch * ctx->cfg.max_h;
-                for (int i = 0; i < 2 * d.n_lanes; i++) {
-                    uint8_t* dst = ctx->d_img0_ring[slot] + (size_t)i * img_bytes;
-                    HIPCHECK(hipMemcpy2DAsync(dst, ipitch, ptrs[i], (size_t)stride, (size_t)w, (size_t)h, hipMemcpyDeviceToDevice, st));
-                    ptrs[i] = dst;
-                }
-                d.img0_pitch = ipitch;
-            }
-        } else if (!prepare) {
-            rc = upload_frames(ctx, frames, w, h, (flags & SVO_FLAG_PINNED_IMAGES) != 0, st, ptrs, idle); if (rc) return rc;
-            d.img0_pitch = ipitch;
-        } else {
-            if (!ctx->d_src) { ctx->src_pitch = align_up(3 * ctx->cfg.max_w, 64); HIPCHECK(dev_alloc(ctx, &ctx->d_src, (size_t)2 * ctx->cfg.n_lanes * ctx->src_pitch * ctx->cfg.max_h)); }
-            for (int l = 0; l < d.n_lanes; l++)
-                for (int s = 0; s < 2; s++) {
-                    if (is_idle(l)) continue;
-                    const svo_image& im = s ? frames[l].right : frames[l].left;
-                    uint8_t* dst = ctx->d_src + (size_t)(2 * l + s) * ctx->src_pitch * ctx->cfg.max_h;
-                    HIPCHECK(hipMemcpy2DAsync(dst, ctx->src_pitch, im.data, (size_t)im.stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
-                    prep.src[2 * l + s] = dst;
-                }
-            prep.src_stride = ctx->src_pitch;
-        }
-        if (prepare) {       // stage 1 writes the context's own level-0 buffers; detection reads those
-            for (int i = 0; i < 2 * d.n_lanes; i++) ptrs[i] = ctx->d_img0 + (size_t)i * ipitch * ctx->cfg.max_h;
-            d.img0_pitch = ipitch;
-            prep.maps = ctx->n_maps > 0 ? (const uint2* const*)ctx->d_map_ptrs : nullptr;
-            prep.dst = ctx->d_img0; prep.dst_img_stride = (long long)ipitch * ctx->cfg.max_h; prep.dst_pitch = ipitch;
-            prep.channels = ch; prep.w = w; prep.h = h; prep.idle = idle;
-        }
+        { const int rc_in = intake_frames(ctx, frames, flags, idle, false, st, ptrs, prep, &prepare); if (rc_in) return rc_in; }
     } else if (!ctx->geom_ready && (flags & (SVO_RUN_MATCH | SVO_RUN_OPTIMIZE))) return SVO_ERR_STATE;
     d.fast_th = ctx->fast_th; d.orb_th = ctx->orb_th;
     if (flags & SVO_RUN_DETECT) d.tl_step++;                 // (a frame of the detect-ahead schedule is a detect call and then a post call)
@@ -1581,7 +1610,22 @@ extern "C" int svo_put_features_oct(svo_ctx* ctx, int lane, int which, int side,
     const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
     if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.kps + base, kps, sizeof(svo_keypoint) * n, hipMemcpyHostToDevice));
     if (n > 0 && desc) HIPCHECK(hipMemcpy(ctx->dc.desc + base * 32, desc, (size_t)32 * n, hipMemcpyHostToDevice));
-    (which ? ctx->sad_prev : ctx->sad_cur)[lane] = 0;                      // caller features come without an image: no windows for smSAD / ifmSAD
+    (which ? ctx->sad_prev : ctx->sad_cur)[lane] = 0;                      // caller features come without an image: no windows for smSAD / ifmSAD (until svo_gather_windows brings one)
+    {   // pyr_feats_index of the list just put (m_update_indexes, S2:103-129, as k_nms_rowsort leaves it): idx[r] = #keypoints with (int)y <= r
+        // for first_row <= r < last_row, 0 elsewhere.  The reference builds it in stage 2 only, which this path skips; its row-by-row stereo
+        // matchers (smDescRbR, smSAD: S3:253-256) would read a table nobody built.  Every entry is <= n whatever the caller's order is.
+        const int H = std::max(0, std::min(ctx->dc.oh[octave], ctx->dc.max_h));
+        std::vector<int32_t> ri((size_t)H, 0);
+        if (n > 0 && H > 0) {
+            auto row_of = [](float y) { return y >= 0.0f ? (y < 1.0e9f ? (long long)y : 1000000000LL) : (y > -1.0e9f ? (long long)y : -1000000000LL); };     // (a NaN lands in row 0)
+            std::vector<int32_t> cnt((size_t)H + 1, 0);
+            for (int i = 0; i < n; i++) { const long long r = row_of(kps[i].y); cnt[(size_t)(r < 0 ? 0 : (r > H ? H : r))]++; }
+            const long long first_row = row_of(kps[0].y), last_row = row_of(kps[n - 1].y);
+            int acc = 0;
+            for (int r = 0; r < H; r++) { acc += cnt[(size_t)r]; if (r >= first_row && r < last_row) ri[(size_t)r] = acc; }
+        }
+        if (H > 0) HIPCHECK(hipMemcpy(ctx->dc.row_index + (long long)((vl * 2 + slot) * 2 + side) * ctx->dc.max_h, ri.data(), sizeof(int32_t) * H, hipMemcpyHostToDevice));
+    }
     HIPCHECK(hipMemcpy(ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, &n, sizeof(int), hipMemcpyHostToDevice));
     if (which == 0) {                                                      // result.detected_feats[octave] (P:171-176)
         int32_t* cnt = side ? ctx->dc.results[lane].detected_right : ctx->dc.results[lane].detected_left;
@@ -1661,6 +1705,77 @@ extern "C" int svo_put_tracked(svo_ctx* ctx, int lane, const svo_index_pair* t, 
     if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.tracked + (long long)vl * ctx->dc.max_kps, t, sizeof(svo_index_pair) * n, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ctx->dc.n_tracked + vl, &n, sizeof(int), hipMemcpyHostToDevice));
     return SVO_OK;
+}
+
+// ---- windows for frames the library did not detect --------------------------------------------------------------------
+// svo_gather_windows (svo_hip.h): the images of put / loaded lists arrive here, the x1/2 octave images are built from them as a detect
+// call builds them, and ONE launch gathers the 8 x 8 window and border flag of every keypoint of slot `which` of the active lanes.
+// Plain launches; nothing of the lane state, the records, the lists or the status words is written -- k_begin_frame would do all of
+// that, hence k_publish_img0 for the level-0 pointer table.
+extern "C" int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, int which, const uint64_t lanes[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    char msg[200];
+    if (which != 0 && which != 1) { snprintf(msg, sizeof(msg), "which = %d: 0 (current frame) or 1 (previous frame)", which); ctx->last_error = msg; return SVO_ERR_ARG; }
+    if (flags & ~(uint32_t)(SVO_FLAG_DEVICE_IMAGES | SVO_FLAG_PINNED_IMAGES | SVO_FLAG_BGR_IMAGES)) {
+        snprintf(msg, sizeof(msg), "flags %#x: svo_gather_windows takes SVO_FLAG_DEVICE_IMAGES, SVO_FLAG_PINNED_IMAGES and SVO_FLAG_BGR_IMAGES only", flags);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    if (!frames) { ctx->last_error = "frames == NULL"; return SVO_ERR_ARG; }
+    LaneMask active, idle;
+    for (int wd = 0; wd < 2; wd++) {
+        const int n = ctx->cfg.n_lanes - wd * 64 < 0 ? 0 : (ctx->cfg.n_lanes - wd * 64 > 64 ? 64 : ctx->cfg.n_lanes - wd * 64);
+        const unsigned long long all = n == 64 ? ~0ull : ((1ull << n) - 1ull), a = lanes ? (unsigned long long)lanes[wd] : all;
+        if (a & ~all) {
+            snprintf(msg, sizeof(msg), "active[%d] = %016llx selects a lane at or above n_lanes = %d", wd, a, ctx->cfg.n_lanes);
+            ctx->last_error = msg; return SVO_ERR_ARG;
+        }
+        active.w[wd] = a; idle.w[wd] = all & ~a;
+    }
+    if (!(active.w[0] | active.w[1])) return SVO_OK;       // nobody takes part: nothing is enqueued
+    if (!ctx->geom_ready) { ctx->last_error = "no geometry yet: put or load the lists first (svo_set_params clears the geometry of the lists before it)"; return SVO_ERR_STATE; }
+    DevCtx& d = ctx->dc;
+    const hipStream_t st = ctx->stream;
+    const uint8_t* ptrs[2 * SVO_MAX_LANES];
+    PrepArgs prep; memset(&prep, 0, sizeof(prep)); bool prepare = false;
+    // (the buffers before the intake: a failed allocation must not leave an upload behind)
+    { const int rc = ensure_sad_buffers(ctx); if (rc) return rc; }
+    note_stream(ctx);
+    struct MarkGuard { svo_ctx* c; ~MarkGuard() { mark_stream(c); } } mark_guard{ ctx };
+    { const int rc = intake_frames(ctx, frames, flags, idle, true, st, ptrs, prep, &prepare); if (rc) return rc; }
+    d.idle = idle;
+    struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } } idle_guard{ &d };
+    launch_publish_img0(d, ptrs, st);
+    if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); }
+    if (d.fast_orb) { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }       // S1:82-83: the octave images ifmSAD reads its windows from (S4:572, 576)
+    { Span s(ctx, KT_GATHER_WIN); launch_sad_patch_slot(d, which, st); }
+    for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) (which ? ctx->sad_prev : ctx->sad_cur)[l] = 1;
+    // the ring slot's reader is through once the gather is: the slot may take the next upload
+    if (ctx->up_ready && ctx->det_slot >= 0) { HIPCHECK(hipEventRecord(ctx->ev_det[ctx->det_slot], st)); ctx->ev_det_valid[ctx->det_slot] = true; }
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_get_windows_oct(svo_ctx* ctx, int lane, int which, int side, int octave, uint8_t* win, uint8_t* flag, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
+    if (which ? !s.has_prev : !s.has_cur) return 0;
+    if (!ctx->dc.sad_patch || !(which ? ctx->sad_prev : ctx->sad_cur)[lane]) {
+        char msg[160]; snprintf(msg, sizeof(msg), "lane %d: the 8 x 8 windows of its %s frame were never gathered", lane, which ? "previous" : "current");
+        ctx->last_error = msg; return SVO_ERR_STATE;
+    }
+    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
+    int n = 0;
+    HIPCHECK(hipMemcpy(&n, ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, sizeof(int), hipMemcpyDeviceToHost));
+    const int m = n < cap ? n : cap;
+    const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
+    if (win && m > 0) HIPCHECK(hipMemcpy(win, ctx->dc.sad_patch + base * 64, (size_t)64 * m, hipMemcpyDeviceToHost));
+    if (flag && m > 0) HIPCHECK(hipMemcpy(flag, ctx->dc.sad_flag + base, (size_t)m, hipMemcpyDeviceToHost));
+    return n;
 }
 
 // ---- getProjectedCoords (common.cpp:415-466) --------------------------------------------------------------------
@@ -1771,91 +1886,67 @@ extern "C" int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes
 }
 
 // ---- saveStateToFile / loadStateFromFile (common.cpp:475-543, 261-350; helpers :88-255) --------------------------
-namespace {
-struct StateList { std::vector<svo_keypoint> kps; std::vector<uint8_t> desc; };
-bool wr(FILE* f, const void* p, size_t n) { return fwrite(p, 1, n, f) == n; }
-bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
-bool dump_keypoints(FILE* f, const StateList& L)              // m_dump_keypoints_to_stream (C:88-133)
+// The bytes are state_format.cpp's business (host only, exercised under sanitizers by tools/state_format_fuzz.cpp); here the lists
+// move between the device and a svo_state::State.
+// the octave count the parameters in force give a frame (ensure_geometry)
+static int params_n_oct(const svo_params& p)
 {
-    const uint64_t n = L.kps.size();
-    if (!wr(f, &n, 8)) return false;
-    for (const svo_keypoint& k : L.kps) {
-        const float v[5] = { k.x, k.y, k.response, k.size, k.angle };
-        const int32_t w[2] = { k.octave, k.class_id };
-        if (!wr(f, v, sizeof(v)) || !wr(f, w, sizeof(w))) return false;
-    }
-    const int32_t hdr[3] = { (int32_t)n, n ? 32 : 0, 0 /* CV_8UC1 */ };
-    return wr(f, hdr, sizeof(hdr)) && (L.desc.empty() || wr(f, L.desc.data(), L.desc.size()));
+    const bool fast_orb = p.detect_method == SVO_DM_FAST_ORB || p.detect_method == SVO_DM_FASTER;
+    return fast_orb ? (p.nOctaves < 1 ? 1 : p.nOctaves) : 1;
 }
-bool load_keypoints(FILE* f, StateList& L, size_t cap)         // m_load_keypoints_from_stream (C:168-211)
-{
-    uint64_t n = 0;
-    if (!rd(f, &n, 8) || n > cap) return false;
-    L.kps.resize((size_t)n);
-    for (svo_keypoint& k : L.kps) {
-        float v[5]; int32_t w[2];
-        if (!rd(f, v, sizeof(v)) || !rd(f, w, sizeof(w))) return false;
-        k.x = v[0]; k.y = v[1]; k.response = v[2]; k.size = v[3]; k.angle = v[4]; k.octave = w[0]; k.class_id = w[1];
-    }
-    int32_t hdr[3];
-    if (!rd(f, hdr, sizeof(hdr)) || hdr[0] < 0 || hdr[1] < 0) return false;
-    if ((uint64_t)hdr[0] != n || (n && hdr[1] != 32)) return false;             // this path only knows 256-bit descriptors
-    L.desc.resize((size_t)n * 32);
-    return L.desc.empty() || rd(f, L.desc.data(), L.desc.size());
-}
-bool dump_matches(FILE* f, const std::vector<svo_dmatch>& m, const std::vector<int32_t>& ids)   // m_dump_matches_to_stream (C:138-163)
-{
-    const uint64_t n = m.size(), ni = ids.size();
-    if (!wr(f, &n, 8) || !wr(f, &ni, 8)) return false;
-    for (size_t i = 0; i < m.size(); i++) {
-        if (n == ni) { const uint64_t id = (uint64_t)(int64_t)ids[i]; if (!wr(f, &id, 8)) return false; }
-        if (!wr(f, &m[i].queryIdx, 4) || !wr(f, &m[i].trainIdx, 4) || !wr(f, &m[i].distance, 4) || !wr(f, &m[i].imgIdx, 4)) return false;
-    }
-    return true;
-}
-bool load_matches(FILE* f, std::vector<svo_dmatch>& m, std::vector<int32_t>& ids, size_t cap)    // m_load_matches_from_stream (C:216-255)
-{
-    uint64_t n = 0, ni = 0;
-    if (!rd(f, &n, 8) || !rd(f, &ni, 8) || n > cap || ni > cap) return false;
-    m.resize((size_t)n); ids.assign((size_t)ni, 0);
-    for (size_t i = 0; i < m.size(); i++) {
-        if (n == ni) { uint64_t id; if (!rd(f, &id, 8)) return false; ids[i] = (int32_t)id; }
-        if (!rd(f, &m[i].queryIdx, 4) || !rd(f, &m[i].trainIdx, 4) || !rd(f, &m[i].distance, 4) || !rd(f, &m[i].imgIdx, 4)) return false;
-    }
-    return true;
-}
-}  // namespace
 
 extern "C" int svo_save_state(svo_ctx* ctx, int lane, const char* path)
 {
     if (ctx) use_device(ctx);
     if (!ctx || !path || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
-    if (ctx->dc.n_oct > 1) return SVO_ERR_UNSUPPORTED;                 // the reference's format holds one list per eye
     int rc = svo_wait(ctx); if (rc) return rc;
     LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    StateList L[2][2]; std::vector<svo_dmatch> M[2]; std::vector<int32_t> I[2];           // [which: 0 cur, 1 prev]
-    for (int which = 0; which < 2; which++) {
-        for (int side = 0; side < 2; side++) {
-            const int n = svo_get_keypoints_oct(ctx, lane, which, side, 0, nullptr, nullptr, 0); if (n < 0) return n;
-            L[which][side].kps.resize(n); L[which][side].desc.resize((size_t)n * 32);
-            if (n) { rc = svo_get_keypoints_oct(ctx, lane, which, side, 0, L[which][side].kps.data(), L[which][side].desc.data(), n); if (rc < 0) return rc; }
+    const int n_oct = ctx->dc.n_oct;
+    svo_state::State S;                                                                    // frame[0] = PRE (which 1), frame[1] = CUR (which 0)
+    for (int f = 0; f < 2; f++) {
+        const int which = 1 - f;
+        S.frame[f].resize((size_t)n_oct);
+        for (int o = 0; o < n_oct; o++) {
+            svo_state::Group& G = S.frame[f][(size_t)o];
+            for (int side = 0; side < 2; side++) {
+                svo_state::List& L = side ? G.right : G.left;
+                const int n = svo_get_keypoints_oct(ctx, lane, which, side, o, nullptr, nullptr, 0); if (n < 0) return n;
+                L.kps.resize((size_t)n); L.desc.resize((size_t)n * 32);
+                if (n) { rc = svo_get_keypoints_oct(ctx, lane, which, side, o, L.kps.data(), L.desc.data(), n); if (rc < 0) return rc; }
+            }
+            int n = svo_get_matches_oct(ctx, lane, which, o, nullptr, 0); if (n < 0) return n;
+            G.matches.resize((size_t)n); if (n) { rc = svo_get_matches_oct(ctx, lane, which, o, G.matches.data(), n); if (rc < 0) return rc; }
+            n = svo_get_match_ids(ctx, lane, which, o, nullptr, 0); if (n < 0) return n;
+            G.ids.resize((size_t)n); if (n) { rc = svo_get_match_ids(ctx, lane, which, o, G.ids.data(), n); if (rc < 0) return rc; }
         }
-        int n = svo_get_matches_oct(ctx, lane, which, 0, nullptr, 0); if (n < 0) return n;
-        M[which].resize(n); if (n) { rc = svo_get_matches_oct(ctx, lane, which, 0, M[which].data(), n); if (rc < 0) return rc; }
-        n = svo_get_match_ids(ctx, lane, which, 0, nullptr, 0); if (n < 0) return n;
-        I[which].resize(n); if (n) { rc = svo_get_match_ids(ctx, lane, which, 0, I[which].data(), n); if (rc < 0) return rc; }
+        // the frame's windows travel when it exists and they were gathered ("true" on the host also stands for "no such frame yet")
+        const bool present = which ? s.has_prev != 0 : s.has_cur != 0;
+        S.has_win[f] = (present && ctx->dc.sad_patch && (which ? ctx->sad_prev : ctx->sad_cur)[lane]) ? 1 : 0;
+        if (!S.has_win[f]) continue;
+        S.win[f].resize((size_t)2 * n_oct);
+        for (int o = 0; o < n_oct; o++)
+            for (int side = 0; side < 2; side++) {
+                svo_state::Windows& Wn = S.win[f][(size_t)o * 2 + side];
+                const int n = svo_get_windows_oct(ctx, lane, which, side, o, nullptr, nullptr, 0); if (n < 0) return n;
+                Wn.flag.resize((size_t)n); Wn.win.resize((size_t)n * 64);
+                if (n) { rc = svo_get_windows_oct(ctx, lane, which, side, o, Wn.win.data(), Wn.flag.data(), n); if (rc < 0) return rc; }
+                // (a flagged keypoint has no window: whatever the buffer held there does not belong in a file)
+                for (int i = 0; i < n; i++) if (Wn.flag[(size_t)i]) memset(Wn.win.data() + (size_t)i * 64, 0, 64);
+            }
     }
     svo_result res; HIPCHECK(hipMemcpy(&res, ctx->dc.results + lane, sizeof(res), hipMemcpyDeviceToHost));
+    S.npyr = (uint64_t)n_oct;                                                              // C:488-489
+    S.m_reset = s.reset_ids ? 1 : 0;
+    S.tail[0] = 0 /* m_lastID: legacy, never used */; S.tail[1] = (uint64_t)s.num_tracked_last_kf; S.tail[2] = (uint64_t)res.tracked_feats_from_last_frame;
+    S.tail[3] = (uint64_t)s.last_match_id; S.tail[4] = (uint64_t)s.last_kf_max_id;
+    // the extension block: only where the reference's layout cannot hold the state (more octaves than one, or windows)
+    S.has_ext = n_oct > 1 || S.has_win[0] || S.has_win[1];
+    S.n_oct = (uint32_t)n_oct; S.w = (uint32_t)ctx->dc.W; S.h = (uint32_t)ctx->dc.H;
+    std::vector<uint8_t> bytes;
+    if (!svo_state::write(S, bytes)) { ctx->last_error = "internal: inconsistent state record"; return SVO_ERR_STATE; }
     FILE* f = fopen(path, "wb");
     if (!f) { ctx->last_error = std::string("cannot open ") + path; return SVO_ERR_ARG; }
-    const uint64_t npyr = 1;
-    bool ok = wr(f, &npyr, 8);
-    for (int which = 1; which >= 0 && ok; which--)                       // PRE first, then CUR (C:491-527)
-        ok = dump_keypoints(f, L[which][0]) && dump_keypoints(f, L[which][1]) && dump_matches(f, M[which], I[which]);
-    const uint8_t m_reset = s.reset_ids ? 1 : 0;
-    const uint64_t tail[5] = { 0 /* m_lastID: legacy, never used */, (uint64_t)s.num_tracked_last_kf, (uint64_t)res.tracked_feats_from_last_frame,
-                               (uint64_t)s.last_match_id, (uint64_t)s.last_kf_max_id };
-    ok = ok && wr(f, &m_reset, 1) && wr(f, tail, sizeof(tail));
+    bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
     ok = (fclose(f) == 0) && ok;
     if (!ok) { ctx->last_error = std::string("short write to ") + path; return SVO_ERR_STATE; }
     return SVO_OK;
@@ -1865,34 +1956,62 @@ extern "C" int svo_load_state(svo_ctx* ctx, int lane, const char* path)
 {
     if (ctx) use_device(ctx);
     if (!ctx || !path || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
-    if (ctx->dc.oct_cap > 1 && ctx->dc.n_oct > 1) return SVO_ERR_UNSUPPORTED;
-    FILE* f = fopen(path, "rb");
-    if (!f) { ctx->last_error = std::string("cannot open ") + path; return SVO_ERR_ARG; }
-    StateList L[2][2]; std::vector<svo_dmatch> M[2]; std::vector<int32_t> I[2];
-    uint64_t npyr = 0, tail[5]; uint8_t m_reset = 0;
-    const size_t cap = (size_t)ctx->dc.max_kps;
-    bool ok = rd(f, &npyr, 8);
-    for (int which = 1; which >= 0 && ok; which--)
-        ok = load_keypoints(f, L[which][0], cap) && load_keypoints(f, L[which][1], cap) && load_matches(f, M[which], I[which], cap);
-    ok = ok && rd(f, &m_reset, 1) && rd(f, tail, sizeof(tail));
-    fclose(f);
-    if (!ok) { ctx->last_error = std::string("malformed or truncated state file ") + path; return SVO_ERR_ARG; }
-    // the file carries no image size: the geometry of the last frame, or the context's maximum for a fresh context
-    const int gw = ctx->geom_ready ? ctx->geom_w : ctx->cfg.max_w, gh = ctx->geom_ready ? ctx->geom_h : ctx->cfg.max_h;
-    int rc = svo_reset(ctx, lane); if (rc) return rc;
-    for (int which = 1; which >= 0; which--) {
-        for (int side = 0; side < 2; side++) {
-            rc = svo_put_features(ctx, lane, which, side, L[which][side].kps.data(), L[which][side].desc.data(), (int)L[which][side].kps.size(), gw, gh);
-            if (rc) return rc;
+    std::vector<uint8_t> bytes;
+    {
+        FILE* f = fopen(path, "rb");
+        if (!f) { ctx->last_error = std::string("cannot open ") + path; return SVO_ERR_ARG; }
+        uint8_t chunk[1 << 16]; size_t k;
+        while ((k = fread(chunk, 1, sizeof(chunk), f)) > 0) bytes.insert(bytes.end(), chunk, chunk + k);
+        fclose(f);
+    }
+    // the whole file is validated before the lane is touched
+    svo_state::State S; std::string why;
+    if (!svo_state::parse(bytes.data(), bytes.size(), (size_t)ctx->dc.max_kps, S, why)) { ctx->last_error = std::string("malformed or truncated state file ") + path + ": " + why; return SVO_ERR_ARG; }
+    const int ctx_oct = params_n_oct(ctx->params);
+    char msg[200];
+    if ((int)S.n_oct != ctx_oct) {                         // (a file of the reference's layout alone holds octave 0: n_oct = 1)
+        snprintf(msg, sizeof(msg), "the state file holds n_oct = %u%s, the context's parameters give n_oct = %d", S.n_oct, S.has_ext ? "" : " (no extension block: octave 0 only)", ctx_oct);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    if (S.has_ext && ((int)S.w > ctx->cfg.max_w || (int)S.h > ctx->cfg.max_h || S.w < 64 || S.h < 64)) {
+        snprintf(msg, sizeof(msg), "the state file's image size %u x %u is outside what the context takes (64 x 64 .. %d x %d)", S.w, S.h, ctx->cfg.max_w, ctx->cfg.max_h);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    if (S.has_ext && ctx_oct > ctx->dc.oct_cap) return SVO_ERR_CAPACITY;
+    // a file without the block carries no image size: the geometry of the last frame, or the context's maximum for a fresh context
+    const int gw = S.has_ext ? (int)S.w : (ctx->geom_ready ? ctx->geom_w : ctx->cfg.max_w), gh = S.has_ext ? (int)S.h : (ctx->geom_ready ? ctx->geom_h : ctx->cfg.max_h);
+    const bool any_win = S.has_win[0] || S.has_win[1];
+    int rc = ensure_geometry(ctx, gw, gh); if (rc) return rc;                             // (refusals of the geometry come before the lane is reset)
+    if (any_win) { rc = ensure_sad_buffers(ctx); if (rc) return rc; }
+    rc = svo_reset(ctx, lane); if (rc) return rc;
+    const int n_oct = S.has_ext ? (int)S.n_oct : 1;
+    for (int f = 0; f < 2; f++) {                                                        // PRE, then CUR
+        const int which = 1 - f;
+        for (int o = 0; o < n_oct; o++) {
+            const svo_state::Group& G = S.frame[f][(size_t)o];
+            for (int side = 0; side < 2; side++) {
+                const svo_state::List& L = side ? G.right : G.left;
+                rc = svo_put_features_oct(ctx, lane, which, side, o, L.kps.data(), L.desc.data(), (int)L.kps.size(), gw, gh);
+                if (rc) return rc;
+            }
+            rc = svo_put_matches_oct(ctx, lane, which, o, G.matches.data(), (int)G.matches.size()); if (rc) return rc;
+            LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
+            const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + o, ni = (int)G.ids.size();
+            if (ni > 0) HIPCHECK(hipMemcpy(ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, G.ids.data(), sizeof(int32_t) * ni, hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(ctx->dc.n_ids + vl * 2 + slot, &ni, sizeof(int), hipMemcpyHostToDevice));
+            if (!S.has_win[f]) continue;
+            for (int side = 0; side < 2; side++) {
+                const svo_state::Windows& Wn = S.win[f][(size_t)o * 2 + side];
+                const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
+                if (Wn.flag.empty()) continue;
+                HIPCHECK(hipMemcpy(ctx->dc.sad_flag + base, Wn.flag.data(), Wn.flag.size(), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(ctx->dc.sad_patch + base * 64, Wn.win.data(), Wn.win.size(), hipMemcpyHostToDevice));
+            }
         }
-        rc = svo_put_matches(ctx, lane, which, M[which].data(), (int)M[which].size()); if (rc) return rc;
-        LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
-        const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap, ni = (int)I[which].size();
-        if (ni > 0) HIPCHECK(hipMemcpy(ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, I[which].data(), sizeof(int32_t) * ni, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(ctx->dc.n_ids + vl * 2 + slot, &ni, sizeof(int), hipMemcpyHostToDevice));
+        (which ? ctx->sad_prev : ctx->sad_cur)[lane] = S.has_win[f];                      // (svo_put_features_oct cleared it: lists without an image)
     }
     LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    s.reset_ids = m_reset; s.num_tracked_last_kf = (int)tail[1]; s.last_match_id = (int)tail[3]; s.last_kf_max_id = (int)tail[4];
+    s.reset_ids = S.m_reset; s.num_tracked_last_kf = (int)S.tail[1]; s.last_match_id = (int)S.tail[3]; s.last_kf_max_id = (int)S.tail[4];
     HIPCHECK(hipMemcpy(ctx->dc.lane + lane, &s, sizeof(s), hipMemcpyHostToDevice));
     return SVO_OK;
 }

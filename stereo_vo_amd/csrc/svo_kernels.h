@@ -51,6 +51,8 @@ void launch_fast(const DevCtx& c, hipStream_t st);
 void launch_select(const DevCtx& c, hipStream_t st);
 void launch_describe(const DevCtx& c, int pre, hipStream_t st);
 void launch_sad_patch(const DevCtx& c, hipStream_t st);       // needs DevCtx.sad_patch / sad_flag (allocated when a SAD selector is first in force)
+void launch_publish_img0(const DevCtx& c, const uint8_t* const* ptrs, hipStream_t st);      // svo_gather_windows: the level-0 pointer table of the active lanes, nothing else
+void launch_sad_patch_slot(const DevCtx& c, int which, hipStream_t st);                    // the same gather for slot `which` (0 current, 1 previous) of put / loaded lists
 hipError_t configure_nms_rowsort(const DevCtx& c);
 size_t nms_rowsort_scratch_bytes(const DevCtx& c);
 int nms_rowsort_items(const DevCtx& c);           // keys per thread of the k_nms_rowsort instantiation this geometry launches: 4, 8 or 16

@@ -28,7 +28,7 @@ EXPORTS = [
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
-    "svo_handover_bytes", "svo_export_frame", "svo_import_frame",
+    "svo_handover_bytes", "svo_export_frame", "svo_import_frame", "svo_gather_windows", "svo_get_windows_oct",
     "svo_use_graphs", "svo_record_after_post", "svo_wait_upload", "svo_host_alloc", "svo_host_free", "svo_host_register", "svo_host_unregister",
 ]
 
@@ -95,6 +95,7 @@ def lib():
         L.svo_batch_create_sized.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
         _LIB = L
     return _LIB
 
@@ -316,6 +317,49 @@ class Context:
         fr, words = self._ptr_frames(ptr_pairs, w, h, stride, active)
         self._process(fr, (flags | FLAG_PINNED_IMAGES) & ~FLAG_DEVICE_IMAGES, words)
 
+    # -- windows for lists the library did not detect (svo_gather_windows) ------------------------------------
+    def _gather(self, fr, flags, which, words):
+        m = None
+        if words is not None:
+            w = list(words) + [0]
+            m = (C.c_uint64 * 2)(w[0], w[1])
+        self._ck(self.L.svo_gather_windows(self.h, fr, C.c_uint32(flags), int(which), m), "svo_gather_windows")
+
+    def gather_windows(self, pairs, which=0, active=None):
+        """The images of put / loaded lists: gathers the SAD windows of the current (which=0) or previous (which=1) frame of the
+        active lanes.  pairs: (left, right) uint8 numpy arrays per lane, [h, w] grey or [h, w, 3] BGR; entries of idle lanes may be None."""
+        assert len(pairs) == self.n_lanes
+        fr = (Frame * self.n_lanes)()
+        keep, flags = [], 0
+        words, idle = self._mask(active)
+        for i, pr in enumerate(pairs):
+            if i in idle:
+                continue
+            l, r = (np.ascontiguousarray(x, np.uint8) for x in pr)
+            keep += [l, r]
+            h, w = l.shape[:2]
+            if l.ndim == 3:
+                assert l.shape[2] == 3 and r.shape == l.shape
+                flags |= FLAG_BGR_IMAGES
+            fr[i].left = Image(l.ctypes.data, w, h, l.strides[0])
+            fr[i].right = Image(r.ctypes.data, w, h, r.strides[0])
+        self._keep = keep
+        self._gather(fr, flags, which, words)
+
+    def gather_windows_device(self, ptr_pairs, w, h, stride, which=0, active=None, flags=0):
+        """the same from device addresses (read in place under the read contract of svo_image.stride)"""
+        fr, words = self._ptr_frames(ptr_pairs, w, h, stride, active)
+        self._gather(fr, flags | FLAG_DEVICE_IMAGES, which, words)
+
+    def windows(self, lane=0, which=0, side=0, octave=0):
+        """(windows [n, 8, 8] uint8, border flags [n] uint8) of one list; SvoError when that frame's windows were never gathered"""
+        n = self._ck(self.L.svo_get_windows_oct(self.h, lane, which, side, octave, None, None, 0), "svo_get_windows_oct")
+        win = np.zeros((n, 8, 8), np.uint8)
+        flag = np.zeros(n, np.uint8)
+        if n:
+            self._ck(self.L.svo_get_windows_oct(self.h, lane, which, side, octave, _vp(win), _vp(flag), n), "svo_get_windows_oct")
+        return win, flag
+
     def handover_bytes(self):
         self.L.svo_handover_bytes.restype = C.c_size_t
         return int(self.L.svo_handover_bytes(self.h))
@@ -362,11 +406,12 @@ class Context:
         return pix[:n].copy()
 
     def save_state(self, lane, path):
-        """saveStateToFile (common.cpp:475-543) of one lane."""
+        """saveStateToFile (common.cpp:475-543) of one lane: the reference's layout with the octave-0 lists, followed -- for a context
+        that works on several octaves or whose frames have SAD windows -- by the extension block (state_file.py)."""
         self._ck(self.L.svo_save_state(self.h, lane, os.fsencode(path)), "svo_save_state")
 
     def load_state(self, lane, path):
-        """loadStateFromFile (common.cpp:261-350) into one lane."""
+        """loadStateFromFile (common.cpp:261-350) into one lane; a file with the extension block brings every octave and the windows."""
         self._ck(self.L.svo_load_state(self.h, lane, os.fsencode(path)), "svo_load_state")
 
     def run_stages(self, flags, active=None):
@@ -542,12 +587,17 @@ class Context:
         return idx[:len(q)], dist[:len(q)]
 
     # -- timing ----------------------------------------------------------------------------------------
-    def kernel_times(self):
-        names = (C.c_char_p * 32)()
-        tot = (C.c_double * 32)()
-        calls = (C.c_int64 * 32)()
-        n = self._ck(self.L.svo_kernel_times(self.h, names, tot, calls, 32), "svo_kernel_times")
-        return {names[i].decode(): (tot[i], calls[i]) for i in range(n)}
+    FRAME_KERNEL_NAMES = 32
+
+    def kernel_times(self, appended=False):
+        """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
+        hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows) and are
+        included with appended=True, so that a reader of the frame's launches finds the list it always found."""
+        names = (C.c_char_p * 64)()
+        tot = (C.c_double * 64)()
+        calls = (C.c_int64 * 64)()
+        n = self._ck(self.L.svo_kernel_times(self.h, names, tot, calls, 64), "svo_kernel_times")
+        return {names[i].decode(): (tot[i], calls[i]) for i in range(n if appended else min(n, self.FRAME_KERNEL_NAMES))}
 
     def kernel_times_select(self, name=None):
         self._ck(self.L.svo_kernel_times_select(self.h, name.encode() if name else None), "svo_kernel_times_select")

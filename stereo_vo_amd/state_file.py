@@ -14,6 +14,21 @@ helpers m_dump_keypoints_to_stream :88-133 and m_dump_matches_to_stream :138-163
 
 The reference's loadStateFromFile (common.cpp:261-350) expects one more u64 ("v_s", :342-343) before m_last_match_ID
 that its own saver never writes; this module, like svo_load_state, reads what the saver writes.
+
+THE EXTENSION BLOCK.  svo_save_state appends it, directly behind the tail, when the context works on more than one octave or at
+least one of the two frames has the SAD matchers' 8 x 8 windows; the bytes above stay first and unchanged (octave 0; npyr is then
+the octave count), so a reader of the reference's layout still gets octave 0.  Little-endian, no padding:
+
+    magic u32 = 0x58455653 ("SVEX"), version u32 = 1, n_oct u32 (1 .. 4), w u32, h u32      the octave-0 image size
+    has_windows u8 x 2                                                                      PRE, CUR
+    for octave 1 .. n_oct - 1:  PRE left, PRE right, PRE pairings, CUR left, CUR right, CUR pairings   (sub-layouts as above)
+    for frame in (PRE, CUR) with has_windows, for octave 0 .. n_oct - 1, for side in (left, right):
+        count u64 (= the list's keypoint count), count flag bytes (1: no window, too close to the border),
+        count * 64 window bytes (8 rows of 8 pixels, top to bottom; zero where the flag is set)
+
+read_state reports it under three more keys: `size` = (w, h), `octaves` = [{"pre": group, "cur": group}] for octaves 1 .. n_oct - 1
+and `windows` = {"pre": w, "cur": w} with w = None or, per octave from 0, {"left": (windows [n, 8, 8], flags [n]), "right": ...}.
+Without a block they are None, [] and None.  An independent reading of the layout: nothing here calls the library.
 """
 import struct
 
@@ -67,12 +82,49 @@ def _load_matches(buf, off):
     return m, ids, off
 
 
-def write_state(path, pre, cur, reset=False, num_tracked_last_kf=0, num_tracked_last_frame=0, last_match_id=0, kf_max_match_id=0, npyr=1):
-    """pre / cur: dicts with left=(kps, desc), right=(kps, desc), matches, ids."""
+EXT_MAGIC, EXT_VERSION = 0x58455653, 1
+
+
+def _dump_group(d):
+    return [_dump_keypoints(*d["left"]), _dump_keypoints(*d["right"]), _dump_matches(d["matches"], d["ids"])]
+
+
+def _load_group(buf, off):
+    lk, ld, off = _load_keypoints(buf, off)
+    rk, rd, off = _load_keypoints(buf, off)
+    m, ids, off = _load_matches(buf, off)
+    return {"left": (lk, ld), "right": (rk, rd), "matches": m, "ids": ids}, off
+
+
+def write_state(path, pre, cur, reset=False, num_tracked_last_kf=0, num_tracked_last_frame=0, last_match_id=0, kf_max_match_id=0, npyr=1,
+                octaves=None, windows=None, size=None):
+    """pre / cur: dicts with left=(kps, desc), right=(kps, desc), matches, ids.  octaves / windows / size as read_state returns them:
+    the extension block is written when any of them is given (size is then required)."""
     blob = [struct.pack("<Q", npyr)]
     for d in (pre, cur):
-        blob += [_dump_keypoints(*d["left"]), _dump_keypoints(*d["right"]), _dump_matches(d["matches"], d["ids"])]
+        blob += _dump_group(d)
     blob.append(struct.pack("<BQQQQQ", 1 if reset else 0, 0, num_tracked_last_kf, num_tracked_last_frame, last_match_id, kf_max_match_id))
+    if octaves or windows is not None or size is not None:
+        octaves = list(octaves or [])
+        windows = windows or {"pre": None, "cur": None}
+        n_oct = 1 + len(octaves)
+        groups = [{"pre": pre, "cur": cur}] + octaves
+        blob.append(struct.pack("<IIIIIBB", EXT_MAGIC, EXT_VERSION, n_oct, int(size[0]), int(size[1]),
+                                1 if windows.get("pre") is not None else 0, 1 if windows.get("cur") is not None else 0))
+        for o in octaves:
+            blob += _dump_group(o["pre"]) + _dump_group(o["cur"])
+        for name in ("pre", "cur"):
+            wn = windows.get(name)
+            if wn is None:
+                continue
+            assert len(wn) == n_oct, "windows of a frame: one entry per octave"
+            for o in range(n_oct):
+                for side in ("left", "right"):
+                    win, flag = wn[o][side]
+                    flag = np.ascontiguousarray(flag, np.uint8).reshape(-1)
+                    win = np.ascontiguousarray(win, np.uint8).reshape(len(flag), 64)
+                    assert len(flag) == len(groups[o][name][side][0]), "a windows count must equal its list's count"
+                    blob += [struct.pack("<Q", len(flag)), flag.tobytes(), win.tobytes()]
     with open(path, "wb") as f:
         f.write(b"".join(blob))
 
@@ -87,6 +139,35 @@ def read_state(path):
         m, ids, off = _load_matches(buf, off)
         out[name] = {"left": (lk, ld), "right": (rk, rd), "matches": m, "ids": ids}
     r, last_id, nkf, nfr, lm, kfm = struct.unpack_from("<BQQQQQ", buf, off); off += 41
-    assert off == len(buf), "trailing bytes in the state file"
     out.update(reset=bool(r), last_id=last_id, num_tracked_last_kf=nkf, num_tracked_last_frame=nfr, last_match_id=lm, kf_max_match_id=kfm)
+    out.update(size=None, octaves=[], windows=None)
+    if off == len(buf):
+        return out
+    assert len(buf) - off >= 22, "trailing bytes in the state file"
+    magic, version, n_oct, w, h, hw_pre, hw_cur = struct.unpack_from("<IIIIIBB", buf, off); off += 22
+    assert magic == EXT_MAGIC, "trailing bytes in the state file"
+    assert version == EXT_VERSION and 1 <= n_oct <= 4 and hw_pre in (0, 1) and hw_cur in (0, 1), "unknown extension block"
+    out["size"] = (w, h)
+    for _ in range(1, n_oct):
+        o = {}
+        o["pre"], off = _load_group(buf, off)
+        o["cur"], off = _load_group(buf, off)
+        out["octaves"].append(o)
+    groups = [{"pre": out["pre"], "cur": out["cur"]}] + out["octaves"]
+    out["windows"] = {"pre": None, "cur": None}
+    for name, has in (("pre", hw_pre), ("cur", hw_cur)):
+        if not has:
+            continue
+        wn = []
+        for o in range(n_oct):
+            e = {}
+            for side in ("left", "right"):
+                (n,) = struct.unpack_from("<Q", buf, off); off += 8
+                assert n == len(groups[o][name][side][0]), "a windows count differs from its list's count"
+                flag = np.frombuffer(buf, np.uint8, n, off).copy(); off += n
+                win = np.frombuffer(buf, np.uint8, n * 64, off).reshape(n, 8, 8).copy(); off += n * 64
+                e[side] = (win, flag)
+            wn.append(e)
+        out["windows"][name] = wn
+    assert off == len(buf), "trailing bytes behind the extension block"
     return out
