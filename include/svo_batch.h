@@ -78,6 +78,9 @@ svo_ctx* svo_batch_context(svo_batch* b, int k);
 int  svo_batch_set_params(svo_batch* b, const svo_params* p);   /* every context (loadParamsFromConfigFile, H:554-663) */
 int  svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam);   /* global lane index, -1 = every stream */
 int  svo_batch_set_klt_win(svo_batch* b, int klt_win);          /* every context (svo_hip.h: dmFASTER's KLT_win, 1 .. 15) */
+/* svo_set_pose_covariance on every context (waits for the steps in flight first).  The records are read with svo_batch_pose_covariances;
+ * they stay in the contexts (there is no device-buffer variant: svo_copy_pose_covariances_async on svo_batch_context(b, k) serves that). */
+int  svo_batch_set_pose_covariance(svo_batch* b, int enable);
 /* Where every step leaves the result records: caller-owned DEVICE memory of svo_batch_lanes() * sizeof(svo_result) bytes, in
  * lane order (lane = context * lanes_per_context + lane_in_context) -- e.g. this rank's slot of an all-gather buffer.
  * NULL: a buffer of the batch's own (svo_batch_results reads it). */
@@ -108,6 +111,8 @@ int  svo_batch_wait_on_stream(svo_batch* b, void* stream);
 int  svo_batch_hold_for_event(svo_batch* b, void* event);
 int  svo_batch_synchronize(svo_batch* b);
 int  svo_batch_results(svo_batch* b, svo_result* res /* svo_batch_lanes() entries */);    /* implies svo_batch_synchronize */
+/* the pose-covariance record of every stream, global lane order; implies svo_batch_synchronize.  SVO_ERR_STATE while the feature is off */
+int  svo_batch_pose_covariances(svo_batch* b, svo_pose_cov* cov /* svo_batch_lanes() entries */);
 int  svo_batch_reset(svo_batch* b);                             /* every stream a freshly constructed estimator again (C:28-50) */
 
 typedef struct svo_fpstream svo_fpstream;
@@ -124,6 +129,9 @@ svo_ctx* svo_fpstream_last_owner(svo_fpstream* f);              /* the context t
 int  svo_fpstream_set_params(svo_fpstream* f, const svo_params* p);
 int  svo_fpstream_set_camera(svo_fpstream* f, int lane, const svo_stereo_camera* cam);
 int  svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win);    /* every context */
+/* svo_set_pose_covariance on every context.  The record of the frame pushed last is in its owner: svo_get_pose_covariance(s) on
+ * svo_fpstream_last_owner.  (The hand-over records do not carry it.) */
+int  svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable);
 /* the next frame of the stream(s): frames[lane]; flags as for svo_batch_step.  Enqueues and returns; the frame's result records
  * (n_lanes of them) land in the owner context -- svo_get_result(s) on svo_fpstream_last_owner waits for them. */
 int  svo_fpstream_push(svo_fpstream* f, const svo_frame* frames, uint32_t flags);

@@ -183,7 +183,7 @@ int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
  * frame (H:732-831: all state is per instance).  For every lane whose bit is CLEAR the call is AS IF IT HAD NOT BEEN MADE: nothing that a
  * getter, a later frame, a hand-over record or a state file can observe changes -- the result record, both slots' keypoint /
  * descriptor / pairing / ID lists with their counts and row-index tables, the tracked list, residuals and outliers, the lane state
- * (iteration counter, m_error, which slot is the previous frame, the match-ID counters), the status word, the speculative FAST
+ * (iteration counter, m_error, which slot is the previous frame, the match-ID counters), the status word, its pose-covariance record, the speculative FAST
  * thresholds of its two images, its gathered SAD windows and the host-side record of which of its frames have them.  No shift, no
  * zero-motion frame, no match IDs consumed.  Only per-frame scratch (pyramid, candidate lists, matcher and RANSAC tables) may be
  * rewritten.  For every lane whose bit is SET the call is exactly svo_process; with every bit set it IS svo_process, launch for launch.
@@ -251,6 +251,28 @@ int svo_get_results(svo_ctx* ctx, svo_result* res /* n_lanes entries */);
 /* enqueue a device-to-device copy of the n_lanes result records into caller-owned device memory (e.g. the send
  * buffer of an RCCL all-gather of poses) on the context's stream; no host synchronisation */
 int svo_copy_results_async(svo_ctx* ctx, void* dst_device, size_t bytes);
+
+/* THE COVARIANCE OF EVERY POSE INCREMENT (no reference counterpart; the quantity and the states are defined at svo_pose_cov in
+ * svo_types.h).  Off by default; while off a context allocates and launches nothing for it and every result is what it was.
+ * svo_set_pose_covariance(ctx, 1) allocates one record per lane (all SVO_COV_NONE) and the array stage 5 leaves its final mask in, at
+ * once (before any graph capture); from then on every call that runs stage 5 -- svo_process / svo_process_lanes with SVO_RUN_OPTIMIZE,
+ * and svo_change_in_pose -- launches k_pose_covariance behind k_gauss_newton ("pose_covariance" in svo_kernel_times, a name listed only while the
+ * feature is on: with it off the list is the one it always was), which rewrites the
+ * record of every ACTIVE lane: one more evaluation at the returned delta over the mask stage 5 ended with.  `info` is WEIGHTED by the
+ * robust kernel's weights, unlike the Hessian the iteration solves with (S5:364-369).  A record is SVO_COV_NONE unless the stage 5 of
+ * that very call ended with valid = 1: the kernel is told so by k_gauss_newton itself, not by svo_result.valid, so nothing stale can
+ * leak in on any path.  svo_change_in_pose writes lane 0's record, as it uses lane 0's warm start.  A change of value drops the
+ * captured graphs (svo_use_graphs); a call with idle lanes still runs as plain launches, and an idle lane keeps its record.
+ * Other entry points treat the record as they treat the lane's svo_result: svo_reset zeroes it; svo_import_frame and svo_load_state
+ * leave it as it is (they bring lists and inherited members, not results; hand-over records and state files do not carry it).
+ * The getters imply svo_wait; with the feature off they and the copy return SVO_ERR_STATE with a text in svo_last_error.
+ * svo_copy_pose_covariances_async is the twin of svo_copy_results_async: n_lanes records, device to device, on the context's stream.
+ * svo_pose_cov_size() = sizeof(svo_pose_cov) as this library was compiled (888), for a binding to check its mirror. */
+int svo_set_pose_covariance(svo_ctx* ctx, int enable);
+int svo_get_pose_covariance(svo_ctx* ctx, int lane, svo_pose_cov* cov);
+int svo_get_pose_covariances(svo_ctx* ctx, svo_pose_cov* cov /* n_lanes entries */);
+int svo_copy_pose_covariances_async(svo_ctx* ctx, void* dst_device, size_t bytes);
+size_t svo_pose_cov_size(void);
 
 /* getValues (H:704-724) and friends.  which: 0 = current frame, 1 = previous frame; side: 0 left, 1 right.
  * Each returns the list length (possibly > cap; only min(len,cap) entries are written) or <0. */
@@ -442,7 +464,10 @@ int svo_debug_get_redo_count(svo_ctx* ctx, uint32_t* pairs, int reset);
 int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
 
 /* per-kernel HIP-event timing (svo_config.kernel_times = 1): names[i] points to static storage.
- * total_ms[i] / calls[i] accumulate since the last svo_kernel_times_reset. Returns number of kernels. */
+ * total_ms[i] / calls[i] accumulate since the last svo_kernel_times_reset. Returns number of kernels.
+ * THE NUMBER RETURNED DEPENDS ON THE CONTEXT'S STATE in one respect: the last name, "pose_covariance", is listed only while
+ * svo_set_pose_covariance is on, so a context that has it off returns the list (and the count) it always did.  Size arrays by the
+ * value of the same call, or for the largest list (cap 64 always suffices). */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

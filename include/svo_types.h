@@ -129,6 +129,32 @@ enum {
     SVO_TS_TRACKED = 7       /* also pass the left/right consistency check (S4:282): tracked_pairs */
 };
 
+/* The covariance of a lane's pose increment (svo_set_pose_covariance in svo_hip.h; no reference counterpart).  All matrices 6 x 6, row-major.
+ *   theta* = svo_result.delta of the same call (w1 w2 w3 t1 t2 t3); M = the tracked pairs still in stage 5's mask when it ended (the mask
+ *   itself, not the `outliers` list: with initial_max_iters = 0 that list is empty while the mask is the NMS survivors).
+ *   ONE MORE EVALUATION at theta*, written as m_evalRGN writes one (S5:275-390) over the landmarks as last triangulated: predicted
+ *   pixels cast to float, residuals r_i in R^4 float minus float, s_i = |r_i|^2, Jacobian J_i (4 x 6); a point whose J_i is not finite is
+ *   dropped (S5:322).  U = the n_used points that remain.  w_i = 1 / sqrt(1 + s_i / kernel_param^2) under use_robust_kernel, else 1.
+ *   info      = A = sum_U w_i J_i^T J_i: the information for unit pixel variance.  WEIGHTED, unlike the Hessian the iteration solves with
+ *               (S5:364-369 weights the gradient only)
+ *   sigma2    = sum_U w_i s_i / dof, dof = 4 n_used - 6: the a-posteriori variance factor, px^2
+ *   cov_delta = sigma2 * A^-1, in the order of delta
+ *   cov_pose  = G cov_delta G^T, G = d outPose / d delta (x y z yaw pitch roll of the inverse transform, S5:717-718), analytic
+ * state:
+ *   SVO_COV_NONE            the feature is off, or this call's stage 5 did not end with valid = 1 (first frame, bad tracking, every early
+ *                           return of stage 5, a cost abort): everything zero
+ *   SVO_COV_NO_DOF          dof <= 0: info, n_used, dof set, the rest zero
+ *   SVO_COV_RANK_DEFICIENT  A fails the positive-definiteness test of stage 5's own Cholesky solve (k_gn.hip, chol6): info, sigma2,
+ *                           n_used, dof set, both covariances zero
+ *   SVO_COV_DELTA_ONLY      cos^2(pitch) < 1e-12, where G is singular: cov_pose zero, the rest as for SVO_COV_OK
+ *   SVO_COV_OK              every field */
+enum { SVO_COV_NONE = 0, SVO_COV_OK = 1, SVO_COV_RANK_DEFICIENT = 2, SVO_COV_NO_DOF = 3, SVO_COV_DELTA_ONLY = 4 };
+typedef struct svo_pose_cov {
+    double info[36], cov_delta[36], cov_pose[36];
+    double sigma2;
+    int32_t n_used, dof, state, reserved;
+} svo_pose_cov;
+
 #define SVO_MAX_OCTAVES 4
 #define SVO_DESC_BYTES 32
 

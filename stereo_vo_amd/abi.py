@@ -65,6 +65,21 @@ class Result(C.Structure):
         ("track_stats", C.c_int32 * 8),
     ]
 
+COV_NONE, COV_OK, COV_RANK_DEFICIENT, COV_NO_DOF, COV_DELTA_ONLY = range(5)
+
+
+class PoseCov(C.Structure):
+    """svo_pose_cov (include/svo_types.h): the covariance of a lane's pose increment; matrices 6 x 6 row-major"""
+    _fields_ = [("info", C.c_double * 36), ("cov_delta", C.c_double * 36), ("cov_pose", C.c_double * 36),
+                ("sigma2", C.c_double), ("n_used", C.c_int32), ("dof", C.c_int32), ("state", C.c_int32), ("reserved", C.c_int32)]
+
+    def matrix(self, name):
+        """numpy 6 x 6 view of info / cov_delta / cov_pose (shares the record's memory)"""
+        return np.ctypeslib.as_array(getattr(self, name)).reshape(6, 6)
+
+
+assert C.sizeof(PoseCov) == 888
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

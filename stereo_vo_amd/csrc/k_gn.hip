@@ -226,6 +226,7 @@ __device__ void delta_to_pose(const double* dp, double* pose)
 // therefore depends on what a frame of the workload tracks (a few hundred pairs), not on the capacity of the context's lists:
 // 33 KB instead of 123 KB at max_kps 4096, so that a lane's block finds room on a CU beside the detector's tiles (round 5).
 #define GN_LCAP 1024
+#define GN_MASK_HEAD 16       // bytes in front of a lane's mask in the mask-out array: int ended_valid, int T (gn_mask_bytes_per_lane)
 struct GnShared {
     double part[GN_NT_MAX / 64][GN_NSUM];      // the 28 sums of every wave (reduced inside the wave on the DPP / permlane network)
     double tot[GN_NSUM];
@@ -297,9 +298,10 @@ __device__ __forceinline__ void gn_wave_sums(const double* acc, double* out)
 // passed the first test: the step then had a component of ~2000 times its norm along the direction the pseudo-inverse cuts
 // (tests/test_gpu_stage5.py, collinear-eps0).  So a pivot must also exceed 4 * DBL_EPSILON * H_jj * prod_{k<j} H_kk / d_k, the noise
 // the columns before it can have put into it; the product is 1 ... 1e4 on ordinary frames.
-__device__ __forceinline__ bool chol6(const double* H, const double* g, double dmax, double* x)
+// (Split in two so that k_pose_covariance can factor once and solve six times; chol6 below is the pair, as the iteration uses it.)
+__device__ __forceinline__ bool chol6_factor(const double* H, double dmax, double (&L)[6][6], double (&inv)[6])
 {
-    double L[6][6], d[6], inv[6];
+    double d[6];
     bool ok = true;
     double amp = 4.0 * DBL_EPSILON;
 #pragma unroll
@@ -320,6 +322,10 @@ __device__ __forceinline__ bool chol6(const double* H, const double* g, double d
             L[i][j] = t * inv[j];
         }
     }
+    return ok;
+}
+__device__ __forceinline__ void chol6_solve(const double (&L)[6][6], const double (&inv)[6], const double* g, double* x)
+{
     double y[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) { double t = g[i];
@@ -331,7 +337,75 @@ __device__ __forceinline__ bool chol6(const double* H, const double* g, double d
 #pragma unroll
         for (int k = i + 1; k < 6; k++) t = __builtin_fma(-L[k][i], x[k], t);
         x[i] = t; }
+}
+__device__ __forceinline__ bool chol6(const double* H, const double* g, double dmax, double* x)
+{
+    double L[6][6], inv[6];
+    const bool ok = chol6_factor(H, dmax, L, inv);
+    chol6_solve(L, inv, g, x);
     return ok;
+}
+
+// One landmark of m_evalRGN: the projection through R, t (S5:180-195), its 4 x 6 Jacobian (S5:197-257) and, when that is finite
+// (S5:322), the four float-minus-float residuals (S5:335-338).  Shared by eval_rgn and k_pose_covariance: one copy of the formulas.
+__device__ __forceinline__ bool gn_point(const svo_stereo_camera& cam, const Rot& R, bool small_angle, double t1, double t2, double t3,
+                                         const double* lmk, const float* obs, int m, double (&J)[4][6], double (&ri)[4])
+{
+#pragma clang fp contract(fast)
+    const double X1p = lmk[3 * m], Y1p = lmk[3 * m + 1], Z1p = lmk[3 * m + 2];
+    const double* r = R.r;
+    const double X1c = r[0] * X1p + r[1] * Y1p + r[2] * Z1p + t1;
+    const double Y1c = r[3] * X1p + r[4] * Y1p + r[5] * Z1p + t2;
+    const double Z1c = r[6] * X1p + r[7] * Y1p + r[8] * Z1p + t3;
+    const double X2c = X1c - cam.baseline;
+    // S5:189-193 and 251-254 with the 28 divisions by Z1c / Z1c^2 folded into two reciprocals
+    const double iz = gn_rcp(Z1c), iz2 = iz * iz;
+    const float pl_x = (float)(cam.l_fx * X1c * iz + cam.l_cx), pl_y = (float)(cam.l_fy * Y1c * iz + cam.l_cy);
+    const float pr_x = (float)(cam.r_fx * X2c * iz + cam.r_cx), pr_y = (float)(cam.r_fy * Y1c * iz + cam.r_cy);
+    bool good = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double X1cd, Y1cd, Z1cd;
+        if (j < 3) {
+            if (small_angle) {
+                if (j == 0) { X1cd = 0; Y1cd = -Z1p; Z1cd = Y1p; }
+                else if (j == 1) { X1cd = Z1p; Y1cd = 0; Z1cd = -X1p; }
+                else { X1cd = -Y1p; Y1cd = X1p; Z1cd = 0; }
+            } else {
+                const double* d = R.dr[j];
+                X1cd = d[0] * X1p + d[1] * Y1p + d[2] * Z1p;
+                Y1cd = d[3] * X1p + d[4] * Y1p + d[5] * Z1p;
+                Z1cd = d[6] * X1p + d[7] * Y1p + d[8] * Z1p;
+            }
+        } else { X1cd = j == 3; Y1cd = j == 4; Z1cd = j == 5; }
+        const double ju = (X1cd * Z1c - X1c * Z1cd) * iz2, jv = (Y1cd * Z1c - Y1c * Z1cd) * iz2, jur = (X1cd * Z1c - X2c * Z1cd) * iz2;
+        J[0][j] = cam.l_fx * ju; J[1][j] = cam.l_fy * jv; J[2][j] = cam.r_fx * jur; J[3][j] = cam.r_fy * jv;
+        if (isnan(ju) || isinf(ju) || isnan(jv) || isinf(jv) || isnan(jur) || isinf(jur)) good = false;
+    }
+    if (!good) return false;                                               // S5:322
+    const float* o = obs + 8 * (long long)m;
+    ri[0] = (double)(o[4] - pl_x); ri[1] = (double)(o[5] - pl_y); ri[2] = (double)(o[6] - pr_x); ri[3] = (double)(o[7] - pr_y);   // float subtraction, S5:335-338
+    return true;
+}
+
+// Block reduction of the 28 sums: inside every wave on the permlane / DPP network (no LDS), then GN_NT / 64 x 28 doubles through
+// LDS (1.3 KB; rounds 1-4 staged all 28 x GN_NT values there: 86 KB, and one more barrier).  Wave 0 adds the wave sums into tot; its
+// first thread may go on to read them: LDS operations of one wave are ordered, so no block barrier in between.
+template <int GN_NT>
+__device__ __forceinline__ void gn_block_sums(const double* acc, double (*part)[GN_NSUM], double* tot)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    gn_wave_sums(acc, part[wid]);
+    __syncthreads();
+    if (wid == 0) {
+        if (lane < GN_NSUM) {
+            double sum = part[0][lane];
+#pragma unroll
+            for (int w = 1; w < GN_NT / 64; w++) sum += part[w][lane];
+            tot[lane] = sum;
+        }
+        wave_lds_sync();
+    }
 }
 
 // one m_evalRGN (S5:275-390) with the rotation taken from sh.R / sh.delta (prepared by thread 0).  On return every
@@ -344,7 +418,7 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
     // bit): stage 5 is held to the oracle by a tolerance, and a lone wave pays ~5 cycles per instruction whatever it is, so
     // a * b + c as one v_fma_f64 instead of two instructions is a third of this function's arithmetic.
 #pragma clang fp contract(fast)
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const double b2 = P.use_robust_kernel ? P.kernel_param * P.kernel_param : 0;
     const double b2_1 = P.use_robust_kernel ? 1. / b2 : 0;
     const double t1 = sh.delta[3], t2 = sh.delta[4], t3 = sh.delta[5];
@@ -354,40 +428,8 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
     for (int i = 0; i < GN_NSUM; i++) acc[i] = 0;
     for (int m = tid; m < T; m += blockDim.x) {
         if (!mask[m] || dbg == 60) continue;
-        const double X1p = lmk[3 * m], Y1p = lmk[3 * m + 1], Z1p = lmk[3 * m + 2];
-        const double* r = sh.R.r;
-        const double X1c = r[0] * X1p + r[1] * Y1p + r[2] * Z1p + t1;
-        const double Y1c = r[3] * X1p + r[4] * Y1p + r[5] * Z1p + t2;
-        const double Z1c = r[6] * X1p + r[7] * Y1p + r[8] * Z1p + t3;
-        const double X2c = X1c - cam.baseline;
-        // S5:189-193 and 251-254 with the 28 divisions by Z1c / Z1c^2 folded into two reciprocals
-        const double iz = gn_rcp(Z1c), iz2 = iz * iz;
-        const float pl_x = (float)(cam.l_fx * X1c * iz + cam.l_cx), pl_y = (float)(cam.l_fy * Y1c * iz + cam.l_cy);
-        const float pr_x = (float)(cam.r_fx * X2c * iz + cam.r_cx), pr_y = (float)(cam.r_fy * Y1c * iz + cam.r_cy);
-        double J[4][6];
-        bool good = true;
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            double X1cd, Y1cd, Z1cd;
-            if (j < 3) {
-                if (small_angle) {
-                    if (j == 0) { X1cd = 0; Y1cd = -Z1p; Z1cd = Y1p; }
-                    else if (j == 1) { X1cd = Z1p; Y1cd = 0; Z1cd = -X1p; }
-                    else { X1cd = -Y1p; Y1cd = X1p; Z1cd = 0; }
-                } else {
-                    const double* d = sh.R.dr[j];
-                    X1cd = d[0] * X1p + d[1] * Y1p + d[2] * Z1p;
-                    Y1cd = d[3] * X1p + d[4] * Y1p + d[5] * Z1p;
-                    Z1cd = d[6] * X1p + d[7] * Y1p + d[8] * Z1p;
-                }
-            } else { X1cd = j == 3; Y1cd = j == 4; Z1cd = j == 5; }
-            const double ju = (X1cd * Z1c - X1c * Z1cd) * iz2, jv = (Y1cd * Z1c - Y1c * Z1cd) * iz2, jur = (X1cd * Z1c - X2c * Z1cd) * iz2;
-            J[0][j] = cam.l_fx * ju; J[1][j] = cam.l_fy * jv; J[2][j] = cam.r_fx * jur; J[3][j] = cam.r_fy * jv;
-            if (isnan(ju) || isinf(ju) || isnan(jv) || isinf(jv) || isnan(jur) || isinf(jur)) good = false;
-        }
-        if (!good) continue;                                                   // S5:322
-        const float* o = obs + 8 * (long long)m;
-        const double ri[4] = { (double)(o[4] - pl_x), (double)(o[5] - pl_y), (double)(o[6] - pr_x), (double)(o[7] - pr_y) };   // float subtraction, S5:335-338
+        double J[4][6], ri[4];
+        if (!gn_point(cam, sh.R, small_angle, t1, t2, t3, lmk, obs, m, J, ri)) continue;          // S5:322
         const double s = ri[0] * ri[0] + ri[1] * ri[1] + ri[2] * ri[2] + ri[3] * ri[3];
         residual[m] = s;                                                        // S5:345
         double rho_p = 1, fi;
@@ -403,20 +445,7 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
             for (int b = a; b < 6; b++) { acc[h] += J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b] + J[3][a] * J[3][b]; h++; }   // ... Hessian NOT (S5:364-369)
         }
     }
-    // block reduction of the 28 sums: inside every wave on the permlane / DPP network (no LDS), then GN_NT / 64 x 28 doubles through
-    // LDS (1.3 KB; rounds 1-4 staged all 28 x GN_NT values there: 86 KB, and one more barrier).  Wave 0 adds the wave sums and its
-    // first thread goes on to the solve: LDS operations of one wave are ordered, so no block barrier in between.
-    gn_wave_sums(acc, sh.part[wid]);
-    __syncthreads();
-    if (wid == 0) {
-        if (lane < GN_NSUM) {
-            double sum = sh.part[0][lane];
-#pragma unroll
-            for (int w = 1; w < GN_NT / 64; w++) sum += sh.part[w][lane];
-            sh.tot[lane] = sum;
-        }
-        wave_lds_sync();
-    }
+    gn_block_sums<GN_NT>(acc, sh.part, sh.tot);
     if (tid == 0) {
         double H[36], g[6], x[6] = { 0, 0, 0, 0, 0, 0 };
         {
@@ -652,6 +681,12 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         res.n_residual = n_res > T ? n_res : T; res.n_outliers = n_out;
         res.valid = !abort_;                                                                                         // S5:727
     }
+    // svo_set_pose_covariance: the final mask, T and whether this run ended valid, for k_pose_covariance (layout at gn_mask_bytes_per_lane)
+    if (P.mask_out) {
+        uint8_t* mo = P.mask_out + (size_t)lane_id * ((size_t)PM + GN_MASK_HEAD);
+        for (int m = tid; m < T; m += blockDim.x) mo[GN_MASK_HEAD + m] = mask[m];
+        if (tid == 0) { ((int*)mo)[0] = !abort_; ((int*)mo)[1] = T; }
+    }
 }
 
 static size_t gn_smem(int pmax)
@@ -687,15 +722,198 @@ hipError_t configure_gauss_newton(int pmax)
     return hipSuccess;
 }
 
-void launch_gauss_newton(const DevCtx& c, const GNParams& P, hipStream_t st)
+// threads per lane: one pass of the per-track loop covers that many tracks per iteration (config 2 tracks ~290: 256 threads walk
+// the loop twice); SVO_GN_NT = 256 / 384 / 512 overrides the default for an A/B
+static int gn_threads()
 {
-    // threads per lane: one pass of the per-track loop covers that many tracks per iteration (config 2 tracks ~290: 256 threads walk
-    // the loop twice); SVO_GN_NT = 256 / 384 / 512 overrides the default for an A/B
     static int nt = 0;
     if (!nt) { const char* e = getenv("SVO_GN_NT"); const int v = e ? atoi(e) : 0; nt = (v == 256 || v == 384 || v == 512) ? v : 384; }
+    return nt;
+}
+
+void launch_gauss_newton(const DevCtx& c, const GNParams& P, hipStream_t st)
+{
+    const int nt = gn_threads();
     if (nt == 512) hipLaunchKernelGGL(k_gauss_newton<512>, dim3(c.n_lanes), dim3(512), gn_smem(P.pmax), st, c, P, c.gn_scratch);
     else if (nt == 384) hipLaunchKernelGGL(k_gauss_newton<384>, dim3(c.n_lanes), dim3(384), gn_smem(P.pmax), st, c, P, c.gn_scratch);
     else hipLaunchKernelGGL(k_gauss_newton<256>, dim3(c.n_lanes), dim3(256), gn_smem(P.pmax), st, c, P, c.gn_scratch);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The covariance of the pose increment (svo_set_pose_covariance, contract at svo_pose_cov in svo_types.h): no reference
+// counterpart.  One more evaluation at the delta stage 5 returned, over the mask k_gauss_newton ended with (its mask-out array:
+// per lane GN_MASK_HEAD bytes {int ended_valid, int T}, then pmax mask bytes) and the landmarks as it last triangulated them.
+// A kernel of its own and not a tail of k_gauss_newton: the tail would add its 6 x 6 algebra to a kernel whose iteration body is
+// sized to the instruction cache (see there), and to every context that never asks for a covariance.
+// ------------------------------------------------------------------------------------------------------------
+size_t gn_mask_bytes_per_lane(int pmax) { return (size_t)pmax + GN_MASK_HEAD; }
+
+struct CovShared {
+    double part[GN_NT_MAX / 64][GN_NSUM];
+    double tot[GN_NSUM];          // 0..20 the upper triangle of A, 21 the weighted sum of squares, 22 the number of points
+    double delta[6];
+    Rot R;
+    double A[36], C[36], G[36], M[36];
+    double Rm[9], dR[27];         // the exact Rodrigues rotation of delta and its derivatives, for G
+    int ended_valid, T;
+};
+
+// R = I + a K + b K^2 of the rotation vector w (delta_to_pose's matrix) and dR/dw_k, k = 0..2, for G.  Not Rot::dr: that holds the
+// reference's S5:162 entry and is empty below 1e-5 rad, where m_evalRGN switches to the generators -- right for the Jacobian the
+// iteration uses, wrong by 1e-5 for a derivative of outPose.  a = sin t / t, b = (1 - cos t) / t^2 and the factors of their
+// derivatives, alpha = (cos t - a) / t^2 and beta = (a - 2 b) / t^2, by their series below 0.5 rad (the closed forms cancel).
+__device__ void cov_rotation_derivs(const double* w, double* Rm, double* dR)
+{
+    const double z = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double a, b, al, be;
+    if (z < 0.25) {
+        double t = 1.0, p = 1.0 / 6.0;             // t_n = (-z)^n / (2n+1)!,  p_n = (-z)^n / (2n+3)!
+        a = 0; b = 0; al = 0; be = 0;
+        for (int n = 0; n < 12; n++) {
+            a += t; b += t / (double)(2 * n + 2);
+            al -= (double)(2 * n + 2) * p; be -= (double)(2 * n + 2) * p / (double)(2 * n + 4);
+            t = -t * z / (double)((2 * n + 2) * (2 * n + 3));
+            p = -p * z / (double)((2 * n + 4) * (2 * n + 5));
+        }
+    } else {
+        const double th = sqrt(z), sn = sin(th), cs = cos(th);
+        a = sn / th; b = (1.0 - cs) / z; al = (cs - a) / z; be = (a - 2.0 * b) / z;
+    }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            // K_ij = sg * w[3 - i - j] off the diagonal, sg = -1 where j follows i cyclically
+            const double sg = i == j ? 0.0 : (((j - i + 3) % 3 == 1) ? -1.0 : 1.0);
+            const int kk = i == j ? 0 : 3 - i - j;
+            const double Kij = sg * w[kk], dij = i == j ? 1.0 : 0.0;
+            Rm[i * 3 + j] = dij * (1.0 - b * z) + a * Kij + b * w[i] * w[j];
+            for (int k = 0; k < 3; k++) {
+                const double gk = (i != j && k == kk) ? sg : 0.0;
+                dR[k * 9 + i * 3 + j] = al * w[k] * Kij + a * gk + be * w[k] * (w[i] * w[j] - z * dij)
+                                        + b * ((i == k ? w[j] : 0.0) + (j == k ? w[i] : 0.0) - 2.0 * w[k] * dij);
+            }
+        }
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, svo_pose_cov* out)
+{
+    SVO_TL_SCOPE(c, TL_GN, 1);
+    SVO_LATENCY_CHAIN(c);
+    __shared__ CovShared sh;
+    const int lane_id = blockIdx.x, tid = threadIdx.x;
+    if (lane_idle(c, lane_id)) return;                                       // an idle lane keeps its record
+    uint8_t* mo = P.mask_out + (size_t)lane_id * ((size_t)P.pmax + GN_MASK_HEAD);
+    svo_pose_cov& o = out[lane_id];
+    if (tid == 0) {
+        sh.ended_valid = ((const int*)mo)[0]; sh.T = ((const int*)mo)[1];
+        ((int*)mo)[0] = 0;                                                   // consumed: a later call whose stage 5 returns early finds no mask
+        double d6[6];
+        for (int k = 0; k < 6; k++) { d6[k] = c.results[lane_id].delta[k]; sh.delta[k] = d6[k]; }
+        rodrigues_with_derivs(d6, sh.R);
+    }
+    {   // SVO_COV_NONE until proven otherwise: all zero
+        double* w = (double*)&o;
+        for (int i = tid; i < (int)(sizeof(svo_pose_cov) / sizeof(double)); i += NT) w[i] = 0.0;
+    }
+    __syncthreads();
+    if (!sh.ended_valid) return;
+    const int T = sh.T < P.pmax ? sh.T : P.pmax;
+    const unsigned char* mask = mo + GN_MASK_HEAD;
+    const svo_stereo_camera cam = c.cams[lane_id];
+    const float* obs = c.gn_obs + (long long)lane_id * c.max_kps * 8;
+    const double* lmk = c.gn_lmk + (long long)lane_id * c.max_kps * 3;
+    double acc[GN_NSUM];
+#pragma unroll
+    for (int i = 0; i < GN_NSUM; i++) acc[i] = 0;
+    {
+#pragma clang fp contract(fast)
+        const double b2_1 = P.use_robust_kernel ? 1. / (P.kernel_param * P.kernel_param) : 0;
+        const double t1 = sh.delta[3], t2 = sh.delta[4], t3 = sh.delta[5];
+        const bool small_angle = sh.R.small_angle != 0;
+        for (int m = tid; m < T; m += NT) {
+            if (!mask[m]) continue;
+            double J[4][6], ri[4];
+            if (!gn_point(cam, sh.R, small_angle, t1, t2, t3, lmk, obs, m, J, ri)) continue;
+            const double s = ri[0] * ri[0] + ri[1] * ri[1] + ri[2] * ri[2] + ri[3] * ri[3];
+            const double wt = P.use_robust_kernel ? gn_rsqrt(1 + (s * b2_1)) : 1.0;
+            acc[21] += wt * s;
+            acc[22] += 1.0;
+            int h = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+#pragma unroll
+                for (int b = a; b < 6; b++) { acc[h] += wt * (J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b] + J[3][a] * J[3][b]); h++; }
+            }
+        }
+    }
+    gn_block_sums<NT>(acc, sh.part, sh.tot);
+    if (tid != 0) return;
+    // ---- one thread: A, sigma2, A^-1, G and the two products.  Every value that has a mirror image is written to both places ----
+    {
+        int h = 0;
+        for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { const double v = sh.tot[h++]; sh.A[a * 6 + b] = v; sh.A[b * 6 + a] = v; }
+    }
+    for (int i = 0; i < 36; i++) o.info[i] = sh.A[i];
+    const int n_used = (int)sh.tot[22], dof = 4 * n_used - 6;
+    o.n_used = n_used; o.dof = dof;
+    if (dof <= 0) { o.state = SVO_COV_NO_DOF; return; }
+    const double sigma2 = sh.tot[21] / (double)dof;
+    o.sigma2 = sigma2;
+    double dmax = 0;
+    for (int a = 0; a < 6; a++) dmax = fmax(dmax, fabs(sh.A[a * 7]));
+    double L[6][6], inv[6];
+    if (!(dmax > 0) || !chol6_factor(sh.A, dmax, L, inv)) { o.state = SVO_COV_RANK_DEFICIENT; return; }    // chol6's own pivot rule (NaN fails it too)
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {                                            // column k of A^-1
+        double g[6], x[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) g[i] = i == k ? 1.0 : 0.0;
+        chol6_solve(L, inv, g, x);
+#pragma unroll
+        for (int i = 0; i < 6; i++) sh.M[i * 6 + k] = x[i];
+    }
+    for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) {
+        const double v = sigma2 * sh.M[a * 6 + b];
+        sh.C[a * 6 + b] = v; sh.C[b * 6 + a] = v; o.cov_delta[a * 6 + b] = v; o.cov_delta[b * 6 + a] = v;
+    }
+    // G = d outPose / d delta (rows x y z yaw pitch roll, columns w1 w2 w3 t1 t2 t3) with M = R^T the pose's rotation:
+    // xyz = -R^T t;  yaw = atan2(M10, M00), pitch = atan2(-M20, hypot(M00, M10)), roll = atan2(M21, M22)  (delta_to_pose)
+    cov_rotation_derivs(sh.delta, sh.Rm, sh.dR);
+    const double m00 = sh.Rm[0], m10 = sh.Rm[1], m20 = sh.Rm[2], m21 = sh.Rm[5], m22 = sh.Rm[8];
+    const double c2 = m00 * m00 + m10 * m10;                                 // cos^2(pitch)
+    if (c2 < 1e-12) { o.state = SVO_COV_DELTA_ONLY; return; }                // yaw and roll are not separable there: G is singular
+    const double hy = sqrt(c2), r2 = m21 * m21 + m22 * m22, n2 = m20 * m20 + c2;
+    for (int i = 0; i < 36; i++) sh.G[i] = 0;
+    for (int k = 0; k < 3; k++) {
+        const double* d = sh.dR + 9 * k;
+        for (int i = 0; i < 3; i++) {
+            sh.G[i * 6 + k] = -(d[0 * 3 + i] * sh.delta[3] + d[1 * 3 + i] * sh.delta[4] + d[2 * 3 + i] * sh.delta[5]);
+            sh.G[i * 6 + 3 + k] = -sh.Rm[k * 3 + i];
+        }
+        const double d00 = d[0], d10 = d[1], d20 = d[2], d21 = d[5], d22 = d[8];
+        sh.G[3 * 6 + k] = (m00 * d10 - m10 * d00) / c2;
+        sh.G[4 * 6 + k] = (-hy * d20 + m20 * (m00 * d00 + m10 * d10) / hy) / n2;
+        sh.G[5 * 6 + k] = (m22 * d21 - m21 * d22) / r2;
+    }
+    for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) {
+        double v = 0;
+        for (int k = 0; k < 6; k++) v += sh.G[a * 6 + k] * sh.C[k * 6 + b];
+        sh.M[a * 6 + b] = v;                                                 // G C
+    }
+    for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) {
+        double v = 0;
+        for (int k = 0; k < 6; k++) v += sh.M[a * 6 + k] * sh.G[b * 6 + k];
+        o.cov_pose[a * 6 + b] = v; o.cov_pose[b * 6 + a] = v;
+    }
+    o.state = SVO_COV_OK;
+}
+
+void launch_pose_covariance(const DevCtx& c, const GNParams& P, svo_pose_cov* out, hipStream_t st)
+{
+    const int nt = gn_threads();
+    if (nt == 512) hipLaunchKernelGGL(k_pose_covariance<512>, dim3(c.n_lanes), dim3(512), 0, st, c, P, out);
+    else if (nt == 384) hipLaunchKernelGGL(k_pose_covariance<384>, dim3(c.n_lanes), dim3(384), 0, st, c, P, out);
+    else hipLaunchKernelGGL(k_pose_covariance<256>, dim3(c.n_lanes), dim3(256), 0, st, c, P, out);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -124,6 +124,21 @@ public:
         applyParams();                                                                   // resetFASTThreshold / resetORBThreshold, H:662-663
     }
     void setVerbosityLevel(int level) { m_verbose_level = level; }                       // H:527
+    /** The covariance of the pose increment (no reference counterpart; svo_pose_cov in svo_types.h).  enablePoseCovariance() before the
+      * frames; getPoseCovariance() after processNewImagePair / getChangeInPose fills a plain struct: 6 x 6 row-major matrices in the order
+      * of the increment (cov_delta: w1 w2 w3 t1 t2 t3) and of outPose (cov_pose: x y z yaw pitch roll).  Returns false unless state is ok. */
+    struct TPoseCovariance {
+        double info[36], cov_delta[36], cov_pose[36], sigma2;
+        int n_used, dof, state;                   // state: SVO_COV_*
+        TPoseCovariance() : info(), cov_delta(), cov_pose(), sigma2(0), n_used(0), dof(0), state(SVO_COV_NONE) {}
+    };
+    void enablePoseCovariance(bool enable = true) { check(svo_set_pose_covariance(m_ctx, enable ? 1 : 0), "svo_set_pose_covariance"); }
+    bool getPoseCovariance(TPoseCovariance& out) {
+        svo_pose_cov r; check(svo_get_pose_covariance(m_ctx, 0, &r), "svo_get_pose_covariance");
+        for (int i = 0; i < 36; i++) { out.info[i] = r.info[i]; out.cov_delta[i] = r.cov_delta[i]; out.cov_pose[i] = r.cov_pose[i]; }
+        out.sigma2 = r.sigma2; out.n_used = r.n_used; out.dof = r.dof; out.state = r.state;
+        return r.state == SVO_COV_OK;
+    }
     int getFASTThreshold() { return svo_get_fast_threshold(m_ctx); }                     // H:530
     void setFASTThreshold(int v) { check(svo_set_fast_threshold(m_ctx, v), "svo_set_fast_threshold"); }   // H:531
     void resetFASTThreshold() { setFASTThreshold(params.initial_FAST_threshold); }       // H:532

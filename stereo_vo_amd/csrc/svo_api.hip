@@ -29,13 +29,16 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // dmFASTER (only a context that selects it counts a call here)
        KT_FASTER, KT_FASTER_NMS,
        // svo_gather_windows: the slot-selecting window gather (only a caller of that entry point counts a call here)
-       KT_GATHER_WIN, KT_COUNT };
+       KT_GATHER_WIN,
+       // svo_set_pose_covariance (only a context that enables it counts a call here)
+       KT_POSE_COV,      // keep it last: svo_kernel_times lists it only while the feature is on
+       KT_COUNT };
 static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
     "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
-    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows" };
+    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -107,6 +110,8 @@ struct svo_ctx {
     // svo_get_values: device packing buffer and its page-locked host mirror
     uint8_t* d_vals; uint8_t* h_vals; size_t vals_bytes;
     uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
+    // svo_set_pose_covariance: one record per lane and the array k_gauss_newton leaves its final mask in; nullptr until first enabled
+    bool pose_cov; svo_pose_cov* d_cov; uint8_t* d_cov_mask;
     unsigned long long* d_cand64;                      // dmFASTER's 64-bit candidate keys (n_img x cand_total), allocated by the first svo_process made while it is selected
     // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
     // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
@@ -372,7 +377,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
-    memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr;
+    memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
     ctx->sad_cur.assign((size_t)cfg->n_lanes, 1); ctx->sad_prev.assign((size_t)cfg->n_lanes, 1); ctx->sad_drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
@@ -585,6 +590,63 @@ extern "C" int svo_set_klt_win(svo_ctx* ctx, int v)
 }
 extern "C" int svo_get_klt_win(const svo_ctx* ctx) { return ctx ? ctx->klt_win : SVO_ERR_ARG; }
 
+// The covariance of every pose increment (svo_types.h, svo_pose_cov).  Off: nothing is allocated, nothing launched.  The buffers are made
+// here and not at the first frame: hipMalloc / hipMemset are refused on a capturing thread (as d_anms).  The launch sequence of a
+// frame changes with the value, so the captured graphs go.
+extern "C" int svo_set_pose_covariance(svo_ctx* ctx, int enable)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    const bool on = enable != 0;
+    if (on == ctx->pose_cov) return SVO_OK;
+    drop_graphs(ctx);
+    HIPCHECK(sync_all(ctx));
+    if (on) {
+        const size_t L = (size_t)ctx->cfg.n_lanes, mb = gn_mask_bytes_per_lane(ctx->dc.max_kps) * L;
+        if (!ctx->d_cov) HIPCHECK(dev_alloc(ctx, &ctx->d_cov, L));
+        if (!ctx->d_cov_mask) HIPCHECK(dev_alloc(ctx, &ctx->d_cov_mask, mb));      // (each on its own: a failed second allocation is made again by the next call)
+        HIPCHECK(hipMemset(ctx->d_cov, 0, sizeof(svo_pose_cov) * L));          // SVO_COV_NONE until a stage 5 has run
+        HIPCHECK(hipMemset(ctx->d_cov_mask, 0, mb));
+    }
+    ctx->pose_cov = on;
+    return SVO_OK;
+}
+static int pose_cov_ready(svo_ctx* ctx)
+{
+    if (ctx->pose_cov) return SVO_OK;
+    ctx->last_error = "the pose covariance is off: svo_set_pose_covariance(ctx, 1) before the frame";
+    return SVO_ERR_STATE;
+}
+extern "C" size_t svo_pose_cov_size(void) { return sizeof(svo_pose_cov); }
+extern "C" int svo_get_pose_covariances(svo_ctx* ctx, svo_pose_cov* cov)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !cov) return SVO_ERR_ARG;
+    int rc = pose_cov_ready(ctx); if (rc) return rc;
+    rc = svo_wait(ctx); if (rc) return rc;
+    HIPCHECK(hipMemcpy(cov, ctx->d_cov, sizeof(svo_pose_cov) * ctx->cfg.n_lanes, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+extern "C" int svo_get_pose_covariance(svo_ctx* ctx, int lane, svo_pose_cov* cov)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !cov || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    int rc = pose_cov_ready(ctx); if (rc) return rc;
+    rc = svo_wait(ctx); if (rc) return rc;
+    HIPCHECK(hipMemcpy(cov, ctx->d_cov + lane, sizeof(svo_pose_cov), hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+extern "C" int svo_copy_pose_covariances_async(svo_ctx* ctx, void* dst, size_t bytes)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !dst || bytes < sizeof(svo_pose_cov) * (size_t)ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    { const int rc = pose_cov_ready(ctx); if (rc) return rc; }
+    note_stream(ctx);
+    HIPCHECK(hipMemcpyAsync(dst, ctx->d_cov, sizeof(svo_pose_cov) * ctx->cfg.n_lanes, hipMemcpyDeviceToDevice, ctx->stream));
+    mark_stream(ctx);
+    return SVO_OK;
+}
+
 extern "C" int svo_set_stream(svo_ctx* ctx, void* stream)
 {
     if (ctx) use_device(ctx);
@@ -665,6 +727,7 @@ extern "C" int svo_reset(svo_ctx* ctx, int lane)
             HIPCHECK(hipMemset(ctx->dc.n_tracked + (size_t)l * OC, 0, (size_t)OC * sizeof(int)));
             HIPCHECK(hipMemset(ctx->dc.n_ids + (size_t)l * OC * 2, 0, (size_t)OC * 2 * sizeof(int)));
             HIPCHECK(hipMemset(ctx->dc.results + l, 0, sizeof(svo_result)));
+            if (ctx->pose_cov) HIPCHECK(hipMemset(ctx->d_cov + l, 0, sizeof(svo_pose_cov)));
             HIPCHECK(hipMemset(ctx->dc.fast_th_dyn + (size_t)2 * l * SVO_MAX_LEVELS, 0, (size_t)2 * SVO_MAX_LEVELS * sizeof(uint32_t)));   // a fresh estimator speculates nothing
             ctx->sad_cur[l] = ctx->sad_prev[l] = 1; ctx->sad_drop[l] = 0;                       // no frames: nothing a SAD stage could miss
         }
@@ -843,8 +906,10 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    for (int i = 0; i < KT_COUNT && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
-    return KT_COUNT;
+    // "pose_covariance" (the last name) is listed while svo_set_pose_covariance is on: a context that has it off reports the list it always did
+    const int n = ctx->pose_cov ? KT_COUNT : KT_POSE_COV;
+    for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
+    return n;
 }
 extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
 {
@@ -1338,7 +1403,9 @@ static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, 
         g.min_distance = p.min_distance; g.img_w = d.W; g.img_h = d.H; g.pmax = d.max_kps; g.standalone = 0;
         g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
         if (p.use_custom_initial_pose) g.use_custom_initial_pose = 1;        // deltaPose = initial_estimation = zeros (S5:504-505, default argument H:1045)
+        if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
         { Span s(ctx, KT_GN); launch_gauss_newton(d, g, st); }
+        if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, g, ctx->d_cov, st); }
     }
     if (capturing) {
         hipGraph_t graph = nullptr;
@@ -2095,7 +2162,10 @@ extern "C" int svo_change_in_pose(svo_ctx* ctx, const svo_index_pair* tracked, i
     g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
     for (int k = 0; k < 6; k++) g.init[k] = init6 ? init6[k] : 0.0;
     note_stream(ctx);
+    // (the scratch lane's record of the covariance is lane 0's, and its mask goes through lane 0's part of the mask array: svo_wait above)
+    if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
     { Span sp(ctx, KT_GN); launch_gauss_newton(s, g, ctx->stream); }
+    if (ctx->pose_cov) { Span sp(ctx, KT_POSE_COV); launch_pose_covariance(s, g, ctx->d_cov, ctx->stream); }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(res, s.results, sizeof(*res), hipMemcpyDeviceToHost));

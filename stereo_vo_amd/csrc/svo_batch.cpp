@@ -164,6 +164,14 @@ extern "C" int svo_batch_set_klt_win(svo_batch* b, int klt_win)
     return SVO_OK;
 }
 
+extern "C" int svo_batch_set_pose_covariance(svo_batch* b, int enable)
+{
+    if (!b) return SVO_ERR_ARG;
+    int rc = svo_batch_synchronize(b); if (rc) return rc;
+    for (svo_ctx* c : b->ctx) BSVO(b, c, svo_set_pose_covariance(c, enable));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam)
 {
     if (!b || !cam || lane < -1 || lane >= b->B) return SVO_ERR_ARG;
@@ -316,6 +324,14 @@ extern "C" int svo_batch_results(svo_batch* b, svo_result* res)
     return SVO_OK;
 }
 
+extern "C" int svo_batch_pose_covariances(svo_batch* b, svo_pose_cov* cov)
+{
+    if (!b || !cov) return SVO_ERR_ARG;
+    int rc = svo_batch_synchronize(b); if (rc) return rc;
+    for (int k = 0; k < b->NC; k++) BSVO(b, b->ctx[(size_t)k], svo_get_pose_covariances(b->ctx[(size_t)k], cov + (size_t)k * b->Bc));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_reset(svo_batch* b)
 {
     if (!b) return SVO_ERR_ARG;
@@ -408,6 +424,13 @@ extern "C" int svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win)
 {
     if (!f) return SVO_ERR_ARG;
     for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_klt_win(c, klt_win));
+    return SVO_OK;
+}
+
+extern "C" int svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable)
+{
+    if (!f) return SVO_ERR_ARG;
+    for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_pose_covariance(c, enable));
     return SVO_OK;
 }
 

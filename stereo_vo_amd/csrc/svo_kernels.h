@@ -11,6 +11,7 @@ struct GNParams {
     int pad;
     double kernel_param, min_mod_out_vector, residual_threshold;
     double init[6];
+    uint8_t* mask_out;                   // nullptr, or the array k_gauss_newton leaves its final mask in for k_pose_covariance (gn_mask_bytes_per_lane each)
 };
 
 // Which kernel forms are the PRODUCT and which are kept as A/B anchors only.  Every form below is compiled and run
@@ -80,3 +81,6 @@ size_t gn_scratch_bytes_per_lane(int pmax);
 hipError_t configure_match(int max_kps);
 void launch_project_points(const float* uvu, int n, const svo_stereo_camera& cam, const double* delta6, float* pix, hipStream_t st);
 void launch_gauss_newton(const DevCtx& c, const GNParams& P, hipStream_t st);
+// svo_set_pose_covariance: P as handed to launch_gauss_newton just before (mask_out set), out = one record per lane
+size_t gn_mask_bytes_per_lane(int pmax);
+void launch_pose_covariance(const DevCtx& c, const GNParams& P, svo_pose_cov* out, hipStream_t st);

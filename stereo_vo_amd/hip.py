@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import Params, Result, StereoCamera, keypoint_dtype, dmatch_dtype, index_pair_dtype
+from .abi import Params, PoseCov, Result, StereoCamera, keypoint_dtype, dmatch_dtype, index_pair_dtype
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -22,6 +22,7 @@ EXPORTS = [
     "svo_config_defaults", "svo_params_defaults", "svo_create", "svo_destroy", "svo_strerror", "svo_last_error",
     "svo_set_params", "svo_get_params", "svo_params_load_ini", "svo_set_fast_threshold", "svo_set_orb_threshold", "svo_get_fast_threshold",
     "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
+    "svo_set_pose_covariance", "svo_get_pose_covariance", "svo_get_pose_covariances", "svo_copy_pose_covariances_async", "svo_pose_cov_size",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
@@ -37,6 +38,7 @@ BATCH_EXPORTS = [
     "svo_batch_abi_sizes", "svo_batch_config_defaults", "svo_batch_create", "svo_batch_create_sized", "svo_batch_destroy", "svo_batch_last_error", "svo_batch_lanes", "svo_batch_contexts",
     "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_klt_win", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step", "svo_batch_step_lanes",
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
+    "svo_batch_set_pose_covariance", "svo_batch_pose_covariances", "svo_fpstream_set_pose_covariance",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
     "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
 ]
@@ -93,6 +95,9 @@ def lib():
             getattr(L, n).restype = None
         L.svo_batch_destroy.argtypes = [C.c_void_p]; L.svo_fpstream_destroy.argtypes = [C.c_void_p]
         L.svo_batch_create_sized.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(L, "svo_pose_cov_size"):          # (absent from a library of an earlier commit loaded through SVO_HIP_LIB for an A/B)
+            L.svo_pose_cov_size.restype = C.c_size_t; L.svo_pose_cov_size.argtypes = []
+            L.svo_copy_pose_covariances_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -431,6 +436,24 @@ class Context:
         arr = (Result * self.n_lanes)()
         self._ck(self.L.svo_get_results(self.h, arr), "svo_get_results")
         return list(arr)
+
+    def set_pose_covariance(self, enable=True):
+        """svo_set_pose_covariance: from now on every stage 5 leaves a PoseCov record per active lane"""
+        self._ck(self.L.svo_set_pose_covariance(self.h, 1 if enable else 0), "svo_set_pose_covariance")
+
+    def pose_covariance(self, lane=0) -> PoseCov:
+        """the lane's record (waits); .matrix("info" | "cov_delta" | "cov_pose") are numpy 6 x 6 views of it"""
+        r = PoseCov()
+        self._ck(self.L.svo_get_pose_covariance(self.h, lane, C.byref(r)), "svo_get_pose_covariance")
+        return r
+
+    def pose_covariances(self):
+        arr = (PoseCov * self.n_lanes)()
+        self._ck(self.L.svo_get_pose_covariances(self.h, arr), "svo_get_pose_covariances")
+        return list(arr)
+
+    def copy_pose_covariances_async(self, dst_ptr, nbytes):
+        self._ck(self.L.svo_copy_pose_covariances_async(self.h, C.c_void_p(dst_ptr), C.c_size_t(nbytes)), "svo_copy_pose_covariances_async")
 
     def copy_results_async(self, dst_ptr, nbytes):
         self._ck(self.L.svo_copy_results_async(self.h, C.c_void_p(dst_ptr), C.c_size_t(nbytes)), "svo_copy_results_async")

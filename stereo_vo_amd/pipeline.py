@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import hip
-from .abi import Result
+from .abi import PoseCov, Result
 
 
 def _frames(ptrs, w, h, stride):
@@ -155,6 +155,17 @@ class StreamBatch:
         self._ck(self.L.svo_batch_results(self.h, arr), "svo_batch_results")
         return list(arr)
 
+    def set_pose_covariance(self, enable=True):
+        """svo_batch_set_pose_covariance: every context leaves a PoseCov record per stream from the next step on"""
+        torch.cuda.synchronize(self.dev)
+        self._ck(self.L.svo_batch_set_pose_covariance(self.h, 1 if enable else 0), "svo_batch_set_pose_covariance")
+
+    def pose_covariances(self):
+        """the record of every stream, global lane order (waits for the steps in flight)"""
+        arr = (PoseCov * self.B)()
+        self._ck(self.L.svo_batch_pose_covariances(self.h, arr), "svo_batch_pose_covariances")
+        return list(arr)
+
     def pooled_kernel_times(self):
         """launches of all contexts pooled: ms and launch counts add up, a launch covers lanes_per_context streams"""
         acc = {}
@@ -216,6 +227,10 @@ class FrameParallelStream:
         """New parameters for every context, also in mid-stream.  Selecting smSAD or ifmSAD for the first time makes the
         hand-over records carry the 8 x 8 windows: the stream re-reads svo_handover_bytes and reallocates its records."""
         self._ck(self.L.svo_fpstream_set_params(self.h, C.byref(params)), "svo_fpstream_set_params")
+
+    def set_pose_covariance(self, enable=True):
+        """svo_fpstream_set_pose_covariance: every context; a pushed frame's records are read from the context push() returned"""
+        self._ck(self.L.svo_fpstream_set_pose_covariance(self.h, 1 if enable else 0), "svo_fpstream_set_pose_covariance")
 
     def push(self, ptrs, stride=None):
         """Enqueue the next frame (ptrs[lane] = (left, right) device addresses).  Returns the context that owns it."""
