@@ -6,6 +6,7 @@
 #include "svo_device.h"
 #include "svo_kernels.h"
 #include "state_format.hpp"
+#include "frame_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -117,7 +118,7 @@ struct svo_ctx {
     // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
     // such frame yet" (the kernels then read nothing).  The device decides the prev/cur shift (the recovery rule of P:86-95 needs
     // m_error), so the previous frame after a shift is known to have patches only when both candidates for it had them.
-    std::vector<uint8_t> sad_cur, sad_prev, sad_drop;  // sad_drop: the lane's next shift forgets its previous frame (svo_hip.h)
+    svo_call::SadWindows sad;                          // sad.drop: the lane's next shift forgets its previous frame (svo_hip.h)
     LaneMask imported;                                 // lanes that svo_import_frame has written and that have not had a svo_process call since (an idle lane keeps its bit)
     // svo_process_lanes: the active mask of the call that began the frame in flight.  The later calls of a multi-call frame (the post
     // call of a detect call, stages run with SVO_FLAG_NO_SHIFT) must carry the same one.
@@ -127,6 +128,7 @@ struct svo_ctx {
     // svo_use_graphs: the kernel sequence of a frame captured once per (flags, ring slot, thresholds) and replayed
     struct GraphEntry { uint32_t flags; int slot, fast_th, orb_th; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs; bool use_graphs; unsigned graph_replays;      // graph_replays: calls served by an earlier capture (svo_debug_get_graph_count)
+    bool capturing;                                    // the call being enqueued is capturing its launches on the stream (CaptureGuard)
     // every stream that has had work of this context enqueued since the last full synchronisation (svo_set_stream), each with
     // a context-owned event recorded behind the last work enqueued on it.  Synchronising waits on the EVENTS, never on the
     // foreign stream handles: a caller may synchronise and destroy its own stream and switch back with svo_set_stream(NULL);
@@ -135,8 +137,8 @@ struct svo_ctx {
     std::vector<UsedStream> used_streams;
 };
 
+using namespace svo_call;
 static void drop_graphs(svo_ctx* ctx);
-static inline bool lane_in(const LaneMask& m, int l) { return ((m.w[l >> 6] >> (l & 63)) & 1ull) != 0; }
 static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
 static void sampler_table_release(int device, int nmax);
@@ -377,8 +379,8 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
-    memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
-    ctx->sad_cur.assign((size_t)cfg->n_lanes, 1); ctx->sad_prev.assign((size_t)cfg->n_lanes, 1); ctx->sad_drop.assign((size_t)cfg->n_lanes, 0);
+    memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
+    ctx->sad.cur.assign((size_t)cfg->n_lanes, 1); ctx->sad.prev.assign((size_t)cfg->n_lanes, 1); ctx->sad.drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
@@ -729,7 +731,7 @@ extern "C" int svo_reset(svo_ctx* ctx, int lane)
             HIPCHECK(hipMemset(ctx->dc.results + l, 0, sizeof(svo_result)));
             if (ctx->pose_cov) HIPCHECK(hipMemset(ctx->d_cov + l, 0, sizeof(svo_pose_cov)));
             HIPCHECK(hipMemset(ctx->dc.fast_th_dyn + (size_t)2 * l * SVO_MAX_LEVELS, 0, (size_t)2 * SVO_MAX_LEVELS * sizeof(uint32_t)));   // a fresh estimator speculates nothing
-            ctx->sad_cur[l] = ctx->sad_prev[l] = 1; ctx->sad_drop[l] = 0;                       // no frames: nothing a SAD stage could miss
+            ctx->sad.cur[l] = ctx->sad.prev[l] = 1; ctx->sad.drop[l] = 0;                       // no frames: nothing a SAD stage could miss
         }
     return SVO_OK;
 }
@@ -1137,78 +1139,190 @@ static int intake_frames(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, 
     return SVO_OK;
 }
 
+// ---- what a call that enqueues leaves behind, whichever way it ends ---------------------------------------------------------
+// Records the event armed by svo_record_after_post behind what the stream holds, and disarms it.  consumes: the call runs the detector's
+// post-processing and somebody takes part (a call in which nobody takes part is no call: it leaves the event armed).  Never while the
+// stream captures: inside this call's own capture the event stays armed for the launch of the graph; on the way out of a call
+// (leaving, PostDisarm) it is disarmed whatever the stream is doing, so that a later, unrelated call cannot record it at the wrong point.
+static hipError_t record_post_event(svo_ctx* ctx, bool consumes, bool leaving = false)
+{
+    if (!consumes || !ctx->post_event || ctx->capturing) return hipSuccess;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (leaving) hipStreamIsCapturing(ctx->stream, &cs);
+    const hipError_t e = cs == hipStreamCaptureStatusNone ? hipEventRecord(ctx->post_event, ctx->stream) : hipSuccess;
+    ctx->post_event = nullptr;
+    return e;
+}
+// the reader of the level-0 images is through (stage 2, the window gather): the upload ring's slot may take the next frame
+static hipError_t release_ring_slot(svo_ctx* ctx)
+{
+    if (!ctx->up_ready || ctx->det_slot < 0) return hipSuccess;
+    const hipError_t e = hipEventRecord(ctx->ev_det[ctx->det_slot], ctx->stream);
+    if (e == hipSuccess) ctx->ev_det_valid[ctx->det_slot] = true;
+    return e;
+}
+// svo_record_after_post arms ONE call: the next one that runs the detector's post-processing.  Whatever way that call leaves -- an
+// argument check (the mask's included), SVO_ERR_STATE, a failed launch -- the event is recorded behind what was enqueued (possibly
+// nothing) and disarmed, so that a waiter is released
+struct PostDisarm { svo_ctx* c; bool consumes; ~PostDisarm() { (void)record_post_event(c, consumes, true); } };
+// whatever was enqueued before an error exit is still covered by the stream's event (declared before the capture guard: a capture is
+// closed first)
+struct MarkGuard { svo_ctx* c; ~MarkGuard() { mark_stream(c); } };
+// the idle lanes travel in DevCtx to every launch of a call; outside it the mask is all zero (the other entry points launch with it)
+struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } };
+// a capture that an error exit leaves open is closed and thrown away
+struct CaptureGuard { svo_ctx* c; ~CaptureGuard() { if (c->capturing) { hipGraph_t g = nullptr; hipStreamEndCapture(c->stream, &g); if (g) hipGraphDestroy(g); c->capturing = false; } } };
+
+// ---- the launches of a frame, one function per stage --------------------------------------------------------------------
+// kernel_times: the instantiations of a 16384-entry context are counted under their own names (kt_names)
+static int kt_select(const DevCtx& d) { return d.sel_max > 4096 ? KT_SELECT_8192 : KT_SELECT; }
+static int kt_nms(const DevCtx& d) { return nms_rowsort_items(d) > 8 ? KT_NMS_16 : KT_NMS; }
+static bool wide_lists(const DevCtx& d) { return d.max_kps > 8192; }
+
+// stage 2 up to the detector's own output: pyramid, corners, the detector's selection (and, where the detector describes, description)
+static void enqueue_detect(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    if (call.faster) {      // stage2_detect.cpp:519-576: FAST-12 at the constant initial_FAST_threshold (m_threshold never moves: processNewImagePair
+                            // passes no update_dyn_thresholds), KLT response, grid NMS; svo_set_fast_threshold has no part in it
+        { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
+        { Span s(ctx, KT_FASTER); launch_faster(d, ctx->d_cand64, p.initial_FAST_threshold, ctx->klt_win, st); }
+        { Span s(ctx, KT_FASTER_NMS); launch_faster_nms(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, st); }
+    } else if (d.fast_orb) {       // stage2_detect.cpp:502-515 on the x1/2 octave pyramid
+        { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
+        { Span s(ctx, KT_FAST); launch_fast(d, st); }
+        if (p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {      // S2:599-606 on the FAST detector's output
+            Span s(ctx, KT_SELECT); launch_fastorb_anms(d, ctx->d_anms, st);
+        } else { Span s(ctx, KT_SELECT); launch_fastorb_nms(d, p.non_maximal_suppression, p.min_distance, st); }
+        { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
+    } else {                // stage2_detect.cpp:458-497
+        { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_resize(d, l, st); }
+        { Span s(ctx, KT_FAST); launch_fast(d, st); }
+        if (!call.select_in_post) { Span s(ctx, kt_select(d)); launch_select(d, st); }
+        // debug mode 9 keeps the detector's order: describe everything, then NMS -- that is what svo_debug_get_raw_keypoints shows
+        if (d.debug_mode == 9) { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
+    }
+}
+// The reference's own post-processing of the detector output: grid NMS and row sort.  The one copy: run by a detect call that does not
+// leave it out (SVO_FLAG_DETECT_NO_POST) and by the SVO_RUN_DETECT_POST call that makes up for it.
+static void enqueue_detect_post(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    if (call.select_in_post && !d.fast_orb) { Span s(ctx, kt_select(d)); launch_select(d, st); }
+    // The x1/2-octave detectors have run their NMS and described (0: the NMS ran above; 3: none, raster order).  dmORB: the reference's NMS
+    // needs positions and responses only, so it runs BEFORE orientation + description and only its survivors are described (unless
+    // debug mode 9 has described everything already)
+    const bool described = d.fast_orb || d.debug_mode == 9;
+    { Span s(ctx, kt_nms(d)); launch_nms_rowsort(d, d.fast_orb ? call.nms_mode_oct : call.nms_mode, p.min_distance, described ? 0 : 1, st); }
+    if (!described) { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
+}
+static void enqueue_match(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    Section sec("_stg3"), sec2("stg3.find_pairings");                           // S3:64, 77
+    // (the brute-force result words were set to all ones by k_begin_frame)
+    if (p.match_method == SVO_SM_DESC_BF) {
+        { Span s(ctx, wide_lists(d) ? KT_HAM_LR_WIDE : KT_HAM_LR); launch_hamming(d, 0, hamming_splits(ctx), st); }
+        { Span s(ctx, KT_LR_FILTER); launch_match_lr_filter(d, p.enable_robust_1to1_match, p.max_y_diff, st); }
+    } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
+        Span s(ctx, KT_LR_FILTER);
+        launch_match_lr_rbr(d, false, p.enable_robust_1to1_match, p.max_y_diff, call.minresp, (int)(size_t)p.orb_max_distance, st);
+    } else {                                                // smSAD: the same loop on the gathered windows
+        Span s(ctx, KT_LR_SAD);
+        launch_match_lr_rbr(d, true, p.enable_robust_1to1_match, p.max_y_diff, call.minresp, call.max_sad_match, st);
+    }
+}
+static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    Section sec("_stg4"), sec2("stg4.track");                                    // S4:76, 457
+    const int win = p.ifm_method == SVO_IFM_DESC_WIN || p.ifm_method == SVO_IFM_SAD;
+    // The chunks of the RANSAC's sample schedule (set before the tracker kernels: phase 0 of the schedule rides in them).  A handful of
+    // lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
+    // there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
+    {
+        static const int forced = [] { const char* e = getenv("SVO_RS_C0"); const int v = e ? atoi(e) : 0; return (v == SVO_RANSAC_CHUNK0 || v == SVO_RANSAC_CHUNK1 || v == SVO_RANSAC_FEW) ? v : 0; }();
+        d.rs_c0 = forced ? forced : (d.n_lanes * d.n_oct > 8 ? SVO_RANSAC_CHUNK0 : SVO_RANSAC_FEW);
+        d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
+    }
+    if (!win) {
+        { Span s(ctx, wide_lists(d) ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, 1, hamming_splits(ctx), st); }
+        { Span s(ctx, wide_lists(d) ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
+    } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
+        Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
+    } else {                                                // ifmSAD
+        Span s(ctx, KT_TRK_SAD); launch_track_win(d, true, p.ifm_win_w, p.ifm_win_h, call.max_sad_track, st);
+    }
+    // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
+    // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
+    { Span s(ctx, KT_RANSAC_HYP); launch_ransac_hyp(d, 0, st); }
+    { Span s(ctx, KT_RANSAC_CNT); launch_ransac_count(d, 0, st); }
+    if (d.rs_c0 < d.rs_c1) {
+        { Span s(ctx, KT_RANSAC_HYP1); launch_ransac_hyp(d, 1, st); }
+        { Span s(ctx, KT_RANSAC_CNT1); launch_ransac_count(d, 1, st); }
+    }
+    { Span s(ctx, KT_RANSAC_HYP2); launch_ransac_hyp(d, 2, st); }
+    { Span s(ctx, KT_RANSAC_CNT2); launch_ransac_count(d, 2, st); }
+    { Span s(ctx, KT_TRK_FINAL); launch_track_finalize(d, p.bad_tracking_th, win, st); }
+}
+static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    Section sec("_stg5");                                                        // S5:398, 729
+    GNParams g; memset(&g, 0, sizeof(g));
+    g.use_robust_kernel = p.use_robust_kernel; g.max_iters = p.max_iters; g.initial_max_iters = p.initial_max_iters; g.max_incr_cost = p.max_incr_cost;
+    g.use_previous_pose_as_initial = p.use_previous_pose_as_initial; g.use_custom_initial_pose = 0;   // processNewImagePair passes no initial estimate (P:338)
+    g.min_distance = p.min_distance; g.img_w = d.W; g.img_h = d.H; g.pmax = d.max_kps; g.standalone = 0;
+    g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
+    if (p.use_custom_initial_pose) g.use_custom_initial_pose = 1;        // deltaPose = initial_estimation = zeros (S5:504-505, default argument H:1045)
+    if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
+    { Span s(ctx, KT_GN); launch_gauss_newton(d, g, st); }
+    if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, g, ctx->d_cov, st); }
+}
+
+// Every lazily allocated buffer a frame may need exists BEFORE a capture begins: hipMalloc / hipMemset are refused on a capturing
+// thread and would invalidate the capture.  The adaptive NMS after the FAST+ORB detector has such a buffer, dmFASTER its 64-bit keys;
+// the window buffer of smSAD / ifmSAD exists from the first call made while either is selected (a context that never selects them
+// allocates and launches nothing).
+static int ensure_call_buffers(svo_ctx* ctx, const FrameCall& call)
+{
+    const DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    if ((call.flags & SVO_RUN_DETECT) && d.fast_orb && !call.faster && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
+        HIPCHECK(dev_alloc(ctx, &ctx->d_anms, (size_t)3 * d.n_img * ctx->cand_total_alloc));
+    if ((call.flags & SVO_RUN_DETECT) && call.faster && !ctx->d_cand64) HIPCHECK(dev_alloc(ctx, &ctx->d_cand64, (size_t)d.n_img * ctx->cand_total_alloc));
+    return call.sad_any ? ensure_sad_buffers(ctx) : SVO_OK;
+}
+// what follows the last launch of a call, replayed or not: the armed event of a call that ran as a graph goes behind the whole graph
+// (plain launches recorded it right behind the post-processing); stage 2 is the only reader of the level-0 images
+static int finish_call(svo_ctx* ctx, const FrameCall& call)
+{
+    HIPCHECK(record_post_event(ctx, call.runs_post));
+    if (call.flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) HIPCHECK(release_ring_slot(ctx));
+    return SVO_OK;
+}
+
 // ---- processNewImagePair ---------------------------------------------------------------------------------
-// The body of svo_process (lanes == NULL: every lane) and svo_process_lanes (one bit per lane that takes part).
+// The body of svo_process (lanes == NULL: every lane) and svo_process_lanes (one bit per lane that takes part): what the call is
+// (frame_call.hpp), then its launches, stage by stage.
 static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, const svo_frame* frames, uint32_t flags)
 {
-    // the mask first, without leaving: who is active, who sits out, and whether the mask itself is acceptable
-    LaneMask active, idle; bool bad_mask = masked && !lanes; unsigned long long bad_word = 0; int bad_wd = 0;
-    for (int wd = 0; wd < 2; wd++) {
-        const int n = ctx->cfg.n_lanes - wd * 64 < 0 ? 0 : (ctx->cfg.n_lanes - wd * 64 > 64 ? 64 : ctx->cfg.n_lanes - wd * 64);
-        const unsigned long long all = n == 64 ? ~0ull : ((1ull << n) - 1ull), a = lanes ? (unsigned long long)lanes[wd] : all;
-        if ((a & ~all) && !bad_mask) { bad_mask = true; bad_word = a; bad_wd = wd; }
-        active.w[wd] = a & all; idle.w[wd] = all & ~a;
-    }
-    const bool partial = (idle.w[0] | idle.w[1]) != 0, nobody = !bad_mask && (active.w[0] | active.w[1]) == 0;
-    auto is_idle = [&](int l) { return lane_in(idle, l); };
-    // svo_record_after_post arms ONE call: the next one that runs the detector's post-processing.  Whatever way that call leaves --
-    // an argument check (the mask's included), SVO_ERR_STATE, a failed launch -- the event is recorded behind what was enqueued
-    // (possibly nothing) and disarmed, so that a waiter is released and a later, unrelated call cannot record it at the wrong point
-    // (ADVICE r04).  A call in which nobody takes part is no call: it leaves the event armed.
-    struct PostDisarm { svo_ctx* c; bool consumes; ~PostDisarm() { if (consumes && c->post_event) { hipStreamCaptureStatus cs = hipStreamCaptureStatusNone; hipStreamIsCapturing(c->stream, &cs);
-                                                                    if (cs == hipStreamCaptureStatusNone) hipEventRecord(c->post_event, c->stream); c->post_event = nullptr; } } }
-        post_disarm{ ctx, !nobody && ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST))) };
-    if (bad_mask) {
-        char msg[160];
-        if (!lanes) snprintf(msg, sizeof(msg), "active == NULL");
-        else snprintf(msg, sizeof(msg), "active[%d] = %016llx selects a lane at or above n_lanes = %d", bad_wd, bad_word, ctx->cfg.n_lanes);
-        ctx->last_error = msg; return SVO_ERR_ARG;
-    }
-    if (nobody) return SVO_OK;                              // nothing is enqueued, no state moves
     const svo_params& p = ctx->params;
-    // P:54-76: invalid selectors are hard errors; the variants outside the hot path are refused explicitly
-    if (p.detect_method < 0 || p.detect_method > 3 || p.match_method < 0 || p.match_method > 2 || p.ifm_method < 0 || p.ifm_method > 3) return SVO_ERR_ARG;
-    if ((flags & SVO_RUN_DETECT) && p.detect_method == SVO_DM_KLT) return SVO_ERR_UNSUPPORTED;                                         // dmKLT: out of scope
-    if ((flags & SVO_RUN_TRACK) && p.ifm_method == SVO_IFM_OPTICAL_FLOW) return SVO_ERR_UNSUPPORTED;                                   // optical flow: out of scope
-    if (p.non_maximal_suppression && p.nmsMethod != SVO_NMS_STANDARD && p.nmsMethod != SVO_NMS_ADAPTIVE) return SVO_ERR_ARG;          // S2:608
-    if (p.min_distance < 2) return SVO_ERR_ARG;            // cell size 0 divides by zero in the reference (S2:331-332)
-    // dmFASTER (S2:519-576) produces keypoints without descriptors: only the SAD stages can consume its lists
-    const bool faster = p.detect_method == SVO_DM_FASTER;
-    if (faster) {
-        if ((flags & SVO_RUN_MATCH) && p.match_method != SVO_SM_SAD) { ctx->last_error = "dmFASTER computes no descriptors: stage 3 needs match_method = smSAD"; return SVO_ERR_STATE; }
-        if ((flags & SVO_RUN_TRACK) && p.ifm_method != SVO_IFM_SAD) { ctx->last_error = "dmFASTER computes no descriptors: stage 4 needs ifm_method = ifmSAD"; return SVO_ERR_STATE; }
-        if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {
-            ctx->last_error = "the adaptive NMS is not built for dmFASTER: use nmsMethod = nmsmStandard"; return SVO_ERR_UNSUPPORTED;
-        }
-        if ((flags & SVO_RUN_DETECT) && (p.initial_FAST_threshold < 0 || p.initial_FAST_threshold > 255)) {
-            char msg[128]; snprintf(msg, sizeof(msg), "initial_FAST_threshold %d: dmFASTER takes 0 .. 255", p.initial_FAST_threshold);
-            ctx->last_error = msg; return SVO_ERR_ARG;
-        }
-    }
-    // SVO_FLAG_DETECT_AHEAD: a detect call that leaves lane state and records alone (it may overlap stages 3-5 of the frame before),
-    // or the post call that completes it (and therefore runs the shift itself)
-    const bool ahead = (flags & SVO_FLAG_DETECT_AHEAD) != 0;
-    if (ahead) {
-        if (flags & SVO_RUN_DETECT) { if (!(flags & SVO_FLAG_DETECT_NO_POST) || (flags & (SVO_RUN_MATCH | SVO_RUN_TRACK | SVO_RUN_OPTIMIZE | SVO_RUN_DETECT_POST))) return SVO_ERR_ARG; }
-        else if (!(flags & SVO_RUN_DETECT_POST) || (flags & SVO_FLAG_NO_SHIFT)) return SVO_ERR_ARG;
-    }
+    const FrameCall call = make_frame_call(flags, p);
+    // the mask first, without leaving: who is active, who sits out, and whether the mask itself is acceptable
+    LaneMask active, idle; std::string why;
+    const bool mask_ok = parse_lane_mask(lanes, masked, ctx->cfg.n_lanes, active, idle, why);
+    const bool partial = lane_any(idle), nobody = mask_ok && !lane_any(active);
+    PostDisarm post_disarm{ ctx, !nobody && call.runs_post };
+    if (!mask_ok) { ctx->last_error = why; return SVO_ERR_ARG; }
+    if (nobody) return SVO_OK;                              // nothing is enqueued, no state moves
+    // the refusals: before anything is enqueued or noted
+    { const int rc = check_frame_call(call, p, active, ctx->frame_active_set ? &ctx->frame_active : nullptr, why); if (rc) { ctx->last_error = why; return rc; } }
     DevCtx& d = ctx->dc;
-    // the calls of one frame carry one mask: what a frame's first call (any call that is not a continuation) ran with is what its
-    // post call and its SVO_FLAG_NO_SHIFT stages must run with -- refused here, before anything is enqueued or noted
-    const bool continuation = !(flags & SVO_RUN_DETECT) && (flags & (SVO_FLAG_NO_SHIFT | SVO_RUN_DETECT_POST));
-    if (continuation && ctx->frame_active_set && memcmp(&active, &ctx->frame_active, sizeof(active)) != 0) {
-        char msg[256];
-        snprintf(msg, sizeof(msg), "active lanes %016llx:%016llx, but the frame in flight began with %016llx:%016llx: every call of a frame carries the same mask",
-                 active.w[1], active.w[0], ctx->frame_active.w[1], ctx->frame_active.w[0]);
-        ctx->last_error = msg; return SVO_ERR_STATE;
-    }
     Section sec_all("processNewImagePair");                                       // P:79, 377
     const hipStream_t st = ctx->stream;
     note_stream(ctx);
-    bool capturing = false;
-    // whatever was enqueued before an error exit is still covered by the stream's event (declared before the capture guard: a
-    // capture is closed first)
-    struct MarkGuard { svo_ctx* c; ~MarkGuard() { mark_stream(c); } } mark_guard{ ctx };
+    MarkGuard mark_guard{ ctx };
+    // intake: the images of a detect call on their way to the level-0 addresses
     const uint8_t* ptrs[2 * SVO_MAX_LANES];
     PrepArgs prep; memset(&prep, 0, sizeof(prep)); bool prepare = false;
     if (flags & SVO_RUN_DETECT) {
@@ -1216,200 +1330,58 @@ static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, 
     } else if (!ctx->geom_ready && (flags & (SVO_RUN_MATCH | SVO_RUN_OPTIMIZE))) return SVO_ERR_STATE;
     d.fast_th = ctx->fast_th; d.orb_th = ctx->orb_th;
     if (flags & SVO_RUN_DETECT) d.tl_step++;                 // (a frame of the detect-ahead schedule is a detect call and then a post call)
-    // svo_use_graphs: the launches below are captured once into a hipGraph per (flags, ring slot, thresholds) and replayed:
-    // ~30 kernel launches of a frame become one graph launch (what bounds ONE stream is launch latency, not the kernels)
-    // every lazily allocated buffer a frame may need exists BEFORE a capture begins: hipMalloc / hipMemset are refused on a
-    // capturing thread and would invalidate the capture (the adaptive NMS after the FAST+ORB detector has such a buffer)
-    if ((flags & SVO_RUN_DETECT) && d.fast_orb && !faster && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
-        HIPCHECK(dev_alloc(ctx, &ctx->d_anms, (size_t)3 * d.n_img * ctx->cand_total_alloc));
-    if ((flags & SVO_RUN_DETECT) && faster && !ctx->d_cand64) HIPCHECK(dev_alloc(ctx, &ctx->d_cand64, (size_t)d.n_img * ctx->cand_total_alloc));
-    // smSAD / ifmSAD: the window buffer exists from the first call made while either is selected (a context that never selects
-    // them allocates and launches nothing), and a SAD stage on a frame whose windows were never gathered is refused here
-    const bool sad_m = p.match_method == SVO_SM_SAD, sad_t = p.ifm_method == SVO_IFM_SAD, sad_any = sad_m || sad_t;
-    if (sad_any) { const int rc_sad = ensure_sad_buffers(ctx); if (rc_sad) return rc_sad; }
-    const bool runs_post = (flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST));
-    LaneMask drop_prev; memset(&drop_prev, 0, sizeof(drop_prev)); bool any_drop = false;
-    {
-        const bool shifts = !(flags & SVO_FLAG_NO_SHIFT) && !(ahead && (flags & SVO_RUN_DETECT)), repeat = (flags & SVO_FLAG_REPEAT) != 0;
-        std::vector<uint8_t> cur = ctx->sad_cur, prev = ctx->sad_prev, drop = ctx->sad_drop;
-        int bad_lane = -1; bool bad_prev = false;
-        for (int l = 0; l < d.n_lanes; l++) {
-            if (is_idle(l)) continue;                        // (sad_drop of an idle lane waits for the lane's next active frame)
-            if (shifts) {
-                if (drop[l]) { drop_prev.w[l >> 6] |= 1ull << (l & 63); any_drop = true; prev[l] = 1; drop[l] = 0; }
-                else if (!repeat) prev[l] = prev[l] && cur[l];
-                cur[l] = 0;                                  // an empty list until the post-processing has run
-            }
-            if (runs_post) cur[l] = sad_any ? 1 : 0;
-            if (bad_lane < 0 && (flags & SVO_RUN_MATCH) && sad_m && !cur[l]) bad_lane = l;
-            if (bad_lane < 0 && (flags & SVO_RUN_TRACK) && sad_t && !(cur[l] && prev[l])) { bad_lane = l; bad_prev = cur[l] != 0; }
-        }
-        if (bad_lane >= 0) {
-            char msg[320];
-            snprintf(msg, sizeof(msg), "lane %d: %s selects SAD but the 8 x 8 windows of its %s frame were never gathered (features put, loaded or imported, "
-                     "or detected while no SAD method was selected)%s", bad_lane, bad_prev ? "ifm_method" : (((flags & SVO_RUN_MATCH) && sad_m) ? "match_method" : "ifm_method"),
-                     bad_prev ? "previous" : "current", (bad_prev && shifts && !repeat) ? ": this frame is refused, the next one starts the lane's track afresh" : "");
-            ctx->last_error = msg;
-            // the frame before cannot be tracked from with SAD, and its image is gone: the next frame of such a lane forgets it
-            if (bad_prev && shifts && !repeat) for (int l = 0; l < d.n_lanes; l++) if (!is_idle(l) && (!ctx->sad_prev[l] || !ctx->sad_cur[l])) ctx->sad_drop[l] = 1;
-            return SVO_ERR_STATE;
-        }
-        ctx->sad_cur = cur; ctx->sad_prev = prev; ctx->sad_drop = drop;
-    }
-    if (!continuation) { ctx->frame_active = active; ctx->frame_active_set = true; }
-    // the idle lanes travel in DevCtx to every launch below; outside this call the mask is all zero (the other entry points launch with it)
+    { const int rc = ensure_call_buffers(ctx, call); if (rc) return rc; }
+    // which frames have their windows after this call; a SAD stage on a frame whose windows were never gathered is refused here
+    SadStep step = sad_window_step(ctx->sad, idle, call);
+    ctx->sad = std::move(step.next);
+    if (step.bad_lane >= 0) { ctx->last_error = step.why; return SVO_ERR_STATE; }
+    if (!call.continuation) { ctx->frame_active = active; ctx->frame_active_set = true; }
     d.idle = idle;
-    struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } } idle_guard{ &d };
-    // (a call with idle lanes runs as plain launches, as one with any_drop does: the mask is a kernel argument)
+    IdleGuard idle_guard{ &d };
     // svo_import_frame writes every lane; the lanes of this call that it wrote and that have had no call since (all of them or none)
     const bool imported_pending = ((ctx->imported.w[0] & active.w[0]) | (ctx->imported.w[1] & active.w[1])) != 0;
-    const bool graph_ok = ctx->use_graphs && !partial && !prepare && !ctx->cfg.kernel_times && !any_drop && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
+    // svo_use_graphs: the launches below are captured once into a hipGraph per (flags, ring slot, thresholds) and replayed:
+    // ~30 kernel launches of a frame become one graph launch (what bounds ONE stream is launch latency, not the kernels).
+    // (a call with idle lanes runs as plain launches, as one with any_drop does: the mask is a kernel argument)
+    const bool graph_ok = ctx->use_graphs && !partial && !prepare && !ctx->cfg.kernel_times && !step.any_drop && (!(flags & SVO_RUN_DETECT) || ctx->det_slot >= 0);
     const uint32_t gflags = flags & ~(uint32_t)(SVO_FLAG_DEVICE_IMAGES | SVO_FLAG_PINNED_IMAGES);
     const int gslot = (flags & SVO_RUN_DETECT) ? ctx->det_slot : -1;
-    if (graph_ok) {
-        const bool ids_first = p.vo_use_matches_ids && imported_pending;            // changes one kernel argument: not replayable
+    if (graph_ok && !(p.vo_use_matches_ids && imported_pending)) {                  // (the IDs' first frame after an import changes one kernel argument: not replayable)
         for (auto& g : ctx->graphs)
-            if (!ids_first && g.flags == gflags && g.slot == gslot && g.fast_th == ctx->fast_th && g.orb_th == ctx->orb_th) {
+            if (g.flags == gflags && g.slot == gslot && g.fast_th == ctx->fast_th && g.orb_th == ctx->orb_th) {
                 HIPCHECK(hipGraphLaunch(g.exec, st));
                 ctx->graph_replays++;
                 for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];
-                if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && ctx->up_ready && ctx->det_slot >= 0) { HIPCHECK(hipEventRecord(ctx->ev_det[ctx->det_slot], st)); ctx->ev_det_valid[ctx->det_slot] = true; }
-                if (ctx->post_event && ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST)))) { HIPCHECK(hipEventRecord(ctx->post_event, st)); ctx->post_event = nullptr; }
-                return SVO_OK;
+                return finish_call(ctx, call);
             }
-        if (!ids_first) { HIPCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal)); capturing = true; }
+        HIPCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal)); ctx->capturing = true;
     }
-    struct CaptureGuard { hipStream_t st; bool* on; ~CaptureGuard() { if (*on) { hipGraph_t g = nullptr; hipStreamEndCapture(st, &g); if (g) hipGraphDestroy(g); *on = false; } } } guard{ st, &capturing };
-    d.det_ahead = (ahead && (flags & SVO_RUN_DETECT)) ? 1 : 0;
-    // kernel_times: the instantiations of a 16384-entry context are counted under their own names (kt_names)
-    const bool wide = d.max_kps > 8192;
-    const int kt_select = d.sel_max > 4096 ? KT_SELECT_8192 : KT_SELECT;
-    auto kt_nms = [&]() -> int { return nms_rowsort_items(d) > 8 ? KT_NMS_16 : KT_NMS; };
-    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, (flags & SVO_RUN_DETECT) ? ptrs : nullptr, flags, drop_prev, st); if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); } }
-    // the detector's per-image scratch has had its last reader: the armed event (svo_record_after_post) goes here
-    auto after_post = [&]() -> hipError_t {
-        if (!ctx->post_event || capturing) return hipSuccess;
-        const hipError_t e = hipEventRecord(ctx->post_event, st);
-        ctx->post_event = nullptr;
-        return e;
-    };
+    CaptureGuard capture_guard{ ctx };
+    d.det_ahead = (call.ahead && (flags & SVO_RUN_DETECT)) ? 1 : 0;
+    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, (flags & SVO_RUN_DETECT) ? ptrs : nullptr, flags, step.drop_prev, st); if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); } }
     if (flags & SVO_RUN_DETECT) {
         Section sec("_stg2");                                                        // S2:392, 670
-        if (faster) {           // stage2_detect.cpp:519-576: FAST-12 at the constant initial_FAST_threshold (m_threshold never moves: processNewImagePair
-                                // passes no update_dyn_thresholds), KLT response, grid NMS, row sort; svo_set_fast_threshold has no part in it
-            { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
-            { Span s(ctx, KT_FASTER); launch_faster(d, ctx->d_cand64, p.initial_FAST_threshold, ctx->klt_win, st); }
-            { Span s(ctx, KT_FASTER_NMS); launch_faster_nms(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, st); }
-            if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, p.non_maximal_suppression ? 0 : 3, p.min_distance, 0, st); }
-        } else if (d.fast_orb) {       // stage2_detect.cpp:502-515 on the x1/2 octave pyramid
-            { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
-            { Span s(ctx, KT_FAST); launch_fast(d, st); }
-            if (p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {      // S2:599-606 on the FAST detector's output
-                Span s(ctx, KT_SELECT); launch_fastorb_anms(d, ctx->d_anms, st);
-            } else { Span s(ctx, KT_SELECT); launch_fastorb_nms(d, p.non_maximal_suppression, p.min_distance, st); }
-            { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
-            if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, p.non_maximal_suppression ? 0 : 3, p.min_distance, 0, st); }   // 0: the NMS ran above; 3: none, raster order
-        } else {                // stage2_detect.cpp:458-497
-            { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_resize(d, l, st); }
-            { Span s(ctx, KT_FAST); launch_fast(d, st); }
-            const bool split_early = (flags & SVO_FLAG_DETECT_NO_POST) && (flags & SVO_FLAG_DETECT_SPLIT_AT_SELECT);
-            if (!split_early) { Span s(ctx, kt_select); launch_select(d, st); }
-            // The reference's NMS needs positions and responses only, so it runs BEFORE orientation + description and only
-            // its survivors are described (debug mode 9 keeps the detector's order: describe everything, then NMS --
-            // that is what svo_debug_get_raw_keypoints shows)
-            const int nms_mode = p.non_maximal_suppression ? (p.nmsMethod == SVO_NMS_ADAPTIVE ? 2 : 1) : 0;
-            if (d.debug_mode == 9) {
-                { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
-                if (!(flags & SVO_FLAG_DETECT_NO_POST)) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 0, st); }
-            } else if (!(flags & SVO_FLAG_DETECT_NO_POST)) {
-                { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
-                { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
-            }
-        }
+        enqueue_detect(ctx, call, st);
+        if (!(flags & SVO_FLAG_DETECT_NO_POST)) enqueue_detect_post(ctx, call, st);
     } else if (flags & SVO_RUN_DETECT_POST) {       // the post-processing a SVO_FLAG_DETECT_NO_POST call left out
         if (!ctx->geom_ready) return SVO_ERR_STATE;
         Section sec("_stg2");
-        const int nms_mode = p.non_maximal_suppression ? (p.nmsMethod == SVO_NMS_ADAPTIVE ? 2 : 1) : 0;
-        if ((flags & SVO_FLAG_DETECT_SPLIT_AT_SELECT) && !d.fast_orb) { Span s(ctx, kt_select); launch_select(d, st); }
-        if (d.fast_orb || d.debug_mode == 9) { Span s(ctx, kt_nms()); launch_nms_rowsort(d, d.fast_orb ? (p.non_maximal_suppression ? 0 : 3) : nms_mode, p.min_distance, 0, st); }
-        else {
-            { Span s(ctx, kt_nms()); launch_nms_rowsort(d, nms_mode, p.min_distance, 1, st); }
-            { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
-        }
+        enqueue_detect_post(ctx, call, st);
     }
     // the final keypoint lists exist: the windows of the SAD matchers, while the octave images are still this frame's
-    if (runs_post && sad_any) { Span s(ctx, KT_SAD_PATCH); launch_sad_patch(d, st); }
-    if (runs_post) HIPCHECK(after_post());
-    const int nsplit = hamming_splits(ctx);
-    if (flags & SVO_RUN_MATCH) {
-        Section sec("_stg3"), sec2("stg3.find_pairings");                           // S3:64, 77
-        // (the brute-force result words were set to all ones by k_begin_frame)
-        if (p.match_method == SVO_SM_DESC_BF) {
-            { Span s(ctx, wide ? KT_HAM_LR_WIDE : KT_HAM_LR); launch_hamming(d, 0, nsplit, st); }
-            { Span s(ctx, KT_LR_FILTER); launch_match_lr_filter(d, p.enable_robust_1to1_match, p.max_y_diff, st); }
-        } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
-            const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
-            Span s(ctx, KT_LR_FILTER);
-            launch_match_lr_rbr(d, false, p.enable_robust_1to1_match, p.max_y_diff, minresp, (int)(size_t)p.orb_max_distance, st);
-        } else {                                                // smSAD: the same loop on the gathered windows
-            const double minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;   // S3:189-193
-            // size_t(sad_max_distance) (S3:201): 0 = the reference's default 200 (S3:48), negative = no threshold (a SAD is <= 16320)
-            const int max_sad = p.sad_max_distance == 0 ? 200 : (p.sad_max_distance < 0 ? INT32_MAX : p.sad_max_distance);
-            Span s(ctx, KT_LR_SAD);
-            launch_match_lr_rbr(d, true, p.enable_robust_1to1_match, p.max_y_diff, minresp, max_sad, st);
-        }
-    }
-    if (flags & SVO_RUN_TRACK) {
-        Section sec("_stg4"), sec2("stg4.track");                                    // S4:76, 457
-        const int win = p.ifm_method == SVO_IFM_DESC_WIN || p.ifm_method == SVO_IFM_SAD;
-        // The chunks of the RANSAC's sample schedule (set before the tracker kernels: phase 0 of the schedule rides in them).  A handful of
-        // lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
-        // there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
-        {
-            static const int forced = [] { const char* e = getenv("SVO_RS_C0"); const int v = e ? atoi(e) : 0; return (v == SVO_RANSAC_CHUNK0 || v == SVO_RANSAC_CHUNK1 || v == SVO_RANSAC_FEW) ? v : 0; }();
-            d.rs_c0 = forced ? forced : (d.n_lanes * d.n_oct > 8 ? SVO_RANSAC_CHUNK0 : SVO_RANSAC_FEW);
-            d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
-        }
-        if (!win) {
-            { Span s(ctx, wide ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, 1, nsplit, st); }
-            { Span s(ctx, wide ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
-        } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
-            Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
-        } else {                                                // ifmSAD: uint32_t MAX_SAD (S4:448); 0 = "~200" (H:297), negative wraps to no threshold
-            const unsigned max_sad = p.ifm_sad_max_distance == 0 ? 200u : (unsigned)p.ifm_sad_max_distance;
-            Span s(ctx, KT_TRK_SAD); launch_track_win(d, true, p.ifm_win_w, p.ifm_win_h, max_sad, st);
-        }
-        // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
-        // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
-        { Span s(ctx, KT_RANSAC_HYP); launch_ransac_hyp(d, 0, st); }
-        { Span s(ctx, KT_RANSAC_CNT); launch_ransac_count(d, 0, st); }
-        if (d.rs_c0 < d.rs_c1) {
-            { Span s(ctx, KT_RANSAC_HYP1); launch_ransac_hyp(d, 1, st); }
-            { Span s(ctx, KT_RANSAC_CNT1); launch_ransac_count(d, 1, st); }
-        }
-        { Span s(ctx, KT_RANSAC_HYP2); launch_ransac_hyp(d, 2, st); }
-        { Span s(ctx, KT_RANSAC_CNT2); launch_ransac_count(d, 2, st); }
-        { Span s(ctx, KT_TRK_FINAL); launch_track_finalize(d, p.bad_tracking_th, win, st); }
-    }
+    if (call.runs_post && call.sad_any) { Span s(ctx, KT_SAD_PATCH); launch_sad_patch(d, st); }
+    // the detector's per-image scratch has had its last reader: the armed event (svo_record_after_post) goes here
+    HIPCHECK(record_post_event(ctx, call.runs_post));
+    if (flags & SVO_RUN_MATCH) enqueue_match(ctx, call, st);
+    if (flags & SVO_RUN_TRACK) enqueue_track(ctx, call, st);
     // (after svo_import_frame the lane may turn out to be at its stream's FIRST frame: the first-frame ID rule of S3:172-173
     // then applies in this call although stage 3 ran in an earlier one)
     if (p.vo_use_matches_ids && (flags & (SVO_RUN_MATCH | SVO_RUN_TRACK))) { Span s(ctx, KT_TRK_FINAL); launch_match_ids(d, flags | (imported_pending ? SVO_RUN_MATCH : 0), st); }
     for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];       // (a lane that sat this call out keeps its bit for its own next call)
-    if (flags & SVO_RUN_OPTIMIZE) {
-        Section sec("_stg5");                                                        // S5:398, 729
-        GNParams g; memset(&g, 0, sizeof(g));
-        g.use_robust_kernel = p.use_robust_kernel; g.max_iters = p.max_iters; g.initial_max_iters = p.initial_max_iters; g.max_incr_cost = p.max_incr_cost;
-        g.use_previous_pose_as_initial = p.use_previous_pose_as_initial; g.use_custom_initial_pose = 0;   // processNewImagePair passes no initial estimate (P:338)
-        g.min_distance = p.min_distance; g.img_w = d.W; g.img_h = d.H; g.pmax = d.max_kps; g.standalone = 0;
-        g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
-        if (p.use_custom_initial_pose) g.use_custom_initial_pose = 1;        // deltaPose = initial_estimation = zeros (S5:504-505, default argument H:1045)
-        if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
-        { Span s(ctx, KT_GN); launch_gauss_newton(d, g, st); }
-        if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, g, ctx->d_cov, st); }
-    }
-    if (capturing) {
+    if (flags & SVO_RUN_OPTIMIZE) enqueue_optimize(ctx, call, st);
+    if (ctx->capturing) {
         hipGraph_t graph = nullptr;
-        capturing = false;
+        ctx->capturing = false;
         HIPCHECK(hipStreamEndCapture(st, &graph));
         hipGraphExec_t exec = nullptr;
         const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -1417,12 +1389,8 @@ static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, 
         HIPCHECK(e);
         ctx->graphs.push_back({ gflags, gslot, ctx->fast_th, ctx->orb_th, exec });
         HIPCHECK(hipGraphLaunch(exec, st));
-        if ((flags & SVO_RUN_DETECT_POST) || ((flags & SVO_RUN_DETECT) && !(flags & SVO_FLAG_DETECT_NO_POST))) HIPCHECK(after_post());
     }
-    // stage 2 is the only reader of the level-0 images: once it is through, the ring slot may take the next upload
-    if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && ctx->up_ready && ctx->det_slot >= 0) {
-        HIPCHECK(hipEventRecord(ctx->ev_det[ctx->det_slot], st)); ctx->ev_det_valid[ctx->det_slot] = true;
-    }
+    { const int rc = finish_call(ctx, call); if (rc) return rc; }
     HIPCHECK(hipGetLastError());
     return SVO_OK;
 }
@@ -1460,6 +1428,47 @@ static int lane_state(svo_ctx* ctx, int lane, LaneState* s)
 }
 static int slot_of(const LaneState& s, int which) { return which ? s.prev_slot : 1 - s.prev_slot; }
 
+// The lists of one lane-octave (vl = lane * oct_cap + octave) in one frame slot: the host's one address computation for every per-lane
+// list array of DevCtx (the kernels have feat_base / match_base, svo_device.h)
+struct ListAt {
+    const DevCtx* d; int vl, slot;
+    long long list() const { return (long long)vl * 2 + slot; }                       // [n_vl][2 slots]
+    long long feat(int side) const { return list() * 2 + side; }                     // [n_vl][2 slots][2 sides]
+    svo_keypoint* kps(int side) const { return d->kps + feat(side) * d->max_kps; }
+    uint8_t* desc(int side) const { return d->desc + feat(side) * d->max_kps * 32; }
+    int* n_kps(int side) const { return d->n_kps + feat(side); }
+    uint8_t* windows(int side) const { return d->sad_patch + feat(side) * d->max_kps * 64; }
+    uint8_t* flags(int side) const { return d->sad_flag + feat(side) * d->max_kps; }
+    int* row_index(int side) const { return d->row_index + feat(side) * d->max_h; }
+    svo_dmatch* matches() const { return d->matches + list() * d->max_kps; }
+    int* n_matches() const { return d->n_matches + list(); }
+    int* mrow_index() const { return d->mrow_index + list() * (d->max_h + 1); }
+    int* ids() const { return d->ids + list() * d->max_kps; }
+    int* n_ids() const { return d->n_ids + list(); }
+};
+static ListAt list_at(const svo_ctx* ctx, int lane, const LaneState& s, int which, int octave) { return { &ctx->dc, lane * ctx->dc.oct_cap + octave, slot_of(s, which) }; }
+// the argument check of every entry point that names a list (an entry point without a side passes 0)
+static bool bad_list_args(const svo_ctx* ctx, int lane, int which, int side, int octave)
+{
+    return !ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap;
+}
+static bool frame_absent(const LaneState& s, int which) { return which ? !s.has_prev : !s.has_cur; }
+// the tail of a getter of a counted list: the count from the device, and as many entries as the caller has room for.  Returns the
+// count, or the status of a failed copy.
+static int read_count(svo_ctx* ctx, const int* d_n, int cap, int* m)
+{
+    int n = 0;
+    HIPCHECK(hipMemcpy(&n, d_n, sizeof(int), hipMemcpyDeviceToHost));
+    *m = n < cap ? n : cap;
+    return n;
+}
+template <typename T>
+static int read_list(svo_ctx* ctx, T* dst, const T* d_src, int m, size_t per = 1)
+{
+    if (dst && m > 0) HIPCHECK(hipMemcpy(dst, d_src, sizeof(T) * per * m, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
 extern "C" int svo_get_results(svo_ctx* ctx, svo_result* res)
 {
     if (ctx) use_device(ctx);
@@ -1489,16 +1498,13 @@ extern "C" int svo_get_result(svo_ctx* ctx, int lane, svo_result* res)
 extern "C" int svo_get_keypoints_oct(svo_ctx* ctx, int lane, int which, int side, int octave, svo_keypoint* kps, uint8_t* desc, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, side, octave)) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    if (which ? !s.has_prev : !s.has_cur) return 0;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, sizeof(int), hipMemcpyDeviceToHost));
-    const int m = n < cap ? n : cap;
-    const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
-    if (kps && m > 0) HIPCHECK(hipMemcpy(kps, ctx->dc.kps + base, sizeof(svo_keypoint) * m, hipMemcpyDeviceToHost));
-    if (desc && m > 0) HIPCHECK(hipMemcpy(desc, ctx->dc.desc + base * 32, (size_t)32 * m, hipMemcpyDeviceToHost));
+    if (frame_absent(s, which)) return 0;
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    int m; const int n = read_count(ctx, at.n_kps(side), cap, &m); if (n < 0) return n;
+    if ((rc = read_list(ctx, kps, at.kps(side), m))) return rc;
+    if ((rc = read_list(ctx, desc, at.desc(side), m, 32))) return rc;
     return n;
 }
 extern "C" int svo_get_keypoints(svo_ctx* ctx, int lane, int which, int side, svo_keypoint* kps, uint8_t* desc, int cap)
@@ -1510,25 +1516,22 @@ extern "C" int svo_get_keypoints(svo_ctx* ctx, int lane, int which, int side, sv
 extern "C" int svo_get_row_index(svo_ctx* ctx, int lane, int which, int side, int octave, int32_t* idx, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || !ctx->geom_ready || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, side, octave) || !ctx->geom_ready) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave, H = ctx->dc.oh[octave];
-    const int m = H < cap ? H : cap;
-    if (idx && m > 0) HIPCHECK(hipMemcpy(idx, ctx->dc.row_index + (long long)((vl * 2 + slot) * 2 + side) * ctx->dc.max_h, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    const int H = ctx->dc.oh[octave];
+    if ((rc = read_list(ctx, idx, list_at(ctx, lane, s, which, octave).row_index(side), H < cap ? H : cap))) return rc;
     return H;
 }
 
 extern "C" int svo_get_matches_oct(svo_ctx* ctx, int lane, int which, int octave, svo_dmatch* mm, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave)) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    if (which ? !s.has_prev : !s.has_cur) return 0;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_matches + vl * 2 + slot, sizeof(int), hipMemcpyDeviceToHost));
-    const int m = n < cap ? n : cap;
-    if (mm && m > 0) HIPCHECK(hipMemcpy(mm, ctx->dc.matches + ((long long)vl * 2 + slot) * ctx->dc.max_kps, sizeof(svo_dmatch) * m, hipMemcpyDeviceToHost));
+    if (frame_absent(s, which)) return 0;
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    int m; const int n = read_count(ctx, at.n_matches(), cap, &m); if (n < 0) return n;
+    if ((rc = read_list(ctx, mm, at.matches(), m))) return rc;
     return n;
 }
 extern "C" int svo_get_matches(svo_ctx* ctx, int lane, int which, svo_dmatch* mm, int cap) { return svo_get_matches_oct(ctx, lane, which, 0, mm, cap); }
@@ -1537,7 +1540,7 @@ extern "C" int svo_get_matches(svo_ctx* ctx, int lane, int which, svo_dmatch* mm
 extern "C" int svo_get_values(svo_ctx* ctx, int lane, int which, int octave, svo_values* v)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || !v || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap || v->cap_kps < 0 || v->cap_matches < 0) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave) || !v || v->cap_kps < 0 || v->cap_matches < 0) return SVO_ERR_ARG;
     const int MK = ctx->dc.max_kps;
     if (!ctx->d_vals) {
         ctx->vals_bytes = 64 + (size_t)MK * (2 * (sizeof(svo_keypoint) + 32) + sizeof(svo_dmatch) + sizeof(int32_t));
@@ -1571,24 +1574,21 @@ extern "C" int svo_get_values(svo_ctx* ctx, int lane, int which, int octave, svo
 extern "C" int svo_get_matches_row_index(svo_ctx* ctx, int lane, int which, int octave, int32_t* idx, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || !ctx->geom_ready || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave) || !ctx->geom_ready) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave, H1 = ctx->dc.oh[octave] + 1;
-    const int m = H1 < cap ? H1 : cap;
-    if (idx && m > 0) HIPCHECK(hipMemcpy(idx, ctx->dc.mrow_index + (long long)(vl * 2 + slot) * (ctx->dc.max_h + 1), sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    const int H1 = ctx->dc.oh[octave] + 1;
+    if ((rc = read_list(ctx, idx, list_at(ctx, lane, s, which, octave).mrow_index(), H1 < cap ? H1 : cap))) return rc;
     return H1;
 }
 
 extern "C" int svo_get_tracked_oct(svo_ctx* ctx, int lane, int octave, svo_index_pair* t, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, 0, 0, octave)) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    const int vl = lane * ctx->dc.oct_cap + octave;
-    int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_tracked + vl, sizeof(int), hipMemcpyDeviceToHost));
-    const int m = n < cap ? n : cap;
-    if (t && m > 0) HIPCHECK(hipMemcpy(t, ctx->dc.tracked + (long long)vl * ctx->dc.max_kps, sizeof(svo_index_pair) * m, hipMemcpyDeviceToHost));
+    const int vl = lane * ctx->dc.oct_cap + octave;                          // (one track list per lane-octave: no slot)
+    int m; const int n = read_count(ctx, ctx->dc.n_tracked + vl, cap, &m); if (n < 0) return n;
+    if ((rc = read_list(ctx, t, ctx->dc.tracked + (long long)vl * ctx->dc.max_kps, m))) return rc;
     return n;
 }
 extern "C" int svo_get_tracked(svo_ctx* ctx, int lane, svo_index_pair* t, int cap) { return svo_get_tracked_oct(ctx, lane, 0, t, cap); }
@@ -1596,14 +1596,12 @@ extern "C" int svo_get_tracked(svo_ctx* ctx, int lane, svo_index_pair* t, int ca
 extern "C" int svo_get_match_ids(svo_ctx* ctx, int lane, int which, int octave, int32_t* ids, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave)) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    if (which ? !s.has_prev : !s.has_cur) return 0;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_ids + vl * 2 + slot, sizeof(int), hipMemcpyDeviceToHost));
-    const int m = n < cap ? n : cap;
-    if (ids && m > 0) HIPCHECK(hipMemcpy(ids, ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    if (frame_absent(s, which)) return 0;
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    int m; const int n = read_count(ctx, at.n_ids(), cap, &m); if (n < 0) return n;
+    if ((rc = read_list(ctx, ids, at.ids(), m))) return rc;
     return n;
 }
 
@@ -1624,12 +1622,12 @@ extern "C" int svo_set_this_frame_as_kf(svo_ctx* ctx, int lane)
     if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
     if (!s.has_cur) return SVO_ERR_STATE;                 // ASSERTMSG_ "Current frame does not exist" (H:677)
-    const int vl = lane * ctx->dc.oct_cap, slot = slot_of(s, 0);
+    const ListAt at = list_at(ctx, lane, s, 0, 0);
     int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_ids + vl * 2 + slot, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(&n, at.n_ids(), sizeof(int), hipMemcpyDeviceToHost));
     if (n <= 0) return SVO_ERR_STATE;
     std::vector<int32_t> ids((size_t)n);
-    HIPCHECK(hipMemcpy(ids.data(), ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(ids.data(), at.ids(), sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     int mx = ids[0]; for (int i = 1; i < n; i++) if (ids[i] > mx) mx = ids[i];
     s.last_kf_max_id = mx;
     HIPCHECK(hipMemcpy(ctx->dc.lane + lane, &s, sizeof(s), hipMemcpyHostToDevice));
@@ -1668,16 +1666,15 @@ static int mark_present(svo_ctx* ctx, int lane, int which)
 extern "C" int svo_put_features_oct(svo_ctx* ctx, int lane, int which, int side, int octave, const svo_keypoint* kps, const uint8_t* desc, int n, int img_w, int img_h)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || n < 0 || (n > 0 && !kps) || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, side, octave) || n < 0 || (n > 0 && !kps)) return SVO_ERR_ARG;
     if (n > ctx->dc.max_kps) return SVO_ERR_CAPACITY;
     int rc = ensure_geometry(ctx, img_w, img_h); if (rc) return rc;
     if (octave >= ctx->dc.n_oct) return SVO_ERR_ARG;                       // P:139: the octave count of the data must match the system's
     LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
-    if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.kps + base, kps, sizeof(svo_keypoint) * n, hipMemcpyHostToDevice));
-    if (n > 0 && desc) HIPCHECK(hipMemcpy(ctx->dc.desc + base * 32, desc, (size_t)32 * n, hipMemcpyHostToDevice));
-    (which ? ctx->sad_prev : ctx->sad_cur)[lane] = 0;                      // caller features come without an image: no windows for smSAD / ifmSAD (until svo_gather_windows brings one)
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    if (n > 0) HIPCHECK(hipMemcpy(at.kps(side), kps, sizeof(svo_keypoint) * n, hipMemcpyHostToDevice));
+    if (n > 0 && desc) HIPCHECK(hipMemcpy(at.desc(side), desc, (size_t)32 * n, hipMemcpyHostToDevice));
+    (which ? ctx->sad.prev : ctx->sad.cur)[lane] = 0;                      // caller features come without an image: no windows for smSAD / ifmSAD (until svo_gather_windows brings one)
     {   // pyr_feats_index of the list just put (m_update_indexes, S2:103-129, as k_nms_rowsort leaves it): idx[r] = #keypoints with (int)y <= r
         // for first_row <= r < last_row, 0 elsewhere.  The reference builds it in stage 2 only, which this path skips; its row-by-row stereo
         // matchers (smDescRbR, smSAD: S3:253-256) would read a table nobody built.  Every entry is <= n whatever the caller's order is.
@@ -1691,9 +1688,9 @@ extern "C" int svo_put_features_oct(svo_ctx* ctx, int lane, int which, int side,
             int acc = 0;
             for (int r = 0; r < H; r++) { acc += cnt[(size_t)r]; if (r >= first_row && r < last_row) ri[(size_t)r] = acc; }
         }
-        if (H > 0) HIPCHECK(hipMemcpy(ctx->dc.row_index + (long long)((vl * 2 + slot) * 2 + side) * ctx->dc.max_h, ri.data(), sizeof(int32_t) * H, hipMemcpyHostToDevice));
+        if (H > 0) HIPCHECK(hipMemcpy(at.row_index(side), ri.data(), sizeof(int32_t) * H, hipMemcpyHostToDevice));
     }
-    HIPCHECK(hipMemcpy(ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, &n, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(at.n_kps(side), &n, sizeof(int), hipMemcpyHostToDevice));
     if (which == 0) {                                                      // result.detected_feats[octave] (P:171-176)
         int32_t* cnt = side ? ctx->dc.results[lane].detected_right : ctx->dc.results[lane].detected_left;
         HIPCHECK(hipMemcpy(cnt + octave, &n, sizeof(int), hipMemcpyHostToDevice));
@@ -1709,26 +1706,25 @@ extern "C" int svo_put_features(svo_ctx* ctx, int lane, int which, int side, con
 extern "C" int svo_put_matches_oct(svo_ctx* ctx, int lane, int which, int octave, const svo_dmatch* m, int n)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || n < 0 || (n > 0 && !m) || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave) || n < 0 || (n > 0 && !m)) return SVO_ERR_ARG;
     if (n > ctx->dc.max_kps) return SVO_ERR_CAPACITY;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.matches + ((long long)vl * 2 + slot) * ctx->dc.max_kps, m, sizeof(svo_dmatch) * n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->dc.n_matches + vl * 2 + slot, &n, sizeof(int), hipMemcpyHostToDevice));
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    if (n > 0) HIPCHECK(hipMemcpy(at.matches(), m, sizeof(svo_dmatch) * n, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(at.n_matches(), &n, sizeof(int), hipMemcpyHostToDevice));
     if (which == 0) HIPCHECK(hipMemcpy(ctx->dc.results[lane].stereo_matches + octave, &n, sizeof(int), hipMemcpyHostToDevice));   // P:274-276
     // matches_lr_row_index (S3:425-445) of the list just put.  The reference builds it in stage 3 only, which the precomputed-data path
     // (P:219-251) and the state loader skip: its windowed tracker (S4:517-530) then reads an index nobody built.  Here it is built from the
     // left keypoints put BEFORE the pairings (the oracle's sequential rule, ri[H] = n as there), so that ifmDescWin works on caller data.
     if (ctx->geom_ready && octave < ctx->dc.n_oct) {
         int nl = 0;
-        const long long kbase = (((long long)vl * 2 + slot) * 2 + 0) * ctx->dc.max_kps;
-        HIPCHECK(hipMemcpy(&nl, ctx->dc.n_kps + (vl * 2 + slot) * 2 + 0, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&nl, at.n_kps(0), sizeof(int), hipMemcpyDeviceToHost));
         nl = std::max(0, std::min(nl, ctx->dc.max_kps));
         bool ok = true;
         for (int i = 0; i < n && ok; i++) ok = m[i].queryIdx >= 0 && m[i].queryIdx < nl;
         if (ok) {
             std::vector<svo_keypoint> kl((size_t)nl);
-            if (nl > 0) HIPCHECK(hipMemcpy(kl.data(), ctx->dc.kps + kbase, sizeof(svo_keypoint) * nl, hipMemcpyDeviceToHost));
+            if (nl > 0) HIPCHECK(hipMemcpy(kl.data(), at.kps(0), sizeof(svo_keypoint) * nl, hipMemcpyDeviceToHost));
             const int H = std::max(0, std::min(ctx->dc.oh[octave], ctx->dc.max_h));
             std::vector<int32_t> ri((size_t)H + 1);
             int idx = 0;
@@ -1737,7 +1733,7 @@ extern "C" int svo_put_matches_oct(svo_ctx* ctx, int lane, int which, int octave
                 while (idx < n && kl[m[idx].queryIdx].y <= (float)y) idx++;               // S3:441
             }
             ri[H] = n;
-            HIPCHECK(hipMemcpy(ctx->dc.mrow_index + (long long)(vl * 2 + slot) * (ctx->dc.max_h + 1), ri.data(), sizeof(int32_t) * (H + 1), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(at.mrow_index(), ri.data(), sizeof(int32_t) * (H + 1), hipMemcpyHostToDevice));
         }
     }
     return mark_present(ctx, lane, which);
@@ -1747,12 +1743,12 @@ extern "C" int svo_put_matches(svo_ctx* ctx, int lane, int which, const svo_dmat
 extern "C" int svo_put_match_ids_oct(svo_ctx* ctx, int lane, int which, int octave, const int32_t* ids, int n)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || n < 0 || (n > 0 && !ids) || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, 0, octave) || n < 0 || (n > 0 && !ids)) return SVO_ERR_ARG;
     if (n > ctx->dc.max_kps) return SVO_ERR_CAPACITY;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->dc.n_ids + vl * 2 + slot, &n, sizeof(int), hipMemcpyHostToDevice));
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    if (n > 0) HIPCHECK(hipMemcpy(at.ids(), ids, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(at.n_ids(), &n, sizeof(int), hipMemcpyHostToDevice));
     int mx = octave == 0 ? 0 : s.last_match_id;                                                    // P:236: m_last_match_ID = 0, then the maximum over the octaves (P:243)
     for (int i = 0; i < n; i++) if (ids[i] > mx) mx = ids[i];
     s.last_match_id = mx;
@@ -1791,17 +1787,9 @@ extern "C" int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_
         ctx->last_error = msg; return SVO_ERR_ARG;
     }
     if (!frames) { ctx->last_error = "frames == NULL"; return SVO_ERR_ARG; }
-    LaneMask active, idle;
-    for (int wd = 0; wd < 2; wd++) {
-        const int n = ctx->cfg.n_lanes - wd * 64 < 0 ? 0 : (ctx->cfg.n_lanes - wd * 64 > 64 ? 64 : ctx->cfg.n_lanes - wd * 64);
-        const unsigned long long all = n == 64 ? ~0ull : ((1ull << n) - 1ull), a = lanes ? (unsigned long long)lanes[wd] : all;
-        if (a & ~all) {
-            snprintf(msg, sizeof(msg), "active[%d] = %016llx selects a lane at or above n_lanes = %d", wd, a, ctx->cfg.n_lanes);
-            ctx->last_error = msg; return SVO_ERR_ARG;
-        }
-        active.w[wd] = a; idle.w[wd] = all & ~a;
-    }
-    if (!(active.w[0] | active.w[1])) return SVO_OK;       // nobody takes part: nothing is enqueued
+    LaneMask active, idle; std::string why;
+    if (!parse_lane_mask(lanes, false, ctx->cfg.n_lanes, active, idle, why)) { ctx->last_error = why; return SVO_ERR_ARG; }      // (NULL: every lane)
+    if (!lane_any(active)) return SVO_OK;                  // nobody takes part: nothing is enqueued
     if (!ctx->geom_ready) { ctx->last_error = "no geometry yet: put or load the lists first (svo_set_params clears the geometry of the lists before it)"; return SVO_ERR_STATE; }
     DevCtx& d = ctx->dc;
     const hipStream_t st = ctx->stream;
@@ -1810,17 +1798,17 @@ extern "C" int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_
     // (the buffers before the intake: a failed allocation must not leave an upload behind)
     { const int rc = ensure_sad_buffers(ctx); if (rc) return rc; }
     note_stream(ctx);
-    struct MarkGuard { svo_ctx* c; ~MarkGuard() { mark_stream(c); } } mark_guard{ ctx };
+    MarkGuard mark_guard{ ctx };
     { const int rc = intake_frames(ctx, frames, flags, idle, true, st, ptrs, prep, &prepare); if (rc) return rc; }
     d.idle = idle;
-    struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } } idle_guard{ &d };
+    IdleGuard idle_guard{ &d };
     launch_publish_img0(d, ptrs, st);
     if (prepare) { Section sec("_stg1"); launch_prepare(prep, 2 * d.n_lanes, st); }
     if (d.fast_orb) { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }       // S1:82-83: the octave images ifmSAD reads its windows from (S4:572, 576)
     { Span s(ctx, KT_GATHER_WIN); launch_sad_patch_slot(d, which, st); }
-    for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) (which ? ctx->sad_prev : ctx->sad_cur)[l] = 1;
+    for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) (which ? ctx->sad.prev : ctx->sad.cur)[l] = 1;
     // the ring slot's reader is through once the gather is: the slot may take the next upload
-    if (ctx->up_ready && ctx->det_slot >= 0) { HIPCHECK(hipEventRecord(ctx->ev_det[ctx->det_slot], st)); ctx->ev_det_valid[ctx->det_slot] = true; }
+    HIPCHECK(release_ring_slot(ctx));
     HIPCHECK(hipGetLastError());
     return SVO_OK;
 }
@@ -1828,20 +1816,17 @@ extern "C" int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_
 extern "C" int svo_get_windows_oct(svo_ctx* ctx, int lane, int which, int side, int octave, uint8_t* win, uint8_t* flag, int cap)
 {
     if (ctx) use_device(ctx);
-    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || (which | 1) != 1 || (side | 1) != 1 || octave < 0 || octave >= ctx->dc.oct_cap) return SVO_ERR_ARG;
+    if (bad_list_args(ctx, lane, which, side, octave)) return SVO_ERR_ARG;
     LaneState s; int rc = lane_state(ctx, lane, &s); if (rc) return rc;
-    if (which ? !s.has_prev : !s.has_cur) return 0;
-    if (!ctx->dc.sad_patch || !(which ? ctx->sad_prev : ctx->sad_cur)[lane]) {
+    if (frame_absent(s, which)) return 0;
+    if (!ctx->dc.sad_patch || !(which ? ctx->sad.prev : ctx->sad.cur)[lane]) {
         char msg[160]; snprintf(msg, sizeof(msg), "lane %d: the 8 x 8 windows of its %s frame were never gathered", lane, which ? "previous" : "current");
         ctx->last_error = msg; return SVO_ERR_STATE;
     }
-    const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + octave;
-    int n = 0;
-    HIPCHECK(hipMemcpy(&n, ctx->dc.n_kps + (vl * 2 + slot) * 2 + side, sizeof(int), hipMemcpyDeviceToHost));
-    const int m = n < cap ? n : cap;
-    const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
-    if (win && m > 0) HIPCHECK(hipMemcpy(win, ctx->dc.sad_patch + base * 64, (size_t)64 * m, hipMemcpyDeviceToHost));
-    if (flag && m > 0) HIPCHECK(hipMemcpy(flag, ctx->dc.sad_flag + base, (size_t)m, hipMemcpyDeviceToHost));
+    const ListAt at = list_at(ctx, lane, s, which, octave);
+    int m; const int n = read_count(ctx, at.n_kps(side), cap, &m); if (n < 0) return n;
+    if ((rc = read_list(ctx, win, at.windows(side), m, 64))) return rc;
+    if ((rc = read_list(ctx, flag, at.flags(side), m))) return rc;
     return n;
 }
 
@@ -1923,8 +1908,8 @@ extern "C" int svo_export_frame(svo_ctx* ctx, void* dev_blob, size_t bytes)
     note_stream(ctx);
     LaneMask win_cur, win_prev; memset(&win_cur, 0, sizeof(win_cur)); memset(&win_prev, 0, sizeof(win_prev));
     for (int l = 0; l < ctx->cfg.n_lanes; l++) {
-        if (ctx->sad_cur[l]) win_cur.w[l >> 6] |= 1ull << (l & 63);
-        if (ctx->sad_prev[l] && !ctx->sad_drop[l]) win_prev.w[l >> 6] |= 1ull << (l & 63);
+        if (ctx->sad.cur[l]) win_cur.w[l >> 6] |= 1ull << (l & 63);
+        if (ctx->sad.prev[l] && !ctx->sad.drop[l]) win_prev.w[l >> 6] |= 1ull << (l & 63);
     }
     { Span s(ctx, ctx->dc.carry_win ? KT_EXPORT_WIN : KT_EXPORT); launch_export_frame(ctx->dc, (uint8_t*)dev_blob, win_cur, win_prev, ctx->stream); }
     mark_stream(ctx);
@@ -1946,7 +1931,7 @@ extern "C" int svo_import_frame(svo_ctx* ctx, const void* dev_blob, size_t bytes
     for (int l = 0; l < ctx->cfg.n_lanes; l++) ctx->imported.w[l >> 6] |= 1ull << (l & 63);
     // a record without windows leaves none behind; one with them brings them, and where it does not (an older kind of record, a frame
     // whose windows were never gathered) the device has already made the lane start afresh if the tracker in force is ifmSAD
-    for (int l = 0; l < ctx->cfg.n_lanes; l++) { ctx->sad_prev[l] = ctx->dc.carry_win ? 1 : 0; if (ctx->dc.carry_win) ctx->sad_drop[l] = 0; }
+    for (int l = 0; l < ctx->cfg.n_lanes; l++) { ctx->sad.prev[l] = ctx->dc.carry_win ? 1 : 0; if (ctx->dc.carry_win) ctx->sad.drop[l] = 0; }
     mark_stream(ctx);
     HIPCHECK(hipGetLastError());
     return SVO_OK;
@@ -1988,7 +1973,7 @@ extern "C" int svo_save_state(svo_ctx* ctx, int lane, const char* path)
         }
         // the frame's windows travel when it exists and they were gathered ("true" on the host also stands for "no such frame yet")
         const bool present = which ? s.has_prev != 0 : s.has_cur != 0;
-        S.has_win[f] = (present && ctx->dc.sad_patch && (which ? ctx->sad_prev : ctx->sad_cur)[lane]) ? 1 : 0;
+        S.has_win[f] = (present && ctx->dc.sad_patch && (which ? ctx->sad.prev : ctx->sad.cur)[lane]) ? 1 : 0;
         if (!S.has_win[f]) continue;
         S.win[f].resize((size_t)2 * n_oct);
         for (int o = 0; o < n_oct; o++)
@@ -2062,20 +2047,18 @@ extern "C" int svo_load_state(svo_ctx* ctx, int lane, const char* path)
                 if (rc) return rc;
             }
             rc = svo_put_matches_oct(ctx, lane, which, o, G.matches.data(), (int)G.matches.size()); if (rc) return rc;
-            LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
-            const int slot = slot_of(s, which), vl = lane * ctx->dc.oct_cap + o, ni = (int)G.ids.size();
-            if (ni > 0) HIPCHECK(hipMemcpy(ctx->dc.ids + ((long long)vl * 2 + slot) * ctx->dc.max_kps, G.ids.data(), sizeof(int32_t) * ni, hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(ctx->dc.n_ids + vl * 2 + slot, &ni, sizeof(int), hipMemcpyHostToDevice));
+            rc = svo_put_match_ids_oct(ctx, lane, which, o, G.ids.data(), (int)G.ids.size()); if (rc) return rc;   // (last_match_id: the file's tail, below)
             if (!S.has_win[f]) continue;
+            LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
+            const ListAt at = list_at(ctx, lane, s, which, o);
             for (int side = 0; side < 2; side++) {
                 const svo_state::Windows& Wn = S.win[f][(size_t)o * 2 + side];
-                const long long base = (((long long)vl * 2 + slot) * 2 + side) * ctx->dc.max_kps;
                 if (Wn.flag.empty()) continue;
-                HIPCHECK(hipMemcpy(ctx->dc.sad_flag + base, Wn.flag.data(), Wn.flag.size(), hipMemcpyHostToDevice));
-                HIPCHECK(hipMemcpy(ctx->dc.sad_patch + base * 64, Wn.win.data(), Wn.win.size(), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(at.flags(side), Wn.flag.data(), Wn.flag.size(), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(at.windows(side), Wn.win.data(), Wn.win.size(), hipMemcpyHostToDevice));
             }
         }
-        (which ? ctx->sad_prev : ctx->sad_cur)[lane] = S.has_win[f];                      // (svo_put_features_oct cleared it: lists without an image)
+        (which ? ctx->sad.prev : ctx->sad.cur)[lane] = S.has_win[f];                      // (svo_put_features_oct cleared it: lists without an image)
     }
     LaneState s; rc = lane_state(ctx, lane, &s); if (rc) return rc;
     s.reset_ids = S.m_reset; s.num_tracked_last_kf = (int)S.tail[1]; s.last_match_id = (int)S.tail[3]; s.last_kf_max_id = (int)S.tail[4];

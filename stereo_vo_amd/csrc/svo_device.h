@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/svo_hip.h"
+#include "frame_call.hpp"      // LaneMask (one bit per lane): the host decides with it, the kernels take it as an argument
 
 #define SVO_EDGE 31
 #define SVO_RANSAC_HYP 1000         // sample schedule of one F-matrix RANSAC (oracle: RANSAC_MAX_HYP): minimal samples of seven pairs
@@ -89,9 +90,6 @@ struct LaneState {
     int num_tracked_last_kf;   // m_num_tracked_pairs_from_last_kf (S4:743-751)
     int prev_no_win;      // the previous frame came in through a hand-over record without the SAD matchers' windows (k_handover.hip); cleared by the next shift
 };
-
-// one bit per lane: bit l of w[l >> 6] (kernel argument of k_begin_frame and the hand-over kernels, and DevCtx.idle)
-struct LaneMask { unsigned long long w[(SVO_MAX_LANES + 63) / 64]; };
 
 // Octaves: in the FAST+ORB mode (stage2_detect.cpp:502-515) the reference works on nOctaves x1/2 images per eye and
 // keeps one feature / pairing / track list per octave.  Every per-lane list below is therefore indexed by the
