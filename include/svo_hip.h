@@ -311,6 +311,11 @@ int svo_set_this_frame_as_kf(svo_ctx* ctx, int lane);   /* H:675-683; SVO_ERR_ST
  * load caller-supplied features / pairings into a lane's current (which=0) or previous (which=1) frame. */
 int svo_put_features(svo_ctx* ctx, int lane, int which, int side, const svo_keypoint* kps, const uint8_t* desc, int n,
                      int img_w, int img_h);
+/* (Coordinates are taken as they come, as in the reference: none is checked against img_w x img_h.  One claim depends on them: stage 4's
+ * inlier counts on the matrix cores -- contexts of more than 8 lane-octaves -- are the reference's bit for bit for keypoints with
+ * |x| <= img_w and |y| <= img_h (proven with a margin up to about 1.6 times that; lists reaching from -1 to 4 times the image size are
+ * tested and agree, without a proof).  A caller whose coordinates lie outside the image declares an img_w x img_h that covers them;
+ * contexts of up to 8 lane-octaves evaluate the reference's own expression and need no such premise.) */
 /* (svo_put_matches also builds the list's matches_lr_row_index (S3:425-445) from the LEFT keypoints put before it: the reference builds that
  * index in stage 3 only, which this path skips (P:219-251), and its windowed tracker (S4:517-530) would read an index nobody built.) */
 int svo_put_matches(svo_ctx* ctx, int lane, int which, const svo_dmatch* m, int n);

@@ -1180,7 +1180,13 @@ __device__ __forceinline__ void store_model(const DevCtx& c, int vl, int side, i
     for (int j = 0; j < 9; j++) F[j] = Fv[j];
     c.rs_k[o] = sample;
     // guards of the matrix-core line evaluation in k_ransac_count (see there): E bounds how far its numerators can be from
-    // the oracle's operation order, given coordinates inside the image; a side is trusted when |l| >= 2^28 E
+    // the oracle's operation order, given coordinates inside the image; a side is trusted when |l| >= 2^28 E.
+    // "Inside the image" (|x| <= W, |y| <= H of the size the lists were put with) is a premise nobody checks: svo_put_features takes any
+    // coordinates.  Coordinates k times as large make the shift up to k^2 E; what the 64 u here has in hand over the 30 u of the derivation
+    // and the band's 2^-26 over the 2 x 2^-28 it has to cover carries the proof to about 1.6 times the image size, no further.  Lists
+    // from -1 to 4 times the image size (tests/ransac_scenes.py: far_scene, pairs at error exactly 1 and a hair beyond) give the oracle's
+    // counts all the same -- integer coordinates round far less than the worst case --, which is an observation, not a bound:
+    // include/svo_hip.h tells a caller with such coordinates to declare the size that covers them.
     double aF[9];
 #pragma unroll
     for (int j = 0; j < 9; j++) aF[j] = fabs(Fv[j]);

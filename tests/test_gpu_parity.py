@@ -4,12 +4,16 @@ Bar (BASELINE.json north_star): keypoints, descriptors, pairings and tracked pai
 1e-4 rad / 1e-3 m.  Every test here needs a real MI355X: run with `pytest -m gpu`."""
 import ctypes as C
 import os
+import sys
 import numpy as np
 import pytest
 
 from stereo_vo_amd import hip
 from stereo_vo_amd.abi import StereoCamera, north_star_params, keypoint_dtype, dmatch_dtype, index_pair_dtype
 from stereo_vo_amd.synth import SyntheticStereoWorld
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ransac_scenes import line_scene                            # noqa: E402  (the hand-built stage-4 lists live there, with the scenes of test_gpu_ransac_forms.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -108,7 +112,8 @@ def test_every_ransac_kernel_form_gives_the_oracle_models(golden_dir, monkeypatc
     matrices, hence same inlier counts, masks, tracked pairs and stage-4 counters, whichever form the lane count selects.
     Likewise the inlier counts: sixteen hypotheses per block on the VALU (14), matrix-core tiles of 4 hypotheses x 4 line
     components (52), of 16 hypotheses x 16 pairs with the numerator on the matrix cores too (53: the many-lane default), and
-    the latter with every verdict replayed through the oracle's own expression (54)."""
+    the latter with every verdict replayed through the oracle's own expression (54).  Well-behaved frames only: the inputs built to reach
+    the screen's band, its guards, the tile tails and the chunked schedule are in tests/test_gpu_ransac_forms.py."""
     monkeypatch.setenv("SVO_DEBUG_MODE", mode)
     g, cam, p = load_small(golden_dir)
     ctx = hip.Context(n_lanes=1, max_w=int(g["W"]), max_h=int(g["H"]), max_kps=1024, max_cand=1 << 15)
@@ -342,39 +347,6 @@ def test_few_candidates_reach_the_sampler_edge_cases(golden_dir, ifm_method):
     assert 7 in seen and any(8 <= n <= 14 for n in seen) and any(n < 7 for n in seen) and any(n >= 15 for n in seen), sorted(seen)
     # below 14 points LMedS's median is one of the seven fitted residuals: the mask is the sample (seven, under S4:205's eight); at 14 it can pass
     assert all(7 <= l <= 9 and 7 <= r <= 9 for n, l, r in lmeds_inliers if n <= 13) and len(lmeds_inliers) >= 6, lmeds_inliers
-
-
-def line_scene(n, ys, d, outlier_frac, seed, W=640, H=480, disp=20, off_line=True):
-    """Stage-4 input lists built by hand: n pairings whose keypoints sit on the rows `ys` at INTEGER x; the current frame is the previous
-    one shifted by d pixels in x (pure translation: every correspondence satisfies F = [t]_x exactly); a fraction of the pairings is
-    moved somewhere else in the current frame (outliers).  Every keypoint has a random descriptor of its own, so the brute-force tracker
-    pairs pairing k of the previous frame with its own continuation."""
-    rng = np.random.RandomState(seed)
-    per = max(1, n // len(ys))
-    pts = []
-    for y in ys:
-        xs = rng.choice(np.arange(60, W - 60), per, replace=False)
-        pts += [(float(x), float(y)) for x in np.sort(xs)]
-    pts = np.array(pts, np.float32)
-    n = len(pts)
-
-    def kps(xy):
-        k = np.zeros(len(xy), keypoint_dtype)
-        k["x"], k["y"], k["size"], k["response"], k["class_id"] = xy[:, 0], xy[:, 1], 31.0, 1.0, -1
-        return k
-    desc, descr = rng.randint(0, 256, (n, 32)).astype(np.uint8), rng.randint(0, 256, (n, 32)).astype(np.uint8)
-    m = np.zeros(n, dmatch_dtype); m["queryIdx"] = np.arange(n); m["trainIdx"] = np.arange(n); m["distance"] = 10.0
-    cur = pts + np.array([d, 0], np.float32)
-    out = rng.rand(n) < outlier_frac
-    if off_line:
-        cur[out, 1] = rng.randint(40, H - 40, int(out.sum())).astype(np.float32); cur[out, 0] = rng.randint(60, W - 60, int(out.sum())).astype(np.float32)
-    else:
-        yi = np.searchsorted(np.array(ys, np.float32), pts[:, 1])
-        cur[out, 1] = np.array(ys, np.float32)[(yi[out] + 1) % len(ys)]
-    order = np.lexsort((cur[:, 0], cur[:, 1]))                             # the current lists are row-sorted too
-    curL = cur[order]
-    sh = np.array([disp, 0], np.float32)
-    return dict(pkl=kps(pts), pkr=kps(pts - sh), pdl=desc, pdr=descr, pm=m, ckl=kps(curL), ckr=kps(curL - sh), cdl=desc[order], cdr=descr[order], cm=m.copy(), W=W, H=H)
 
 
 def test_collinear_point_sets_continue_the_sampler_past_its_table(golden_dir):
