@@ -107,7 +107,7 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask d
             c.cand_cnt[t * SVO_CNT_STRIDE] = 0; c.lvl_n[t] = 0;
             // this frame's FAST threshold per (image, level): the speculated one when there is one (ORB mode only; debug
             // mode 12 switches the speculation off), never below the caller's threshold
-            const uint32_t dyn = (c.fast_orb || c.debug_mode == 12) ? 0u : c.fast_th_dyn[t];
+            const uint32_t dyn = (c.fast_orb || c.debug_mode == DBG_NO_SPEC_FAST_TH) ? 0u : c.fast_th_dyn[t];
             c.fast_th_used[t] = max((uint32_t)c.fast_th, min(dyn, 250u));
             c.redo_flag[t] = 0;
         }
@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
     // one L2 they are fetched once, through eight they were fetched twice (measured 940 MB -> for 475 MB of source).
     const int ntx = (d.w + RZ_W - 1) / RZ_W, nty = (d.h + RZ_H - 1) / RZ_H, per_img = ntx * nty;
     const uint32_t slot = blockIdx.x >> 3;
-    const uint32_t work = c.debug_mode == 8 ? blockIdx.x : (((slot / RZ_CHUNK) * 8 + (blockIdx.x & 7)) * RZ_CHUNK + slot % RZ_CHUNK);
+    const uint32_t work = c.debug_mode == DBG_LINEAR_TILES ? blockIdx.x : (((slot / RZ_CHUNK) * 8 + (blockIdx.x & 7)) * RZ_CHUNK + slot % RZ_CHUNK);
     const int img = (int)fastdiv(work, div_img);
     if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const int tt = (int)work - img * per_img, tby = (int)fastdiv((uint32_t)tt, div_ntx), tbx = tt - tby * ntx;
@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
         yw[tid - RZ_W] = (uint32_t)yf[y];                                                          // b0 | b1 << 16
         yr[tid - RZ_W] = (uint32_t)(yi[y] - sy0);
     }
-    if (c.debug_mode == 5) { /* ablation: no staging */ }
+    if (c.debug_mode == DBG_RESIZE_NO_STAGING) { /* ablation: no staging */ }
     else if ((spitch & 15) == 0) {
         // LDS-DMA: chunk i = (row i / 11, piece i % 11) lands at LDS byte 16 i.  The source base may sit at any byte alignment
         // (tools/ubench/glds_align.hip); with the origin 16-aligned in x and a pitch that is a multiple of 16 no chunk
@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
     }
     __syncthreads();
     const int gx = (tid & 31) * 4, x4 = dx0 + gx;                       // 4 adjacent pixels per row, 4 rows per thread
-    if (x4 >= d.w || c.debug_mode == 6) return;
+    if (x4 >= d.w || c.debug_mode == DBG_RESIZE_NO_BLEND) return;
     // The taps of the thread's 4 adjacent pixels lie within 8 source bytes (3 x 1.2 px apart + the second tap): per source
     // row ONE 12-byte fetch from the aligned dword of the first tap, funnel-shifted to an 8-byte window starting at that
     // tap, serves all four -- LDS reads were what bounded this kernel (16 dword gathers per pixel quad before).
@@ -301,7 +301,7 @@ __global__ void __launch_bounds__(256) k_resize(DevCtx c, int level, FastDiv div
         }
         const rz_u16x2 p01 = __builtin_bit_cast(rz_u16x2, v[0] | (v[1] << 16)) >> 2, p23 = __builtin_bit_cast(rz_u16x2, v[2] | (v[3] << 16)) >> 2;
         const uint32_t out = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, p23), __builtin_bit_cast(uint32_t, p01), 0x06040200u);
-        if (c.debug_mode == 7 && out != 0x12345678u) continue;
+        if (c.debug_mode == DBG_RESIZE_NO_STORE && out != 0x12345678u) continue;
         *(uint32_t*)(dst + (long long)y * d.pitch + x4) = out;   // pitch is a multiple of 64: the tail of the last dword is padding
     }
 }
@@ -497,7 +497,7 @@ __device__ __forceinline__ void fast_compute(const DevCtx& c, uint8_t* tile, uin
 {
     uint32_t* out_keys = (uint32_t*)tile;
     const int tid = threadIdx.x;
-    if (c.debug_mode == 1) return;
+    if (c.debug_mode == DBG_FAST_STOP_STAGED) return;
     // ---- (1) packed cardinal test: thread -> group column gq (positions q = 4 gq .. 4 gq + 3), score rows 8 rb .. 8 rb + 7 ----
     const uint32_t th = (uint32_t)th_fast;
     const u16x2 t2h = { (unsigned short)(th << 8), (unsigned short)(th << 8) };
@@ -572,7 +572,7 @@ __device__ __forceinline__ void fast_compute(const DevCtx& c, uint8_t* tile, uin
     __syncthreads();
     const int ns_all = (int)s_count, ns = min(ns_all, FT_LIST_CAP);
     const bool overflow = ns_all > FT_LIST_CAP;                              // block-uniform
-    if (c.debug_mode == 2) return;
+    if (c.debug_mode == DBG_FAST_STOP_COMPACTED) return;
     // ---- (2) score on the survivors only ----
     auto win_off = [&](int e) -> int { return (e >> 6) * FT_LW + (e & 63) + (3 * FT_LW + 4); };
     for (int i = tid; i < ns; i += FT_NT) {
@@ -586,7 +586,7 @@ __device__ __forceinline__ void fast_compute(const DevCtx& c, uint8_t* tile, uin
         }
     }
     __syncthreads();
-    if (c.debug_mode == 3) return;
+    if (c.debug_mode == DBG_FAST_STOP_SCORED) return;
     // ---- (3) 3x3 NMS on the listed interior positions; one global atomic per tile ----
     auto nms_round = [&](bool has, int e) {
         bool keep = false; uint32_t key = 0;
@@ -631,7 +631,7 @@ __device__ __forceinline__ void fast_compute(const DevCtx& c, uint8_t* tile, uin
     // stalls one wave per tile instead of the whole workgroup
     if (tid < 64) {
         const unsigned nout = s_nout;
-        if (nout != 0 && c.debug_mode != 4) {
+        if (nout != 0 && c.debug_mode != DBG_FAST_NO_PUBLISH) {
             const LevelGeom& g = c.lv[level];
             unsigned gbase = 0;
             if (tid == 0) gbase = atomicAdd(&c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE], nout);
@@ -661,7 +661,7 @@ __global__ void __launch_bounds__(FT_NT) __attribute__((amdgpu_waves_per_eu(8, 8
     // it comes from a table (svo_api.hip fills it with the level geometry), next to the image's eight thresholds and its
     // level-0 pointer -- one round of scalar loads after the kernel arguments.
     const uint32_t slot = blockIdx.x >> 3;
-    const uint32_t work = c.debug_mode == 8 ? blockIdx.x : (((slot / FT_CHUNK) * 8 + (blockIdx.x & 7)) * FT_CHUNK + slot % FT_CHUNK);
+    const uint32_t work = c.debug_mode == DBG_LINEAR_TILES ? blockIdx.x : (((slot / FT_CHUNK) * 8 + (blockIdx.x & 7)) * FT_CHUNK + slot % FT_CHUNK);
     const int img = (int)fastdiv(work, c.div_tiles), tile_id = (int)work - img * c.n_tiles;
     if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const uint4 e = c.fast_tiles[tile_id];                  // x0 | y0 << 16, w | h << 16, level | pitch << 8, level offset in the pyramid
@@ -825,7 +825,7 @@ __device__ __forceinline__ int select_block(const DevCtx& c, int redo_pass, int 
         for (int u = 0; u < 8; u++) if (base + u * 512 < nc) atomicAdd(&hist[k[u] >> 24], 1u);
     }
     __syncthreads();
-    if (c.debug_mode == 31) return 0;
+    if (c.debug_mode == DBG_SELECT_STOP_HIST) return 0;
     unsigned prefix = 0, mask = 0, need = K;
     {
         const int mine = tid < 256 ? (int)hist[255 - tid] : 0;         // bins in DESCENDING order: thread t owns bin 255 - t
@@ -993,7 +993,7 @@ __device__ __forceinline__ void rank_block(const DevCtx& c, int img, int level, 
         lmn = min(lmn, (unsigned)__shfl_xor((int)lmn, o, 64)); lmx = max(lmx, (unsigned)__shfl_xor((int)lmx, o, 64));
         lmnp = min(lmnp, (unsigned)__shfl_xor((int)lmnp, o, 64)); lnp += __shfl_xor(lnp, o, 64);
     }
-    if (c.debug_mode == 41) return;
+    if (c.debug_mode == DBG_SSORT_STOP_RANGE) return;
     if ((tid & 63) == 0) { atomicMin(&s_mn, lmn); atomicMax(&s_mx, lmx); atomicMin(&s_mnp, lmnp); atomicAdd(&s_np, lnp); }
     __syncthreads();
     const unsigned mn = s_np >= g.quota ? s_mnp : s_mn;
@@ -1009,7 +1009,7 @@ __device__ __forceinline__ void rank_block(const DevCtx& c, int img, int level, 
         }
     }
     __syncthreads();
-    if (c.debug_mode == 42) return;
+    if (c.debug_mode == DBG_SSORT_STOP_BUCKETS) return;
     int run = 0;
     for (int base = 0; base < SS_NB; base += 512) {
         int tot;
@@ -1018,11 +1018,11 @@ __device__ __forceinline__ void rank_block(const DevCtx& c, int img, int level, 
         run += tot;
         __syncthreads();
     }
-    if (c.debug_mode == 43) return;
+    if (c.debug_mode == DBG_SSORT_STOP_OFFSETS) return;
 #pragma unroll
     for (int it = 0; it < SEL_MAX / 512; it++) { const int i = tid + it * 512; if (i < K) tmp[off[myb[it]] + mypos[it]] = mykey[it]; }
     __syncthreads();
-    if (c.debug_mode == 44) return;
+    if (c.debug_mode == DBG_SSORT_STOP_SCATTER) return;
 #pragma unroll
     for (int it = 0; it < SEL_MAX / 512; it++) {
         const int i = tid + it * 512;
@@ -1035,7 +1035,7 @@ __device__ __forceinline__ void rank_block(const DevCtx& c, int img, int level, 
         }
     }
     __syncthreads();
-    if (c.debug_mode == 45) return;
+    if (c.debug_mode == DBG_SSORT_STOP_RANK) return;
     const int nout = min(K, g.quota);
     for (int i = tid; i < nout; i += blockDim.x) {
         const unsigned long long k = keys[i];
@@ -1151,7 +1151,7 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
     __shared__ __attribute__((aligned(16))) uint4 s_gh[TL ? 3 * 64 : 1], s_gv[TL ? 3 * 64 : 1];
     // an idle lane's blocks (svo_process_lanes) leave ahead of the tables and the barrier: the test needs the block's image only
     if (c.idle.w[0] | c.idle.w[1]) {
-        const int img_b = c.debug_mode == 8 ? (int)(blockIdx.x / gx_div.d) : (int)(fastdiv(blockIdx.x >> 3, gx_div) * 8 + (blockIdx.x & 7));
+        const int img_b = c.debug_mode == DBG_LINEAR_TILES ? (int)(blockIdx.x / gx_div.d) : (int)(fastdiv(blockIdx.x >> 3, gx_div) * 8 + (blockIdx.x & 7));
         if (img_b < c.n_img && lane_idle(c, img_b >> 1)) return;
     }
     s_pat[threadIdx.x] = g_brief_patf[threadIdx.x]; s_disc_m[threadIdx.x] = g_disc_m[threadIdx.x]; s_disc_x[threadIdx.x] = g_disc_x[threadIdx.x];
@@ -1165,7 +1165,7 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
     // two 128-byte lines and neighbouring keypoints share most of them; with an image's keypoints spread over eight
     // L2s each line was fetched again per XCD, through one L2 the image's pyramid (3.8 MB < 4 MB) is fetched about once.
     int img, bx;
-    if (c.debug_mode == 8) { img = blockIdx.x / gx_div.d; bx = blockIdx.x - img * gx_div.d; }
+    if (c.debug_mode == DBG_LINEAR_TILES) { img = blockIdx.x / gx_div.d; bx = blockIdx.x - img * gx_div.d; }
     else { const uint32_t r = blockIdx.x >> 3, grp = fastdiv(r, gx_div); bx = (int)(r - grp * gx_div.d); img = (int)(grp * 8 + (blockIdx.x & 7)); }
     if (img >= c.n_img) return;
     // pre != 0: the NMS ran first (k_nms_rowsort, pre mode); work item = final keypoint fi of the image's current list, which
@@ -1254,7 +1254,7 @@ __global__ void __launch_bounds__(NW * 64) k_describe(DevCtx c, FastDiv gx_div, 
             const int m10 = wave_sum_uniform((int)m10u - 15 * msum);
             m01 = wave_sum_uniform(m01);
             float angle, sn, cs;
-            if (c.debug_mode == 46) { angle = (float)(m10 & 255); sn = (float)(m01 & 255) * 0.001f; cs = 1.f - sn; }      /* ablation: no trigonometry (results differ) */
+            if (c.debug_mode == DBG_DESCRIBE_NO_TRIG) { angle = (float)(m10 & 255); sn = (float)(m01 & 255) * 0.001f; cs = 1.f - sn; }      /* ablation: no trigonometry (results differ) */
             else { angle = atan2_deg((float)m01, (float)m10); sincos_f32(angle * 0.017453292f, sn, cs); }
             // ---- C: horizontal pass on the matrix cores: S[mt][nt] = H - 32768 for window rows 16 mt + 4 q + r, blurred columns 16 nt + n ----
             dp_v4i S[3][3];
@@ -1480,7 +1480,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
         }
     }
     __syncthreads();
-    if (c.debug_mode == 21) return;
+    if (c.debug_mode == DBG_NMS_STOP_KEYS) return;
     int P = 64; while (P < n) P <<= 1;
     if (do_nms && !c.fast_orb) {
         // (response desc, raw index asc) order by bucket sort: buckets over the order-preserving bit pattern of the
@@ -1556,7 +1556,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
         }
         __syncthreads();
     } else if (do_nms) bitonic_sort_lds<true>(keys, P);
-    if (c.debug_mode == 22) return;
+    if (c.debug_mode == DBG_NMS_STOP_SORT) return;
     auto slot_of = [&](int raw_i) { int l = l_first; for (int q = l_first + 1; q < SVO_MAX_LEVELS; q++) if (q < l_last && raw_i >= lvl_base[q]) l = q; return c.lv[l].slot_off + (raw_i - lvl_base[l]); };
     const int W = c.ow[oct], H = c.oh[oct], num_out_points = c.kps_to_detect[oct];
     int nacc = 0;
@@ -1617,9 +1617,9 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
             cellxy[i] = (ux < glx && uy < gly) ? (((uint32_t)ux << 16) | (uint32_t)uy) : 0xFFFFFFFFu;
         }
         __syncthreads();
-        if (c.debug_mode == 26) return;
+        if (c.debug_mode == DBG_NMS_STOP_CELLS) return;
         grid_nms_block<(NI > 8 ? 0 : NI)>(n, gly, cellxy, hkey, hval, NS_HASH, state, flag);      // sixteen keys per thread: the form without the register cache
-        if (c.debug_mode == 23) return;
+        if (c.debug_mode == DBG_NMS_STOP_GRID) return;
         // survivors in rank order, at most num_out_points of them (S2:342)
         for (int base = 0; base < n && nacc < num_out_points; base += blockDim.x) {
             const int i = base + tid;
@@ -1648,7 +1648,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
         nacc = n;
         __syncthreads();
     }
-    if (c.debug_mode == 24) return;
+    if (c.debug_mode == DBG_NMS_STOP_ACCEPT) return;
     if (nacc > c.max_kps) { nacc = c.max_kps; if (tid == 0) { atomicOr(&c.status[lane_id], SVO_ST_KPS_OVERFLOW); atomicOr(&c.results[lane_id].status, (int)SVO_ST_KPS_OVERFLOW); } }
     // row sort: (pt.y asc, survivor rank asc)
     __syncthreads();
@@ -1704,7 +1704,7 @@ __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int 
         P = 64; while (P < nacc) P <<= 1;
         bitonic_sort_lds<false>(keys, P);
     }
-    if (c.debug_mode == 25) return;
+    if (c.debug_mode == DBG_NMS_STOP_ROWSORT) return;
     const int cur = 1 - c.lane[lane_id].prev_slot;
     const long long ob = feat_base(c, vl, cur, side);
     for (int i = tid; i < nacc; i += blockDim.x) {
@@ -2276,16 +2276,12 @@ void launch_select(const DevCtx& c, hipStream_t st)
     else hipLaunchKernelGGL(k_select_sort<2048>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)2048 * 16, st, c);
 }
 
-void launch_describe(const DevCtx& c, int pre, hipStream_t st)
+void launch_describe(const DevCtx& c, const Knobs& k, int pre, hipStream_t st)
 {
     if (c.n_slots <= 0) return;
     // keypoints per wave: SVO_DESC_KPW overrides the default for an A/B (1 = a wave per keypoint, as rounds 1-3)
-    static int kpw = 0;
-    if (!kpw) { const char* e = getenv("SVO_DESC_KPW"); const int v = e ? atoi(e) : 0; kpw = (v >= 1 && v <= 64) ? v : 8; }       // <= 64: a wave keeps its work items one per lane
-    const int per = 4 * kpw, gx = (c.n_slots + per - 1) / per, img8 = (c.n_img + 7) / 8 * 8;
-    static int tl = -1;
-    if (tl < 0) { const char* e = getenv("SVO_DESC_TL"); tl = (e && atoi(e) == 0) ? 0 : 1; }       // default: operands in LDS (0.204 -> 0.198 ms at 64 lanes, profiles/r04i); SVO_DESC_TL=0 keeps them in registers
-    if (tl) hipLaunchKernelGGL((k_describe<4, true>), dim3((unsigned)((long long)gx * img8)), dim3(256), 0, st, c, make_fastdiv((uint32_t)gx), (pre && !c.fast_orb) ? 1 : 0, kpw);
+    const int kpw = k.desc_kpw, per = 4 * kpw, gx = (c.n_slots + per - 1) / per, img8 = (c.n_img + 7) / 8 * 8;
+    if (k.desc_tl) hipLaunchKernelGGL((k_describe<4, true>), dim3((unsigned)((long long)gx * img8)), dim3(256), 0, st, c, make_fastdiv((uint32_t)gx), (pre && !c.fast_orb) ? 1 : 0, kpw);
     else hipLaunchKernelGGL((k_describe<4, false>), dim3((unsigned)((long long)gx * img8)), dim3(256), 0, st, c, make_fastdiv((uint32_t)gx), (pre && !c.fast_orb) ? 1 : 0, kpw);
 }
 
@@ -2348,14 +2344,12 @@ hipError_t configure_nms_rowsort(const DevCtx& c)
     return svo_raise_dyn_smem((const void*)k_nms_rowsort<4>, nms_rowsort_smem(pmax > 4096 ? 4096 : pmax));
 }
 
-void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, hipStream_t st)
+void launch_nms_rowsort(const DevCtx& c, const Knobs& k, int do_nms, int min_distance, int pre, hipStream_t st)
 {
     const int pmax = nms_pmax(c);
     // threads per image: every phase strides by blockDim.x and a thread holds NI = 4 keys, so lists of up to 2048 keys also run on 512
     // threads (8 waves instead of 16 to find room for on a CU that the detector's tiles fill); SVO_NMS_NT = 512 / 1024 for an A/B
-    static int nt_knob = -1;
-    if (nt_knob < 0) { const char* e = getenv("SVO_NMS_NT"); nt_knob = e ? atoi(e) : 0; }
-    const int nt = (pmax <= 2048 && nt_knob == 512) ? 512 : 1024;
+    const int nt = (pmax <= 2048 && k.nms_nt == 512) ? 512 : 1024;
     const dim3 grid(c.n_img, c.n_oct);
     const size_t lds = nms_rowsort_smem(pmax);
     const int mode = c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, pre_pass = (pre && !c.fast_orb) ? 1 : 0;

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <map>
 #include <utility>
+#include <type_traits>
 #include "svo_device.h"
 #include "svo_kernels.h"
 #include <float.h>
@@ -427,7 +428,7 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
 #pragma unroll
     for (int i = 0; i < GN_NSUM; i++) acc[i] = 0;
     for (int m = tid; m < T; m += blockDim.x) {
-        if (!mask[m] || dbg == 60) continue;
+        if (!mask[m] || dbg == DBG_GN_NO_TRACK_LOOP) continue;
         double J[4][6], ri[4];
         if (!gn_point(cam, sh.R, small_angle, t1, t2, t3, lmk, obs, m, J, ri)) continue;          // S5:322
         const double s = ri[0] * ri[0] + ri[1] * ri[1] + ri[2] * ri[2] + ri[3] * ri[3];
@@ -463,7 +464,7 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
         for (int i = 0; i < 36; i++) bad = bad || isnan(H[i]) || isinf(H[i]);
         int ok;
         if (bad) ok = 0;
-        else if (dbg == 61 || dbg == 63) ok = 1;
+        else if (dbg == DBG_GN_NO_SOLVE || dbg == DBG_GN_NO_SOLVE_NO_ROT) ok = 1;
         else if (dmax > 0 && chol6(H, g, dmax, x)) ok = 1;
         else { ok = solve_sym6_from_sums(sh.tot, sh.step);                      // rank-deficient: pseudo-inverse path (out of line)
 #pragma unroll
@@ -472,7 +473,7 @@ __device__ void eval_rgn(const GNParams& P, const svo_stereo_camera& cam, int T,
         sh.cost = sh.tot[27];
 #pragma unroll
         for (int a = 0; a < 6; a++) { sh.step[a] = x[a]; sh.delta[a] += x[a]; }
-        if (ok && dbg != 62 && dbg != 63) { double d6[6]; for (int a = 0; a < 6; a++) d6[a] = sh.delta[a]; rodrigues_with_derivs(d6, sh.R); }
+        if (ok && dbg != DBG_GN_NO_ROT_UPDATE && dbg != DBG_GN_NO_SOLVE_NO_ROT) { double d6[6]; for (int a = 0; a < 6; a++) d6[a] = sh.delta[a]; rodrigues_with_derivs(d6, sh.R); }
     }
     __syncthreads();
 }
@@ -536,7 +537,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         keys[i] = ((unsigned long long)ord32(l1.response) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
     }
     __threadfence_block();
-    if (c.debug_mode == 64) return;                                            // timing probes 64-67: the set-up, phase by phase (tests/dev/gn_breakdown.py)
+    if (c.debug_mode == DBG_GN_STOP_GATHER) return;                                            // timing probes 64-67: the set-up, phase by phase (tests/dev/gn_breakdown.py)
     // ---- m_non_max_sup mask overload on the previous-left coordinates (S5:465-474 -> S2:225-283); cap = T ----
     if (!big) {
         // at most GN_LCAP keys, a few hundred as a rule: every key counts the keys above it (the keys are unique, so the counts are the descending ranks).
@@ -561,7 +562,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         for (int i = tid; i < T; i += blockDim.x) keys[i] = sorted[i];
         __syncthreads();
     } else bitonic_sort_lds<true>(keys, Pn);
-    if (c.debug_mode == 65) return;
+    if (c.debug_mode == DBG_GN_STOP_SORT) return;
     {
         const unsigned cell = (unsigned)((double)P.min_distance / 2.0);
         const float inv = 1.0f / (float)cell;
@@ -581,7 +582,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         __syncthreads();
     }
     int n_non_masked = sh.n_non_masked;
-    if (c.debug_mode == 66) return;
+    if (c.debug_mode == DBG_GN_STOP_MASK) return;
     if (n_non_masked < 8) { if (tid == 0) { res.valid = 0; res.n_residual = 0; res.n_outliers = 0; } return; }       // S5:521-526
     // ---- triangulation (S5:529-544) ----
     const double cul = cam.l_cx, cvl = cam.l_cy, fl = cam.l_fx, cur_ = cam.r_cx, fr = cam.r_fx, baseline = cam.baseline;
@@ -594,7 +595,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         }
     };
     triangulate();
-    if (c.debug_mode == 67) return;
+    if (c.debug_mode == DBG_GN_STOP_TRIANGULATE) return;
     if (tid == 0) {
         double d6[6] = { 0, 0, 0, 0, 0, 0 };
         if (P.use_custom_initial_pose) { for (int k = 0; k < 6; k++) d6[k] = P.init[k]; }                            // S5:504-505
@@ -604,14 +605,14 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
     }
     __threadfence_block();
     __syncthreads();
-    if (c.debug_mode == 10) return;
+    if (c.debug_mode == DBG_GN_STOP_SETUP) return;
     double pCost = 0, cCost = 0; bool done = false, abort_ = false;
     unsigned timesInc = 0; int num_it = 0, num_it_final = 0, err_code = res.error_code;
     bool first = true;
     // Both phases run through ONE copy of the iteration body (a second inlined copy of eval_rgn made the kernel ~100 KB of code, more
     // than the instruction cache holds: every iteration then fetched its code again).  phase 0 = S5:549-598, phase 1 = S5:650-700;
     // timesInc, pCost, cCost carry over from one to the other.
-    const bool cap1 = (c.debug_mode == 11) || (c.debug_mode >= 60 && c.debug_mode <= 63);
+    const bool cap1 = c.debug_mode == DBG_GN_ONE_ITER || debug_mode_gn_loop_ablation(c.debug_mode);
     int n_res = 0, n_out = 0;
     for (int phase = 0; phase < 2; phase++) {
         const int limit = phase ? P.max_iters : P.initial_max_iters;
@@ -711,32 +712,30 @@ hipError_t svo_raise_dyn_smem(const void* kernel, size_t bytes)
     return e;
 }
 
+// Every instantiation gets the limit.  A plain list and not gn_for_threads below: the three are first named here, ascending, and the
+// order of first naming is the order in which the compiler emits them into the code object (the ladder would name them descending).
 hipError_t configure_gauss_newton(int pmax)
 {
-    const void* fn[3] = { (const void*)k_gauss_newton<256>, (const void*)k_gauss_newton<384>, (const void*)k_gauss_newton<512> };
-    const int nt[3] = { 256, 384, 512 };
-    for (int i = 0; i < 3; i++) {
-        const hipError_t e = svo_raise_dyn_smem(fn[i], gn_smem(pmax)); (void)nt;
+    for (const void* fn : { (const void*)k_gauss_newton<256>, (const void*)k_gauss_newton<384>, (const void*)k_gauss_newton<512> }) {
+        const hipError_t e = svo_raise_dyn_smem(fn, gn_smem(pmax));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
 // threads per lane: one pass of the per-track loop covers that many tracks per iteration (config 2 tracks ~290: 256 threads walk
-// the loop twice); SVO_GN_NT = 256 / 384 / 512 overrides the default for an A/B
-static int gn_threads()
+// the loop twice); SVO_GN_NT = 256 / 384 / 512 overrides the default for an A/B (Knobs.gn_nt).  The one ladder over the three
+// instantiations of k_gauss_newton and k_pose_covariance: f(std::integral_constant<int, nt>)
+template <class F> static void gn_for_threads(int nt, F f)
 {
-    static int nt = 0;
-    if (!nt) { const char* e = getenv("SVO_GN_NT"); const int v = e ? atoi(e) : 0; nt = (v == 256 || v == 384 || v == 512) ? v : 384; }
-    return nt;
+    if (nt == 512) f(std::integral_constant<int, 512>());
+    else if (nt == 384) f(std::integral_constant<int, 384>());
+    else f(std::integral_constant<int, 256>());
 }
 
-void launch_gauss_newton(const DevCtx& c, const GNParams& P, hipStream_t st)
+void launch_gauss_newton(const DevCtx& c, const Knobs& k, const GNParams& P, hipStream_t st)
 {
-    const int nt = gn_threads();
-    if (nt == 512) hipLaunchKernelGGL(k_gauss_newton<512>, dim3(c.n_lanes), dim3(512), gn_smem(P.pmax), st, c, P, c.gn_scratch);
-    else if (nt == 384) hipLaunchKernelGGL(k_gauss_newton<384>, dim3(c.n_lanes), dim3(384), gn_smem(P.pmax), st, c, P, c.gn_scratch);
-    else hipLaunchKernelGGL(k_gauss_newton<256>, dim3(c.n_lanes), dim3(256), gn_smem(P.pmax), st, c, P, c.gn_scratch);
+    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_gauss_newton<NT>, dim3(c.n_lanes), dim3(NT), gn_smem(P.pmax), st, c, P, c.gn_scratch); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -908,12 +907,9 @@ __global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, sv
     o.state = SVO_COV_OK;
 }
 
-void launch_pose_covariance(const DevCtx& c, const GNParams& P, svo_pose_cov* out, hipStream_t st)
+void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, hipStream_t st)
 {
-    const int nt = gn_threads();
-    if (nt == 512) hipLaunchKernelGGL(k_pose_covariance<512>, dim3(c.n_lanes), dim3(512), 0, st, c, P, out);
-    else if (nt == 384) hipLaunchKernelGGL(k_pose_covariance<384>, dim3(c.n_lanes), dim3(384), 0, st, c, P, out);
-    else hipLaunchKernelGGL(k_pose_covariance<256>, dim3(c.n_lanes), dim3(256), 0, st, c, P, out);
+    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_pose_covariance<NT>, dim3(c.n_lanes), dim3(NT), 0, st, c, P, out); });
 }
 
 // ------------------------------------------------------------------------------------------------------------

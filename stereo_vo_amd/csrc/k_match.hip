@@ -1629,7 +1629,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma(DevCtx c, int chunk)
             gsum += __builtin_amdgcn_update_dpp(0, gsum, 0x4E, 0xF, 0xF, false);
             gsum += __builtin_amdgcn_update_dpp(0, gsum, 0x141, 0xF, 0xF, false);
             gsum += __builtin_amdgcn_update_dpp(0, gsum, 0x140, 0xF, 0xF, false);
-            if (__ballot(gsum + (n - base) <= floor_cnt) == ~0ull && c.debug_mode != 16) break;
+            if (__ballot(gsum + (n - base) <= floor_cnt) == ~0ull && c.debug_mode != DBG_RC_NO_EARLY_STOP) break;
         }
         const int pi = base + j;
         const float4 p = pts[min(pi, n - 1)];
@@ -1646,7 +1646,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma(DevCtx c, int chunk)
         const bool inA = okA & (ddA <= denA * lo), inB = okB & (ddB <= denB * lo);
         const bool outA = okA & (ddA >= denA * hi), outB = okB & (ddB >= denB * hi);
         int v = (inA & inB) ? 1 : 0;
-        if (__builtin_expect(!((inA & inB) | outA | outB) || c.debug_mode == 13, 0)) v = fm_inlier(Fe, p.x, p.y, p.z, p.w);
+        if (__builtin_expect(!((inA & inB) | outA | outB) || c.debug_mode == DBG_RC_REPLAY_ALL, 0)) v = fm_inlier(Fe, p.x, p.y, p.z, p.w);
         cnt += pi < n ? v : 0;
     }
     // the 16 lanes of a group hold the partial counts of one model
@@ -1686,7 +1686,6 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma(DevCtx c, int chunk)
 // groups out of reach (rs_bound moves while the launch runs, so the blocks of one group need not agree) still takes its ticket; the
 // sums it leaves incomplete belong to samples at or beyond rs_bound, which the finalize never visits, and a best count published from
 // incomplete sums is an under-estimate, which only loosens the bound it feeds (as the early exit's partial counts did).
-#define RC16_NSPLIT0 1         // blocks the pairs of a lane are split over in chunk 0 (chunks 1, 2: one; launch_ransac_count)
 __global__ void __launch_bounds__(256) k_ransac_count_mfma16(DevCtx c, int chunk, int nsplit)
 {
     SVO_TL_SCOPE(c, TL_RS_COUNT, chunk);
@@ -1772,7 +1771,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma16(DevCtx c, int chunk
                     gsum += __builtin_amdgcn_update_dpp(0, gsum, 0x140, 0xF, 0xF, false);
                     hopeless = hopeless && (gsum + (n - base) <= floor_cnt);
                 }
-                if (__ballot(hopeless) == ~0ull && c.debug_mode != 16) { dead_late = true; break; }
+                if (__ballot(hopeless) == ~0ull && c.debug_mode != DBG_RC_NO_EARLY_STOP) { dead_late = true; break; }
             }
             const double* ot = ops + t * 256 + l;
             const double b1 = ot[0], b2 = ot[64], b5 = ot[128], b6 = ot[192];
@@ -1795,7 +1794,7 @@ __global__ void __launch_bounds__(256) k_ransac_count_mfma16(DevCtx c, int chunk
                 const bool inA = okA & (dd <= denA * lo), inB = okB & (dd <= denB * lo);
                 const bool outA = okA & (dd >= denA * hi), outB = okB & (dd >= denB * hi);
                 int v = (inA & inB) ? 1 : 0;
-                if (__builtin_expect((valid & !((inA & inB) | outA | outB)) || c.debug_mode == 13 || c.debug_mode == 54, 0)) {
+                if (__builtin_expect((valid & !((inA & inB) | outA | outB)) || c.debug_mode == DBG_RC_REPLAY_ALL || c.debug_mode == DBG_RC_MFMA16_REPLAY, 0)) {
                     const float4 p = pts[min(base + j, n - 1)];
                     v = fm_inlier(F + 9 * (4 * r + q), p.x, p.y, p.z, p.w);
                 }
@@ -2250,7 +2249,7 @@ hipError_t configure_match(int max_kps)
 
 // Which kernel forms this library holds: the product forms always; the A/B anchors (the int8 matcher SVO_HAM_FP4=0, the RANSAC count forms
 // SVO_DEBUG_MODE=14 / 52) only when it was compiled with -DSVO_AB_KERNELS (libsvo_hip_ab.so: tests and A/B runs load it through SVO_HIP_LIB).
-// svo_create refuses a knob that asks for a form the library does not hold.
+// svo_create refuses a knob that asks for a form the library does not hold (svo_ab_form_requested, svo_knobs.hpp).
 bool svo_ab_kernels_built()
 {
 #ifdef SVO_AB_KERNELS
@@ -2259,25 +2258,13 @@ bool svo_ab_kernels_built()
     return false;
 #endif
 }
-bool svo_ab_form_requested(int debug_mode)
-{
-    const char* e = getenv("SVO_HAM_FP4");
-    return (e && atoi(e) == 0) || debug_mode == 14 || debug_mode == 52;
-}
-// the FP4 form of the matrix-core brute force (k_hamming_f4) unless SVO_HAM_FP4=0
-static bool hamming_fp4()
-{
-    static int f4 = -1;
-    if (f4 < 0) { const char* e = getenv("SVO_HAM_FP4"); f4 = (e && atoi(e) == 0) ? 0 : 1; }      // default: FP4 (32.1 against 45.0 us per launch at 64 lanes, profiles/r04n, r04o); SVO_HAM_FP4=0 = the int8 form
-    return f4 != 0;
-}
 
-void launch_hamming(const DevCtx& c, int mode, int nsplit, hipStream_t st)
+void launch_hamming(const DevCtx& c, const Knobs& k, int mode, int nsplit, hipStream_t st)
 {
     const dim3 grid(c.n_lanes * c.oct_cap, (c.max_kps + HM_QB - 1) / HM_QB, (mode ? 2 : 1) * nsplit);
 #ifdef SVO_AB_KERNELS
     // (the int8 form reads the paired descriptors from a list laid out by a kernel of its own; the FP4 form gathers through the pairing lists)
-    if (!hamming_fp4()) {
+    if (!k.ham_fp4) {
         if (mode) hipLaunchKernelGGL(k_gather_mdesc, dim3((c.max_kps * 8 + 255) / 256, c.n_lanes * c.oct_cap, 4), dim3(256), 0, st, c);
         if (c.max_kps > 8192) hipLaunchKernelGGL(k_hamming_wide, grid, dim3(256), 0, st, c, mode, nsplit);
         else hipLaunchKernelGGL(k_hamming, grid, dim3(256), 0, st, c, mode, nsplit);
@@ -2315,13 +2302,13 @@ void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st)
     const int nh = RS_CHUNK_END(chunk) - RS_CHUNK_BEGIN(chunk);
     // one stream (few lanes): 16 lanes per sample, for latency; many lanes: one thread per sample, for instruction count
     // (debug_mode 50 forces the 16-lane form, 51 the one-thread form: tests/test_gpu_parity.py runs both against the oracle)
-    const bool per_thread = c.debug_mode == 51 || (c.debug_mode != 50 && c.n_lanes * c.n_oct > 8);
+    const bool per_thread = c.debug_mode == DBG_RH_THREAD || (c.debug_mode != DBG_RH_LANES16 && c.n_lanes * c.n_oct > 8);
     // (the samples of chunks 0-1 were numbered at the end of the tracker kernel) chunk 2: the rest, for the lanes whose budget reaches it
     if (chunk == 2) hipLaunchKernelGGL(k_ransac_schedule, dim3(c.n_lanes * c.oct_cap), dim3(256), 0, st, c, 1);
     if (per_thread) hipLaunchKernelGGL(k_ransac_hyp_thread, dim3((nh + 63) / 64, 2, c.n_lanes * c.oct_cap), dim3(64), 0, st, c, chunk);
     else hipLaunchKernelGGL(k_ransac_hyp, dim3((nh + 15) / 16, 2, c.n_lanes * c.oct_cap), dim3(256), 0, st, c, chunk);
 }
-void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st)
+void launch_ransac_count(const DevCtx& c, const Knobs& k, int chunk, hipStream_t st)
 {
     // one stream (few lanes): four models per block on the VALU, for latency; many lanes: 16 x 16 matrix-core tiles.
     // debug modes (tests/test_gpu_parity.py runs each against the oracle): 14 = sixteen models per block on the VALU,
@@ -2331,20 +2318,14 @@ void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st)
     const dim3 g16((ns + 15) / 16, 2, c.n_lanes * c.oct_cap);
     const bool many = c.n_lanes * c.n_oct > 8;
 #ifdef SVO_AB_KERNELS
-    if (dm == 14) { hipLaunchKernelGGL(k_ransac_count<16>, g16, dim3(256), 0, st, c, chunk); return; }
-    if (dm == 52) { hipLaunchKernelGGL(k_ransac_count_mfma, g16, dim3(256), 0, st, c, chunk); return; }
+    if (dm == DBG_RC_VALU16) { hipLaunchKernelGGL(k_ransac_count<16>, g16, dim3(256), 0, st, c, chunk); return; }
+    if (dm == DBG_RC_MFMA4) { hipLaunchKernelGGL(k_ransac_count_mfma, g16, dim3(256), 0, st, c, chunk); return; }
 #endif
-    if (many || dm == 53 || dm == 54) {
+    if (many || dm == DBG_RC_MFMA16 || dm == DBG_RC_MFMA16_REPLAY) {
         // The pairs of a lane CAN be split over several blocks per chunk (SVO_RC_SPLIT = s0[,s1[,s2]]): chunk 0 is two blocks per lane and side,
         // a chain of dependent f64 verdicts with one wave per SIMD (43 us alone, 29 us on four blocks each).  In the batched schedule it buys
         // nothing: 70.6 k pairs/s with (4, 1, 1), 71.0 k unsplit, 67.9 k with four everywhere (r05f, r05r).  Default: unsplit.
-        static int split[3] = { 0, 0, 0 };
-        if (!split[0]) {
-            split[0] = RC16_NSPLIT0; split[1] = split[2] = 1;
-            const char* e = getenv("SVO_RC_SPLIT");
-            if (e) { int v[3] = { 0, 0, 0 }; const int k = sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]); for (int i = 0; i < 3; i++) { const int x = i < k ? v[i] : (k > 0 ? v[k - 1] : 0); if (x >= 1 && x <= 8) split[i] = x; } }
-        }
-        const int nsplit = split[chunk];
+        const int nsplit = k.rc_split[chunk];
         hipLaunchKernelGGL(k_ransac_count_mfma16, dim3(((ns + 63) / 64) * nsplit, 2, c.n_lanes * c.oct_cap), dim3(256), 0, st, c, chunk, nsplit);
     }
     else hipLaunchKernelGGL(k_ransac_count<4>, dim3((ns + 3) / 4, 2, c.n_lanes * c.oct_cap), dim3(256), 0, st, c, chunk);

@@ -82,6 +82,7 @@ extern "C" int svo_profiler_sections_enabled(void) { return roctx_api().push != 
 
 struct svo_ctx {
     svo_config cfg;
+    Knobs knobs;                                       // the SVO_* environment of svo_create (svo_knobs.hpp): read once, before the first allocation
     svo_params params;
     int fast_th, orb_th;
     int klt_win;                                       // TDetectParams::KLT_win (S2:47): the window of dmFASTER's response, (2 klt_win + 1)^2 pixels
@@ -387,6 +388,11 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     ctx->kt_mask = ~0ull;
     *out = ctx;                                           // so that the caller can read last_error and destroy
+    knobs_read(&ctx->knobs, knobs_env);
+    if (svo_ab_form_requested(ctx->knobs) && !svo_ab_kernels_built()) {
+        ctx->last_error = "SVO_HAM_FP4=0 / SVO_DEBUG_MODE=14 / 52 ask for an A/B kernel form that this library was built without: load libsvo_hip_ab.so (SVO_HIP_LIB) or build with -DSVO_AB_KERNELS";
+        return SVO_ERR_UNSUPPORTED;
+    }
     HIPCHECK(hipSetDevice(cfg->device));
     if (cfg->stream) { ctx->stream = (hipStream_t)cfg->stream; ctx->own_stream = false; }
     else { HIPCHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); ctx->own_stream = true; }
@@ -473,16 +479,11 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     HIPCHECK(dev_alloc(ctx, &d.det_status, (size_t)L)); d.det_ahead = 0;
     d.sad_patch = nullptr; d.sad_flag = nullptr; d.carry_win = 0;
     d.bf_dist = nullptr;
-    { const char* dm = getenv("SVO_DEBUG_MODE"); d.debug_mode = dm ? atoi(dm) : 0; }
-    if (svo_ab_form_requested(d.debug_mode) && !svo_ab_kernels_built()) {
-        ctx->last_error = "SVO_HAM_FP4=0 / SVO_DEBUG_MODE=14 / 52 ask for an A/B kernel form that this library was built without: load libsvo_hip_ab.so (SVO_HIP_LIB) or build with -DSVO_AB_KERNELS";
-        return SVO_ERR_UNSUPPORTED;
-    }
+    d.debug_mode = ctx->knobs.debug_mode; d.rest_prio = ctx->knobs.rest_prio;
     d.rs_c0 = SVO_RANSAC_CHUNK0; d.rs_c1 = SVO_RANSAC_CHUNK1;      // (set per call where the RANSAC is launched)
-    { const char* rp = getenv("SVO_REST_PRIO"); d.rest_prio = rp ? (atoi(rp) & 3) : 0; }
     // SVO_TIMELINE=1: every kernel stamps the hull of its launch on the device's wall clock (svo_device.h, TlScope; svo_debug_timeline)
     d.tl = nullptr; d.tl_step = 0;
-    { const char* tl = getenv("SVO_TIMELINE"); if (tl && tl[0] == '1') { HIPCHECK(dev_alloc(ctx, &d.tl, (size_t)SVO_TL_STEPS * 256 * SVO_TL_SUB)); HIPCHECK(svo_debug_timeline(ctx, nullptr, 0, 1) < 0 ? hipErrorUnknown : hipSuccess); } }
+    if (ctx->knobs.timeline) { HIPCHECK(dev_alloc(ctx, &d.tl, (size_t)SVO_TL_STEPS * 256 * SVO_TL_SUB)); HIPCHECK(svo_debug_timeline(ctx, nullptr, 0, 1) < 0 ? hipErrorUnknown : hipSuccess); }
     HIPCHECK(configure_gauss_newton(MK));
     HIPCHECK(configure_match(MK));
     return SVO_OK;
@@ -935,9 +936,7 @@ extern "C" int svo_kernel_times_reset(svo_ctx* ctx)
 // 8 query blocks x 8 train tiles; with one split per lane a 16-lane launch keeps ONE wave per SIMD busy)
 static int hamming_splits(const svo_ctx* ctx)
 {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("SVO_HAM_SPLITS"); forced = e ? atoi(e) : 0; }
-    if (forced > 0) return forced;
+    if (ctx->knobs.ham_splits > 0) return ctx->knobs.ham_splits;      // SVO_HAM_SPLITS
     int s = 1024 / (8 * ctx->cfg.n_lanes); return s < 1 ? 1 : (s > 8 ? 8 : s);     // train splits: enough workgroups to fill the GPU, few enough to amortise the query expansion (64 lanes: 2 -- 32.1 us per launch against 34.8 with 4, 38.2 with 6: profiles/r04o)
 }
 
@@ -949,8 +948,7 @@ static int ensure_upload(svo_ctx* ctx)
         // an upload queued at normal priority was scheduled behind it (host-fed batch: 21.3 k -> 16.1 k pairs/s, 52 -> 40 GB/s)
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const char* e = getenv("SVO_COPY_PRIO");
-        HIPCHECK(hipStreamCreateWithPriority(&ctx->s_copy, hipStreamNonBlocking, (e && atoi(e) == 0) ? 0 : greatest));
+        HIPCHECK(hipStreamCreateWithPriority(&ctx->s_copy, hipStreamNonBlocking, ctx->knobs.copy_prio_normal ? 0 : greatest));      // SVO_COPY_PRIO=0
     }
     for (int i = 0; i < 2; i++) { HIPCHECK(hipEventCreateWithFlags(&ctx->ev_h2d[i], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&ctx->ev_det[i], hipEventDisableTiming)); }
     ctx->slot_bytes = (size_t)2 * ctx->cfg.n_lanes * ctx->img0_pitch_internal * ctx->cfg.max_h;
@@ -1194,13 +1192,13 @@ static void enqueue_detect(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
         if (p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {      // S2:599-606 on the FAST detector's output
             Span s(ctx, KT_SELECT); launch_fastorb_anms(d, ctx->d_anms, st);
         } else { Span s(ctx, KT_SELECT); launch_fastorb_nms(d, p.non_maximal_suppression, p.min_distance, st); }
-        { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
+        { Span s(ctx, KT_DESCRIBE); launch_describe(d, ctx->knobs, 0, st); }
     } else {                // stage2_detect.cpp:458-497
         { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_resize(d, l, st); }
         { Span s(ctx, KT_FAST); launch_fast(d, st); }
         if (!call.select_in_post) { Span s(ctx, kt_select(d)); launch_select(d, st); }
         // debug mode 9 keeps the detector's order: describe everything, then NMS -- that is what svo_debug_get_raw_keypoints shows
-        if (d.debug_mode == 9) { Span s(ctx, KT_DESCRIBE); launch_describe(d, 0, st); }
+        if (d.debug_mode == DBG_DESCRIBE_BEFORE_NMS) { Span s(ctx, KT_DESCRIBE); launch_describe(d, ctx->knobs, 0, st); }
     }
 }
 // The reference's own post-processing of the detector output: grid NMS and row sort.  The one copy: run by a detect call that does not
@@ -1212,9 +1210,9 @@ static void enqueue_detect_post(svo_ctx* ctx, const FrameCall& call, hipStream_t
     // The x1/2-octave detectors have run their NMS and described (0: the NMS ran above; 3: none, raster order).  dmORB: the reference's NMS
     // needs positions and responses only, so it runs BEFORE orientation + description and only its survivors are described (unless
     // debug mode 9 has described everything already)
-    const bool described = d.fast_orb || d.debug_mode == 9;
-    { Span s(ctx, kt_nms(d)); launch_nms_rowsort(d, d.fast_orb ? call.nms_mode_oct : call.nms_mode, p.min_distance, described ? 0 : 1, st); }
-    if (!described) { Span s(ctx, KT_DESCRIBE); launch_describe(d, 1, st); }
+    const bool described = d.fast_orb || d.debug_mode == DBG_DESCRIBE_BEFORE_NMS;
+    { Span s(ctx, kt_nms(d)); launch_nms_rowsort(d, ctx->knobs, d.fast_orb ? call.nms_mode_oct : call.nms_mode, p.min_distance, described ? 0 : 1, st); }
+    if (!described) { Span s(ctx, KT_DESCRIBE); launch_describe(d, ctx->knobs, 1, st); }
 }
 static void enqueue_match(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
 {
@@ -1222,7 +1220,7 @@ static void enqueue_match(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
     Section sec("_stg3"), sec2("stg3.find_pairings");                           // S3:64, 77
     // (the brute-force result words were set to all ones by k_begin_frame)
     if (p.match_method == SVO_SM_DESC_BF) {
-        { Span s(ctx, wide_lists(d) ? KT_HAM_LR_WIDE : KT_HAM_LR); launch_hamming(d, 0, hamming_splits(ctx), st); }
+        { Span s(ctx, wide_lists(d) ? KT_HAM_LR_WIDE : KT_HAM_LR); launch_hamming(d, ctx->knobs, 0, hamming_splits(ctx), st); }
         { Span s(ctx, KT_LR_FILTER); launch_match_lr_filter(d, p.enable_robust_1to1_match, p.max_y_diff, st); }
     } else if (p.match_method == SVO_SM_DESC_RBR) {         // smDescRbR (stage3_match_left_right.cpp:185-419)
         Span s(ctx, KT_LR_FILTER);
@@ -1241,12 +1239,12 @@ static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
     // lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
     // there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
     {
-        static const int forced = [] { const char* e = getenv("SVO_RS_C0"); const int v = e ? atoi(e) : 0; return (v == SVO_RANSAC_CHUNK0 || v == SVO_RANSAC_CHUNK1 || v == SVO_RANSAC_FEW) ? v : 0; }();
+        const int forced = ctx->knobs.rs_c0;
         d.rs_c0 = forced ? forced : (d.n_lanes * d.n_oct > 8 ? SVO_RANSAC_CHUNK0 : SVO_RANSAC_FEW);
         d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
     }
     if (!win) {
-        { Span s(ctx, wide_lists(d) ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, 1, hamming_splits(ctx), st); }
+        { Span s(ctx, wide_lists(d) ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, ctx->knobs, 1, hamming_splits(ctx), st); }
         { Span s(ctx, wide_lists(d) ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
     } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
         Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
@@ -1256,13 +1254,13 @@ static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
     // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
     // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
     { Span s(ctx, KT_RANSAC_HYP); launch_ransac_hyp(d, 0, st); }
-    { Span s(ctx, KT_RANSAC_CNT); launch_ransac_count(d, 0, st); }
+    { Span s(ctx, KT_RANSAC_CNT); launch_ransac_count(d, ctx->knobs, 0, st); }
     if (d.rs_c0 < d.rs_c1) {
         { Span s(ctx, KT_RANSAC_HYP1); launch_ransac_hyp(d, 1, st); }
-        { Span s(ctx, KT_RANSAC_CNT1); launch_ransac_count(d, 1, st); }
+        { Span s(ctx, KT_RANSAC_CNT1); launch_ransac_count(d, ctx->knobs, 1, st); }
     }
     { Span s(ctx, KT_RANSAC_HYP2); launch_ransac_hyp(d, 2, st); }
-    { Span s(ctx, KT_RANSAC_CNT2); launch_ransac_count(d, 2, st); }
+    { Span s(ctx, KT_RANSAC_CNT2); launch_ransac_count(d, ctx->knobs, 2, st); }
     { Span s(ctx, KT_TRK_FINAL); launch_track_finalize(d, p.bad_tracking_th, win, st); }
 }
 static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
@@ -1276,8 +1274,8 @@ static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
     g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
     if (p.use_custom_initial_pose) g.use_custom_initial_pose = 1;        // deltaPose = initial_estimation = zeros (S5:504-505, default argument H:1045)
     if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
-    { Span s(ctx, KT_GN); launch_gauss_newton(d, g, st); }
-    if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, g, ctx->d_cov, st); }
+    { Span s(ctx, KT_GN); launch_gauss_newton(d, ctx->knobs, g, st); }
+    if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, ctx->knobs, g, ctx->d_cov, st); }
 }
 
 // Every lazily allocated buffer a frame may need exists BEFORE a capture begins: hipMalloc / hipMemset are refused on a capturing
@@ -2147,8 +2145,8 @@ extern "C" int svo_change_in_pose(svo_ctx* ctx, const svo_index_pair* tracked, i
     note_stream(ctx);
     // (the scratch lane's record of the covariance is lane 0's, and its mask goes through lane 0's part of the mask array: svo_wait above)
     if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
-    { Span sp(ctx, KT_GN); launch_gauss_newton(s, g, ctx->stream); }
-    if (ctx->pose_cov) { Span sp(ctx, KT_POSE_COV); launch_pose_covariance(s, g, ctx->d_cov, ctx->stream); }
+    { Span sp(ctx, KT_GN); launch_gauss_newton(s, ctx->knobs, g, ctx->stream); }
+    if (ctx->pose_cov) { Span sp(ctx, KT_POSE_COV); launch_pose_covariance(s, ctx->knobs, g, ctx->d_cov, ctx->stream); }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(res, s.results, sizeof(*res), hipMemcpyDeviceToHost));

@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "../../include/svo_hip.h"
 #include "frame_call.hpp"      // LaneMask (one bit per lane): the host decides with it, the kernels take it as an argument
+#include "svo_knobs.hpp"       // the names of the SVO_DEBUG_MODE values (DevCtx.debug_mode), SVO_RANSAC_CHUNK0 / CHUNK1 / FEW
 
 #define SVO_EDGE 31
 #define SVO_RANSAC_HYP 1000         // sample schedule of one F-matrix RANSAC (oracle: RANSAC_MAX_HYP): minimal samples of seven pairs
@@ -22,11 +23,7 @@
 #define SVO_RANSAC_REG 16           // samples per region (one DPP row of k_ransac_hyp_thread, one block of k_ransac_hyp)
 #define SVO_RANSAC_RSLOTS 48        // model slots per region: a sample has one or three models (the real roots of the 7-point cubic)
 #define SVO_RANSAC_SLOTS (SVO_RANSAC_PAD / SVO_RANSAC_REG * SVO_RANSAC_RSLOTS)     // stride of the per-(lane, side) model arrays
-#define SVO_RANSAC_CHUNK0 32        // samples [0, CHUNK0) are evaluated unconditionally, [CHUNK0, CHUNK1) and [CHUNK1, HYP) only as far as
-#define SVO_RANSAC_FEW 320          // both chunk ends for a handful of lanes (DevCtx.rs_c0 / rs_c1): one hypothesis + count pair covers what the stop rule usually visits
-#ifndef SVO_RANSAC_CHUNK1
-#define SVO_RANSAC_CHUNK1 160       // the 0.99-confidence stop of the sequential algorithm can still reach (rs_bound)
-#endif
+// (SVO_RANSAC_CHUNK0 / SVO_RANSAC_CHUNK1 / SVO_RANSAC_FEW, the chunk ends of that schedule: svo_knobs.hpp, where SVO_RS_C0 is held to them)
 #define SVO_SEL_MAX 2048     // >= 2 * quota[0]: corners per (image, level) ranked by their Harris response
 #define SVO_FT_W 62          // k_fast tile (interior pixels; 64x64 score window with the NMS halo)
 #define SVO_FT_H 62
@@ -109,19 +106,7 @@ struct DevCtx {
     uint8_t* gn_scratch;      // the same for k_gauss_newton
     FastDiv div_tiles;        // / n_tiles
     int fast_th, orb_th;
-    int debug_mode;           // SVO_DEBUG_MODE in the environment of svo_create; 0 in production.  Timing ablations (results are then
-                              // meaningless) and forced kernel forms (results unchanged: the parity tests run them):
-                              //   1 / 2 / 3 / 4  k_fast returns after staging / compaction / scores, or publishes nothing
-                              //   5 / 6 / 7      k_resize without staging / without the blend / without the store
-                              //   8              linear (not XCD-chunked) tile orders              [results unchanged]
-                              //   9              detector order: describe every raw keypoint, then NMS   [results unchanged]
-                              //   10 / 11        k_gauss_newton returns after its set-up / runs one iteration per phase
-                              //   12             no speculative FAST threshold                     [results unchanged]
-                              //   13 / 16        RANSAC count replays every verdict / never stops early   [results unchanged]
-                              //   14, 50-54      forced RANSAC kernel forms (k_match.hip launchers)        [results unchanged]
-                              //   21-26          k_nms_rowsort returns after a phase (tests/dev/nms_breakdown.py)
-                              //   31, 41-45      k_select / k_select_sort return after a phase
-                              //   60-63          k_gauss_newton without its per-track loop / solve / rotation update (tests/dev/gn_breakdown.py)
+    int debug_mode;           // Knobs.debug_mode (SVO_DEBUG_MODE in the environment of svo_create; 0 in production): a DebugMode of svo_knobs.hpp
     long long pyr_bytes;
     LevelGeom lv[SVO_MAX_LEVELS];
     // buffers

@@ -1,4 +1,5 @@
-// svo_kernels.h -- host-side launchers of the HIP kernels (defined in k_detect.hip, k_match.hip, k_gn.hip)
+// svo_kernels.h -- host-side launchers of the HIP kernels (defined in k_detect.hip, k_match.hip, k_gn.hip).  The launchers that consult a
+// run-time knob take the context's Knobs (svo_knobs.hpp); none reads the environment.
 #pragma once
 #include "svo_device.h"
 
@@ -25,7 +26,7 @@ struct GNParams {
 //                                            under -DSVO_AB_KERNELS: the product libsvo_hip.so does not contain them (svo_create refuses the
 //                                            knobs there), libsvo_hip_ab.so does -- tests and A/B runs load it through SVO_HIP_LIB.
 bool svo_ab_kernels_built();                   // k_match.hip: compiled with -DSVO_AB_KERNELS (libsvo_hip_ab.so)
-bool svo_ab_form_requested(int debug_mode);    // SVO_HAM_FP4=0 or SVO_DEBUG_MODE 14 / 52 in the environment
+// (svo_ab_form_requested(const Knobs&), svo_knobs.hpp: SVO_HAM_FP4=0 or SVO_DEBUG_MODE 14 / 52 in the environment of svo_create)
 hipError_t svo_upload_tables();
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to (kernel, DEVICE) and is shared by every context of the process on that
 // device: keyed by both, only ever raised -- a later, smaller context must not lower the limit under an earlier context's launches,
@@ -50,14 +51,14 @@ void launch_begin_frame(const DevCtx& c, const uint8_t* const* ptrs, unsigned fl
 void launch_resize(const DevCtx& c, int level, hipStream_t st);
 void launch_fast(const DevCtx& c, hipStream_t st);
 void launch_select(const DevCtx& c, hipStream_t st);
-void launch_describe(const DevCtx& c, int pre, hipStream_t st);
+void launch_describe(const DevCtx& c, const Knobs& k, int pre, hipStream_t st);
 void launch_sad_patch(const DevCtx& c, hipStream_t st);       // needs DevCtx.sad_patch / sad_flag (allocated when a SAD selector is first in force)
 void launch_publish_img0(const DevCtx& c, const uint8_t* const* ptrs, hipStream_t st);      // svo_gather_windows: the level-0 pointer table of the active lanes, nothing else
 void launch_sad_patch_slot(const DevCtx& c, int which, hipStream_t st);                    // the same gather for slot `which` (0 current, 1 previous) of put / loaded lists
 hipError_t configure_nms_rowsort(const DevCtx& c);
 size_t nms_rowsort_scratch_bytes(const DevCtx& c);
 int nms_rowsort_items(const DevCtx& c);           // keys per thread of the k_nms_rowsort instantiation this geometry launches: 4, 8 or 16
-void launch_nms_rowsort(const DevCtx& c, int do_nms, int min_distance, int pre, hipStream_t st);
+void launch_nms_rowsort(const DevCtx& c, const Knobs& k, int do_nms, int min_distance, int pre, hipStream_t st);
 void launch_half(const DevCtx& c, int level, hipStream_t st);
 void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st);     // scratch3: 3 x n_img x cand_total words
 void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream_t st);
@@ -65,11 +66,11 @@ void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream
 void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st);
 hipError_t configure_faster_nms(const DevCtx& c);
 void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st);
-void launch_hamming(const DevCtx& c, int mode, int nsplit, hipStream_t st);
+void launch_hamming(const DevCtx& c, const Knobs& k, int mode, int nsplit, hipStream_t st);
 void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, hipStream_t st);
 void launch_track_filter(const DevCtx& c, hipStream_t st);
 void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st);
-void launch_ransac_count(const DevCtx& c, int chunk, hipStream_t st);
+void launch_ransac_count(const DevCtx& c, const Knobs& k, int chunk, hipStream_t st);
 void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, hipStream_t st);
 // sad = false: smDescRbR / ifmDescWin on the descriptors; sad = true: smSAD / ifmSAD on the windows of launch_sad_patch (max_sad: ifmSAD's threshold)
 void launch_match_lr_rbr(const DevCtx& c, bool sad, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
@@ -80,7 +81,7 @@ hipError_t configure_gauss_newton(int pmax);
 size_t gn_scratch_bytes_per_lane(int pmax);
 hipError_t configure_match(int max_kps);
 void launch_project_points(const float* uvu, int n, const svo_stereo_camera& cam, const double* delta6, float* pix, hipStream_t st);
-void launch_gauss_newton(const DevCtx& c, const GNParams& P, hipStream_t st);
+void launch_gauss_newton(const DevCtx& c, const Knobs& k, const GNParams& P, hipStream_t st);
 // svo_set_pose_covariance: P as handed to launch_gauss_newton just before (mask_out set), out = one record per lane
 size_t gn_mask_bytes_per_lane(int pmax);
-void launch_pose_covariance(const DevCtx& c, const GNParams& P, svo_pose_cov* out, hipStream_t st);
+void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, hipStream_t st);

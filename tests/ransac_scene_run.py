@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_ransac_forms.py: every case of ransac_scenes.all_cases through stage 4 of a one-lane context, under
-whatever launch knobs the environment of THIS process sets (the library reads them once per process); tracked pairs, counters and
+whatever launch knobs the environment of THIS process sets (a context reads them when it is created); tracked pairs, counters and
 status words go to an .npz for the parent to compare with the oracle.
 
 usage: python ransac_scene_run.py <golden directory> <output .npz>"""

@@ -313,7 +313,7 @@ def test_batch_and_device_copy():
 
 
 def gn_nt_child():
-    """the body of the child process of test_other_block_sizes: SVO_GN_NT is read once per process"""
+    """the body of the child process of test_other_block_sizes: SVO_GN_NT is read when a context is created, from the environment of its process"""
     case = [c for c in SINGLE if c[0] == "shape-T1025-mk2048"][0]
     ctx = new_context(case[1]); ctx.set_pose_covariance(True)
     for robust in (1, 0):

@@ -119,7 +119,7 @@ KNOBS = [{"SVO_DEBUG_MODE": "53", "SVO_RC_SPLIT": "4,2,3"}, {"SVO_DEBUG_MODE": "
 def test_pair_splits_and_forced_chunk_ends(golden_dir, tmp_path):
     """The pairs of a lane split over 4 / 2 / 3 blocks per chunk (partial counts, tickets; 17, 33, 255, 257, 272 pairs end `tiles_per * split`
     inside, at and past the list), three blocks everywhere under the many-lane chunk ends 32 / 160, and the one-thread hypothesis kernel
-    under the chunk ends 160 / 160: knobs the library reads once per process, so each setting gets a fresh child (one after the other)
+    under the chunk ends 160 / 160: knobs a context reads when it is created; each setting gets a fresh child (one after the other)
     that runs every case of the forced-form test and writes what it got; the parent compares with the oracle."""
     _, _, p = load_small(golden_dir)
     helper = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ransac_scene_run.py")
@@ -138,3 +138,47 @@ def test_pair_splits_and_forced_chunk_ends(golden_dir, tmp_path):
             except AssertionError as e:
                 failed.append(e.args[0])
         assert not failed, (env, len(failed), failed[:6])
+
+
+def test_a_knob_belongs_to_the_context_created_under_it(golden_dir, monkeypatch):
+    """The SVO_* knobs are read once per context, by svo_create.  In ONE process: context A is created under SVO_RS_C0=32 and SVO_GN_NT=256,
+    both are taken out of the environment, context B is created; the three frames of the small sequence then go through A and B in turn.
+    A runs chunk 1 of the sample schedule (with 32 forced it exists), B never does (one lane defaults to SVO_RANSAC_FEW, whose chunk 1 is
+    empty) -- whichever context launched first --, and both give the golden lists bit for bit and the oracle's result records."""
+    from oracle import oracle as O
+    for k in ("SVO_DEBUG_MODE", "SVO_RC_SPLIT", "SVO_HAM_FP4"):
+        monkeypatch.delenv(k, raising=False)
+    g, cam, p = load_small(golden_dir)
+
+    def make():
+        ctx = hip.Context(n_lanes=1, max_w=int(g["W"]), max_h=int(g["H"]), max_kps=1024, max_cand=1 << 15, kernel_times=True)
+        ctx.set_params(p); ctx.set_camera(cam)
+        return ctx
+    monkeypatch.setenv("SVO_RS_C0", "32"); monkeypatch.setenv("SVO_GN_NT", "256")
+    a = make()
+    monkeypatch.delenv("SVO_RS_C0"); monkeypatch.delenv("SVO_GN_NT")
+    b = make()
+    orc = O.Oracle(p)
+    for t in range(3):
+        ro = orc.process(g["L%d" % t], g["R%d" % t], cam)
+        for tag, ctx in (("A", a), ("B", b)):
+            ctx.process_host([(g["L%d" % t], g["R%d" % t])])
+            r = ctx.result(0)
+            for side in (0, 1):
+                k, d = ctx.keypoints(0, 0, side)
+                assert k.tobytes() == g["kps%d_%d" % (side, t)].tobytes() and (d == g["desc%d_%d" % (side, t)]).all(), (tag, t, "features", side)
+            assert ctx.matches(0).tobytes() == g["matches%d" % t].tobytes(), (tag, t, "pairings")
+            assert ctx.tracked(0).tobytes() == g["tracked%d" % t].tobytes(), (tag, t, "tracked pairs")
+            assert (r.valid, r.error_code) == (ro.valid, ro.error_code), (tag, t, r.valid, r.error_code, ro.valid, ro.error_code)
+            assert (r.detected_left[0], r.detected_right[0], r.stereo_matches[0]) == (ro.detected_left[0], ro.detected_right[0], ro.stereo_matches[0]), (tag, t)
+            assert (r.n_residual, r.n_outliers) == (ro.n_residual, ro.n_outliers), (tag, t)
+            assert list(r.track_stats) == list(ro.track_stats), (tag, t, list(r.track_stats), list(ro.track_stats))
+            if ro.valid:
+                dp = np.abs(np.array(r.outPose) - np.array(ro.outPose))
+                assert dp[:3].max() < 1e-3 and dp[3:].max() < 1e-4, (tag, t, dp)
+                assert r.tracked_feats_from_last_frame == ro.tracked_feats_from_last_frame, (tag, t)
+            assert ctx.status_word(0) == 0, (tag, t)
+    calls_a, calls_b = a.kernel_times()["ransac_hyp_1"][1], b.kernel_times()["ransac_hyp_1"][1]
+    a.close(); b.close()
+    assert calls_a > 0, calls_a
+    assert calls_b == 0, calls_b

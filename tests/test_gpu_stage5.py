@@ -229,7 +229,7 @@ GN_NT_SHAPES = [(t, 2048) for t in (255, 256, 257, 511, 512, 513, 1025)]
 
 
 def gn_nt_child():
-    """the body of the child process of test_other_block_sizes: SVO_GN_NT is read once per process"""
+    """the body of the child process of test_other_block_sizes: SVO_GN_NT is read when a context is created, from the environment of its process"""
     made = {}
     worst = 0.0
     for T, mk in GN_NT_SHAPES:
