@@ -316,6 +316,14 @@ int svo_put_features(svo_ctx* ctx, int lane, int which, int side, const svo_keyp
  * |x| <= img_w and |y| <= img_h (proven with a margin up to about 1.6 times that; lists reaching from -1 to 4 times the image size are
  * tested and agree, without a proof).  A caller whose coordinates lie outside the image declares an img_w x img_h that covers them;
  * contexts of up to 8 lane-octaves evaluate the reference's own expression and need no such premise.) */
+/* (Order: a keypoint list is put in ascending row order -- (int)y never falls from one keypoint to the next --, as every list of the
+ * reference is after stage 2.  The row-by-row stereo matchers smDescRbR and smSAD rest on it: they find a keypoint's row iteration from its
+ * own row, where the reference walks index ranges of the row table, and the two agree for lists in row order only; a list in another
+ * order is matched without a fault and without SVO_ST_INTERNAL, every keypoint paired at most once, but not to the reference's pairings.
+ * Rows below 0 and from img_h on are no breach of it: they are taken as they come, and the reference's loops never visit them.
+ * The brute-force matcher needs the order for the pairings' row table alone.  The windowed tracker ifmDescWin takes every previous
+ * pairing's row iteration from the pairings' row table itself and equals the reference's walk for pairing lists in ANY order, negative
+ * rows included: a pairing whose left keypoint has y <= 0 is visited in iteration 0.  tests/test_gpu_match_scenes.py holds both.) */
 /* (svo_put_matches also builds the list's matches_lr_row_index (S3:425-445) from the LEFT keypoints put before it: the reference builds that
  * index in stage 3 only, which this path skips (P:219-251), and its windowed tracker (S4:517-530) would read an index nobody built.) */
 int svo_put_matches(svo_ctx* ctx, int lane, int which, const svo_dmatch* m, int n);

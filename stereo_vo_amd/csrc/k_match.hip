@@ -652,9 +652,17 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
     __syncthreads();
     for (int pi = tid; pi < npm; pi += blockDim.x) {
         const svo_keypoint pl = pkl[pm[pi].queryIdx], pr = pkr[pm[pi].trainIdx];
-        const int y = (int)ceilf(pl.y);                                          // the row iteration whose range [ri[y], ri[y+1]) holds pi
-        if (y < 0 || y >= H - 1) continue;                                       // S4:514
-        if (!(ri_p[y] <= pi && pi < ri_p[y + 1])) continue;
+        // the row iteration whose range [ri[y], ri[y+1]) holds pi (S4:509-517): the last y < H - 1 with ri[y] <= pi, decided by the row
+        // table itself (ri[0] = 0, ascending), not by the keypoint's own row -- ceilf(pl.y) is that y for a list in row order with
+        // 0 < pl.y, but a pairing on a row <= 0 is visited by iteration 0 (ri[1] counts every y <= 0).  So ceilf(pl.y), clamped, is tried
+        // first and a binary search in the table settles what it misses.  Pairings from ri[H-1] on belong to no iteration.
+        if (H < 2 || pi >= ri_p[H - 1]) continue;                                // S4:509
+        const float cy = ceilf(pl.y);
+        int y = cy > 0.0f ? (cy < (float)(H - 2) ? (int)cy : H - 2) : 0;
+        if (!(ri_p[y] <= pi && pi < ri_p[y + 1])) {
+            y = 0;
+            for (int hi = H - 2; y < hi;) { const int mid = (y + hi + 1) >> 1; if (ri_p[mid] <= pi) y = mid; else hi = mid - 1; }
+        }
         const int wy_min = (y - WIN_W) > LO ? (y - WIN_W) : LO, wy_max = awy < (y + WIN_W) ? awy : (y + WIN_W);   // S4:525-526
         const int c0 = ri_c[wy_min], c1 = ri_c[wy_max + 1];                      // S4:529-530
         const int a = (int)(pl.x - (float)WIN_H), b = (int)(pl.x + (float)WIN_H), cc = (int)(pr.x - (float)WIN_H), d = (int)(pr.x + (float)WIN_H);
@@ -719,7 +727,8 @@ __global__ void __launch_bounds__(256) k_track_win(DevCtx c, int WIN_W, int WIN_
 // are free) is kept at once -- everything earlier that competes for them has been decided, and decided means rejected,
 // or the index would not be free -- then every undecided k whose left or right index was just taken is rejected (by a
 // smaller kept k, as in the walk).  The smallest undecided k overall always qualifies, so a round always makes progress;
-// chains of conflicts are a handful long.  A thread owns k = tid, tid + 256, ... in registers; the per-train-index
+// chains of conflicts are a handful long on real frames (tests/test_gpu_match_scenes.py runs chains of 300, 2100 and 4600 rounds through
+// the three storage forms: tests/match_scenes.py, track-chain-J).  A thread owns k = tid, tid + 256, ... in registers; the per-train-index
 // minima live in LDS.  (One wave walking 64 entries at a time took 70 us; the rounds take a few.)
 // Also gathers the pixel pairs for the two RANSACs (S4:181-189, 216-224).
 // ------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,598 @@
+"""Input lists built by hand for the pairing filters of stage 3 (k_match_lr_filter, k_match_lr_rbr<false>, lr_row_index) and the front end
+of stage 4 (k_track_filter<16|32|64>, k_track_win<false>), with k_hamming_f4 underneath (numpy only: no GPU, and the oracle is imported
+by the functions that need it).  In the style of tests/ransac_scenes.py, whose _kps / put_scene / run_case / check_case / oracle_track /
+pairings_row_index are reused.
+
+Descriptors are made on purpose: every TARGET descriptor is random (redrawn until any two targets are 96 .. 160 bits apart), a QUERY is a
+copy of its target with exactly d chosen bits flipped (d = 256: the complement), and check_planted asserts in numpy that the planted
+match is what a nearest-neighbour search finds: its distance is exactly d and every other candidate is at least 90 bits away.
+Coordinates are small integers or exact binary fractions ("0.999" of a row or a pixel is 1 - 2^-10 here).
+
+A stage-3 scene is a dict: kl dl kr dr (both lists in ascending row order), W H, `variants` (parameter settings the scene is run
+under, next to match_method x enable_robust_1to1_match), `want_r` / `want_d` (per left keypoint its planted right keypoint and distance)
+and `label` (per left keypoint what it is there for).  A stage-4 scene is a dict of ransac_scenes' keys (pkl pkr pdl pdr pm ckl ckr cdl cdr
+cm W H) with `pri` / `cri` (the pairings' row tables), `params` (ifm_method, windows), `want` (the tracked pairs the construction
+predicts, or None) and `th_col` (SVO_TS_THRESHOLD, SVO_TS_COLLISION as predicted).  The motion of every stage-4 scene is sideways -- each
+pairing moves along its own row by a shift of its own --, so the exact F is [(1,0,0)]_x and the RANSAC keeps every survivor.
+tests/test_match_scenes_cpu.py asserts all of that on the oracle alone; tests/test_gpu_match_scenes.py runs the scenes on the kernels."""
+import functools
+
+import numpy as np
+
+from stereo_vo_amd.abi import dmatch_dtype
+
+import ransac_scenes as RS
+from ransac_scenes import _kps, pairings_row_index                                   # noqa: F401
+
+NEAR1 = 1.0 - 2.0 ** -10              # "0.999": an exact binary fraction just under 1
+ORB_TH = 60                           # north_star_params: orb_max_distance 60 = the context's ORB threshold after set_params
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint8)
+
+
+class Retry(Exception):
+    """a draw whose random descriptors came too close to each other: the scene is drawn again from the next sub-seed"""
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# descriptors
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def hamming_matrix(a, b):
+    """all distances between the rows of a (n x 32 bytes) and b (m x 32 bytes): n x m int32"""
+    a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32); b = np.ascontiguousarray(b, np.uint8).reshape(-1, 32)
+    if hasattr(np, "bitwise_count"):
+        a, b = a.view(np.uint64), b.view(np.uint64)
+        return sum(np.bitwise_count(a[:, None, w] ^ b[None, :, w]).astype(np.int32) for w in range(4))
+    return _POP8[a[:, None, :] ^ b[None, :, :]].sum(2, dtype=np.int32)
+
+
+def extremes(Q, T, skip):
+    """per query: (distance to T[skip[q]], smallest and largest distance to every OTHER row of T); 999 / -1 where there is no other"""
+    n = len(Q)
+    own, lo, hi = np.zeros(n, np.int32), np.full(n, 999, np.int32), np.full(n, -1, np.int32)
+    for s in range(0, n, 256):
+        D = hamming_matrix(Q[s:s + 256], T)
+        r = np.arange(len(D)); k = np.asarray(skip[s:s + 256])
+        has = k >= 0
+        own[s:s + 256][has] = D[r[has], k[has]]
+        if len(T) > 1 or not has.all():
+            D[r[has], k[has]] = 999; lo[s:s + 256] = D.min(1)
+            D[r[has], k[has]] = -1; hi[s:s + 256] = D.max(1)
+    return own, lo, hi
+
+
+def targets(rng, n, lo=96, hi=160):
+    """n random descriptors, any two of them lo .. hi bits apart (offenders are drawn again)"""
+    T = rng.randint(0, 256, (n, 32)).astype(np.uint8)
+    _, mn, mx = extremes(T, T, np.arange(n))
+    bad = np.flatnonzero((mn < lo) | (mx > hi))
+    for _ in range(40):
+        if not len(bad):
+            return T
+        T[bad] = rng.randint(0, 256, (len(bad), 32)).astype(np.uint8)
+        _, mn, mx = extremes(T[bad], T, bad)                                      # a redrawn row against every other row (distances are symmetric)
+        bad = bad[(mn < lo) | (mx > hi)]
+    raise Retry("targets")
+
+
+def flipped(rng, desc, d):
+    """a copy of desc with exactly d bits flipped, chosen by rng (256: the complement)"""
+    out = desc.copy()
+    for b in rng.choice(256, int(d), replace=False):
+        out[b >> 3] ^= np.uint8(1 << (b & 7))
+    return out
+
+
+def check_planted(Q, T, want, d, floor=90):
+    """the planted match is what it is meant to be: distance exactly d, every other candidate at least `floor` bits away (want < 0: no
+    planted match, every candidate that far).  Raises Retry where the draw does not give that."""
+    want, d = np.asarray(want, np.int64), np.asarray(d, np.int64)
+    if len(Q) == 0 or len(T) == 0:
+        return
+    own, lo, _ = extremes(Q, T, want)
+    if not ((own[want >= 0] == d[want >= 0]).all() and (lo >= floor).all()):
+        raise Retry("planted")
+
+
+def drawn(build):
+    """a generator `build(rng, ...)` run on sub-seeds seed * 100, + 1, ... until its descriptors are separated as check_planted asks"""
+    @functools.wraps(build)
+    def run(seed, *args, **kw):
+        for sub in range(100):
+            try:
+                return build(np.random.RandomState(seed * 100 + sub), *args, **kw)
+            except Retry:
+                continue
+        raise AssertionError("no separated draw", build.__name__, seed)
+    return run
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the row tables the library builds for put lists, from the rules in include/svo_hip.h (svo_put_features / svo_put_matches)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def features_row_index(kps, H):
+    """pyr_feats_index of a put keypoint list: idx[r] = #keypoints with row <= r for first_row <= r < last_row, 0 elsewhere, where a
+    keypoint's row is (int)y (towards zero), rows below 0 count as row 0, rows from H on are never counted, and first_row / last_row are
+    the rows of the list's first / last keypoint.  H entries."""
+    idx = np.zeros(H, np.int64)
+    if len(kps) == 0:
+        return idx
+    rows = np.trunc(kps["y"].astype(np.float64)).astype(np.int64)
+    cnt = np.bincount(np.clip(rows, 0, H), minlength=H + 1)
+    acc = np.cumsum(cnt[:H])
+    r = np.arange(H)
+    on = (r >= rows[0]) & (r < rows[-1])
+    idx[on] = acc[on]
+    return idx
+
+
+def matches_row_index(m, kl, H):
+    """matches_lr_row_index of a put pairing list (svo_put_matches): ri[0] = 0, ri[y] = #pairings the walk `left y <= y - 1` has passed,
+    ri[H] = the number of pairings.  H + 1 entries."""
+    return pairings_row_index(m, kl, H)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# stage 3
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _stereo(W, H, left, right, variants):
+    """left: [(x, y, desc, response, label, key of the planted right keypoint or None, planted distance)], right: [(key, x, y, desc, response)]
+    -> the scene, both lists in ascending (y, x) order"""
+    lx = np.array([(l[0], l[1]) for l in left], np.float64).reshape(-1, 2); rx = np.array([(r[1], r[2]) for r in right], np.float64).reshape(-1, 2)
+    assert (lx.astype(np.float32) == lx).all() and (rx.astype(np.float32) == rx).all()                  # exact in binary32
+    ol, orr = np.lexsort((lx[:, 0], lx[:, 1])), np.lexsort((rx[:, 0], rx[:, 1]))
+    kl, kr = _kps(lx[ol].astype(np.float32)), _kps(rx[orr].astype(np.float32))
+    kl["response"] = np.array([left[i][3] for i in ol], np.float32); kr["response"] = np.array([right[i][4] for i in orr], np.float32)
+    dl = np.array([left[i][2] for i in ol], np.uint8).reshape(-1, 32); dr = np.array([right[i][3] for i in orr], np.uint8).reshape(-1, 32)
+    at = {right[j][0]: pos for pos, j in enumerate(orr)}
+    assert len(at) == len(right)
+    want_r = np.array([-1 if left[i][5] is None else at[left[i][5]] for i in ol], np.int64)
+    want_d = np.array([left[i][6] for i in ol], np.int64)
+    return dict(kl=kl, dl=dl, kr=kr, dr=dr, W=W, H=H, variants=variants, want_r=want_r, want_d=want_d, label=[left[i][4] for i in ol], right_at=at)
+
+
+def _fill(rng, left, right, n, W, H, rows, T, t0):
+    """n plain pairs (distance 5, disparity 10, same row) on the given rows, to bring a scene to its size"""
+    for i in range(n):
+        x, y = float(40 + 6 * (i % 40)), float(rows[i % len(rows)])
+        right.append(("fill%d" % i, x - 10.0, y, T[t0 + i], 1.0)); left.append((x, y, flipped(rng, T[t0 + i], 5), 1.0, "fill", "fill%d" % i, 5))
+
+
+@drawn
+def bf_threshold(rng, W=320, H=240):
+    """planted distances 0, orb_th - 1, orb_th, orb_th + 1 and 256 (the right descriptor is the left one's complement), each on a row of its own"""
+    ds = [0, ORB_TH - 1, ORB_TH, ORB_TH + 1, 256]
+    n = 45
+    T = targets(rng, n)
+    left, right = [], []
+    for i in range(n):
+        d = ds[i % 5]; x, y = float(60 + 5 * i), float(6 + 5 * i)
+        right.append((i, x - float(3 + i % 30), y, T[i], 1.0)); left.append((x, y, flipped(rng, T[i], d), 1.0, "d=%d" % d, i, d))
+    s = _stereo(W, H, left, right, [{}])
+    # the complemented ones have no match within reach: whatever is nearest to them is 90 bits away or more
+    check_planted(s["dl"], s["dr"], np.where(s["want_d"] <= 62, s["want_r"], -1), s["want_d"])
+    return s
+
+
+DY = [0.0, 0.5, -0.5, NEAR1, -NEAR1, 1.0, -1.0, 1.5, -1.5, 1.0 + NEAR1, -1.0 - NEAR1, 2.0, -2.0]
+
+
+def dxs(W):
+    """kl.x - kr.x around the disparity limits 1 and W (S3:163), the negative ones truncating to 0 and to -1"""
+    return [0.5, NEAR1, 1.0, 1.5, W - 0.5, float(W), W + NEAR1, W + 1.0, -0.5, -NEAR1, -1.0]
+
+
+@drawn
+def bf_epipolar(rng, W=320, H=240):
+    """kl.y - kr.y and kl.x - kr.x around the (int) truncations of S3:162-163; run under max_y_diff 1.0 and 0.0"""
+    cases = [(dy, 10.0) for dy in DY] + [(0.0, dx) for dx in dxs(W)]
+    n = len(cases)
+    T = targets(rng, n + 20)
+    left, right = [], []
+    for i, (dy, dx) in enumerate(cases):
+        x, y = 300.0, float(8 + 8 * i)
+        right.append((i, x - dx, y - dy, T[i], 1.0)); left.append((x, y, flipped(rng, T[i], 7), 1.0, "dy=%r dx=%r" % (dy, dx), i, 7))
+    _fill(rng, left, right, 20, W, H, [204, 212, 220, 228], T, n)
+    s = _stereo(W, H, left, right, [dict(max_y_diff=1.0), dict(max_y_diff=0.0)])
+    check_planted(s["dl"], s["dr"], s["want_r"], s["want_d"])
+    return s
+
+
+@drawn
+def bf_one_to_one(rng, W=320, H=240):
+    """groups of 2, 3 and 40 left keypoints claiming one right keypoint: at equal distance, at unequal distance (the last one nearest),
+    with a winner that fails the epipolar filter, and with losers that would have passed"""
+    kinds = ["equal", "unequal", "winner-fails", "loser-passes"]
+    groups = [(k, size) for k in kinds for size in (2, 3, 40)]
+    T = targets(rng, len(groups) + 30)
+    left, right = [], []
+    for g, (kind, size) in enumerate(groups):
+        xr, yr = 20.0, float(10 + 16 * g)
+        right.append((g, xr, yr, T[g], 1.0))
+        for i in range(size):
+            d = 10 if kind == "equal" else 5 + i if kind == "unequal" else 5 + (size - 1 - i)      # unequal: the first claimant is nearest; the other two kinds: the last one
+            y = yr + 3.0 if kind == "winner-fails" and i == size - 1 else yr       # the winner three rows off: dropped by S3:162
+            left.append((xr + 5.0 + 2 * i, y, flipped(rng, T[g], d), 1.0, "%s-%d #%d" % (kind, size, i), g, d))
+    _fill(rng, left, right, 30, W, H, [204, 212, 220, 228, 236], T, len(groups))
+    s = _stereo(W, H, left, right, [{}])
+    check_planted(s["dl"], s["dr"], s["want_r"], s["want_d"])
+    return s
+
+
+@drawn
+def bf_rows(rng, W=320, H=240):
+    """pairings on row 0, 70 of them on one row, on rows H - 2 and H - 1, whole rows empty between: lr_row_index (ri[0] = 0, ri[H] = M)"""
+    rows = [0] * 5 + [50] * 70 + [120] * 3 + [H - 2] * 4 + [H - 1] * 4
+    T = targets(rng, len(rows))
+    left, right = [], []
+    for i, y in enumerate(rows):
+        x = float(30 + 4 * (i % 72))
+        right.append((i, x - float(10 + i % 7), float(y), T[i], 1.0)); left.append((x, float(y), flipped(rng, T[i], 5), 1.0, "row %d" % y, i, 5))
+    s = _stereo(W, H, left, right, [{}])
+    check_planted(s["dl"], s["dr"], s["want_r"], s["want_d"])
+    return s
+
+
+@drawn
+def rbr_wrap(rng, W=320, H=240):
+    """smDescRbR's 8-bit accumulator: a left keypoint with a 3-bit candidate and its own complement (256 wraps to 0: the best match) on its
+    row, in either order; max_distance on the edge; responses on and just under minimum_ORB_response (variant 2); first claimant against best
+    claimant on one right keypoint"""
+    T = targets(rng, 60)
+    left, right = [], []
+    t = 0
+    for g in range(6):                                                            # the complement beside a 3-bit candidate
+        y = float(10 + 6 * g); L = flipped(rng, T[t], 3)
+        xs = (100.0, 120.0) if g % 2 else (120.0, 100.0)                          # which of the two the walk meets first
+        right.append(("near%d" % g, xs[0], y, T[t], 1.0)); right.append(("wrap%d" % g, xs[1], y, np.bitwise_not(L), 1.0))
+        left.append((150.0, y, L, 1.0, "wrap", "near%d" % g, 3)); t += 1
+    for i, d in enumerate([ORB_TH - 1, ORB_TH, ORB_TH + 1] * 2):                 # max_distance = (int)orb_max_distance: `>` rejects
+        y = float(50 + 6 * i)
+        right.append(("edge%d" % i, 100.0, y, T[t], 1.0)); left.append((150.0, y, flipped(rng, T[t], d), 1.0, "d=%d" % d, "edge%d" % i, d)); t += 1
+    under = float(np.nextafter(np.float32(0.5), np.float32(0)))
+    for i, (rl, rr) in enumerate([(0.5, 0.5), (under, 0.5), (0.5, under), (under, under)] * 2):      # minimum_ORB_response 0.5: `<` rejects
+        y = float(90 + 6 * i)
+        right.append(("resp%d" % i, 100.0, y, T[t], rr)); left.append((150.0, y, flipped(rng, T[t], 4), rl, "resp %r %r" % (rl == 0.5, rr == 0.5), "resp%d" % i, 4)); t += 1
+    for i in range(4):                                                            # two claimants, the first one (the row above) farther than the second
+        y = float(142 + 8 * i)
+        right.append(("claim%d" % i, 100.0, y, T[t], 1.0))
+        left.append((150.0, y, flipped(rng, T[t], 10), 1.0, "claim-first", "claim%d" % i, 10))
+        left.append((160.0, y + 1.0, flipped(rng, T[t], 4 if i % 2 == 0 else 10), 1.0, "claim-second", "claim%d" % i, 4 if i % 2 == 0 else 10)); t += 1
+    _fill(rng, left, right, 24, W, H, [180, 186, 192, 198, 204, 210], T, t)
+    left.append((10.0, 230.0, T[59], 1.0, "last row", None, 0)); right.append(("last", 5.0, 231.0, T[58], 1.0))      # close the row tables below the rows in use
+    s = _stereo(W, H, left, right, [{}, dict(minimum_ORB_response=0.5)])
+    # the brute-force matcher sees the complement at 256: the 3-bit candidate is its nearest, everything else 90 bits away or more
+    own, lo, _ = extremes(s["dl"], s["dr"], s["want_r"])
+    if not ((own[s["want_r"] >= 0] == s["want_d"][s["want_r"] >= 0]).all() and (lo >= 90).all()):
+        raise Retry("planted")
+    return s
+
+
+RBR_Y_DIFFS = [0.0, 0.4, 0.5, 1.0, 1.5, 2.5]                                      # round(): 0 0 1 1 2 3
+
+
+@drawn
+def rbr_rows(rng, W=320, H=120):
+    """smDescRbR's row tables: right keypoints 4 rows above .. 4 rows below their left one (which max_y_diff reaches which: round()),
+    disparities 1, (int)(0.7 W) and one more, left keypoints on the first occupied row, on rows 1 and 2 and H - 2 and H - 1 (the right
+    range clamps at 0 and H - 1) and on the last occupied row (never matched); one keypoint per side beyond the image closes the tables"""
+    T = targets(rng, 80)
+    left, right = [], []
+    t = 0
+
+    def pair(x, y, dx, dr_rows, label):
+        nonlocal t
+        right.append((t, x - dx, y + dr_rows, T[t], 1.0)); left.append((x, y, flipped(rng, T[t], 6), 1.0, label, t, 6)); t += 1
+    for i, off in enumerate(range(-4, 5)):                                        # rows 20 .. 100, ten rows apart: no range reaches a neighbour's
+        pair(200.0, float(20 + 10 * i), 12.0, float(off), "offset %d" % off)
+    big = float(int(W * 0.7))
+    for i, dx in enumerate([1.0, NEAR1, big, big + NEAR1, big + 1.0, 0.5]):
+        pair(300.0, float(24 + 10 * i), dx, 0.0, "disparity %r" % dx)
+    for y in (1.0, 1.0, 2.0, 2.0, float(H - 2), float(H - 2), float(H - 1), float(H - 1)):
+        for off in (-1.0, 1.0):
+            pair(40.0 + 8 * len(left), y, 9.0, off, "border row %d offset %d" % (y, off))
+    for i in range(12):
+        pair(40.0 + 6 * i, float(30 + 5 * i) + 0.5, 7.0, 0.0, "fill")
+    pair(30.0, 0.0, 5.0, 0.0, "first row")
+    pair(30.0, float(H + 2), 5.0, 1.0, "last row")
+    s = _stereo(W, H, left, right, [dict(max_y_diff=v) for v in RBR_Y_DIFFS])
+    check_planted(s["dl"], s["dr"], s["want_r"], s["want_d"])
+    return s
+
+
+@drawn
+def stereo_tiny(rng, nl, nr, d=5, W=320, H=240):
+    """0 or 1 keypoints on a side (the one pair: distance d, 256 = the complement), or one against forty"""
+    T = targets(rng, max(nr, 1))
+    right = [(j, 100.0 + 4 * j, 100.0, T[j], 1.0) for j in range(nr)]
+    left = [(150.0 + 4 * i, 100.0, flipped(rng, T[i % max(nr, 1)], d), 1.0, "tiny", (i % nr) if nr else None, d) for i in range(nl)]
+    s = _stereo(W, H, left, right, [{}])
+    if d <= 62:
+        check_planted(s["dl"], s["dr"], s["want_r"], s["want_d"])
+    return s
+
+
+STEREO = [
+    ("bf-threshold", bf_threshold, (1,)), ("bf-epipolar", bf_epipolar, (1,)), ("bf-one-to-one", bf_one_to_one, (1,)), ("bf-rows", bf_rows, (1,)),
+    ("rbr-wrap", rbr_wrap, (1,)), ("rbr-rows", rbr_rows, (1,)),
+    ("stereo-0-0", stereo_tiny, (1, 0, 0)), ("stereo-0-40", stereo_tiny, (1, 0, 40)), ("stereo-40-0", stereo_tiny, (1, 40, 0)),
+    ("stereo-1-1", stereo_tiny, (1, 1, 1)), ("stereo-1-1-complement", stereo_tiny, (1, 1, 1, 256)), ("stereo-1-40", stereo_tiny, (1, 1, 40)), ("stereo-40-1", stereo_tiny, (1, 40, 1)),
+]
+
+
+def stereo_params(p, variant, match_method, robust):
+    """the parameter record a stage-3 scene variant is run under"""
+    q = p.copy()
+    q.match_method, q.enable_robust_1to1_match = match_method, robust
+    for k, v in variant.items():
+        setattr(q, k, v)
+    return q
+
+
+def expected_bf(s, p):
+    """What smDescBF leaves of a scene, from the PLANTED structure alone (no descriptor is compared): left keypoint i is matched to want_r[i]
+    at want_d[i]; with the 1-to-1 filter a right keypoint keeps its claimant of the smallest (distance, index) (S3:124-147); then
+    |(int)(yl - yr)| <= max_y_diff, distance <= orb_th, 1 <= (int)(xl - xr) <= W (S3:159-168).  A left keypoint planted beyond 62 bits
+    matches something at 90 bits or more and is dropped whatever that is.  -> [(left, right, distance)]"""
+    kl, kr = s["kl"], s["kr"]
+    cand = [(i, int(s["want_r"][i]), int(s["want_d"][i])) for i in range(len(kl)) if s["want_r"][i] >= 0 and s["want_d"][i] <= 62]
+    if p.enable_robust_1to1_match:
+        best = {}
+        for i, j, d in cand:
+            if j not in best or (d, i) < best[j]:
+                best[j] = (d, i)
+        cand = [(i, j, d) for i, j, d in cand if best[j][1] == i]
+    out = []
+    for i, j, d in cand:
+        dy, dx = int(np.float32(kl["y"][i]) - np.float32(kr["y"][j])), int(np.float32(kl["x"][i]) - np.float32(kr["x"][j]))
+        if abs(dy) <= p.max_y_diff and d <= ORB_TH and 1 <= dx <= s["W"]:
+            out.append((i, j, float(d)))
+    return out
+
+
+def oracle_match(p, s):
+    """the oracle's stage 3 on a scene, under the row tables the library builds for put lists: (pairings, their row table)"""
+    from oracle import oracle
+    return oracle.match_lr(p, ORB_TH, s["kl"], s["dl"], features_row_index(s["kl"], s["H"]), s["kr"], s["dr"], features_row_index(s["kr"], s["H"]), s["W"], s["H"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# stage 4
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _identity(n):
+    m = np.zeros(n, dmatch_dtype); m["queryIdx"] = np.arange(n); m["trainIdx"] = np.arange(n); m["distance"] = 10.0
+    return m
+
+
+def _track(W, H, cur, cdl, cdr, prev, pdl, pdr, params, want, th_col, disp=20.0):
+    """cur / prev: n x 2 left pixel positions, both in ascending row order; right = left - disp; pairing k = keypoint k on both sides"""
+    cur, prev = np.asarray(cur, np.float64).reshape(-1, 2), np.asarray(prev, np.float64).reshape(-1, 2)
+    assert (cur.astype(np.float32) == cur).all() and (prev.astype(np.float32) == prev).all()
+    sh = np.array([disp, 0.0])
+    s = dict(pkl=_kps((prev).astype(np.float32)), pkr=_kps((prev - sh).astype(np.float32)), pdl=np.asarray(pdl, np.uint8).reshape(-1, 32), pdr=np.asarray(pdr, np.uint8).reshape(-1, 32), pm=_identity(len(prev)),
+             ckl=_kps(cur.astype(np.float32)), ckr=_kps((cur - sh).astype(np.float32)), cdl=np.asarray(cdl, np.uint8).reshape(-1, 32), cdr=np.asarray(cdr, np.uint8).reshape(-1, 32), cm=_identity(len(cur)),
+             W=W, H=H, params=params, want=want, th_col=th_col)
+    s["pri"] = matches_row_index(s["pm"], s["pkl"], H); s["cri"] = matches_row_index(s["cm"], s["ckl"], H)
+    return s
+
+
+def _grid(rng, n, W=640, H=480, step=4, rows=None):
+    """n distinct points of an integer grid inside the image, in ascending (y, x) order"""
+    xs = np.arange(64, W - 80, step)
+    ys = np.arange(40, H - 40, step) if rows is None else np.asarray(rows)
+    cell = rng.choice(len(xs) * len(ys), n, replace=False)
+    pts = np.stack([xs[cell % len(xs)], ys[cell // len(xs)]], 1).astype(np.float64)
+    return pts[np.lexsort((pts[:, 0], pts[:, 1]))]
+
+
+BF = dict(ifm_method=0)
+
+
+def track_chain(seed, J):
+    """J + 1 current pairings; previous pairing 2j wants (left j, right j), previous pairing 2j + 1 wants (left j, right j + 1): it is
+    rejected because left j is taken, and must not mark right j + 1.  The sequential walk keeps exactly the even pairings; the round form
+    of k_track_filter decides one pairing pair per round -- right j + 1 has the undecided claimant 2j + 1 ahead of 2j + 2 until round j + 1."""
+    rng = np.random.RandomState(seed)
+    n = J + 1
+    cur = _grid(rng, n)
+    cdl, cdr = targets(rng, n), targets(rng, n)
+    tl = np.repeat(np.arange(J), 2); tr = tl + (np.arange(2 * J) % 2)
+    dL, dR = 1 + np.arange(2 * J) % 5, 1 + np.arange(2 * J) % 3
+    pdl = np.stack([flipped(rng, cdl[t], d) for t, d in zip(tl, dL)]); pdr = np.stack([flipped(rng, cdr[t], d) for t, d in zip(tr, dR)])
+    shift = rng.randint(2, 41, n).astype(np.float64)
+    prev = cur[tl] - np.stack([shift[tl], np.zeros(2 * J)], 1)
+    s = _track(640, 480, cur, cdl, cdr, prev, pdl, pdr, BF, [(2 * j, j) for j in range(J)], (2 * J, J))
+    s.update(tl=tl, tr=tr, dL=dL, dR=dR)
+    check_planted(pdl, cdl, tl, dL); check_planted(pdr, cdr, tr, dR)          # (targets 96 apart, 5 bits flipped at most: no draw fails this)
+    return s
+
+
+def _specs_scene(rng, cur, specs, params, W=640, H=480):
+    """specs: per previous pairing (left target, left distance, right target, right distance), in ascending target row order"""
+    n = len(cur)
+    cdl, cdr = targets(rng, n), targets(rng, n)
+    tl, dL, tr, dR = (np.array([sp[i] for sp in specs], np.int64) for i in range(4))
+    pdl = np.stack([flipped(rng, cdl[t], d) for t, d in zip(tl, dL)]); pdr = np.stack([flipped(rng, cdr[t], d) for t, d in zip(tr, dR)])
+    shift = rng.randint(2, 41, len(specs)).astype(np.float64)
+    prev = cur[tl] - np.stack([shift, np.zeros(len(specs))], 1)
+    check_planted(pdl, cdl, tl, dL); check_planted(pdr, cdr, tr, dR)
+    # the sequential joint filter (S4:145-160), on the planted structure alone
+    ltm, rtm, kept, n_th = set(), set(), [], 0
+    for k, (a, da, b, db) in enumerate(specs):
+        if da > ORB_TH or db > ORB_TH:
+            continue
+        n_th += 1
+        if a in ltm or b in rtm:
+            continue
+        ltm.add(a); rtm.add(b); kept.append(k)
+    s = _track(W, H, cur, cdl, cdr, prev, pdl, pdr, params, [(k, int(tl[k])) for k in kept if tl[k] == tr[k]], (n_th, len(kept)))
+    s.update(tl=tl, tr=tr, dL=dL, dR=dR, n_inconsistent=sum(1 for k in kept if tl[k] != tr[k]))
+    return s
+
+
+@drawn
+def track_threshold(rng):
+    """left / right distances on orb_th and one beyond, on either side only; a pairing over the threshold ahead of one that wants the same
+    train index (it must not block it); two pairings within the threshold on one train index (the second is a collision)"""
+    cur = _grid(rng, 64, step=8)
+    edge = [(ORB_TH, 5), (ORB_TH + 1, 5), (5, ORB_TH), (5, ORB_TH + 1), (ORB_TH, ORB_TH), (ORB_TH + 1, ORB_TH + 1)]
+    specs = []
+    for t in range(64):
+        if t < 24:
+            specs.append((t, edge[t % 6][0], t, edge[t % 6][1]))
+        elif t < 34:                                                              # over the threshold on one side, then a good one for the same pair
+            specs.append((t, ORB_TH + 1, t, 3) if t % 2 else (t, 3, t, ORB_TH + 1)); specs.append((t, 4, t, 4))
+        elif t < 42:                                                              # two good ones: the second collides
+            specs.append((t, 6, t, 6)); specs.append((t, 2, t, 2))
+        else:
+            specs.append((t, 1 + t % 9, t, 1 + t % 7))
+    return _specs_scene(rng, cur, specs, BF)
+
+
+@drawn
+def track_inconsistent(rng):
+    """survivors whose left and right train indices differ (S4:282): current pairings in same-row couples (a, b), one previous pairing that
+    wants (left a, right b) and none that wants a or b otherwise"""
+    cur = _grid(rng, 72, step=8)
+    couples = [i for i in range(len(cur) - 1) if cur[i, 1] == cur[i + 1, 1]][::3][:6]
+    assert len(couples) == 6
+    used = set(couples) | {c + 1 for c in couples}
+    specs = sorted([(t, 1 + t % 9, t, 1 + t % 7) for t in range(72) if t not in used] + [(c, 3, c + 1, 3) for c in couples])
+    return _specs_scene(rng, cur, specs, BF)
+
+
+WIN = dict(ifm_method=1, ifm_win_w=4, ifm_win_h=10)
+
+
+@drawn
+def win_edges(rng, W=320, H=120):
+    """ifmDescWin with windows of +-4 rows and +-10 pixels, one test per cell of a coarse grid (no window reaches a neighbour's candidates):
+    previous rows 0, 0.5, H - 2 and H - 1 (never visited), x windows whose (int) ends land on a current x and 0.5 short of it, the
+    complement (wraps to 0: wins) beside a 3-bit candidate, a lone candidate at 255 (never wins), two claimants of one current pairing"""
+    T = targets(rng, 64)
+    cur, prev, want = [], [], []                                                  # cur: (x, y, desc); prev: (x, y, desc, key of the expected current pairing or None)
+    t = [0]
+
+    def new():
+        t[0] += 1
+        return T[t[0] - 1]
+    cells = [(x, y) for y in (16, 30, 44, 58, 72, 86, 100) for x in (40, 80, 120, 160, 200, 240, 280)]
+    ci = iter(cells)
+    for row, (px, seen) in ((0.0, (40.5, True)), (0.5, (90.5, True)), (float(H - 2), (140.5, True)), (float(H - 1), (190.5, False))):   # rows at the table's ends
+        d = new(); cur.append((px + 3.0, row, d, "row%r" % row)); prev.append((px, row, flipped(rng, d, 5), "row%r" % row if seen else None))
+    for k, (off, seen) in enumerate([(-10.5, True), (-11.0, False), (9.5, True), (10.0, False)]):      # previous x = c + 0.5: (int)(x - 10) = c - 10, (int)(x + 10) = c + 10
+        x, y = next(ci); d = new()
+        cur.append((x + 0.5 + off, float(y), d, "xwin%d" % k)); prev.append((x + 0.5, float(y), flipped(rng, d, 5), "xwin%d" % k if seen else None))
+    for k in range(2):                                                            # the complement wraps to 0 and beats a 3-bit candidate, before or behind it
+        x, y = next(ci); d = new(); q = flipped(rng, d, 3)
+        xs = (x - 4.0, x + 4.0) if k == 0 else (x + 4.0, x - 4.0)
+        cur.append((xs[0], float(y), d, "near%d" % k)); cur.append((xs[1], float(y), np.bitwise_not(q), "wrap%d" % k))
+        prev.append((x, float(y), q, "wrap%d" % k))
+    x, y = next(ci); d = new(); q = np.bitwise_not(d).copy(); q[0] ^= 1                  # a lone candidate at distance 255: `<` from 255 never takes it
+    cur.append((x + 2.0, float(y), d, "d255")); prev.append((x, float(y), q, None))
+    for k, (d1, d2) in enumerate([(6, 6), (9, 4), (4, 9)]):                      # two claimants: the first keeps it unless the second is strictly better
+        x, y = next(ci); d = new()
+        cur.append((x, float(y), d, "claim%d" % k))
+        prev.append((x - 3.0, float(y), flipped(rng, d, d1), "claim%d" % k if d1 <= d2 else None)); prev.append((x + 3.0, float(y), flipped(rng, d, d2), "claim%d" % k if d2 < d1 else None))
+    for k in range(20):                                                           # plain cells: enough survivors for a RANSAC
+        x, y = next(ci); d = new()
+        cur.append((x + float(2 + k % 7), float(y + k % 5), d, "plain%d" % k)); prev.append((x, float(y + k % 5), flipped(rng, d, 1 + k % 8), "plain%d" % k))
+    co = np.lexsort(([c[0] for c in cur], [c[1] for c in cur])); po = np.lexsort(([p[0] for p in prev], [p[1] for p in prev]))
+    cur, prev = [cur[i] for i in co], [prev[i] for i in po]
+    at = {c[3]: i for i, c in enumerate(cur)}
+    want = sorted(((pi, at[p[3]]) for pi, p in enumerate(prev) if p[3] is not None), key=lambda v: v[1])
+    junk = targets(rng, len(prev) + len(cur))                                     # right descriptors play no part in this tracker
+    s = _track(W, H, [c[:2] for c in cur], [c[2] for c in cur], junk[:len(cur)], [p[:2] for p in prev], [p[2] for p in prev], junk[len(cur):], WIN, want, (len(want), len(want)))
+    return s
+
+
+def win_negative_rows(which):
+    """ransac_scenes.sideways_scene with rows from -24 (0) or rows from -48 and columns from -64 (1): previous AND current pairings on
+    negative rows, which the oracle's walk visits in iteration 0 (ri[1] counts every y <= 0); windows 20 / 45"""
+    s = dict(RS.sideways_scene(200, 1, 0.0, 0.0, yr=(-24, 200), step=8) if which == 0 else RS.sideways_scene(150, 2, 0.0, 0.0, xr=(-64, 400), yr=(-48, 160), step=8))
+    s["pri"] = matches_row_index(s["pm"], s["pkl"], s["H"]); s["cri"] = matches_row_index(s["cm"], s["ckl"], s["H"])
+    s.update(params=dict(ifm_method=1, ifm_win_w=20, ifm_win_h=45), want=None, th_col=None)
+    return s
+
+
+def track_tiny(seed, n_prev, n_cur, method, W=320, H=120):
+    """0 or 1 pairings in the previous or the current frame (the keypoint lists stay: 8 per frame)"""
+    rng = np.random.RandomState(seed)
+    cur = _grid(rng, 8, W=W, H=H, step=8)
+    T, R = targets(rng, 8), targets(rng, 8)
+    s = _track(W, H, cur, T, R, cur - np.array([5.0, 0.0]), np.stack([flipped(rng, d, 2) for d in T]), np.stack([flipped(rng, d, 2) for d in R]),
+               dict(WIN, ifm_win_w=20, ifm_win_h=45) if method else BF, None, None)
+    s["pm"], s["cm"] = s["pm"][:n_prev].copy(), s["cm"][:n_cur].copy()
+    s["pri"] = matches_row_index(s["pm"], s["pkl"], s["H"]); s["cri"] = matches_row_index(s["cm"], s["ckl"], s["H"])
+    return s
+
+
+TRACK = [
+    ("track-chain-300", track_chain, (1, 300)), ("track-chain-2100", track_chain, (1, 2100)), ("track-chain-4600", track_chain, (1, 4600)),
+    ("track-chain-40", track_chain, (2, 40)),
+    ("track-threshold", track_threshold, (1,)), ("track-inconsistent", track_inconsistent, (1,)),
+    ("win-edges", win_edges, (1,)), ("win-edges-640", win_edges, (1, 640, 480)),
+    ("track-tiny-0-8-bf-640", track_tiny, (3, 0, 8, 0, 640, 480)), ("track-tiny-8-0-win-640", track_tiny, (3, 8, 0, 1, 640, 480)),
+    ("win-negative-rows-0", win_negative_rows, (0,)), ("win-negative-rows-1", win_negative_rows, (1,)),
+] + [("track-tiny-%d-%d-%s" % (a, b, "win" if m else "bf"), track_tiny, (3, a, b, m)) for m in (0, 1) for a, b in ((0, 8), (8, 0), (1, 1), (0, 0), (1, 8), (8, 1))]
+CHAIN_MAX_KPS = {"track-chain-300": 1024, "track-chain-2100": 8192, "track-chain-4600": 16384}      # k_track_filter<16>, <32>, <64>
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    for nm, gen, args in STEREO + TRACK:
+        if nm == name:
+            return gen(*args)
+    raise KeyError(name)
+
+
+def stereo_names():
+    return [nm for nm, _, _ in STEREO]
+
+
+def track_names(small_only=False):
+    return [nm for nm, _, _ in TRACK if not (small_only and nm in ("track-chain-2100", "track-chain-4600"))]
+
+
+def track_params(p, s):
+    q = p.copy()
+    for k, v in s["params"].items():
+        setattr(q, k, v)
+    return q
+
+
+def filter_rounds(tl, tr, ok, n_cur):
+    """k_track_filter's round rule replayed in numpy: among the undecided candidates every k that is the smallest undecided claimant of both
+    its train indices is kept, then every undecided k with a taken train index is rejected.  -> (kept mask, number of rounds)"""
+    state = np.where(ok, 2, 0)
+    takenL, takenR = np.zeros(n_cur, bool), np.zeros(n_cur, bool)
+    rounds = 0
+    while (state == 2).any():
+        rounds += 1
+        u = np.flatnonzero(state == 2)
+        firstL, firstR = np.full(n_cur, 1 << 30), np.full(n_cur, 1 << 30)
+        np.minimum.at(firstL, tl[u], u); np.minimum.at(firstR, tr[u], u)
+        win = u[(firstL[tl[u]] == u) & (firstR[tr[u]] == u)]
+        state[win] = 1; takenL[tl[win]] = True; takenR[tr[win]] = True
+        u = np.flatnonzero(state == 2)
+        state[u[takenL[tl[u]] | takenR[tr[u]]]] = 0
+    return state == 1, rounds
+
+
+def unsorted_stereo():
+    """bf-rows with both lists in a shuffled order: outside the precondition of svo_put_features (ascending rows)"""
+    s = dict(scene("bf-rows"))
+    rng = np.random.RandomState(5)
+    pl, pr = rng.permutation(len(s["kl"])), rng.permutation(len(s["kr"]))
+    s.update(kl=s["kl"][pl], dl=s["dl"][pl], kr=s["kr"][pr], dr=s["dr"][pr])
+    return s
+
+
+def unsorted_track():
+    """win-edges with the previous pairing list in a shuffled order (the current one stays): the walk over the row table visits a pairing in
+    the iteration its POSITION in the list falls into, which is no longer the one its keypoint's row names"""
+    s = dict(scene("win-edges-640"))
+    rng = np.random.RandomState(6)
+    s["pm"] = s["pm"][rng.permutation(len(s["pm"]))]
+    s["pri"] = matches_row_index(s["pm"], s["pkl"], s["H"])
+    s["params"] = dict(ifm_method=1, ifm_win_w=200, ifm_win_h=10)                # rows: a window wide enough for a pairing met in another row's iteration
+    return s

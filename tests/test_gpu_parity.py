@@ -195,6 +195,14 @@ def test_hamming_match_against_oracle_and_properties():
         assert (idx == io).all() and (dist == do).all(), (nq, nt)
     idx, dist = ctx.hamming_match(q[:4], np.zeros((0, 32), np.uint8))
     assert (idx == -1).all()
+    # the extremes random bytes never reach: every bit different (256 -- beyond the 8 bits the row-by-row matchers keep), alone and for every
+    # train of a list, and a train list of one descriptor 257 times over (the first one wins)
+    zeros, ones = np.zeros((300, 32), np.uint8), np.full((300, 32), 255, np.uint8)
+    one = np.random.RandomState(1).randint(0, 256, (1, 32)).astype(np.uint8)                      # (a generator of its own: the draws below stay what they were)
+    for qq, tt in ((zeros, ones), (ones[:1], zeros[:1]), (np.bitwise_not(one), np.repeat(one, 300, 0)), (np.concatenate([one, np.bitwise_not(one), q[:5]]), np.repeat(one, 257, 0))):
+        idx, dist = ctx.hamming_match(qq, tt)
+        io, do = O().hamming_bf(qq, tt)
+        assert (idx == io).all() and (dist == do).all() and (idx[:2] == 0).all() and dist[min(1, len(qq) - 1)] == 256
     # full size beyond what the oracle covers quickly: size-independent properties on a sample of queries
     nq = nt = 30000
     q = rng.randint(0, 256, (nq, 32)).astype(np.uint8); t = rng.randint(0, 256, (nt, 32)).astype(np.uint8)
