@@ -146,8 +146,8 @@ __global__ void k_begin_frame(DevCtx c, ImgPtrs ptrs, unsigned flags, LaneMask d
     }
 }
 
-// getValues (H:704-724) packed for ONE transfer: header {n_left, n_right, n_matches, n_ids} at byte 0, then at byte 64 the
-// six lists at max_kps-strided offsets (left kps | right kps | left desc | right desc | pairings | pairing IDs); the
+// getValues (H:704-724) packed for ONE transfer, as ValuesRecord (svo_device.h) lays it out: header {n_left, n_right, n_matches,
+// n_ids}, then the six lists at max_kps-strided offsets (left kps | right kps | left desc | right desc | pairings | pairing IDs); the
 // previous / current slot is resolved here, on the device, so that the host needs no round trip to learn it.
 __global__ void __launch_bounds__(256) k_pack_values(DevCtx c, int lane, int which, int octave, uint8_t* dst)
 {
@@ -156,21 +156,20 @@ __global__ void __launch_bounds__(256) k_pack_values(DevCtx c, int lane, int whi
     const bool present = which ? s.has_prev != 0 : s.has_cur != 0;
     const int nl = present ? c.n_kps[feat_cnt_idx(vl, slot, 0)] : 0, nr = present ? c.n_kps[feat_cnt_idx(vl, slot, 1)] : 0;
     const int nm = present ? c.n_matches[vl * 2 + slot] : 0, ni = present ? c.n_ids[vl * 2 + slot] : 0;
-    const size_t MK = (size_t)c.max_kps;
-    uint4* out = (uint4*)(dst + 64);
+    const ValuesRecord V{c.max_kps};
     const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
     if (t == 0) { int32_t* h = (int32_t*)dst; h[0] = nl; h[1] = nr; h[2] = nm; h[3] = ni; }
     // everything is copied as 4-byte words (28-byte keypoints are not 16-byte multiples)
     auto copy_words = [&](const void* src, size_t dst_off, size_t nbytes) {
-        const uint32_t* sp = (const uint32_t*)src; uint32_t* dp = (uint32_t*)((uint8_t*)out + dst_off);
+        const uint32_t* sp = (const uint32_t*)src; uint32_t* dp = (uint32_t*)(dst + dst_off);
         for (size_t i = (size_t)t; i < nbytes / 4; i += (size_t)nt) dp[i] = sp[i];
     };
-    copy_words(c.kps + feat_base(c, vl, slot, 0), 0, (size_t)nl * sizeof(svo_keypoint));
-    copy_words(c.kps + feat_base(c, vl, slot, 1), MK * sizeof(svo_keypoint), (size_t)nr * sizeof(svo_keypoint));
-    copy_words(c.desc + feat_base(c, vl, slot, 0) * 32, 2 * MK * sizeof(svo_keypoint), (size_t)nl * 32);
-    copy_words(c.desc + feat_base(c, vl, slot, 1) * 32, 2 * MK * sizeof(svo_keypoint) + MK * 32, (size_t)nr * 32);
-    copy_words(c.matches + match_base(c, vl, slot), 2 * MK * (sizeof(svo_keypoint) + 32), (size_t)nm * sizeof(svo_dmatch));
-    copy_words(c.ids + match_base(c, vl, slot), 2 * MK * (sizeof(svo_keypoint) + 32) + MK * sizeof(svo_dmatch), (size_t)ni * 4);
+    copy_words(c.kps + feat_base(c, vl, slot, 0), V.left_kps(), (size_t)nl * sizeof(svo_keypoint));
+    copy_words(c.kps + feat_base(c, vl, slot, 1), V.right_kps(), (size_t)nr * sizeof(svo_keypoint));
+    copy_words(c.desc + feat_base(c, vl, slot, 0) * 32, V.left_desc(), (size_t)nl * 32);
+    copy_words(c.desc + feat_base(c, vl, slot, 1) * 32, V.right_desc(), (size_t)nr * 32);
+    copy_words(c.matches + match_base(c, vl, slot), V.matches(), (size_t)nm * sizeof(svo_dmatch));
+    copy_words(c.ids + match_base(c, vl, slot), V.ids(), (size_t)ni * 4);
 }
 void launch_pack_values(const DevCtx& c, int lane, int which, int octave, uint8_t* dst, hipStream_t st)
 {
@@ -1047,13 +1046,33 @@ __device__ __forceinline__ void rank_block(const DevCtx& c, int img, int level, 
 }
 
 
+// ------------------------------------------------------------------------------------------------------------
+// Dynamic LDS and global scratch of the detector kernels: ONE description per kernel, in the form of k_match.hip's.  A layout names
+// the arrays of the kernel's extern __shared__ block (and of its scratch region) in their order, each with its element type and
+// count, and the totals in bytes.  The kernel walks the block by these counts, the launcher passes total(), configure_nms_rowsort /
+// configure_faster_nms raise hipFuncAttributeMaxDynamicSharedMemorySize to total(), svo_api.hip allocates the scratch from the
+// exported *_scratch_* functions beside the layouts: no size of these kernels is written anywhere else.  Static __shared__ members
+// are not part of a layout; the static_asserts add them where they hold a total to the CU's 160 KB.
+// ------------------------------------------------------------------------------------------------------------
+#define LDS_FN __host__ __device__ constexpr int
+#define LDS_CU_BYTES (160 * 1024)
+template <int SEL_MAX>
+struct LdsSelectSort {                                   // k_select_sort<SEL_MAX> (+ 8336 B static)
+    LDS_FN n_keys() const { return SEL_MAX; }              // u64
+    LDS_FN n_tmp() const { return SEL_MAX; }               // u64
+    LDS_FN total() const { return 8 * (n_keys() + n_tmp()); }
+};
+static_assert(LdsSelectSort<2048>{}.total() == 32768 && LdsSelectSort<4096>{}.total() == 65536 && LdsSelectSort<8192>{}.total() == 131072, "k_select_sort LDS totals");
+static_assert(LdsSelectSort<8192>{}.total() + 8336 <= LDS_CU_BYTES, "gfx950: 160 KB of LDS per CU");
+
 // K3c: order the keys k_harris left in sel_resp
 template <int SEL_MAX>
 __global__ void __launch_bounds__(512) k_select_sort(DevCtx c)
 {
     SVO_TL_SCOPE(c, TL_SELECT_SORT, 0);
-    extern __shared__ __attribute__((aligned(16))) unsigned char ss_smem[];          // keys[SEL_MAX] | tmp[SEL_MAX] (72 KB of LDS in all at SEL_MAX = 4096)
-    unsigned long long* keys = (unsigned long long*)ss_smem, *tmp = keys + SEL_MAX;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ss_smem[];          // LdsSelectSort<SEL_MAX>
+    constexpr LdsSelectSort<SEL_MAX> L{};
+    unsigned long long* keys = (unsigned long long*)ss_smem, *tmp = keys + L.n_keys();
     __shared__ int cnt[SS_NB], off[SS_NB], scan_s[32];
     __shared__ unsigned sv[4];
     const int level = blockIdx.y, img = blockIdx.x, tid = threadIdx.x;
@@ -1415,31 +1434,56 @@ __global__ void k_publish_img0(DevCtx c, ImgPtrs ptrs)
 //   m_update_indexes(order=true) (stage2_detect.cpp:65-130): re-sort by (pt.y asc, rank asc).
 // Writes the final keypoints + descriptors of the lane's current slot.
 // ------------------------------------------------------------------------------------------------------------
+// The kernel's arrays for lists of ns_max keys (a power of two), in two parts.  The wide part (28 of the 31 bytes per key) lives in
+// LDS up to LDS_KEYS keys; above that it is more LDS than a CU has and lives in this (image, octave)'s region of
+// DevCtx::big_scratch.  The small part always follows in LDS (at its start when the wide part is in scratch).
+struct LdsNmsRowsort {                                   // k_nms_rowsort<NI> (no static LDS)
+    int ns_max;
+    static constexpr int LDS_KEYS = 4096, WIDE_PER_KEY = 8 + 2 * 2 * 4 + 4;
+    // wide part
+    LDS_FN n_keys() const { return ns_max; }               // u64
+    LDS_FN n_hash() const { return 2 * ns_max; }           // uint32_t, twice: hkey, hval
+    LDS_FN n_cellxy() const { return ns_max; }             // uint32_t
+    __host__ __device__ constexpr size_t wide_bytes() const { return (size_t)ns_max * WIDE_PER_KEY; }
+    // small part
+    LDS_FN n_acc_idx() const { return ns_max; }            // unsigned short: raw index of the i-th survivor
+    LDS_FN n_state() const { return ns_max; }              // unsigned char
+    LDS_FN n_scan() const { return 32; }                   // int, at the next 16-byte boundary (16 bytes of the total allow for it)
+    LDS_FN n_flag() const { return 8; }                    // int: the flag and seven spare words
+    LDS_FN small_bytes() const { return 2 * n_acc_idx() + n_state() + 16 + 4 * (n_scan() + n_flag()); }
+    __host__ __device__ constexpr bool wide_in_scratch() const { return ns_max > LDS_KEYS; }
+    LDS_FN total() const { return (wide_in_scratch() ? 0 : (int)wide_bytes()) + small_bytes(); }
+    __host__ __device__ constexpr size_t scratch_bytes(size_t regions) const { return wide_in_scratch() ? regions * wide_bytes() : 0; }      // regions = n_img x oct_cap
+};
+static_assert(LdsNmsRowsort{64}.total() == 31 * 64 + 176 && LdsNmsRowsort{4096}.total() == 31 * 4096 + 176 && LdsNmsRowsort{8192}.total() == 3 * 8192 + 176 && LdsNmsRowsort{16384}.total() == 3 * 16384 + 176, "k_nms_rowsort LDS totals");
+static_assert(LdsNmsRowsort{4096}.wide_bytes() == 28 * 4096 && LdsNmsRowsort{16384}.wide_bytes() == 28 * 16384 && LdsNmsRowsort{4096}.scratch_bytes(6) == 0 && LdsNmsRowsort{8192}.scratch_bytes(6) == 6 * 28 * 8192, "k_nms_rowsort wide part");
+static_assert(8 * LdsNmsRowsort{64}.n_keys() + 4 * (2 * LdsNmsRowsort{64}.n_hash() + LdsNmsRowsort{64}.n_cellxy()) == 28 * 64, "the wide arrays fill wide_bytes()");
+static_assert(LdsNmsRowsort{4096}.total() <= LDS_CU_BYTES && LdsNmsRowsort{16384}.total() <= LDS_CU_BYTES, "gfx950: 160 KB of LDS per CU");
+
 // NI = keys per thread: 4 (lists up to 4096), 8 (up to 8192) or 16 (up to 16384)
 template <int NI>
 __global__ void __launch_bounds__(1024) k_nms_rowsort(DevCtx c, int do_nms, int min_distance, int NS_MAX, int pre, uint8_t* big)
 {
     SVO_TL_SCOPE(c, TL_NMS, pre);
     SVO_LATENCY_CHAIN(c);
-    // dynamic LDS only (G17): keys[NS_MAX] u64 | hkey[2*NS_MAX] | hval[2*NS_MAX] | cellxy[NS_MAX] | acc_idx[NS_MAX] u16 | state[NS_MAX] u8 | scan[32] | flag
-    // Above 4096 keys that is more LDS than a CU has: the first four arrays (24 of the 27 bytes per key) then live in a global
-    // scratch region of this (image, octave) -- `big` -- and only the small ones stay in LDS.  Same code either way: barriers
-    // order a workgroup's global accesses as they order its LDS accesses, the atomics work on both.
+    // dynamic LDS only (G17), LdsNmsRowsort{NS_MAX}: the wide part at `big` when the launcher passes one.  Same code either way:
+    // barriers order a workgroup's global accesses as they order its LDS accesses, the atomics work on both.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int NS_HASH = 2 * NS_MAX;
+    const LdsNmsRowsort L{NS_MAX};
+    const int NS_HASH = L.n_hash();
     const int img = blockIdx.x, oct = blockIdx.y, lane_id = img >> 1, side = img & 1, tid = threadIdx.x;
     if (lane_idle(c, lane_id)) return;
     const bool raster = do_nms == 3;          // FAST + ORB with the NMS switched off: every corner, in cv::FAST's raster order
     if (raster) do_nms = 0;
-    unsigned char* wide = big ? big + ((size_t)img * c.oct_cap + oct) * ((size_t)NS_MAX * 28) : smem;
+    unsigned char* wide = big ? big + ((size_t)img * c.oct_cap + oct) * L.wide_bytes() : smem;
     unsigned long long* keys = (unsigned long long*)wide;
-    uint32_t* hkey = (uint32_t*)(keys + NS_MAX);
-    uint32_t* hval = hkey + NS_HASH;
-    uint32_t* cellxy = hval + NS_HASH;
-    unsigned short* acc_idx = (unsigned short*)(big ? smem : (unsigned char*)(cellxy + NS_MAX));          // raw index of the i-th survivor
-    unsigned char* state = (unsigned char*)(acc_idx + NS_MAX);
-    int* scan = (int*)(((uintptr_t)(state + NS_MAX) + 15) & ~(uintptr_t)15);
-    int* flag = scan + 32;
+    uint32_t* hkey = (uint32_t*)(keys + L.n_keys());
+    uint32_t* hval = hkey + L.n_hash();
+    uint32_t* cellxy = hval + L.n_hash();
+    unsigned short* acc_idx = (unsigned short*)(big ? smem : (unsigned char*)(cellxy + L.n_cellxy()));
+    unsigned char* state = (unsigned char*)(acc_idx + L.n_acc_idx());
+    int* scan = (int*)(((uintptr_t)(state + L.n_state()) + 15) & ~(uintptr_t)15);
+    int* flag = scan + L.n_scan();
     const int vl = lane_id * c.oct_cap + oct;
     const svo_keypoint* rk = c.raw_kps + (long long)img * c.raw_cap;
     // pre != 0 (ORB mode): this kernel runs BEFORE the describe kernel -- the reference's NMS needs positions and
@@ -1808,23 +1852,44 @@ struct FasterKeys {
     }
 };
 
+#define FO_PMAX 2048     // chunk size of k_fastorb_nms / k_faster_nms
+template <class Key>
+struct LdsChunkedNms {                                   // chunked_grid_nms<T>: k_fastorb_nms (32-bit keys), k_faster_nms (64-bit keys); no static LDS
+    int ns_max, acc_max;                                   // chunk size, capacity of the accepted-cell list
+    LDS_FN n_keys() const { return ns_max; }               // u64
+    LDS_FN n_prefix() const { return sizeof(Key) > 4 ? 2 : 0; }      // u64: 64-bit keys keep the prefix of their radix select here (32-bit keys: in sh)
+    LDS_FN n_hash() const { return 4 * ns_max; }           // uint32_t, twice: hkey, hval
+    LDS_FN n_cellxy() const { return ns_max; }             // uint32_t
+    LDS_FN n_acc_cells() const { return acc_max; }         // uint32_t: cell keys of everything accepted so far
+    LDS_FN n_hist() const { return 256; }                  // unsigned
+    LDS_FN n_scan() const { return 32; }                   // int
+    LDS_FN n_flag() const { return 1; }                    // int
+    LDS_FN n_sh() const { return 4; }                      // unsigned: s_need, s_sel, the prefix of 32-bit keys
+    LDS_FN n_state() const { return ns_max; }              // unsigned char
+    LDS_FN n_spare() const { return 7; }                   // words: nothing is carved from them; the total has always asked for them
+    LDS_FN total() const { return 8 * (n_keys() + n_prefix()) + 4 * (2 * n_hash() + n_cellxy() + n_acc_cells() + n_hist() + n_scan() + n_flag() + n_sh()) + n_state() + 4 * n_spare(); }
+};
+static_assert(LdsChunkedNms<uint32_t>{FO_PMAX, 4096}.total() == 109744 && LdsChunkedNms<unsigned long long>{FO_PMAX, 4096}.total() == 109760 &&
+              LdsChunkedNms<uint32_t>{FO_PMAX, 16384}.total() == 158896 && LdsChunkedNms<unsigned long long>{FO_PMAX, 16384}.total() == 158912, "chunked grid-NMS LDS totals");
+static_assert(LdsChunkedNms<unsigned long long>{FO_PMAX, 16384}.total() <= LDS_CU_BYTES, "gfx950: 160 KB of LDS per CU");
+
 template <class T>
 __device__ __forceinline__ void chunked_grid_nms(const DevCtx& c, unsigned char* smem, const typename T::Key* cand, int min_distance, int do_nms, int NS_MAX, int ACC_MAX)
 {
     typedef typename T::Key Key;
-    constexpr int PW = sizeof(Key) > 4 ? 2 : 0;                            // 64-bit keys: two LDS words of their own for the select's prefix
-    const int NS_HASH = 4 * NS_MAX;
-    unsigned long long* keys = (unsigned long long*)smem;                  // NS_MAX
-    uint32_t* hkey = (uint32_t*)(keys + NS_MAX + PW);                      // 4*NS_MAX
-    uint32_t* hval = hkey + NS_HASH;                                       // 4*NS_MAX
-    uint32_t* cellxy = hval + NS_HASH;                                     // NS_MAX
-    uint32_t* acc_cells = cellxy + NS_MAX;                                 // ACC_MAX: cell keys of everything accepted so far
-    unsigned* hist = acc_cells + ACC_MAX;                                  // 256
-    int* scan = (int*)(hist + 256);                                        // 32
-    int* flag = scan + 32;
-    unsigned* sh = (unsigned*)(flag + 1);                                  // s_need, s_sel, the prefix of 32-bit keys
-    Key* s_prefix = PW ? (Key*)(keys + NS_MAX) : (Key*)(sh + 2);
-    unsigned char* state = (unsigned char*)(sh + 4);                       // NS_MAX
+    const LdsChunkedNms<Key> L{NS_MAX, ACC_MAX};
+    const int NS_HASH = L.n_hash();
+    unsigned long long* keys = (unsigned long long*)smem;
+    uint32_t* hkey = (uint32_t*)(keys + L.n_keys() + L.n_prefix());
+    uint32_t* hval = hkey + L.n_hash();
+    uint32_t* cellxy = hval + L.n_hash();
+    uint32_t* acc_cells = cellxy + L.n_cellxy();
+    unsigned* hist = acc_cells + L.n_acc_cells();
+    int* scan = (int*)(hist + L.n_hist());
+    int* flag = scan + L.n_scan();
+    unsigned* sh = (unsigned*)(flag + L.n_flag());
+    Key* s_prefix = L.n_prefix() ? (Key*)(keys + L.n_keys()) : (Key*)(sh + 2);
+    unsigned char* state = (unsigned char*)(sh + L.n_sh());
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     if (lane_idle(c, img >> 1)) return;
     const LevelGeom& g = c.lv[level];
@@ -1977,11 +2042,25 @@ __global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned lo
 // order come from a radix select on the radius (ties at the cut-off by position), then one LDS sort of <= max_kps keys.
 // Scratch (global, per image): by_score[cand_total] (key of every corner, score-descending buckets), xy (their x | y << 16),
 // radius[cand_total].
+struct LdsFastorbAnms {                                  // k_fastorb_anms (+ 3264 B static)
+    int max_kps;
+    LDS_FN n_keys() const { int k = 64; while (k < max_kps) k <<= 1; return k; }      // u64: KMAX, the power of two >= cap
+    LDS_FN total() const { return 8 * n_keys(); }
+    // global scratch: three uint32_t arrays of n_img x cand_total words each
+    static constexpr int N_SCRATCH = 3;                    // by_score, radius, xy
+    static __host__ __device__ constexpr size_t scratch_array_words(int n_img, int cand_total) { return (size_t)n_img * cand_total; }
+    static __host__ __device__ constexpr size_t scratch_words(int n_img, int cand_total) { return N_SCRATCH * scratch_array_words(n_img, cand_total); }
+};
+static_assert(LdsFastorbAnms{16384}.total() == 16384 * 8 && LdsFastorbAnms{5000}.total() == 8192 * 8 && LdsFastorbAnms{16}.total() == 64 * 8, "k_fastorb_anms LDS totals");
+static_assert(LdsFastorbAnms{16384}.total() + 3264 <= LDS_CU_BYTES, "gfx950: 160 KB of LDS per CU");
+static_assert(LdsFastorbAnms::scratch_words(4, 1000) == 12000, "k_fastorb_anms scratch");
+#undef LDS_FN
+
 __global__ void __launch_bounds__(1024) k_fastorb_anms(DevCtx c, uint32_t* by_score_all, uint32_t* radius_all, uint32_t* xy_all, int KMAX)
 {
     SVO_TL_SCOPE(c, TL_NMS, 3);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* keys = (unsigned long long*)smem;                  // KMAX (power of two >= cap)
+    unsigned long long* keys = (unsigned long long*)smem;                  // LdsFastorbAnms: KMAX keys
     __shared__ unsigned hist[256], start[256], prefix_len[256];
     __shared__ int scan[40];
     __shared__ unsigned sh[8];
@@ -2099,10 +2178,11 @@ __global__ void __launch_bounds__(1024) k_fastorb_anms(DevCtx c, uint32_t* by_sc
 
 void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st)
 {
-    int kmax = 64; while (kmax < c.max_kps) kmax <<= 1;
-    const size_t one = (size_t)c.n_img * c.cand_total;
-    hipLaunchKernelGGL(k_fastorb_anms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)kmax * 8, st, c, scratch3, scratch3 + one, scratch3 + 2 * one, kmax);
+    const LdsFastorbAnms L{c.max_kps};
+    const size_t one = L.scratch_array_words(c.n_img, c.cand_total);
+    hipLaunchKernelGGL(k_fastorb_anms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, scratch3, scratch3 + one, scratch3 + 2 * one, L.n_keys());
 }
+size_t fastorb_anms_scratch_words(int n_img, int cand_total) { return LdsFastorbAnms::scratch_words(n_img, cand_total); }
 
 // ------------------------------------------------------------------------------------------------------------
 // dmFASTER (stage2_detect.cpp:519-576): FAST-12 corners of every x1/2 octave image at ONE constant threshold, ranked by
@@ -2259,21 +2339,24 @@ void launch_fast(const DevCtx& c, hipStream_t st)
     hipLaunchKernelGGL(k_fast, dim3((unsigned)((total + unit - 1) / unit * unit)), dim3(FT_NT), 0, st, c);
 }
 
+// The one ladder over the instantiations of k_select / k_select_sort: f(std::integral_constant<int, SEL_MAX>), SEL_MAX >= sel_max
+template <class F> static auto select_form(int sel_max, F f)
+{
+    if (sel_max > 4096) return f(std::integral_constant<int, 8192>());
+    if (sel_max > 2048) return f(std::integral_constant<int, 4096>());
+    return f(std::integral_constant<int, 2048>());
+}
+
 void launch_select(const DevCtx& c, hipStream_t st)
 {
-    const bool big = c.sel_max > 2048, wide = c.sel_max > 4096;
-    if (wide) hipLaunchKernelGGL(k_select<8192>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
-    else if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
-    else hipLaunchKernelGGL(k_select<2048>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 0);
+    const dim3 grid(c.n_img, c.n_levels);
+    auto select = [&](int pass) { select_form(c.sel_max, [&](auto s) { hipLaunchKernelGGL(k_select<decltype(s)::value>, grid, dim3(512), 0, st, c, pass); }); };
+    select(0);
     // the pairs whose speculated FAST threshold was too high (normally none: both launches retire at once)
     hipLaunchKernelGGL(k_fast_redo, dim3(4096), dim3(FT_NT), 0, st, c);
-    if (wide) hipLaunchKernelGGL(k_select<8192>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
-    else if (big) hipLaunchKernelGGL(k_select<4096>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
-    else hipLaunchKernelGGL(k_select<2048>, dim3(c.n_img, c.n_levels), dim3(512), 0, st, c, 1);
+    select(1);
     hipLaunchKernelGGL(k_harris, dim3(c.n_img, c.sel_max / 256, c.n_levels), dim3(256), 0, st, c);
-    if (wide) hipLaunchKernelGGL(k_select_sort<8192>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)8192 * 16, st, c);
-    else if (big) hipLaunchKernelGGL(k_select_sort<4096>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)4096 * 16, st, c);
-    else hipLaunchKernelGGL(k_select_sort<2048>, dim3(c.n_img, c.n_levels), dim3(512), (size_t)2048 * 16, st, c);
+    select_form(c.sel_max, [&](auto s) { constexpr int S = decltype(s)::value; hipLaunchKernelGGL(k_select_sort<S>, grid, dim3(512), (size_t)LdsSelectSort<S>{}.total(), st, c); });
 }
 
 void launch_describe(const DevCtx& c, const Knobs& k, int pre, hipStream_t st)
@@ -2306,7 +2389,8 @@ void launch_sad_patch_slot(const DevCtx& c, int which, hipStream_t st)
     hipLaunchKernelGGL(k_sad_patch_slot, dim3((c.max_kps + 31) / 32, c.n_lanes * c.oct_cap * 2), dim3(256), 0, st, c, which);
 }
 
-#define FO_PMAX 2048     // chunk size of k_fastorb_nms / k_faster_nms (LDS: 45 B per entry)
+// the layout both chunked kernels are launched with: chunks of FO_PMAX keys, room for max_kps accepted cells
+template <class T> static LdsChunkedNms<typename T::Key> chunked_nms_layout(const DevCtx& c) { return {FO_PMAX, c.max_kps}; }
 static int nms_pmax(const DevCtx& c)
 {
     // keys per block: ORB mode gathers every level of an image (n_slots), FAST+ORB mode one octave's quota
@@ -2314,48 +2398,44 @@ static int nms_pmax(const DevCtx& c)
     if (c.fast_orb) { for (int l = 0; l < c.n_levels; l++) if (c.lv[l].quota > n) n = c.lv[l].quota; } else n = c.n_slots;
     int p = 64; while (p < n) p <<= 1; return p;
 }
-static size_t nms_rowsort_smem(int pmax) { return pmax > 4096 ? (size_t)pmax * 3 + 16 + 4 * 40 : (size_t)pmax * (8 + 8 + 8 + 4 + 2 + 1) + 16 + 4 * 40; }
-// LDS of chunked_grid_nms over keys of key_bytes: 64-bit keys add the two prefix words of their radix select
-static size_t chunked_nms_smem(int pmax, int accmax, size_t key_bytes) { return (size_t)pmax * (8 + 16 + 16 + 4 + 1) + (size_t)accmax * 4 + 4 * (256 + 32 + 8) + 16 + (key_bytes > 4 ? 16 : 0); }
-
-int nms_rowsort_items(const DevCtx& c) { const int pmax = nms_pmax(c); return pmax > 8192 ? 16 : (pmax > 4096 ? 8 : 4); }      // the instantiation launch_nms_rowsort picks
-
-size_t nms_rowsort_scratch_bytes(const DevCtx& c)          // global scratch of k_nms_rowsort for lists above 4096 keys (0: everything fits LDS)
+// The one ladder over the instantiations of k_nms_rowsort: f(std::integral_constant<int, NI>), NI keys per thread of a 1024-thread block
+template <class F> static auto nms_rowsort_form(int pmax, F f)
 {
-    const int pmax = nms_pmax(c);
-    return pmax > 4096 ? (size_t)c.n_img * c.oct_cap * (size_t)pmax * 28 : 0;
+    if (pmax > 8192) return f(std::integral_constant<int, 16>());
+    if (pmax > 4096) return f(std::integral_constant<int, 8>());
+    return f(std::integral_constant<int, 4>());
 }
 
+int nms_rowsort_items(const DevCtx& c) { return nms_rowsort_form(nms_pmax(c), [](auto n) { return (int)decltype(n)::value; }); }      // the instantiation launch_nms_rowsort picks
+
+// DevCtx::big_scratch for lists of up to n_keys keys (0: everything fits LDS)
+size_t nms_rowsort_scratch_bytes(int n_img, int oct_cap, int n_keys) { return LdsNmsRowsort{n_keys}.scratch_bytes((size_t)n_img * oct_cap); }
+
+// Every dynamic-LDS kernel of the detector that this geometry launches gets the limit its launcher will ask for.
 hipError_t configure_nms_rowsort(const DevCtx& c)
 {
-    hipError_t e = svo_raise_dyn_smem((const void*)k_fastorb_nms, chunked_nms_smem(FO_PMAX, c.max_kps, 4));
+    hipError_t e = svo_raise_dyn_smem((const void*)k_fastorb_nms, chunked_nms_layout<FastOrbKeys>(c).total());
     if (e != hipSuccess) return e;
-    int kmax = 64; while (kmax < c.max_kps) kmax <<= 1;
-    e = svo_raise_dyn_smem((const void*)k_fastorb_anms, (size_t)kmax * 8);
+    e = svo_raise_dyn_smem((const void*)k_fastorb_anms, LdsFastorbAnms{c.max_kps}.total());
     if (e != hipSuccess) return e;
-    e = svo_raise_dyn_smem((const void*)k_select_sort<4096>, 4096 * 16);
+    e = select_form(c.sel_max, [](auto s) { constexpr int S = decltype(s)::value; return svo_raise_dyn_smem((const void*)k_select_sort<S>, LdsSelectSort<S>{}.total()); });
     if (e != hipSuccess) return e;
-    if (c.sel_max > 4096) { e = svo_raise_dyn_smem((const void*)k_select_sort<8192>, 8192 * 16); if (e != hipSuccess) return e; }
     const int pmax = nms_pmax(c);
     if (pmax > 16384) return hipErrorInvalidValue;
-    if (pmax > 8192) { e = svo_raise_dyn_smem((const void*)k_nms_rowsort<16>, nms_rowsort_smem(16384)); if (e != hipSuccess) return e; }
-    e = svo_raise_dyn_smem((const void*)k_nms_rowsort<8>, nms_rowsort_smem(8192));
-    if (e != hipSuccess) return e;
-    return svo_raise_dyn_smem((const void*)k_nms_rowsort<4>, nms_rowsort_smem(pmax > 4096 ? 4096 : pmax));
+    return nms_rowsort_form(pmax, [&](auto n) { return svo_raise_dyn_smem((const void*)k_nms_rowsort<decltype(n)::value>, LdsNmsRowsort{pmax}.total()); });
 }
 
 void launch_nms_rowsort(const DevCtx& c, const Knobs& k, int do_nms, int min_distance, int pre, hipStream_t st)
 {
-    const int pmax = nms_pmax(c);
+    const LdsNmsRowsort L{nms_pmax(c)};
+    const int pmax = L.ns_max;
     // threads per image: every phase strides by blockDim.x and a thread holds NI = 4 keys, so lists of up to 2048 keys also run on 512
     // threads (8 waves instead of 16 to find room for on a CU that the detector's tiles fill); SVO_NMS_NT = 512 / 1024 for an A/B
     const int nt = (pmax <= 2048 && k.nms_nt == 512) ? 512 : 1024;
-    const dim3 grid(c.n_img, c.n_oct);
-    const size_t lds = nms_rowsort_smem(pmax);
     const int mode = c.fast_orb ? (do_nms == 3 ? 3 : 0) : do_nms, pre_pass = (pre && !c.fast_orb) ? 1 : 0;
-    if (pmax > 8192) hipLaunchKernelGGL(k_nms_rowsort<16>, grid, dim3(1024), lds, st, c, mode, min_distance, pmax, pre_pass, c.big_scratch);
-    else if (pmax > 4096) hipLaunchKernelGGL(k_nms_rowsort<8>, grid, dim3(1024), lds, st, c, mode, min_distance, pmax, pre_pass, c.big_scratch);
-    else hipLaunchKernelGGL(k_nms_rowsort<4>, grid, dim3(nt), lds, st, c, mode, min_distance, pmax, pre_pass, (uint8_t*)nullptr);
+    nms_rowsort_form(pmax, [&](auto n) {
+        hipLaunchKernelGGL(k_nms_rowsort<decltype(n)::value>, dim3(c.n_img, c.n_oct), dim3(nt), (size_t)L.total(), st, c, mode, min_distance, pmax, pre_pass, L.wide_in_scratch() ? c.big_scratch : (uint8_t*)nullptr);
+    });
 }
 
 void launch_half(const DevCtx& c, int level, hipStream_t st)
@@ -2366,7 +2446,8 @@ void launch_half(const DevCtx& c, int level, hipStream_t st)
 
 void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_fastorb_nms, dim3(c.n_levels, c.n_img), dim3(1024), chunked_nms_smem(FO_PMAX, c.max_kps, 4), st, c, min_distance, do_nms, FO_PMAX, c.max_kps);
+    const auto L = chunked_nms_layout<FastOrbKeys>(c);
+    hipLaunchKernelGGL(k_fastorb_nms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, min_distance, do_nms, L.ns_max, L.acc_max);
 }
 
 void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st)
@@ -2375,9 +2456,10 @@ void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int
     hipLaunchKernelGGL(k_faster, dim3((unsigned)((long long)c.n_tiles * c.n_img)), dim3(FK_NT), 0, st, c, cand64, fast_th, klt_win);
 }
 
-hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, chunked_nms_smem(FO_PMAX, c.max_kps, 8)); }
+hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, chunked_nms_layout<FasterKeys>(c).total()); }
 
 void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), chunked_nms_smem(FO_PMAX, c.max_kps, 8), st, c, cand64, min_distance, do_nms, FO_PMAX, c.max_kps);
+    const auto L = chunked_nms_layout<FasterKeys>(c);
+    hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, cand64, min_distance, do_nms, L.ns_max, L.acc_max);
 }

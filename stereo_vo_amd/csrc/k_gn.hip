@@ -227,7 +227,6 @@ __device__ void delta_to_pose(const double* dp, double* pose)
 // therefore depends on what a frame of the workload tracks (a few hundred pairs), not on the capacity of the context's lists:
 // 33 KB instead of 123 KB at max_kps 4096, so that a lane's block finds room on a CU beside the detector's tiles (round 5).
 #define GN_LCAP 1024
-#define GN_MASK_HEAD 16       // bytes in front of a lane's mask in the mask-out array: int ended_valid, int T (gn_mask_bytes_per_lane)
 struct GnShared {
     double part[GN_NT_MAX / 64][GN_NSUM];      // the 28 sums of every wave (reduced inside the wave on the DPP / permlane network)
     double tot[GN_NSUM];
@@ -238,6 +237,39 @@ struct GnShared {
     int ok;
     int n_non_masked;
 };
+
+// Dynamic LDS and scratch of k_gauss_newton<NT>: ONE description (the form of k_match.hip's layouts).  The per-entry arrays keys |
+// hkey, hval | cellxy | state | mask hold n entries each: n = lc() in LDS, n = pmax in the lane's region of DevCtx::gn_scratch.  In
+// LDS scan[] and one GnShared follow them.  No static LDS.
+#define LDS_FN __host__ __device__ constexpr int
+struct LdsGaussNewton {
+    int pmax;
+    static constexpr int PER_ENTRY = 8 + 2 * 2 * 4 + 4 + 1 + 1;
+    LDS_FN lc() const { return pmax < GN_LCAP ? pmax : GN_LCAP; }
+    static LDS_FN n_keys(int n) { return n; }              // u64
+    static LDS_FN n_hash(int n) { return 2 * n; }          // uint32_t, twice: hkey, hval
+    static LDS_FN n_cellxy(int n) { return n; }            // uint32_t
+    static LDS_FN n_state(int n) { return n; }             // unsigned char
+    static LDS_FN n_mask(int n) { return n; }              // unsigned char
+    static __host__ __device__ constexpr size_t entry_bytes(int n) { return (size_t)n * PER_ENTRY; }
+    LDS_FN n_scan() const { return 40; }                   // int
+    LDS_FN n_spare() const { return 16; }                  // bytes behind the GnShared: nothing is carved from them; the total has always asked for them
+    LDS_FN total() const { return (int)entry_bytes(lc()) + 4 * n_scan() + (int)sizeof(GnShared) + n_spare(); }
+    __host__ __device__ constexpr size_t scratch_bytes_per_lane() const { return entry_bytes(pmax); }
+};
+#undef LDS_FN
+static_assert(8 * LdsGaussNewton::n_keys(64) + 4 * (2 * LdsGaussNewton::n_hash(64) + LdsGaussNewton::n_cellxy(64)) + LdsGaussNewton::n_state(64) + LdsGaussNewton::n_mask(64) == 30 * 64, "the per-entry arrays fill entry_bytes()");
+static_assert(sizeof(GnShared) == 2424 && LdsGaussNewton{64}.total() == 4520 && LdsGaussNewton{1024}.total() == 33320 && LdsGaussNewton{16384}.total() == 33320, "k_gauss_newton LDS totals: 30 * min(pmax, 1024) + 160 + 2424 + 16");
+static_assert(LdsGaussNewton{64}.scratch_bytes_per_lane() == 30 * 64 && LdsGaussNewton{16384}.scratch_bytes_per_lane() == 30 * 16384, "k_gauss_newton scratch");
+static_assert(LdsGaussNewton{16384}.total() <= 160 * 1024, "gfx950: 160 KB of LDS per CU");
+// What k_gauss_newton leaves per lane in GNParams::mask_out for k_pose_covariance (svo_set_pose_covariance allocates it):
+// {int ended_valid, int T, pad to HEAD} | mask[pmax]
+struct GnMaskRecord {
+    int pmax;
+    static constexpr int HEAD = 16;
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)pmax + HEAD; }
+};
+static_assert(GnMaskRecord{64}.bytes() == 64 + 16 && GnMaskRecord{16384}.bytes() == 16384 + 16, "mask-out record");
 
 // ---- the 28 sums of a wave without LDS ----------------------------------------------------------------------------------
 // v_permlane16_swap / v_permlane32_swap (gfx950) exchange the odd rows of one register with the even rows of another (the upper
@@ -483,14 +515,14 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
 {
     SVO_TL_SCOPE(c, TL_GN, 0);
     SVO_LATENCY_CHAIN(c);
-    // dynamic LDS: keys[LC] u64 | hkey[2 LC] | hval[2 LC] | cellxy[LC] | state[LC] u8 | mask[LC] u8 | scan[40] | GnShared, LC = min(pmax, GN_LCAP).
-    // A lane that tracks more than LC pairs (`big`) keeps the same arrays, sized pmax, in its region of c.gn_scratch.
+    // dynamic LDS: LdsGaussNewton{pmax}.  A lane that tracks more than LC pairs (`big`) keeps the per-entry arrays, sized pmax, in its region of c.gn_scratch.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int PM = P.pmax, LC = PM < GN_LCAP ? PM : GN_LCAP;
+    const LdsGaussNewton L{P.pmax};
+    const int PM = P.pmax, LC = L.lc();
     const int lane_id = blockIdx.x, tid = threadIdx.x;
     if (lane_idle(c, lane_id)) return;
-    int* scan = (int*)(smem + (size_t)LC * 30);
-    GnShared& sh = *(GnShared*)(scan + 40);
+    int* scan = (int*)(smem + L.entry_bytes(LC));
+    GnShared& sh = *(GnShared*)(scan + L.n_scan());
     LaneState& ls = c.lane[lane_id];
     svo_result& res = c.results[lane_id];
     if (!P.standalone && (!ls.has_prev || ls.m_error == SVO_VOEC_BAD_TRACKING)) return;      // P:305, P:332
@@ -511,13 +543,13 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
 
     const bool big = T > LC;                                                     // block-uniform
     const int AN = big ? PM : LC;
-    unsigned char* abase = big ? scratch + (size_t)lane_id * ((size_t)PM * 30) : smem;
+    unsigned char* abase = big ? scratch + (size_t)lane_id * L.scratch_bytes_per_lane() : smem;
     unsigned long long* keys = (unsigned long long*)abase;
-    uint32_t* hkey = (uint32_t*)(keys + AN);
-    uint32_t* hval = hkey + 2 * AN;
-    uint32_t* cellxy = hval + 2 * AN;
-    unsigned char* state = (unsigned char*)(cellxy + AN);
-    unsigned char* mask = state + AN;
+    uint32_t* hkey = (uint32_t*)(keys + L.n_keys(AN));
+    uint32_t* hval = hkey + L.n_hash(AN);
+    uint32_t* cellxy = hval + L.n_hash(AN);
+    unsigned char* state = (unsigned char*)(cellxy + L.n_cellxy(AN));
+    unsigned char* mask = state + L.n_state(AN);
     int Pn = 64; while (Pn < T) Pn <<= 1;
     // ---- gather the four keypoint lists (S5:419-461, single octave) and the NMS sort keys ----
     for (int i = tid; i < Pn; i += blockDim.x) keys[i] = 0;
@@ -682,20 +714,15 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         res.n_residual = n_res > T ? n_res : T; res.n_outliers = n_out;
         res.valid = !abort_;                                                                                         // S5:727
     }
-    // svo_set_pose_covariance: the final mask, T and whether this run ended valid, for k_pose_covariance (layout at gn_mask_bytes_per_lane)
+    // svo_set_pose_covariance: the final mask, T and whether this run ended valid, for k_pose_covariance (GnMaskRecord)
     if (P.mask_out) {
-        uint8_t* mo = P.mask_out + (size_t)lane_id * ((size_t)PM + GN_MASK_HEAD);
-        for (int m = tid; m < T; m += blockDim.x) mo[GN_MASK_HEAD + m] = mask[m];
+        uint8_t* mo = P.mask_out + (size_t)lane_id * GnMaskRecord{PM}.bytes();
+        for (int m = tid; m < T; m += blockDim.x) mo[GnMaskRecord::HEAD + m] = mask[m];
         if (tid == 0) { ((int*)mo)[0] = !abort_; ((int*)mo)[1] = T; }
     }
 }
 
-static size_t gn_smem(int pmax)
-{
-    const int lc = pmax < GN_LCAP ? pmax : GN_LCAP;
-    return (size_t)lc * 30 + sizeof(int) * 40 + sizeof(GnShared) + 16;
-}
-size_t gn_scratch_bytes_per_lane(int pmax) { return (size_t)pmax * 30; }
+size_t gn_scratch_bytes_per_lane(int pmax) { return LdsGaussNewton{pmax}.scratch_bytes_per_lane(); }
 
 hipError_t svo_raise_dyn_smem(const void* kernel, size_t bytes)
 {
@@ -717,7 +744,7 @@ hipError_t svo_raise_dyn_smem(const void* kernel, size_t bytes)
 hipError_t configure_gauss_newton(int pmax)
 {
     for (const void* fn : { (const void*)k_gauss_newton<256>, (const void*)k_gauss_newton<384>, (const void*)k_gauss_newton<512> }) {
-        const hipError_t e = svo_raise_dyn_smem(fn, gn_smem(pmax));
+        const hipError_t e = svo_raise_dyn_smem(fn, LdsGaussNewton{pmax}.total());
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -735,17 +762,17 @@ template <class F> static void gn_for_threads(int nt, F f)
 
 void launch_gauss_newton(const DevCtx& c, const Knobs& k, const GNParams& P, hipStream_t st)
 {
-    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_gauss_newton<NT>, dim3(c.n_lanes), dim3(NT), gn_smem(P.pmax), st, c, P, c.gn_scratch); });
+    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_gauss_newton<NT>, dim3(c.n_lanes), dim3(NT), (size_t)LdsGaussNewton{P.pmax}.total(), st, c, P, c.gn_scratch); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // The covariance of the pose increment (svo_set_pose_covariance, contract at svo_pose_cov in svo_types.h): no reference
 // counterpart.  One more evaluation at the delta stage 5 returned, over the mask k_gauss_newton ended with (its mask-out array:
-// per lane GN_MASK_HEAD bytes {int ended_valid, int T}, then pmax mask bytes) and the landmarks as it last triangulated them.
+// one GnMaskRecord per lane) and the landmarks as it last triangulated them.
 // A kernel of its own and not a tail of k_gauss_newton: the tail would add its 6 x 6 algebra to a kernel whose iteration body is
 // sized to the instruction cache (see there), and to every context that never asks for a covariance.
 // ------------------------------------------------------------------------------------------------------------
-size_t gn_mask_bytes_per_lane(int pmax) { return (size_t)pmax + GN_MASK_HEAD; }
+size_t gn_mask_bytes_per_lane(int pmax) { return GnMaskRecord{pmax}.bytes(); }
 
 struct CovShared {
     double part[GN_NT_MAX / 64][GN_NSUM];
@@ -801,7 +828,7 @@ __global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, sv
     __shared__ CovShared sh;
     const int lane_id = blockIdx.x, tid = threadIdx.x;
     if (lane_idle(c, lane_id)) return;                                       // an idle lane keeps its record
-    uint8_t* mo = P.mask_out + (size_t)lane_id * ((size_t)P.pmax + GN_MASK_HEAD);
+    uint8_t* mo = P.mask_out + (size_t)lane_id * GnMaskRecord{P.pmax}.bytes();
     svo_pose_cov& o = out[lane_id];
     if (tid == 0) {
         sh.ended_valid = ((const int*)mo)[0]; sh.T = ((const int*)mo)[1];
@@ -817,7 +844,7 @@ __global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, sv
     __syncthreads();
     if (!sh.ended_valid) return;
     const int T = sh.T < P.pmax ? sh.T : P.pmax;
-    const unsigned char* mask = mo + GN_MASK_HEAD;
+    const unsigned char* mask = mo + GnMaskRecord::HEAD;
     const svo_stereo_camera cam = c.cams[lane_id];
     const float* obs = c.gn_obs + (long long)lane_id * c.max_kps * 8;
     const double* lmk = c.gn_lmk + (long long)lane_id * c.max_kps * 3;

@@ -427,7 +427,8 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     HIPCHECK(dev_alloc(ctx, &d.sel_keys, (size_t)NI * SVO_MAX_LEVELS * d.sel_max));
     HIPCHECK(dev_alloc(ctx, &d.sel_resp, (size_t)NI * SVO_MAX_LEVELS * d.sel_max));
     d.big_scratch = nullptr; d.gn_scratch = nullptr;
-    if (MK > 4096) HIPCHECK(dev_alloc(ctx, &d.big_scratch, (size_t)NI * OC * (size_t)MK * 28));
+    // (the geometry, and with it the kernel's own list length, is not known yet: room for lists of max_kps keys)
+    if (const size_t bytes = nms_rowsort_scratch_bytes(NI, OC, MK)) HIPCHECK(dev_alloc(ctx, &d.big_scratch, bytes));
     HIPCHECK(dev_alloc(ctx, &d.gn_scratch, (size_t)L * gn_scratch_bytes_per_lane(MK)));      // lanes that track more than GN_LCAP pairs (k_gn.hip)
     HIPCHECK(dev_alloc(ctx, &d.sel_n, (size_t)NI * SVO_MAX_LEVELS));
     HIPCHECK(dev_alloc(ctx, &d.lvl_n, (size_t)NI * SVO_MAX_LEVELS));
@@ -1286,7 +1287,7 @@ static int ensure_call_buffers(svo_ctx* ctx, const FrameCall& call)
 {
     const DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
     if ((call.flags & SVO_RUN_DETECT) && d.fast_orb && !call.faster && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE && !ctx->d_anms)
-        HIPCHECK(dev_alloc(ctx, &ctx->d_anms, (size_t)3 * d.n_img * ctx->cand_total_alloc));
+        HIPCHECK(dev_alloc(ctx, &ctx->d_anms, fastorb_anms_scratch_words(d.n_img, ctx->cand_total_alloc)));
     if ((call.flags & SVO_RUN_DETECT) && call.faster && !ctx->d_cand64) HIPCHECK(dev_alloc(ctx, &ctx->d_cand64, (size_t)d.n_img * ctx->cand_total_alloc));
     return call.sad_any ? ensure_sad_buffers(ctx) : SVO_OK;
 }
@@ -1539,9 +1540,9 @@ extern "C" int svo_get_values(svo_ctx* ctx, int lane, int which, int octave, svo
 {
     if (ctx) use_device(ctx);
     if (bad_list_args(ctx, lane, which, 0, octave) || !v || v->cap_kps < 0 || v->cap_matches < 0) return SVO_ERR_ARG;
-    const int MK = ctx->dc.max_kps;
+    const ValuesRecord V{ctx->dc.max_kps};
     if (!ctx->d_vals) {
-        ctx->vals_bytes = 64 + (size_t)MK * (2 * (sizeof(svo_keypoint) + 32) + sizeof(svo_dmatch) + sizeof(int32_t));
+        ctx->vals_bytes = V.total();
         HIPCHECK(dev_alloc(ctx, &ctx->d_vals, ctx->vals_bytes));
         HIPCHECK(hipHostMalloc((void**)&ctx->h_vals, ctx->vals_bytes, hipHostMallocDefault));
     }
@@ -1555,9 +1556,8 @@ extern "C" int svo_get_values(svo_ctx* ctx, int lane, int which, int octave, svo
     collect_spans(ctx);
     const int32_t* hdr = (const int32_t*)ctx->h_vals;
     v->n_left = hdr[0]; v->n_right = hdr[1]; v->n_matches = hdr[2]; v->n_ids = hdr[3];
-    const uint8_t* b = ctx->h_vals + 64;
-    const uint8_t* kl = b, *kr = kl + (size_t)MK * sizeof(svo_keypoint), *dl = kr + (size_t)MK * sizeof(svo_keypoint), *dr = dl + (size_t)MK * 32;
-    const uint8_t* mm = dr + (size_t)MK * 32, *ii = mm + (size_t)MK * sizeof(svo_dmatch);
+    const uint8_t* b = ctx->h_vals;
+    const uint8_t* kl = b + V.left_kps(), *kr = b + V.right_kps(), *dl = b + V.left_desc(), *dr = b + V.right_desc(), *mm = b + V.matches(), *ii = b + V.ids();
     const int nl = v->n_left < v->cap_kps ? v->n_left : v->cap_kps, nr = v->n_right < v->cap_kps ? v->n_right : v->cap_kps;
     const int nm = v->n_matches < v->cap_matches ? v->n_matches : v->cap_matches, ni = v->n_ids < v->cap_matches ? v->n_ids : v->cap_matches;
     if (v->left_kps && nl > 0) memcpy(v->left_kps, kl, sizeof(svo_keypoint) * nl);

@@ -194,6 +194,22 @@ struct DevCtx {
     int carry_win;            // the context's hand-over records carry the SAD windows (version 3): from the first svo_set_params that selects smSAD or ifmSAD, for good
 };
 
+// The record k_pack_values writes and svo_get_values reads back in one transfer: a 64-byte header {int32 n_left, n_right, n_matches,
+// n_ids, rest unused}, then the six lists, each with room for max_kps entries.  Byte offsets from the record's start.
+struct ValuesRecord {
+    int max_kps;
+#define VR_FN __host__ __device__ constexpr size_t
+    VR_FN left_kps() const { return 64; }
+    VR_FN right_kps() const { return left_kps() + (size_t)max_kps * sizeof(svo_keypoint); }
+    VR_FN left_desc() const { return right_kps() + (size_t)max_kps * sizeof(svo_keypoint); }
+    VR_FN right_desc() const { return left_desc() + (size_t)max_kps * 32; }
+    VR_FN matches() const { return right_desc() + (size_t)max_kps * 32; }
+    VR_FN ids() const { return matches() + (size_t)max_kps * sizeof(svo_dmatch); }
+    VR_FN total() const { return ids() + (size_t)max_kps * sizeof(int32_t); }
+#undef VR_FN
+};
+static_assert(ValuesRecord{1024}.total() == 64 + 1024 * 140 && ValuesRecord{1024}.ids() == 64 + 1024 * 136, "svo_get_values record: 2 x (28 + 32) + 16 + 4 bytes per entry");
+
 struct TlRec { unsigned long long t0, t1; };
 #define SVO_TL_STEPS 16
 #define SVO_TL_SUB 128

@@ -56,11 +56,12 @@ void launch_sad_patch(const DevCtx& c, hipStream_t st);       // needs DevCtx.sa
 void launch_publish_img0(const DevCtx& c, const uint8_t* const* ptrs, hipStream_t st);      // svo_gather_windows: the level-0 pointer table of the active lanes, nothing else
 void launch_sad_patch_slot(const DevCtx& c, int which, hipStream_t st);                    // the same gather for slot `which` (0 current, 1 previous) of put / loaded lists
 hipError_t configure_nms_rowsort(const DevCtx& c);
-size_t nms_rowsort_scratch_bytes(const DevCtx& c);
+size_t nms_rowsort_scratch_bytes(int n_img, int oct_cap, int n_keys);      // DevCtx::big_scratch for lists of up to n_keys keys (0 up to 4096: all in LDS)
 int nms_rowsort_items(const DevCtx& c);           // keys per thread of the k_nms_rowsort instantiation this geometry launches: 4, 8 or 16
 void launch_nms_rowsort(const DevCtx& c, const Knobs& k, int do_nms, int min_distance, int pre, hipStream_t st);
 void launch_half(const DevCtx& c, int level, hipStream_t st);
-void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st);     // scratch3: 3 x n_img x cand_total words
+void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st);     // scratch3: fastorb_anms_scratch_words(n_img, cand_total) words
+size_t fastorb_anms_scratch_words(int n_img, int cand_total);
 void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream_t st);
 // dmFASTER (k_detect.hip): cand64 = [n_img][cand_total] 64-bit keys, allocated by the first svo_process made while it is selected
 void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st);
