@@ -81,6 +81,10 @@ int  svo_batch_set_klt_win(svo_batch* b, int klt_win);          /* every context
 /* svo_set_pose_covariance on every context (waits for the steps in flight first).  The records are read with svo_batch_pose_covariances;
  * they stay in the contexts (there is no device-buffer variant: svo_copy_pose_covariances_async on svo_batch_context(b, k) serves that). */
 int  svo_batch_set_pose_covariance(svo_batch* b, int enable);
+/* svo_set_dyn_fast_threshold on every context (waits for the steps in flight first): dmFASTER's per-stream, per-octave threshold,
+ * adapted on the device.  The detect calls of a context are ordered on one stream in every schedule, detect-ahead included, which is
+ * all the thresholds need.  svo_batch_faster_stats reads every stream's record. */
+int  svo_batch_set_dyn_fast_threshold(svo_batch* b, int enable, double target_feats_per_pixel);
 /* Where every step leaves the result records: caller-owned DEVICE memory of svo_batch_lanes() * sizeof(svo_result) bytes, in
  * lane order (lane = context * lanes_per_context + lane_in_context) -- e.g. this rank's slot of an all-gather buffer.
  * NULL: a buffer of the batch's own (svo_batch_results reads it). */
@@ -113,6 +117,8 @@ int  svo_batch_synchronize(svo_batch* b);
 int  svo_batch_results(svo_batch* b, svo_result* res /* svo_batch_lanes() entries */);    /* implies svo_batch_synchronize */
 /* the pose-covariance record of every stream, global lane order; implies svo_batch_synchronize.  SVO_ERR_STATE while the feature is off */
 int  svo_batch_pose_covariances(svo_batch* b, svo_pose_cov* cov /* svo_batch_lanes() entries */);
+/* the thresholds and corner counts of every stream, global lane order; implies svo_batch_synchronize.  SVO_ERR_STATE while the feature is off */
+int  svo_batch_faster_stats(svo_batch* b, svo_faster_stats* out /* svo_batch_lanes() entries */);
 int  svo_batch_reset(svo_batch* b);                             /* every stream a freshly constructed estimator again (C:28-50) */
 
 typedef struct svo_fpstream svo_fpstream;
@@ -132,6 +138,9 @@ int  svo_fpstream_set_klt_win(svo_fpstream* f, int klt_win);    /* every context
 /* svo_set_pose_covariance on every context.  The record of the frame pushed last is in its owner: svo_get_pose_covariance(s) on
  * svo_fpstream_last_owner.  (The hand-over records do not carry it.) */
 int  svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable);
+/* dmFASTER's dynamic threshold cannot run frame-parallel: the detection of frame t needs the corner count of frame t - 1, the very
+ * stage this schedule overlaps.  enable = 1 is SVO_ERR_UNSUPPORTED with a text; enable = 0 is accepted (the target is checked and ignored). */
+int  svo_fpstream_set_dyn_fast_threshold(svo_fpstream* f, int enable, double target_feats_per_pixel);
 /* the next frame of the stream(s): frames[lane]; flags as for svo_batch_step.  Enqueues and returns; the frame's result records
  * (n_lanes of them) land in the owner context -- svo_get_result(s) on svo_fpstream_last_owner waits for them. */
 int  svo_fpstream_push(svo_fpstream* f, const svo_frame* frames, uint32_t flags);

@@ -147,6 +147,45 @@ int svo_get_klt_win(const svo_ctx* ctx);
 /* the INI half: reads `KLT_win` from the DETECT section of a file written for the reference.  *klt_win keeps its value when the
  * section or the key is absent (an empty or NULL section name reads nothing); SVO_ERR_ARG when the file cannot be opened.  Host only. */
 int svo_klt_win_load_ini(const char* path, const char* detect_section, int32_t* klt_win);
+/* dmFASTER's DYNAMIC THRESHOLD (TDetectParams::target_feats_per_pixel, H:393, H:409; the controller of S2:522-550).  The reference
+ * keeps one m_threshold[octave] per estimator and moves it by one after every detection so that the corner density stays within
+ * +-20 % of the target -- but only under update_dyn_thresholds, which processNewImagePair never passes.  Here it is an opt-in of the
+ * context (svo_params is frozen), OFF by default: while off every launch, list and result is what it always was.
+ * While on, a frame of an ACTIVE lane under SVO_RUN_DETECT and dmFASTER runs the reference's two calls (P:166-167) as if each had
+ * update_dyn_thresholds = true.  Per octave o, with T = the lane's m_threshold[o]:
+ *     left image:   detected at T;   nL = ALL its FAST-12 corners;  T'  = step(T,  nL, w_o * h_o)
+ *     right image:  detected at T';  nR likewise;                   T'' = step(T', nR, w_o * h_o);   m_threshold[o] = T''
+ *     step(T, n, wh): d = n / (double)wh;  d < 0.8 target ? max(1, T - 1) : (d > 1.2 target ? T + 1 : T)        -- IEEE double
+ * so the right image of a frame is detected at a threshold that depends on the left image of the SAME frame.  n is the full count:
+ * a candidate list that overflows (status bit 1, as ever) cuts the list, not the rule's input.  A threshold that starts in 0 .. 255
+ * stays there (at 255 nothing is a corner).  Everything downstream -- KLT response, NMS, row sort, windows, SAD stages -- is unchanged.
+ * Under any other detector the setting is accepted and inert.
+ * The thresholds live ON THE DEVICE, one int32 per lane and octave: no call synchronises for them, and the graphs of svo_use_graphs
+ * stay valid while they move.  They are persistent detector scratch, read and committed by the detect call itself and ordered on
+ * the stream it runs on, like the speculative thresholds of the ORB path: correct under SVO_FLAG_DETECT_NO_POST / SVO_RUN_DETECT_POST
+ * and SVO_FLAG_DETECT_AHEAD as long as the detect calls of a context are ordered among themselves, which those schedules need anyway.
+ * m_threshold[o] becomes svo_params.initial_FAST_threshold (S2:522-523)
+ *     - for every lane when the feature is switched on (off -> on; a call that only changes the target moves nothing),
+ *     - for the lane(s) of svo_reset,
+ *     - for every lane by a svo_set_params that changes the octave count (nOctaves) -- and by no other svo_set_params: one that changes
+ *       initial_FAST_threshold alone does NOT move it.
+ * Nothing else moves it: not svo_gather_windows, svo_put_*, svo_import_frame, svo_load_state (hand-over records and state files do
+ * not carry it: the reference's file has no such member), not a call that is refused before anything is enqueued, and not a frame the
+ * lane sits out (svo_process_lanes): an idle lane keeps its thresholds and statistics.
+ * svo_set_dyn_fast_threshold: target must be finite and >= 0, else SVO_ERR_ARG with a text and the values in force stay.  It allocates
+ * at once, and drops the captured graphs on a change.  svo_get_dyn_fast_threshold: either pointer may be NULL; default off, 10 / 1000 (S2:46).
+ * Cost while on: k_faster runs as two launches (left images, then right images; both under "faster" in svo_kernel_times). */
+int svo_set_dyn_fast_threshold(svo_ctx* ctx, int enable, double target_feats_per_pixel);
+int svo_get_dyn_fast_threshold(const svo_ctx* ctx, int* enable, double* target_feats_per_pixel);
+/* the INI half: reads `target_feats_per_pixel` from the DETECT section of a file written for the reference, like svo_klt_win_load_ini.
+ * (svo_params_load_ini keeps ignoring the key: svo_params has no field for it.) */
+int svo_dyn_fast_load_ini(const char* path, const char* detect_section, double* target_feats_per_pixel);
+/* the lane's thresholds and what the reference shows as GUI statistics (S2:548-549): svo_faster_stats in svo_types.h.  Implies svo_wait;
+ * SVO_ERR_STATE with a text while the feature is off.  svo_faster_stats_size() = sizeof(svo_faster_stats) as compiled (96). */
+int svo_get_faster_stats(svo_ctx* ctx, int lane, svo_faster_stats* out);
+size_t svo_faster_stats_size(void);
+/* step() above as a pure host function (no context, no device): the threshold after a detection that found n corners in a w x h image */
+int svo_faster_threshold_step(int T, int n, int w, int h, double target_feats_per_pixel);
 /* Switch the HIP stream that later svo_process / svo_copy_results_async calls enqueue on (NULL: the context's own).
  * Ordering between work already enqueued on the old stream and work on the new one is the caller's business (events):
  * this is what lets a caller run stage 2 of one context on a normal-priority stream and stages 3-5 of another on a
@@ -172,7 +211,8 @@ int svo_set_camera(svo_ctx* ctx, int lane, const svo_stereo_camera* cam);
  * (areImagesRectified(), S1:61-65). */
 int svo_set_rectify_map(svo_ctx* ctx, int lane, int side, const float* map_x, const float* map_y, int w, int h);
 /* forget both frames, the warm start and the match-ID counters of one lane (a freshly constructed estimator, C:28-50); -1 = all.
- * The FAST / ORB thresholds belong to the context (all its lanes share svo_params) and stay as they are: svo_set_*_threshold. */
+ * The FAST / ORB thresholds belong to the context (all its lanes share svo_params) and stay as they are: svo_set_*_threshold.
+ * dmFASTER's dynamic thresholds belong to the lane and start over (svo_set_dyn_fast_threshold). */
 int svo_reset(svo_ctx* ctx, int lane);
 
 /* processNewImagePair for every lane (P:41-385): ENQUEUES the whole frame on the context's stream and
@@ -184,7 +224,7 @@ int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags);
  * getter, a later frame, a hand-over record or a state file can observe changes -- the result record, both slots' keypoint /
  * descriptor / pairing / ID lists with their counts and row-index tables, the tracked list, residuals and outliers, the lane state
  * (iteration counter, m_error, which slot is the previous frame, the match-ID counters), the status word, its pose-covariance record, the speculative FAST
- * thresholds of its two images, its gathered SAD windows and the host-side record of which of its frames have them.  No shift, no
+ * thresholds of its two images, dmFASTER's dynamic thresholds and their statistics (svo_set_dyn_fast_threshold), its gathered SAD windows and the host-side record of which of its frames have them.  No shift, no
  * zero-motion frame, no match IDs consumed.  Only per-frame scratch (pyramid, candidate lists, matcher and RANSAC tables) may be
  * rewritten.  For every lane whose bit is SET the call is exactly svo_process; with every bit set it IS svo_process, launch for launch.
  *   - frames[l] of an idle lane is not read and may hold NULL pointers; it is neither copied nor uploaded.  An active lane with NULL
@@ -218,14 +258,17 @@ int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, con
  * enqueued: the lists and the lane state stay as they were.  When it is the PREVIOUS frame that lacks them (a stream that switches
  * to ifmSAD) and the call would have shifted, the refusal is remembered: the lane's next shifting call forgets that frame, i.e. it is
  * processed as the lane's first frame (voecFirstIteration; the match-ID counter runs on), and the stream is tracked with ifmSAD from the frame after.
- * dmFASTER (detect_method = SVO_DM_FASTER, the reference's default, S2:519-576): FAST-12 corners of every x1/2 octave at the constant
- * svo_params.initial_FAST_threshold (0 .. 255, SVO_ERR_ARG otherwise; svo_set_fast_threshold does not touch it: the reference only moves
- * it under update_dyn_thresholds, which processNewImagePair never passes), each with its KLT response (KLT_win above), then the grid NMS
+ * dmFASTER (detect_method = SVO_DM_FASTER, the reference's default, S2:519-576): FAST-12 corners of every x1/2 octave at
+ * svo_params.initial_FAST_threshold (0 .. 255, SVO_ERR_ARG otherwise; svo_set_fast_threshold does not touch it) -- constant by default, as
+ * in the reference, which only moves it under update_dyn_thresholds and never passes that from processNewImagePair; with
+ * svo_set_dyn_fast_threshold on it is the starting value of a per-lane, per-octave threshold that the device adapts after every image
+ * (above) --, each with its KLT response (KLT_win above), then the grid NMS
  * and the row sort of the FAST+ORB path -- one list per octave, keypoint records (x, y, size 0, angle -1, response, octave 0,
  * class_id -1), all-zero descriptor rows.  It computes no descriptors, so only the SAD stages can follow it: SVO_RUN_MATCH with another
  * match_method or SVO_RUN_TRACK with ifm_method 0 / 1 is SVO_ERR_STATE, and nmsMethod = SVO_NMS_ADAPTIVE under it SVO_ERR_UNSUPPORTED,
- * each with a text and before anything is enqueued.  target_feats_per_pixel and minimum_KLT_response have no effect on any output of the
- * reference's path and are accepted and ignored by the INI loader.
+ * each with a text and before anything is enqueued.  minimum_KLT_response has no effect on any output of the reference's path, and
+ * target_feats_per_pixel none unless update_dyn_thresholds is passed: both are accepted and ignored by svo_params_load_ini
+ * (svo_dyn_fast_load_ini reads the latter for svo_set_dyn_fast_threshold).
  * SVO_IFM_OPTICAL_FLOW and SVO_DM_KLT stay SVO_ERR_UNSUPPORTED. */
 /* block until every enqueued frame has finished */
 int svo_wait(svo_ctx* ctx);

@@ -158,6 +158,20 @@ typedef struct svo_pose_cov {
 #define SVO_MAX_OCTAVES 4
 #define SVO_DESC_BYTES 32
 
+/* dmFASTER's dynamic threshold of one lane (svo_set_dyn_fast_threshold in svo_hip.h; stage2_detect.cpp:522-550), indexed by octave.
+ * What the reference shows as GUI statistics (S2:548-549) plus the thresholds each image was detected at.  Entries of octaves the
+ * parameters do not use, and all of used_* / corners_* / frame before the lane's first detection, are 0.
+ *   next           m_threshold[octave]: what the lane's next left image is detected at
+ *   used_left      the threshold of the last frame's left image; used_right that of its right image (= step(used_left, corners_left))
+ *   corners_left   ALL FAST-12 corners found in that image, also those a full candidate list could not hold; corners_right likewise
+ *   frame          detections that have moved this lane's thresholds since they were last initialised (1 after the first) */
+typedef struct svo_faster_stats {
+    int32_t next[SVO_MAX_OCTAVES];
+    int32_t used_left[SVO_MAX_OCTAVES], used_right[SVO_MAX_OCTAVES];
+    int32_t corners_left[SVO_MAX_OCTAVES], corners_right[SVO_MAX_OCTAVES];
+    int32_t frame, reserved[3];
+} svo_faster_stats;
+
 #ifdef __cplusplus
 }
 #endif

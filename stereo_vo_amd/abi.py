@@ -80,6 +80,20 @@ class PoseCov(C.Structure):
 
 assert C.sizeof(PoseCov) == 888
 
+
+class FasterStats(C.Structure):
+    """svo_faster_stats (include/svo_types.h): dmFASTER's dynamic thresholds of one lane and the corner counts that moved them, per octave"""
+    _fields_ = [("next", C.c_int32 * 4), ("used_left", C.c_int32 * 4), ("used_right", C.c_int32 * 4),
+                ("corners_left", C.c_int32 * 4), ("corners_right", C.c_int32 * 4), ("frame", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self, n_oct=4):
+        d = {k: list(getattr(self, k))[:n_oct] for k in ("next", "used_left", "used_right", "corners_left", "corners_right")}
+        d["frame"] = int(self.frame)
+        return d
+
+
+assert C.sizeof(FasterStats) == 96
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

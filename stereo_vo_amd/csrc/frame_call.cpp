@@ -1,5 +1,7 @@
 // frame_call.cpp -- the per-call decisions of svo_api.hip that need no device (frame_call.hpp).  Host only, built with g++.
 #include "frame_call.hpp"
+#include "faster_dyn.hpp"
+#include <float.h>
 #include <limits.h>
 #include <stdio.h>
 #include <string.h>
@@ -116,4 +118,24 @@ SadStep sad_window_step(const SadWindows& now, const LaneMask& idle, const Frame
     return r;
 }
 
+int check_dyn_fast_target(double target, std::string& why)
+{
+    why.clear();
+    if (target >= 0.0 && target <= DBL_MAX) return SVO_OK;             // (a NaN fails both comparisons)
+    char msg[128]; snprintf(msg, sizeof(msg), "target_feats_per_pixel %g: a finite value >= 0 is expected", target);
+    why = msg; return SVO_ERR_ARG;
+}
+
+bool dyn_fast_octaves_changed(const svo_params& before, const svo_params& after)
+{
+    const int a = before.nOctaves < 1 ? 1 : before.nOctaves, b = after.nOctaves < 1 ? 1 : after.nOctaves;
+    return a != b;
+}
+
+}
+
+// the rule that moves dmFASTER's threshold, as the kernels compile it (faster_dyn.hpp), for a host that predicts or checks a sequence
+extern "C" int svo_faster_threshold_step(int T, int n, int w, int h, double target_feats_per_pixel)
+{
+    return faster_dyn_step(T, (unsigned)n, w, h, target_feats_per_pixel);
 }

@@ -53,4 +53,10 @@ struct SadWindows { std::vector<uint8_t> cur, prev, drop; };
 struct SadStep { SadWindows next; LaneMask drop_prev; bool any_drop; int bad_lane; std::string why; };
 SadStep sad_window_step(const SadWindows& now, const LaneMask& idle, const FrameCall& call);
 
+// svo_set_dyn_fast_threshold: target_feats_per_pixel must be finite and >= 0; SVO_ERR_ARG with the text otherwise
+int check_dyn_fast_target(double target, std::string& why);
+// ... and whether a svo_set_params re-initialises the lanes' thresholds: when the number of octaves m_threshold is sized by changes
+// (S2:522-523: m_threshold.size() != nOctaves), and for no other field -- initial_FAST_threshold included
+bool dyn_fast_octaves_changed(const svo_params& before, const svo_params& after);
+
 }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include "svo_device.h"
 #include "svo_kernels.h"
+#include "faster_dyn.hpp"
 #include "../../include/svo_orb_tables.h"
 
 // device copies of the constant tables
@@ -2031,6 +2032,26 @@ __global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned lo
     chunked_grid_nms<FasterKeys>(c, smem, cand64, min_distance, do_nms, NS_MAX, ACC_MAX);
 }
 
+// svo_set_dyn_fast_threshold: the same kernel, and the one place where the lane's thresholds MOVE (S2:537-549).  Both k_faster_dyn
+// launches are complete, so both corner counts are final: thread 0 of the (octave, right image) block walks the rule over the left
+// and the right count and leaves m_threshold[octave] with the statistics.  Nothing in this launch reads them.
+__global__ void __launch_bounds__(1024) k_faster_nms_dyn(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX,
+                                                         svo_faster_stats* stats, double target)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 4);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int level = blockIdx.x, img = blockIdx.y;
+    if ((img & 1) && threadIdx.x == 0 && level < SVO_MAX_OCTAVES && !lane_idle(c, img >> 1)) {
+        svo_faster_stats& s = stats[img >> 1];
+        const LevelGeom& g = c.lv[level];
+        const unsigned nl = c.cand_cnt[((img - 1) * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE], nr = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
+        const int t0 = s.next[level], t1 = faster_dyn_step(t0, nl, g.w, g.h, target), t2 = faster_dyn_step(t1, nr, g.w, g.h, target);
+        s.used_left[level] = t0; s.used_right[level] = t1; s.corners_left[level] = (int)nl; s.corners_right[level] = (int)nr; s.next[level] = t2;
+        if (level == 0) s.frame++;
+    }
+    chunked_grid_nms<FasterKeys>(c, smem, cand64, min_distance, do_nms, NS_MAX, ACC_MAX);
+}
+
 // FAST+ORB with nmsmAdaptive (stage2_detect.cpp:599-606 applies m_adaptive_non_max_sup, S2:141-215, to whatever the
 // detector produced -- here ALL FAST corners of an octave, tens of thousands).  One 1024-thread block per (octave, image).
 // Reference: sort by (response desc, index asc); radius^2 of rank k1 = min over rank 0 and over the ranks k2 in [1, k1) with
@@ -2251,17 +2272,31 @@ __device__ __forceinline__ float faster_klt_response(const uint8_t* p, int win)
     return 0.5f * (t - sqrtf(rad < 0.0f ? 0.0f : rad));      // (the clamp: rad comes out negative for near-isotropic windows)
 }
 
-__global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* cand64, int th, int win)
+// svo_set_dyn_fast_threshold: where the threshold of a tile comes from when the lane's thresholds live on the device.  A left block
+// reads m_threshold[octave]; a right block derives its own from that and the left image's FINAL corner count of the same frame (the
+// left launch is complete: S2:537-546 after the left call, P:166-167) -- a pure function of two words, the same in every block of
+// the image, so no block waits for another.  Neither launch writes the thresholds: k_faster_nms_dyn commits them.
+struct FasterDyn { const svo_faster_stats* stats; double target; int side; };
+
+// DYN = false: blockIdx.x = img * n_tiles + tile at the threshold `th` of the launch; DYN = true: blockIdx.x = lane * n_tiles + tile of the
+// lane's image dyn.side, `th` unused
+template <bool DYN>
+__device__ __forceinline__ void faster_tile(const DevCtx& c, unsigned long long* cand64, int th, int win, const FasterDyn& dyn)
 {
-    SVO_TL_SCOPE(c, TL_FAST, 2);
     __shared__ __attribute__((aligned(16))) uint8_t tile[FK_LH * FK_LW];
     __shared__ unsigned short list[FK_W * FK_H];
     __shared__ unsigned s_n, s_base;
     const int tid = threadIdx.x;
-    const int img = (int)fastdiv(blockIdx.x, c.div_tiles), tile_id = (int)blockIdx.x - img * c.n_tiles;
+    const int first = (int)fastdiv(blockIdx.x, c.div_tiles), tile_id = (int)blockIdx.x - first * c.n_tiles;
+    const int img = DYN ? 2 * first + dyn.side : first;
     if (img >= c.n_img || lane_idle(c, img >> 1)) return;
     const uint4 e = c.fast_tiles[tile_id];                  // x0 | y0 << 16, w | h << 16, level | pitch << 8, level offset in the pyramid
     const int level = (int)(e.z & 0xFFu), gw = (int)(e.y & 0xFFFFu), gh = (int)(e.y >> 16), x0 = (int)(e.x & 0xFFFFu), y0 = (int)(e.x >> 16);
+    if (DYN) {                                              // block-uniform, once per block, kept in an SGPR
+        int t = dyn.stats[img >> 1].next[min(level, SVO_MAX_OCTAVES - 1)];
+        if (dyn.side) t = faster_dyn_step(t, c.cand_cnt[((img - 1) * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE], gw, gh, dyn.target);
+        th = __builtin_amdgcn_readfirstlane(t);
+    }
     const uint8_t* src = level == 0 ? c.img0[img] : c.pyr + (long long)img * c.pyr_bytes + e.w;
     const int pitch = level == 0 ? c.img0_pitch : (int)(e.z >> 8);
     const int halo = max(3, win + 1), lw = FK_W + 2 * halo, lh = FK_H + 2 * halo;
@@ -2306,6 +2341,19 @@ __global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* 
         if (gbase + i < (unsigned)g.cand_cap) dst[gbase + i] = ((unsigned long long)ord32(resp) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(py * gw + px));
         else raise_detect_status(c, img >> 1, SVO_ST_CAND_OVERFLOW);
     }
+}
+
+__global__ void __launch_bounds__(FK_NT) k_faster(DevCtx c, unsigned long long* cand64, int th, int win)
+{
+    SVO_TL_SCOPE(c, TL_FAST, 2);
+    faster_tile<false>(c, cand64, th, win, FasterDyn{});
+}
+
+// one launch per side, left then right: grid n_lanes * n_tiles
+__global__ void __launch_bounds__(FK_NT) k_faster_dyn(DevCtx c, unsigned long long* cand64, int win, FasterDyn dyn)
+{
+    SVO_TL_SCOPE(c, TL_FAST, 2);
+    faster_tile<true>(c, cand64, 0, win, dyn);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2456,10 +2504,30 @@ void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int
     hipLaunchKernelGGL(k_faster, dim3((unsigned)((long long)c.n_tiles * c.n_img)), dim3(FK_NT), 0, st, c, cand64, fast_th, klt_win);
 }
 
-hipError_t configure_faster_nms(const DevCtx& c) { return svo_raise_dyn_smem((const void*)k_faster_nms, chunked_nms_layout<FasterKeys>(c).total()); }
+// svo_set_dyn_fast_threshold: the left images of every lane at m_threshold, then the right images at the threshold their lane's left
+// count leads to.  stats[lane].next[octave] is m_threshold; neither launch writes it.
+void launch_faster_dyn(const DevCtx& c, unsigned long long* cand64, const svo_faster_stats* stats, double target, int klt_win, hipStream_t st)
+{
+    if (c.n_tiles <= 0) return;
+    for (int side = 0; side < 2; side++)
+        hipLaunchKernelGGL(k_faster_dyn, dim3((unsigned)((long long)c.n_tiles * c.n_lanes)), dim3(FK_NT), 0, st, c, cand64, klt_win, FasterDyn{ stats, target, side });
+}
+
+hipError_t configure_faster_nms(const DevCtx& c)
+{
+    const hipError_t e = svo_raise_dyn_smem((const void*)k_faster_nms, chunked_nms_layout<FasterKeys>(c).total());
+    return e != hipSuccess ? e : svo_raise_dyn_smem((const void*)k_faster_nms_dyn, chunked_nms_layout<FasterKeys>(c).total());
+}
 
 void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st)
 {
     const auto L = chunked_nms_layout<FasterKeys>(c);
     hipLaunchKernelGGL(k_faster_nms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, cand64, min_distance, do_nms, L.ns_max, L.acc_max);
+}
+
+// ... behind launch_faster_dyn: the same NMS, whose (octave, right image) blocks also commit the lane's thresholds and statistics
+void launch_faster_nms_dyn(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, svo_faster_stats* stats, double target, hipStream_t st)
+{
+    const auto L = chunked_nms_layout<FasterKeys>(c);
+    hipLaunchKernelGGL(k_faster_nms_dyn, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, cand64, min_distance, do_nms, L.ns_max, L.acc_max, stats, target);
 }

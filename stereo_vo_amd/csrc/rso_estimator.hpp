@@ -98,7 +98,14 @@ public:
     svo_params params;
     // ... and the one field of TDetectParams the frozen record has no room for: KLT_win (H:561-587, default 4 at S2:47), the window
     // of dmFASTER's KLT response; it lives on the context (svo_set_klt_win) and is pushed with the record by applyParams
-    struct TDetectParams { int KLT_win; TDetectParams() : KLT_win(4) {} } params_detect;
+    // ... and target_feats_per_pixel (H:393, default 10 / 1000 at S2:46), the corner density dmFASTER's dynamic threshold steers to
+    struct TDetectParams { int KLT_win; double target_feats_per_pixel; TDetectParams() : KLT_win(4), target_feats_per_pixel(10. / 1000.) {} } params_detect;
+    /** Mirrors the `update_dyn_thresholds` argument of stage2_detect_features (H:1020), which processNewImagePair never passes (P:166-167):
+      * false, the reference's behaviour, keeps dmFASTER at the constant initial_FAST_threshold; true lets m_threshold[octave] follow
+      * params_detect.target_feats_per_pixel on the device (svo_set_dyn_fast_threshold).  Set it, then applyParams(). */
+    bool update_dyn_thresholds = false;
+    /** m_threshold and the GUI statistics of S2:548-549 (svo_faster_stats); only while update_dyn_thresholds is applied */
+    void getFASTERStats(svo_faster_stats& out) { check(svo_get_faster_stats(m_ctx, 0, &out), "svo_get_faster_stats"); }
 
     explicit CStereoOdometryEstimator(int max_w = 1280, int max_h = 960, int device = 0, int max_octaves = 4) : m_ctx(NULL), m_verbose_level(1) {
         svo_params_defaults(&params);
@@ -112,7 +119,10 @@ public:
     CStereoOdometryEstimator& operator=(const CStereoOdometryEstimator&) = delete;
 
     /** loadParamsFromConfigFile's effect (H:554-663): push `params`, then reset both dynamic thresholds */
-    void applyParams() { check(svo_set_params(m_ctx, &params), "svo_set_params"); check(svo_set_klt_win(m_ctx, params_detect.KLT_win), "svo_set_klt_win"); }
+    void applyParams() {
+        check(svo_set_params(m_ctx, &params), "svo_set_params"); check(svo_set_klt_win(m_ctx, params_detect.KLT_win), "svo_set_klt_win");
+        check(svo_set_dyn_fast_threshold(m_ctx, update_dyn_thresholds ? 1 : 0, params_detect.target_feats_per_pixel), "svo_set_dyn_fast_threshold");
+    }
     /** Loads configuration from an INI file from its name (H:665-672); sections in the order RECTIFY, DETECT, MATCH, IF-MATCH,
       * LEAST_SQUARES, GUI, GENERAL (H:551-553), an empty name skips the group */
     void loadParamsFromConfigFileName(const std::string& fileName, const std::vector<std::string>& sections) {
@@ -121,6 +131,7 @@ public:
         for (int i = 0; i < 7; i++) names[i] = sections[i].c_str();
         check(svo_params_load_ini(fileName.c_str(), names, &params), "svo_params_load_ini");
         { int32_t w = params_detect.KLT_win; check(svo_klt_win_load_ini(fileName.c_str(), names[1], &w), "svo_klt_win_load_ini"); params_detect.KLT_win = w; }
+        check(svo_dyn_fast_load_ini(fileName.c_str(), names[1], &params_detect.target_feats_per_pixel), "svo_dyn_fast_load_ini");
         applyParams();                                                                   // resetFASTThreshold / resetORBThreshold, H:662-663
     }
     void setVerbosityLevel(int level) { m_verbose_level = level; }                       // H:527

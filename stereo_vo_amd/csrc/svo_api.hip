@@ -114,6 +114,9 @@ struct svo_ctx {
     uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
     // svo_set_pose_covariance: one record per lane and the array k_gauss_newton leaves its final mask in; nullptr until first enabled
     bool pose_cov; svo_pose_cov* d_cov; uint8_t* d_cov_mask;
+    // svo_set_dyn_fast_threshold: dmFASTER's m_threshold[octave] of every lane (the `next` member) with its statistics; nullptr until first enabled.
+    // Persistent detector scratch: read and written by detect calls alone, ordered on the stream they run on, like fast_th_dyn
+    bool dyn_fast; double dyn_target; svo_faster_stats* d_fstats;
     unsigned long long* d_cand64;                      // dmFASTER's 64-bit candidate keys (n_img x cand_total), allocated by the first svo_process made while it is selected
     // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
     // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
@@ -140,6 +143,7 @@ struct svo_ctx {
 
 using namespace svo_call;
 static void drop_graphs(svo_ctx* ctx);
+static int dyn_fast_init(svo_ctx* ctx, int lane);
 static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
 static void sampler_table_release(int device, int nmax);
@@ -376,6 +380,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     svo_params_defaults(&ctx->params);
     ctx->fast_th = 20; ctx->orb_th = 60;                  // common.cpp:35-36
     ctx->klt_win = 4; ctx->d_cand64 = nullptr;            // stage2_detect.cpp:47
+    ctx->dyn_fast = false; ctx->dyn_target = 10. / 1000.; ctx->d_fstats = nullptr;      // stage2_detect.cpp:46; update_dyn_thresholds = false (H:1020)
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
@@ -552,7 +557,9 @@ extern "C" int svo_set_params(svo_ctx* ctx, const svo_params* p)
     if (ctx) use_device(ctx);
     if (!ctx || !p) return SVO_ERR_ARG;
     { const int rc = params_fit(ctx, *p); if (rc) return rc; }
+    const bool dyn_reinit = ctx->dyn_fast && dyn_fast_octaves_changed(ctx->params, *p);
     ctx->params = *p;
+    if (dyn_reinit) { const int rc = dyn_fast_init(ctx, -1); if (rc) return rc; }      // S2:522-523: m_threshold.assign(nOctaves, initial_FAST_threshold)
     // a context that has once selected a SAD method hands its frames over with their 8 x 8 windows (k_handover.hip, version 3), for good:
     // svo_handover_bytes grows here and never shrinks again
     if (p->match_method == SVO_SM_SAD || p->ifm_method == SVO_IFM_SAD) ctx->dc.carry_win = 1;
@@ -651,6 +658,52 @@ extern "C" int svo_copy_pose_covariances_async(svo_ctx* ctx, void* dst, size_t b
     return SVO_OK;
 }
 
+// dmFASTER's dynamic threshold (stage2_detect.cpp:522-550; svo_hip.h at svo_set_dyn_fast_threshold).  The thresholds are device data: no
+// host copy exists, a frame never synchronises for them, and a captured graph stays valid while they move.
+// A fresh m_threshold of one lane (-1: every lane): initial_FAST_threshold on every octave, empty statistics.  Waits for the enqueued work.
+static int dyn_fast_init(svo_ctx* ctx, int lane)
+{
+    HIPCHECK(sync_all(ctx));
+    svo_faster_stats fresh; memset(&fresh, 0, sizeof(fresh));
+    for (int o = 0; o < SVO_MAX_OCTAVES; o++) fresh.next[o] = ctx->params.initial_FAST_threshold;
+    for (int l = 0; l < ctx->cfg.n_lanes; l++)
+        if (lane < 0 || lane == l) HIPCHECK(hipMemcpy(ctx->d_fstats + l, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+    return SVO_OK;
+}
+extern "C" int svo_set_dyn_fast_threshold(svo_ctx* ctx, int enable, double target_feats_per_pixel)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    { std::string why; const int rc = check_dyn_fast_target(target_feats_per_pixel, why); if (rc) { ctx->last_error = why; return rc; } }
+    const bool on = enable != 0;
+    if (on == ctx->dyn_fast && target_feats_per_pixel == ctx->dyn_target) return SVO_OK;
+    drop_graphs(ctx);                                        // the launches of a detect call and one of their arguments change
+    if (on && !ctx->dyn_fast) {                              // allocated here, not at the first frame: before any capture (as d_cov)
+        if (!ctx->d_fstats) HIPCHECK(dev_alloc(ctx, &ctx->d_fstats, (size_t)ctx->cfg.n_lanes));
+        const int rc = dyn_fast_init(ctx, -1); if (rc) return rc;
+    }
+    ctx->dyn_fast = on; ctx->dyn_target = target_feats_per_pixel;
+    return SVO_OK;
+}
+extern "C" int svo_get_dyn_fast_threshold(const svo_ctx* ctx, int* enable, double* target_feats_per_pixel)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (enable) *enable = ctx->dyn_fast ? 1 : 0;
+    if (target_feats_per_pixel) *target_feats_per_pixel = ctx->dyn_target;
+    return SVO_OK;
+}
+extern "C" size_t svo_faster_stats_size(void) { return sizeof(svo_faster_stats); }
+extern "C" int svo_get_faster_stats(svo_ctx* ctx, int lane, svo_faster_stats* out)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !out || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    if (!ctx->dyn_fast) { ctx->last_error = "the dynamic FAST threshold is off: svo_set_dyn_fast_threshold(ctx, 1, target) first"; return SVO_ERR_STATE; }
+    const int rc = svo_wait(ctx); if (rc) return rc;
+    HIPCHECK(hipMemcpy(out, ctx->d_fstats + lane, sizeof(*out), hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+// (svo_faster_threshold_step, the rule as a host function, is in frame_call.cpp: it needs no device)
+
 extern "C" int svo_set_stream(svo_ctx* ctx, void* stream)
 {
     if (ctx) use_device(ctx);
@@ -732,6 +785,7 @@ extern "C" int svo_reset(svo_ctx* ctx, int lane)
             HIPCHECK(hipMemset(ctx->dc.n_ids + (size_t)l * OC * 2, 0, (size_t)OC * 2 * sizeof(int)));
             HIPCHECK(hipMemset(ctx->dc.results + l, 0, sizeof(svo_result)));
             if (ctx->pose_cov) HIPCHECK(hipMemset(ctx->d_cov + l, 0, sizeof(svo_pose_cov)));
+            if (ctx->dyn_fast) { const int rc = dyn_fast_init(ctx, l); if (rc) return rc; }     // a fresh estimator: m_threshold is empty (S2:522-523)
             HIPCHECK(hipMemset(ctx->dc.fast_th_dyn + (size_t)2 * l * SVO_MAX_LEVELS, 0, (size_t)2 * SVO_MAX_LEVELS * sizeof(uint32_t)));   // a fresh estimator speculates nothing
             ctx->sad.cur[l] = ctx->sad.prev[l] = 1; ctx->sad.drop[l] = 0;                       // no frames: nothing a SAD stage could miss
         }
@@ -1182,9 +1236,15 @@ static bool wide_lists(const DevCtx& d) { return d.max_kps > 8192; }
 static void enqueue_detect(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
 {
     DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
-    if (call.faster) {      // stage2_detect.cpp:519-576: FAST-12 at the constant initial_FAST_threshold (m_threshold never moves: processNewImagePair
-                            // passes no update_dyn_thresholds), KLT response, grid NMS; svo_set_fast_threshold has no part in it
+    if (call.faster) {      // stage2_detect.cpp:519-576: FAST-12, KLT response, grid NMS; svo_set_fast_threshold has no part in it.  The threshold is the
+                            // constant initial_FAST_threshold (m_threshold never moves: processNewImagePair passes no update_dyn_thresholds) unless
+                            // svo_set_dyn_fast_threshold is on: then the lane's own m_threshold[octave], moved on the device (S2:537-546)
         { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
+        if (ctx->dyn_fast) {
+            { Span s(ctx, KT_FASTER); launch_faster_dyn(d, ctx->d_cand64, ctx->d_fstats, ctx->dyn_target, ctx->klt_win, st); }      // two launches under one name
+            { Span s(ctx, KT_FASTER_NMS); launch_faster_nms_dyn(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, ctx->d_fstats, ctx->dyn_target, st); }
+            return;
+        }
         { Span s(ctx, KT_FASTER); launch_faster(d, ctx->d_cand64, p.initial_FAST_threshold, ctx->klt_win, st); }
         { Span s(ctx, KT_FASTER_NMS); launch_faster_nms(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, st); }
     } else if (d.fast_orb) {       // stage2_detect.cpp:502-515 on the x1/2 octave pyramid

@@ -172,6 +172,14 @@ extern "C" int svo_batch_set_pose_covariance(svo_batch* b, int enable)
     return SVO_OK;
 }
 
+extern "C" int svo_batch_set_dyn_fast_threshold(svo_batch* b, int enable, double target)
+{
+    if (!b) return SVO_ERR_ARG;
+    int rc = svo_batch_synchronize(b); if (rc) return rc;
+    for (svo_ctx* c : b->ctx) BSVO(b, c, svo_set_dyn_fast_threshold(c, enable, target));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam)
 {
     if (!b || !cam || lane < -1 || lane >= b->B) return SVO_ERR_ARG;
@@ -332,6 +340,15 @@ extern "C" int svo_batch_pose_covariances(svo_batch* b, svo_pose_cov* cov)
     return SVO_OK;
 }
 
+extern "C" int svo_batch_faster_stats(svo_batch* b, svo_faster_stats* out)
+{
+    if (!b || !out) return SVO_ERR_ARG;
+    int rc = svo_batch_synchronize(b); if (rc) return rc;
+    for (int k = 0; k < b->NC; k++)
+        for (int l = 0; l < b->Bc; l++) BSVO(b, b->ctx[(size_t)k], svo_get_faster_stats(b->ctx[(size_t)k], l, out + (size_t)k * b->Bc + l));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_reset(svo_batch* b)
 {
     if (!b) return SVO_ERR_ARG;
@@ -431,6 +448,17 @@ extern "C" int svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable)
 {
     if (!f) return SVO_ERR_ARG;
     for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_pose_covariance(c, enable));
+    return SVO_OK;
+}
+
+extern "C" int svo_fpstream_set_dyn_fast_threshold(svo_fpstream* f, int enable, double target)
+{
+    if (!f) return SVO_ERR_ARG;
+    if (!(target >= 0.0 && target <= 1.7976931348623157e308)) { f->last_error = "target_feats_per_pixel: a finite value >= 0 is expected"; return SVO_ERR_ARG; }
+    if (enable) {
+        f->last_error = "dmFASTER's dynamic threshold is not available frame-parallel: detecting frame t needs the corner count of frame t - 1, which this schedule overlaps";
+        return SVO_ERR_UNSUPPORTED;
+    }
     return SVO_OK;
 }
 

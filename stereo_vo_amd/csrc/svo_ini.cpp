@@ -149,3 +149,17 @@ extern "C" int svo_klt_win_load_ini(const char* path, const char* detect_section
     }
     return SVO_OK;
 }
+
+// TDetectParams::target_feats_per_pixel (H:568, read_double; S2:46 defaults it to 10 / 1000): the same for the target of dmFASTER's dynamic
+// threshold; follow it with svo_set_dyn_fast_threshold.  svo_params_load_ini above has no field to put it in and goes on ignoring the key.
+extern "C" int svo_dyn_fast_load_ini(const char* path, const char* detect_section, double* target)
+{
+    if (!path || !target) return SVO_ERR_ARG;
+    Ini ini;
+    if (!parse_ini(path, ini)) return SVO_ERR_ARG;
+    if (detect_section && detect_section[0]) {
+        Reader r{ ini, lower(detect_section) };
+        *target = r.read_double("target_feats_per_pixel", *target);
+    }
+    return SVO_OK;
+}

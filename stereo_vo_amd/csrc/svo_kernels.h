@@ -67,6 +67,10 @@ void launch_fastorb_nms(const DevCtx& c, int do_nms, int min_distance, hipStream
 void launch_faster(const DevCtx& c, unsigned long long* cand64, int fast_th, int klt_win, hipStream_t st);
 hipError_t configure_faster_nms(const DevCtx& c);
 void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, hipStream_t st);
+// ... under svo_set_dyn_fast_threshold: stats = [n_lanes] records whose next[octave] is the lane's m_threshold.  Two k_faster_dyn launches
+// (left images, then right images) read it; the NMS launch behind them commits the new thresholds and the statistics
+void launch_faster_dyn(const DevCtx& c, unsigned long long* cand64, const svo_faster_stats* stats, double target, int klt_win, hipStream_t st);
+void launch_faster_nms_dyn(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, svo_faster_stats* stats, double target, hipStream_t st);
 void launch_hamming(const DevCtx& c, const Knobs& k, int mode, int nsplit, hipStream_t st);
 void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, hipStream_t st);
 void launch_track_filter(const DevCtx& c, hipStream_t st);

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import Params, PoseCov, Result, StereoCamera, keypoint_dtype, dmatch_dtype, index_pair_dtype
+from .abi import FasterStats, Params, PoseCov, Result, StereoCamera, keypoint_dtype, dmatch_dtype, index_pair_dtype
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -21,7 +21,9 @@ FLAG_REPEAT, FLAG_NO_SHIFT, FLAG_DEVICE_IMAGES, FLAG_BGR_IMAGES, FLAG_DETECT_NO_
 EXPORTS = [
     "svo_config_defaults", "svo_params_defaults", "svo_create", "svo_destroy", "svo_strerror", "svo_last_error",
     "svo_set_params", "svo_get_params", "svo_params_load_ini", "svo_set_fast_threshold", "svo_set_orb_threshold", "svo_get_fast_threshold",
-    "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini", "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
+    "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini",
+    "svo_set_dyn_fast_threshold", "svo_get_dyn_fast_threshold", "svo_dyn_fast_load_ini", "svo_get_faster_stats", "svo_faster_stats_size", "svo_faster_threshold_step",
+    "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_set_pose_covariance", "svo_get_pose_covariance", "svo_get_pose_covariances", "svo_copy_pose_covariances_async", "svo_pose_cov_size",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
@@ -39,6 +41,7 @@ BATCH_EXPORTS = [
     "svo_batch_context", "svo_batch_set_params", "svo_batch_set_camera", "svo_batch_set_klt_win", "svo_batch_set_results_buffer", "svo_batch_switch_results_buffer", "svo_batch_step", "svo_batch_step_lanes",
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
     "svo_batch_set_pose_covariance", "svo_batch_pose_covariances", "svo_fpstream_set_pose_covariance",
+    "svo_batch_set_dyn_fast_threshold", "svo_batch_faster_stats", "svo_fpstream_set_dyn_fast_threshold",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
     "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
 ]
@@ -98,6 +101,16 @@ def lib():
         if hasattr(L, "svo_pose_cov_size"):          # (absent from a library of an earlier commit loaded through SVO_HIP_LIB for an A/B)
             L.svo_pose_cov_size.restype = C.c_size_t; L.svo_pose_cov_size.argtypes = []
             L.svo_copy_pose_covariances_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        if hasattr(L, "svo_set_dyn_fast_threshold"):          # (as above: absent from a library of an earlier commit)
+            L.svo_set_dyn_fast_threshold.argtypes = [C.c_void_p, C.c_int, C.c_double]
+            L.svo_get_dyn_fast_threshold.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+            L.svo_dyn_fast_load_ini.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double)]
+            L.svo_get_faster_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            L.svo_faster_stats_size.restype = C.c_size_t; L.svo_faster_stats_size.argtypes = []
+            L.svo_faster_threshold_step.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
+            L.svo_batch_set_dyn_fast_threshold.argtypes = [C.c_void_p, C.c_int, C.c_double]
+            L.svo_batch_faster_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.svo_fpstream_set_dyn_fast_threshold.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -132,6 +145,20 @@ def load_klt_win_ini(path, detect_section, klt_win=4) -> int:
     if rc != 0:
         raise SvoError("svo_klt_win_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
     return int(v.value)
+
+
+def load_dyn_fast_ini(path, detect_section, target=10. / 1000.) -> float:
+    """TDetectParams::target_feats_per_pixel from the DETECT section of the reference's INI file; `target` when the section or key is absent"""
+    v = C.c_double(float(target))
+    rc = lib().svo_dyn_fast_load_ini(str(path).encode(), detect_section.encode() if detect_section else None, C.byref(v))
+    if rc != 0:
+        raise SvoError("svo_dyn_fast_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
+    return float(v.value)
+
+
+def faster_threshold_step(T, n, w, h, target) -> int:
+    """the rule that moves dmFASTER's threshold after a detection that found n corners in a w x h image (host only)"""
+    return int(lib().svo_faster_threshold_step(int(T), int(n), int(w), int(h), float(target)))
 
 
 def _vp(a):
@@ -252,6 +279,22 @@ class Context:
 
     def klt_win(self):
         return self.L.svo_get_klt_win(self.h)
+
+    def set_dyn_fast_threshold(self, enable=True, target=10. / 1000.):
+        """dmFASTER's threshold per lane and octave, adapted on the device towards `target` corners per pixel (svo_set_dyn_fast_threshold)"""
+        self._ck(self.L.svo_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_set_dyn_fast_threshold")
+
+    def dyn_fast_threshold(self):
+        """(enabled, target corners per pixel)"""
+        e, t = C.c_int(0), C.c_double(0.0)
+        self._ck(self.L.svo_get_dyn_fast_threshold(self.h, C.byref(e), C.byref(t)), "svo_get_dyn_fast_threshold")
+        return bool(e.value), float(t.value)
+
+    def faster_stats(self, lane=0) -> FasterStats:
+        """the lane's thresholds and corner counts (waits); SvoError while the feature is off"""
+        r = FasterStats()
+        self._ck(self.L.svo_get_faster_stats(self.h, lane, C.byref(r)), "svo_get_faster_stats")
+        return r
 
     def orb_threshold(self):
         return self.L.svo_get_orb_threshold(self.h)

@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import hip
-from .abi import PoseCov, Result
+from .abi import FasterStats, PoseCov, Result
 
 
 def _frames(ptrs, w, h, stride):
@@ -166,6 +166,17 @@ class StreamBatch:
         self._ck(self.L.svo_batch_pose_covariances(self.h, arr), "svo_batch_pose_covariances")
         return list(arr)
 
+    def set_dyn_fast_threshold(self, enable=True, target=10. / 1000.):
+        """svo_batch_set_dyn_fast_threshold: dmFASTER's per-stream, per-octave threshold on every context, adapted on the device"""
+        torch.cuda.synchronize(self.dev)
+        self._ck(self.L.svo_batch_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_batch_set_dyn_fast_threshold")
+
+    def faster_stats(self):
+        """the FasterStats record of every stream, global lane order (waits for the steps in flight)"""
+        arr = (FasterStats * self.B)()
+        self._ck(self.L.svo_batch_faster_stats(self.h, arr), "svo_batch_faster_stats")
+        return list(arr)
+
     def pooled_kernel_times(self):
         """launches of all contexts pooled: ms and launch counts add up, a launch covers lanes_per_context streams"""
         acc = {}
@@ -231,6 +242,10 @@ class FrameParallelStream:
     def set_pose_covariance(self, enable=True):
         """svo_fpstream_set_pose_covariance: every context; a pushed frame's records are read from the context push() returned"""
         self._ck(self.L.svo_fpstream_set_pose_covariance(self.h, 1 if enable else 0), "svo_fpstream_set_pose_covariance")
+
+    def set_dyn_fast_threshold(self, enable=True, target=10. / 1000.):
+        """refused when enable is set (svo_fpstream_set_dyn_fast_threshold): frame t's detection would need frame t - 1's corner count"""
+        self._ck(self.L.svo_fpstream_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_fpstream_set_dyn_fast_threshold")
 
     def push(self, ptrs, stride=None):
         """Enqueue the next frame (ptrs[lane] = (left, right) device addresses).  Returns the context that owns it."""
