@@ -85,6 +85,9 @@ int  svo_batch_set_pose_covariance(svo_batch* b, int enable);
  * adapted on the device.  The detect calls of a context are ordered on one stream in every schedule, detect-ahead included, which is
  * all the thresholds need.  svo_batch_faster_stats reads every stream's record. */
 int  svo_batch_set_dyn_fast_threshold(svo_batch* b, int enable, double target_feats_per_pixel);
+/* svo_set_faster_adaptive_nms on every context (waits for the steps in flight first): the opt-in to the adaptive NMS under dmFASTER.
+ * Each context allocates its scratch at once. */
+int  svo_batch_set_faster_adaptive_nms(svo_batch* b, int enable);
 /* Where every step leaves the result records: caller-owned DEVICE memory of svo_batch_lanes() * sizeof(svo_result) bytes, in
  * lane order (lane = context * lanes_per_context + lane_in_context) -- e.g. this rank's slot of an all-gather buffer.
  * NULL: a buffer of the batch's own (svo_batch_results reads it). */
@@ -141,6 +144,9 @@ int  svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable);
 /* dmFASTER's dynamic threshold cannot run frame-parallel: the detection of frame t needs the corner count of frame t - 1, the very
  * stage this schedule overlaps.  enable = 1 is SVO_ERR_UNSUPPORTED with a text; enable = 0 is accepted (the target is checked and ignored). */
 int  svo_fpstream_set_dyn_fast_threshold(svo_fpstream* f, int enable, double target_feats_per_pixel);
+/* svo_set_faster_adaptive_nms on every context.  The selection reads and writes per-image scratch of the detect call alone and the
+ * hand-over records carry nothing of it, so frame-parallel streams run it as they run the grid NMS. */
+int  svo_fpstream_set_faster_adaptive_nms(svo_fpstream* f, int enable);
 /* the next frame of the stream(s): frames[lane]; flags as for svo_batch_step.  Enqueues and returns; the frame's result records
  * (n_lanes of them) land in the owner context -- svo_get_result(s) on svo_fpstream_last_owner waits for them. */
 int  svo_fpstream_push(svo_fpstream* f, const svo_frame* frames, uint32_t flags);

@@ -186,6 +186,22 @@ int svo_get_faster_stats(svo_ctx* ctx, int lane, svo_faster_stats* out);
 size_t svo_faster_stats_size(void);
 /* step() above as a pure host function (no context, no device): the threshold after a detection that found n corners in a w x h image */
 int svo_faster_threshold_step(int T, int n, int w, int h, double target_feats_per_pixel);
+/* The adaptive NMS under dmFASTER (stage2_detect.cpp:599-606 applies m_adaptive_non_max_sup, S2:141-215, to whatever detector ran): an
+ * OPT-IN of the context, off by default.  While it is off, a call under dmFASTER with non_maximal_suppression and nmsMethod =
+ * SVO_NMS_ADAPTIVE is refused as it always was (SVO_ERR_UNSUPPORTED, "the adaptive NMS is not built for dmFASTER: use nmsMethod =
+ * nmsmStandard") and every launch, list and record is what it was.  While it is on, such a call is accepted: behind the detector,
+ * k_faster_anms runs where the grid NMS would, per octave image on EVERY FAST-12 corner with its KLT response (rank = response desc,
+ * raster index asc; num_out_points = kps_to_detect[octave], min_radius_th = 0; output = radius desc, index asc), and leaves the same
+ * records in the same place (x, y, size 0, angle -1, response, octave 0, class_id -1; all-zero descriptor rows).  Row sort, windows and
+ * stages 3-5 follow unchanged; SVO_FLAG_DETECT_NO_POST / SVO_RUN_DETECT_POST, SVO_FLAG_DETECT_AHEAD, svo_use_graphs, svo_process_lanes
+ * and svo_set_dyn_fast_threshold work as under the grid NMS.  Every other configuration launches what it launches without the opt-in:
+ * under another detector, or with nmsmStandard, the setting is accepted and inert.  Hand-over records and state files carry nothing of it.
+ * Why a context must ask: the setter allocates 24 bytes x 2 n_lanes x (3.3 max_cand + 8192) of scratch at once (before any graph capture),
+ * and selects the most expensive selection kernel of the detect chain ("faster_nms" in svo_kernel_times counts it).  It drops the
+ * captured graphs on a change.  SVO_ERR_UNSUPPORTED with a text when max_cand exceeds 2^19 (a rank is packed into 19 bits).
+ * svo_get_faster_adaptive_nms: 1 / 0. */
+int svo_set_faster_adaptive_nms(svo_ctx* ctx, int enable);
+int svo_get_faster_adaptive_nms(const svo_ctx* ctx);
 /* Switch the HIP stream that later svo_process / svo_copy_results_async calls enqueue on (NULL: the context's own).
  * Ordering between work already enqueued on the old stream and work on the new one is the caller's business (events):
  * this is what lets a caller run stage 2 of one context on a normal-priority stream and stages 3-5 of another on a
@@ -265,7 +281,8 @@ int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, con
  * (above) --, each with its KLT response (KLT_win above), then the grid NMS
  * and the row sort of the FAST+ORB path -- one list per octave, keypoint records (x, y, size 0, angle -1, response, octave 0,
  * class_id -1), all-zero descriptor rows.  It computes no descriptors, so only the SAD stages can follow it: SVO_RUN_MATCH with another
- * match_method or SVO_RUN_TRACK with ifm_method 0 / 1 is SVO_ERR_STATE, and nmsMethod = SVO_NMS_ADAPTIVE under it SVO_ERR_UNSUPPORTED,
+ * match_method or SVO_RUN_TRACK with ifm_method 0 / 1 is SVO_ERR_STATE, and nmsMethod = SVO_NMS_ADAPTIVE under it SVO_ERR_UNSUPPORTED
+ * unless the context has opted in (svo_set_faster_adaptive_nms above: then the adaptive NMS runs in place of the grid NMS),
  * each with a text and before anything is enqueued.  minimum_KLT_response has no effect on any output of the reference's path, and
  * target_feats_per_pixel none unless update_dyn_thresholds is passed: both are accepted and ignored by svo_params_load_ini
  * (svo_dyn_fast_load_ini reads the latter for svo_set_dyn_fast_threshold).
@@ -498,6 +515,16 @@ int svo_change_in_pose(svo_ctx* ctx, const svo_index_pair* tracked, int n_tracke
  * for each of nq 32-byte query rows the FIRST minimum-distance train row.  idx = -1 when nt == 0. */
 int svo_hamming_match(svo_ctx* ctx, const uint8_t* query, int nq, const uint8_t* train, int nt,
                       int32_t* idx, int32_t* dist);
+
+/* m_adaptive_non_max_sup stand-in (S2:141-215, min_radius_th = 0) on caller arrays (host pointers), like svo_hamming_match: runs the
+ * SAME device code as the adaptive NMS under dmFASTER on one list.  It exists so that the kernel can be held to a reference on hand-built
+ * lists; it needs no opt-in, touches no lane state and synchronises.  Returns the number kept, min(num_out_points, n) -- possibly
+ * > cap --, with the first min(., cap) indices into kps written to out_order in (radius desc, index asc) order.  Requires: integer-valued
+ * x, y inside img_w x img_h; img_w * img_h < 2^24; strictly ascending raster order (y * img_w + x), so that index order is position
+ * order; no NaN response; n <= the context's level-0 candidate capacity (max(1024, max_cand)); min(num_out_points, n) <= max_kps.
+ * Anything else is SVO_ERR_ARG with a text. */
+int svo_adaptive_nms(svo_ctx* ctx, const svo_keypoint* kps, int n, int num_out_points, int img_w, int img_h,
+                     int32_t* out_order, int cap);
 
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);

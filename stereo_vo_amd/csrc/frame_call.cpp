@@ -26,7 +26,7 @@ bool parse_lane_mask(const uint64_t* words, bool masked, int n_lanes, LaneMask& 
     return ok;
 }
 
-FrameCall make_frame_call(uint32_t flags, const svo_params& p)
+FrameCall make_frame_call(uint32_t flags, const svo_params& p, bool faster_adaptive_nms)
 {
     FrameCall c;
     c.flags = flags;
@@ -43,6 +43,8 @@ FrameCall make_frame_call(uint32_t flags, const svo_params& p)
     c.max_sad_match = p.sad_max_distance == 0 ? 200 : (p.sad_max_distance < 0 ? INT32_MAX : p.sad_max_distance);
     c.max_sad_track = p.ifm_sad_max_distance == 0 ? 200u : (unsigned)p.ifm_sad_max_distance;
     c.minresp = p.detect_method == SVO_DM_ORB ? p.minimum_ORB_response : 0.0;
+    c.faster_anms_on = faster_adaptive_nms;
+    c.faster_anms = faster_adaptive_nms && c.faster && c.nms_mode == 2;
     return c;
 }
 
@@ -60,7 +62,8 @@ int check_frame_call(const FrameCall& call, const svo_params& p, const LaneMask&
     if (call.faster) {
         if ((flags & SVO_RUN_MATCH) && p.match_method != SVO_SM_SAD) { why = "dmFASTER computes no descriptors: stage 3 needs match_method = smSAD"; return SVO_ERR_STATE; }
         if ((flags & SVO_RUN_TRACK) && p.ifm_method != SVO_IFM_SAD) { why = "dmFASTER computes no descriptors: stage 4 needs ifm_method = ifmSAD"; return SVO_ERR_STATE; }
-        if ((flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {
+        // ... unless the context has asked for it (svo_set_faster_adaptive_nms): the refusal and its text are what they were while it has not
+        if (!call.faster_anms_on && (flags & (SVO_RUN_DETECT | SVO_RUN_DETECT_POST)) && p.non_maximal_suppression && p.nmsMethod == SVO_NMS_ADAPTIVE) {
             why = "the adaptive NMS is not built for dmFASTER: use nmsMethod = nmsmStandard"; return SVO_ERR_UNSUPPORTED;
         }
         if ((flags & SVO_RUN_DETECT) && (p.initial_FAST_threshold < 0 || p.initial_FAST_threshold > 255)) {
@@ -123,6 +126,34 @@ int check_dyn_fast_target(double target, std::string& why)
     why.clear();
     if (target >= 0.0 && target <= DBL_MAX) return SVO_OK;             // (a NaN fails both comparisons)
     char msg[128]; snprintf(msg, sizeof(msg), "target_feats_per_pixel %g: a finite value >= 0 is expected", target);
+    why = msg; return SVO_ERR_ARG;
+}
+
+int check_adaptive_nms_args(const svo_keypoint* kps, int n, int num_out_points, int img_w, int img_h, const int32_t* out_order, int cap,
+                            int cand_cap, int max_kps, std::string& why)
+{
+    char msg[200]; msg[0] = 0;
+    why.clear();
+    if (n < 0 || (n > 0 && !kps)) snprintf(msg, sizeof(msg), "kps: %d keypoints at %s", n, kps ? "an address" : "NULL");
+    else if (cap < 0 || (cap > 0 && !out_order)) snprintf(msg, sizeof(msg), "out_order: room for %d indices at %s", cap, out_order ? "an address" : "NULL");
+    else if (img_w < 1 || img_h < 1 || img_w > 65535 || img_h > 65535 || (long long)img_w * img_h >= (1 << 24))
+        snprintf(msg, sizeof(msg), "image %d x %d: sizes of 1 .. 65535 with img_w * img_h < 2^24 are expected", img_w, img_h);
+    else if (n > cand_cap) snprintf(msg, sizeof(msg), "%d keypoints: the context's level-0 candidate capacity is %d", n, cand_cap);
+    else if ((num_out_points < n ? num_out_points : n) > max_kps)
+        snprintf(msg, sizeof(msg), "min(num_out_points, n) = %d: the selection keeps at most max_kps = %d", num_out_points < n ? num_out_points : n, max_kps);
+    long long last = -1;
+    for (int i = 0; i < n && !msg[0]; i++) {
+        const float x = kps[i].x, y = kps[i].y;
+        if (!(x >= 0.0f && x < (float)img_w && y >= 0.0f && y < (float)img_h) || x != (float)(int)x || y != (float)(int)y)
+            snprintf(msg, sizeof(msg), "keypoint %d at (%g, %g): integer coordinates inside %d x %d are expected", i, (double)x, (double)y, img_w, img_h);
+        else if (kps[i].response != kps[i].response) snprintf(msg, sizeof(msg), "keypoint %d: its response is NaN", i);
+        else {
+            const long long pos = (long long)(int)y * img_w + (int)x;
+            if (pos <= last) snprintf(msg, sizeof(msg), "keypoint %d at (%d, %d): strictly ascending raster order is expected", i, (int)x, (int)y);
+            last = pos;
+        }
+    }
+    if (!msg[0]) return SVO_OK;
     why = msg; return SVO_ERR_ARG;
 }
 

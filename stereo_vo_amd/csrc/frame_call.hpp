@@ -36,8 +36,10 @@ struct FrameCall {
     int max_sad_match;       // smSAD: size_t(sad_max_distance) (S3:201): 0 = the reference's 200 (S3:48), negative = no threshold
     unsigned max_sad_track;  // ifmSAD: uint32_t MAX_SAD (S4:448): 0 = "~200" (H:297), negative wraps to no threshold
     double minresp;          // S3:189-193: minimum_ORB_response under dmORB, 0 otherwise
+    bool faster_anms_on;     // svo_set_faster_adaptive_nms: the context has opted in to the adaptive NMS under dmFASTER
+    bool faster_anms;        // ... and this call's parameters select it: dmFASTER + non_maximal_suppression + nmsmAdaptive
 };
-FrameCall make_frame_call(uint32_t flags, const svo_params& p);
+FrameCall make_frame_call(uint32_t flags, const svo_params& p, bool faster_adaptive_nms = false);
 
 // The refusals a call meets before anything is enqueued or noted, in their order: selectors, variants outside the hot path, dmFASTER's
 // rules, the detect-ahead flag combinations, then the one-mask-per-frame rule (frame_active: the mask of the frame in flight, NULL when
@@ -58,5 +60,11 @@ int check_dyn_fast_target(double target, std::string& why);
 // ... and whether a svo_set_params re-initialises the lanes' thresholds: when the number of octaves m_threshold is sized by changes
 // (S2:522-523: m_threshold.size() != nOctaves), and for no other field -- initial_FAST_threshold included
 bool dyn_fast_octaves_changed(const svo_params& before, const svo_params& after);
+
+// svo_adaptive_nms: the argument rules that need no device.  kps must be n keypoints in strictly ascending raster order with integer
+// coordinates inside img_w x img_h and no NaN response, img_w * img_h < 2^24, n <= cand_cap (the context's level-0 candidate capacity),
+// min(num_out_points, n) <= max_kps (the selection sorts that many keys in LDS).  SVO_OK, or SVO_ERR_ARG with the text.
+int check_adaptive_nms_args(const svo_keypoint* kps, int n, int num_out_points, int img_w, int img_h, const int32_t* out_order, int cap,
+                            int cand_cap, int max_kps, std::string& why);
 
 }

@@ -2035,11 +2035,10 @@ __global__ void __launch_bounds__(1024) k_faster_nms(DevCtx c, const unsigned lo
 // svo_set_dyn_fast_threshold: the same kernel, and the one place where the lane's thresholds MOVE (S2:537-549).  Both k_faster_dyn
 // launches are complete, so both corner counts are final: thread 0 of the (octave, right image) block walks the rule over the left
 // and the right count and leaves m_threshold[octave] with the statistics.  Nothing in this launch reads them.
-__global__ void __launch_bounds__(1024) k_faster_nms_dyn(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX,
-                                                         svo_faster_stats* stats, double target)
+// (the commit itself: called by every thread of a selection block (octave = blockIdx.x, image = blockIdx.y) behind both k_faster_dyn launches --
+// k_faster_nms_dyn here, k_faster_anms below)
+__device__ __forceinline__ void faster_dyn_commit(const DevCtx& c, svo_faster_stats* stats, double target)
 {
-    SVO_TL_SCOPE(c, TL_NMS, 4);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int level = blockIdx.x, img = blockIdx.y;
     if ((img & 1) && threadIdx.x == 0 && level < SVO_MAX_OCTAVES && !lane_idle(c, img >> 1)) {
         svo_faster_stats& s = stats[img >> 1];
@@ -2049,6 +2048,14 @@ __global__ void __launch_bounds__(1024) k_faster_nms_dyn(DevCtx c, const unsigne
         s.used_left[level] = t0; s.used_right[level] = t1; s.corners_left[level] = (int)nl; s.corners_right[level] = (int)nr; s.next[level] = t2;
         if (level == 0) s.frame++;
     }
+}
+
+__global__ void __launch_bounds__(1024) k_faster_nms_dyn(DevCtx c, const unsigned long long* cand64, int min_distance, int do_nms, int NS_MAX, int ACC_MAX,
+                                                         svo_faster_stats* stats, double target)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 4);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    faster_dyn_commit(c, stats, target);
     chunked_grid_nms<FasterKeys>(c, smem, cand64, min_distance, do_nms, NS_MAX, ACC_MAX);
 }
 
@@ -2204,6 +2211,278 @@ void launch_fastorb_anms(const DevCtx& c, uint32_t* scratch3, hipStream_t st)
     hipLaunchKernelGGL(k_fastorb_anms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, scratch3, scratch3 + one, scratch3 + 2 * one, L.n_keys());
 }
 size_t fastorb_anms_scratch_words(int n_img, int cand_total) { return LdsFastorbAnms::scratch_words(n_img, cand_total); }
+
+// ------------------------------------------------------------------------------------------------------------
+// dmFASTER with nmsmAdaptive (svo_set_faster_adaptive_nms): m_adaptive_non_max_sup (S2:141-215) on dmFASTER's raw list -- EVERY FAST-12
+// corner of an octave image, up to cand_cap of them, ranked by a float KLT response.  k_fastorb_anms above cannot serve: there are no
+// score buckets, and a brute-force scan of "every robustly stronger corner" is N * mean L ~ 10^10 distances on a dense image.  Here,
+// one 1024-thread block per (octave, image), in the oracle's total orders (rank = response desc, index asc; output = radius desc, index asc):
+//   1. the keys ord32(response) << 32 | ~position are sorted descending into global scratch: stable LSB radix passes of 8 bits over
+//      the live bytes (the position's, then the response's four), every wave ranking its own contiguous segment with ballots;
+//   2. L(i) = min(i, #{ j : (double)r_i < 0.9 (double)r_j }) (S2:183; a prefix of the rank order, because 0.9 r_j is monotone in r_j)
+//      by binary search over ranks [0, i) with that very comparison.  The radius of rank i >= 1 is the minimum of d2(i, 0) (S2:176) and
+//      of d2(i, j) over ranks j in [1, L(i)) (S2:179-190: the inner loop only looks below i; the min(i, .) matters for responses <= 0,
+//      where the comparison also holds for weaker corners); rank 0 has radius +inf (S2:167);
+//   3. a uniform grid of <= FA_NCELL cells of 2^s x 2^s pixels: the corners again, sorted by (cell, rank) with two more radix passes, as
+//      cell << 19 | rank in the high word and x | y << 16 in the low one; per cell the first member and the smallest rank, per grid row
+//      and grid column the smallest rank;
+//   4. the nearest corner of rank < L: rings of cells outward from the corner's own.  A ring edge whose row / column holds no rank
+//      below L costs one LDS load, a cell that holds none another, the members of a cell are scanned while their rank is below L.  Ring r
+//      holds no corner closer than m = (r - 1) 2^s + 1 in x or y, so the walk ends when m * m >= best: d2 is the reference's FLOAT
+//      dx * dx + dy * dy (one IEEE operation per operator: -ffp-contract=off; rounded beyond 4096 pixels, so not integer arithmetic), which
+//      is monotone in |dx| and |dy|, hence the same expression at (m, 0) is a valid bound.  L <= FA_DIRECT: the sorted prefix is scanned directly;
+//   5. the first min(cap, N) of (radius desc, position asc): radix select on the radius bits (non-negative floats order as their bits),
+//      ties at the cut by position, one LDS sort, as in k_fastorb_anms.  Positions are unique, so every radius is >= 1 > min_radius_th^2 = 0
+//      and the filter of S2:209 drops nothing.  Each kept corner finds its slot by binary search and is emitted as FasterKeys::emit does.
+// Global scratch per image: three arrays of cand_total 64-bit words (two to sort between, one for the cell members; whichever is
+// free at the end holds the radii).  The input keys are only read.
+#define FA_NCELL 8192        // cells of the grid: 13 bits ...
+#define FA_RANK_BITS 19      // ... beside the rank in one 32-bit word: N <= 2^19 (svo_set_faster_adaptive_nms checks max_cand)
+#define FA_DIRECT 96         // L up to which the sorted prefix is scanned directly
+#define LDS_FN __host__ __device__ constexpr int
+struct LdsFasterAnms {                                   // k_faster_anms, k_anms_list (+ 1216 B static); the three phases alias
+    int max_kps;
+    LDS_FN n_wave_hist() const { return 256 * 16; }        // unsigned: phase 1 and 3, a counter per (digit, wave)
+    LDS_FN n_cell() const { return FA_NCELL; }             // uint32_t, twice: first member, smallest rank
+    LDS_FN n_line() const { return FA_NCELL + 8; }         // uint32_t: smallest rank of every grid row, then of every grid column (gx + gy <= gx * gy + 1)
+    LDS_FN n_keys() const { int k = 64; while (k < max_kps) k <<= 1; return k; }      // u64: phase 5, the power of two >= cap
+    LDS_FN grid_bytes() const { return 4 * (2 * n_cell() + n_line()); }
+    LDS_FN total() const { return 8 * n_keys() > grid_bytes() ? 8 * n_keys() : grid_bytes(); }
+    static constexpr int N_SCRATCH = 3;                    // 64-bit words per candidate
+    static __host__ __device__ constexpr size_t scratch_words(int n_img, int cand_total) { return (size_t)N_SCRATCH * n_img * cand_total; }
+};
+static_assert(LdsFasterAnms{1024}.total() == 98336 && LdsFasterAnms{16384}.total() == 131072 && LdsFasterAnms{16384}.n_wave_hist() * 4 <= LdsFasterAnms{64}.grid_bytes(), "k_faster_anms LDS totals");
+static_assert(LdsFasterAnms{16384}.total() + 1216 <= LDS_CU_BYTES, "gfx950: 160 KB of LDS per CU");
+static_assert(LdsFasterAnms::scratch_words(4, 1000) == 12000 && FA_RANK_BITS + 13 == 32 && (1 << 13) == FA_NCELL, "k_faster_anms scratch, member word");
+#undef LDS_FN
+
+// one stable pass of the block's radix sorts: dst = src ordered by byte `shift` of the key, descending (DESC) or ascending.  Wave v owns
+// the contiguous segment [v * per, (v + 1) * per) and keeps one counter per digit; after the scan over (digit major, wave minor) a
+// counter is where the wave's next key of that digit goes.  Inside a wave the lanes of one digit are found with eight ballots and
+// take consecutive places in lane order.  cnt: 4096 LDS words; scan as for block_exclusive_scan.  All 1024 threads call.
+template <bool DESC>
+__device__ __forceinline__ void anms_radix_pass(const unsigned long long* src, unsigned long long* dst, unsigned n, int shift, unsigned* cnt, int* scan)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned per = ((n + 1023u) >> 10) << 6, beg = min(n, (unsigned)wid * per), end = min(n, beg + per);
+    for (int i = tid; i < 4096; i += 1024) cnt[i] = 0;
+    __syncthreads();
+    for (unsigned i = beg + lane; i < end; i += 64) {
+        const unsigned d = (unsigned)(src[i] >> shift) & 255u;
+        atomicAdd(&cnt[(DESC ? 255u - d : d) * 16 + wid], 1u);
+    }
+    __syncthreads();
+    {
+        const uint4 v = ((const uint4*)cnt)[tid];                          // thread t owns counters 4t .. 4t + 3
+        int tot;
+        const int off = block_exclusive_scan((int)(v.x + v.y + v.z + v.w), scan, &tot);
+        ((uint4*)cnt)[tid] = make_uint4((unsigned)off, (unsigned)off + v.x, (unsigned)off + v.x + v.y, (unsigned)off + v.x + v.y + v.z);
+    }
+    __syncthreads();
+    volatile unsigned* vc = cnt;
+    for (unsigned base = beg; base < end; base += 64) {                    // wave-uniform
+        const unsigned i = base + lane;
+        const bool valid = i < end;
+        const unsigned long long k = valid ? src[i] : 0ull;
+        unsigned d = (unsigned)(k >> shift) & 255u;
+        if (DESC) d = 255u - d;
+        unsigned long long m = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; b++) { const bool bit = (d >> b) & 1u; const unsigned long long bm = __ballot(bit); m &= bit ? bm : ~bm; }
+        const unsigned before = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        unsigned o = 0;
+        if (valid) o = vc[d * 16 + wid];
+        wave_lds_sync();
+        if (valid && before == 0) vc[d * 16 + wid] = o + (unsigned)__popcll(m);
+        wave_lds_sync();
+        if (valid) dst[o + before] = k;
+    }
+    __threadfence_block();
+    __syncthreads();
+}
+
+__device__ __forceinline__ float anms_d2(int dx, int dy) { const float fx = (float)dx, fy = (float)dy; return fx * fx + fy * fy; }      // S2:176 / 185
+
+// The body: ck[nc] keys of one w x h image -> emit(o, key) for the o-th kept corner, o in [0, actual), actual = min(cap, nc) >= 1,
+// actual <= KMAX.  s0, s1, s2: nc 64-bit words of scratch each.  All 1024 threads call.
+template <class Emit>
+__device__ __forceinline__ void faster_anms_block(unsigned char* smem, const unsigned long long* ck, unsigned nc, int w, int h, int actual,
+                                                  unsigned long long* s0, unsigned long long* s1, unsigned long long* s2, int KMAX, Emit emit)
+{
+    unsigned long long* keys = (unsigned long long*)smem;                  // LdsFasterAnms: phase 5
+    unsigned* wave_hist = (unsigned*)smem;                                 // phases 1, 3
+    uint32_t* cellstart = (uint32_t*)smem;                                 // phases 3 (end), 4
+    uint32_t* cellmin = cellstart + FA_NCELL;
+    uint32_t* linemin = cellmin + FA_NCELL;
+    __shared__ unsigned hist[256];
+    __shared__ int scan[40];
+    __shared__ unsigned sh[8];
+    const int tid = threadIdx.x;
+    // ---- 1. the rank order ----
+    const unsigned npix = (unsigned)w * (unsigned)h;
+    const int nb = npix <= 256u ? 1 : (npix <= 65536u ? 2 : (npix <= (1u << 24) ? 3 : 4));      // live bytes of ~position (the others are all ones)
+    const unsigned long long* src = ck;
+    unsigned long long* dst = s0;
+    unsigned long long* other = s1;
+    for (int p = 0; p < nb + 4; p++) {
+        anms_radix_pass<true>(src, dst, nc, p < nb ? 8 * p : 32 + 8 * (p - nb), wave_hist, scan);
+        src = dst; dst = other; other = (unsigned long long*)src;
+    }
+    unsigned long long* sorted = other;                                    // (= src) response << 32 | ~position, by rank
+    unsigned long long* spare = dst;
+    // ---- 3. the cell grid (the positions unpacked once: sorted[] carries x | y << 16 from here on) ----
+    int s = 2;
+    while (((w + (1 << s) - 1) >> s) * ((h + (1 << s) - 1) >> s) > FA_NCELL) s++;
+    const int gx = (w + (1 << s) - 1) >> s, gy = (h + (1 << s) - 1) >> s, ncell = gx * gy;
+    for (unsigned i = tid; i < nc; i += 1024) {
+        const unsigned long long k = sorted[i];
+        const uint32_t pos = 0xFFFFFFFFu - (uint32_t)k, y = pos / (uint32_t)w, x = pos - y * (uint32_t)w, xy = x | (y << 16);
+        const uint32_t cell = (y >> s) * (uint32_t)gx + (x >> s);
+        sorted[i] = (k & 0xFFFFFFFF00000000ull) | xy;
+        s2[i] = ((unsigned long long)((cell << FA_RANK_BITS) | i) << 32) | xy;
+    }
+    __threadfence_block();
+    __syncthreads();
+    anms_radix_pass<false>(s2, spare, nc, 32 + FA_RANK_BITS, wave_hist, scan);
+    const unsigned long long* mem = spare;
+    uint32_t* rad = (uint32_t*)s2;
+    if (ncell > 256) { anms_radix_pass<false>(spare, s2, nc, 32 + FA_RANK_BITS + 8, wave_hist, scan); mem = s2; rad = (uint32_t*)spare; }
+    for (int i = tid; i < ncell; i += 1024) cellmin[i] = 0xFFFFFFFFu;
+    for (int i = tid; i < gx + gy; i += 1024) linemin[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (unsigned i = tid; i < nc; i += 1024) {
+        const uint32_t hi = (uint32_t)(mem[i] >> 32), cell = hi >> FA_RANK_BITS;
+        if (i == 0 || (uint32_t)(mem[i - 1] >> (32 + FA_RANK_BITS)) != cell) {      // the cell's first member: its smallest rank
+            const uint32_t r = hi & ((1u << FA_RANK_BITS) - 1u);
+            cellstart[cell] = i; cellmin[cell] = r;
+            atomicMin(&linemin[cell / (uint32_t)gx], r); atomicMin(&linemin[gy + cell % (uint32_t)gx], r);
+        }
+    }
+    __syncthreads();
+    // ---- 2., 4. radius^2 of every corner (index = rank), as float bits ----
+    const uint32_t top = (uint32_t)sorted[0];
+    const int tx = (int)(top & 0xFFFFu), ty = (int)(top >> 16);
+    for (unsigned i = tid; i < nc; i += 1024) {
+        uint32_t rbits = 0x7F800000u;                                      // the strongest corner: +inf (S2:167)
+        if (i > 0) {
+            const unsigned long long k = sorted[i];
+            const int x = (int)((uint32_t)k & 0xFFFFu), y = (int)((uint32_t)k >> 16);
+            const double ri = (double)inv_ord32((uint32_t)(k >> 32));
+            float best = anms_d2(x - tx, y - ty);                          // S2:176
+            unsigned lo = 0, hi = i;                                       // the comparison holds below lo and fails from hi on
+            while (lo < hi) {
+                const unsigned mid = (lo + hi) >> 1;
+                if (ri < 0.9 * (double)inv_ord32((uint32_t)(sorted[mid] >> 32))) lo = mid + 1; else hi = mid;      // S2:183
+            }
+            const unsigned L = lo;
+            if (L > 1 && L <= FA_DIRECT) {
+                for (unsigned j = 1; j < L; j++) {
+                    const uint32_t pj = (uint32_t)sorted[j];
+                    best = fminf(best, anms_d2(x - (int)(pj & 0xFFFFu), y - (int)(pj >> 16)));                      // S2:185
+                }
+            } else if (L > 1) {
+                const int cx = x >> s, cy = y >> s, rmax = max(max(cx, gx - 1 - cx), max(cy, gy - 1 - cy));
+                auto scan_cell = [&](int cell) {
+                    if (cellmin[cell] >= L) return;
+                    const uint32_t lim = ((uint32_t)cell << FA_RANK_BITS) + L;
+                    for (unsigned m = cellstart[cell]; m < nc; m++) {
+                        const unsigned long long e = mem[m];
+                        if ((uint32_t)(e >> 32) >= lim) break;             // a rank >= L, or the next cell
+                        best = fminf(best, anms_d2(x - (int)((uint32_t)e & 0xFFFFu), y - (int)((uint32_t)e >> 16)));
+                    }
+                };
+                scan_cell(cy * gx + cx);
+                for (int r = 1; r <= rmax; r++) {
+                    const float m = (float)(((r - 1) << s) + 1);
+                    if (m * m >= best) break;                              // nothing from ring r on is closer
+                    const int xa = max(cx - r, 0), xb = min(cx + r, gx - 1), ya = max(cy - r + 1, 0), yb = min(cy + r - 1, gy - 1);
+                    if (cy - r >= 0 && linemin[cy - r] < L) for (int q = xa; q <= xb; q++) scan_cell((cy - r) * gx + q);
+                    if (cy + r < gy && linemin[cy + r] < L) for (int q = xa; q <= xb; q++) scan_cell((cy + r) * gx + q);
+                    if (cx - r >= 0 && linemin[gy + cx - r] < L) for (int q = ya; q <= yb; q++) scan_cell(q * gx + cx - r);
+                    if (cx + r < gx && linemin[gy + cx + r] < L) for (int q = ya; q <= yb; q++) scan_cell(q * gx + cx + r);
+                }
+            }
+            rbits = __float_as_uint(best);
+        }
+        rad[i] = rbits;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ---- 5. the first `actual` of the (radius desc, position asc) order ----
+    auto inv_pos = [&](unsigned i) { const uint32_t xy = (uint32_t)sorted[i]; return 0xFFFFFFu - ((xy >> 16) * (uint32_t)w + (xy & 0xFFFFu)); };      // w * h <= 2^24
+    unsigned prefix = 0, mask = 0, need = (unsigned)actual;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += 1024) hist[i] = 0;
+        __syncthreads();
+        for (unsigned i = tid; i < nc; i += 1024) { const uint32_t r = rad[i]; if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u); }
+        __syncthreads();
+        radix_pick_bin(hist, shift, scan, &sh[1], &sh[2], prefix, need, mask);
+    }
+    const uint32_t rcut = prefix;          // radii > rcut are all in; `need` of the corners with radius == rcut, smallest positions first
+    unsigned p2 = 0, m2 = 0, need2 = need;
+    for (int shift = 16; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += 1024) hist[i] = 0;
+        __syncthreads();
+        for (unsigned i = tid; i < nc; i += 1024) if (rad[i] == rcut) { const uint32_t ip = inv_pos(i); if ((ip & m2) == p2) atomicAdd(&hist[(ip >> shift) & 255u], 1u); }
+        __syncthreads();
+        radix_pick_bin(hist, shift, scan, &sh[3], &sh[4], p2, need2, m2);
+    }
+    const uint32_t ipcut = p2;             // ties with inverted position >= ipcut are in (positions are unique)
+    for (int i = tid; i < KMAX; i += 1024) keys[i] = 0;
+    if (tid == 0) sh[5] = 0;
+    __syncthreads();
+    for (unsigned i = tid; i < nc; i += 1024) {
+        const uint32_t r = rad[i];
+        if (r < rcut) continue;
+        const uint32_t ip = inv_pos(i);
+        if (r > rcut || ip >= ipcut) {
+            const unsigned sl = atomicAdd(&sh[5], 1u);
+            if (sl < (unsigned)KMAX) keys[sl] = ((unsigned long long)r << 32) | ((unsigned long long)ip << 8);
+        }
+    }
+    __syncthreads();
+    int P = 64; while (P < actual) P <<= 1;
+    bitonic_sort_lds<true>(keys, P);
+    for (unsigned i = tid; i < nc; i += 1024) {
+        const uint32_t r = rad[i];
+        if (r < rcut) continue;
+        const uint32_t ip = inv_pos(i);
+        if (!(r > rcut || ip >= ipcut)) continue;
+        const unsigned long long e = ((unsigned long long)r << 32) | ((unsigned long long)ip << 8);
+        int lo = 0, hi = actual - 1;                                       // the keys are unique and e is among the first `actual`
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] > e) lo = mid + 1; else hi = mid; }
+        emit(lo, (sorted[i] & 0xFFFFFFFF00000000ull) | (unsigned long long)(0xFFFFFFFFu - (0xFFFFFFu - ip)));
+    }
+}
+
+// stats != nullptr (svo_set_dyn_fast_threshold): the (octave, right image) block also commits the lane's thresholds, as k_faster_nms_dyn does
+__global__ void __launch_bounds__(1024) k_faster_anms(DevCtx c, const unsigned long long* cand64, unsigned long long* scratch, int KMAX, svo_faster_stats* stats, double target)
+{
+    SVO_TL_SCOPE(c, TL_NMS, 5);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int level = blockIdx.x, img = blockIdx.y;
+    if (lane_idle(c, img >> 1)) return;
+    if (stats) faster_dyn_commit(c, stats, target);
+    const LevelGeom& g = c.lv[level];
+    unsigned nc = c.cand_cnt[(img * SVO_MAX_LEVELS + level) * SVO_CNT_STRIDE];
+    if (nc > (unsigned)g.cand_cap) nc = g.cand_cap;
+    const int cap = min(min(c.kps_to_detect[level], g.quota), c.max_kps);
+    const int actual = min((int)nc, cap);                                  // S2:151
+    if (actual <= 0) { if (threadIdx.x == 0) c.lvl_n[img * SVO_MAX_LEVELS + level] = 0; return; }
+    const size_t one = (size_t)c.n_img * c.cand_total, at = (size_t)img * c.cand_total + g.cand_off;
+    const long long out0 = (long long)img * c.raw_cap + g.slot_off;
+    faster_anms_block(smem, cand64 + at, nc, g.w, g.h, actual, scratch + at, scratch + one + at, scratch + 2 * one + at, KMAX,
+                      [&](int o, unsigned long long key) { FasterKeys::emit(c, out0 + o, key, (uint32_t)g.w); });
+    if (threadIdx.x == 0) c.lvl_n[img * SVO_MAX_LEVELS + level] = actual;
+}
+
+// svo_adaptive_nms: the same body on one caller-built list; out_pos[o] = raster position of the o-th kept corner
+__global__ void __launch_bounds__(1024) k_anms_list(const unsigned long long* keys_in, int n, int w, int h, int actual, unsigned long long* scratch, size_t one, uint32_t* out_pos, int KMAX)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    faster_anms_block(smem, keys_in, (unsigned)n, w, h, actual, scratch, scratch + one, scratch + 2 * one, KMAX,
+                      [&](int o, unsigned long long key) { out_pos[o] = 0xFFFFFFFFu - (uint32_t)key; });
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // dmFASTER (stage2_detect.cpp:519-576): FAST-12 corners of every x1/2 octave image at ONE constant threshold, ranked by
@@ -2530,4 +2809,27 @@ void launch_faster_nms_dyn(const DevCtx& c, const unsigned long long* cand64, in
 {
     const auto L = chunked_nms_layout<FasterKeys>(c);
     hipLaunchKernelGGL(k_faster_nms_dyn, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, cand64, min_distance, do_nms, L.ns_max, L.acc_max, stats, target);
+}
+
+// svo_set_faster_adaptive_nms: the selection behind k_faster / k_faster_dyn in place of k_faster_nms(_dyn).  scratch: faster_anms_scratch_words()
+// 64-bit words; stats: nullptr, or the lanes' records while svo_set_dyn_fast_threshold is on
+hipError_t configure_faster_anms(int max_kps)
+{
+    const hipError_t e = svo_raise_dyn_smem((const void*)k_faster_anms, LdsFasterAnms{max_kps}.total());
+    return e != hipSuccess ? e : svo_raise_dyn_smem((const void*)k_anms_list, LdsFasterAnms{max_kps}.total());
+}
+size_t faster_anms_scratch_words(int n_img, int cand_total) { return LdsFasterAnms::scratch_words(n_img, cand_total); }
+int faster_anms_max_candidates() { return 1 << FA_RANK_BITS; }
+
+void launch_faster_anms(const DevCtx& c, const unsigned long long* cand64, unsigned long long* scratch, svo_faster_stats* stats, double target, hipStream_t st)
+{
+    const LdsFasterAnms L{c.max_kps};
+    hipLaunchKernelGGL(k_faster_anms, dim3(c.n_levels, c.n_img), dim3(1024), (size_t)L.total(), st, c, cand64, scratch, L.n_keys(), stats, target);
+}
+
+// ... and on one list (svo_adaptive_nms): keys[n] as k_faster publishes them, scratch of faster_anms_scratch_words(1, n_cap) words
+void launch_anms_list(const unsigned long long* keys, int n, int w, int h, int actual, int max_kps, unsigned long long* scratch, int n_cap, uint32_t* out_pos, hipStream_t st)
+{
+    const LdsFasterAnms L{max_kps};
+    hipLaunchKernelGGL(k_anms_list, dim3(1), dim3(1024), (size_t)L.total(), st, keys, n, w, h, actual, scratch, (size_t)n_cap, out_pos, L.n_keys());
 }

@@ -104,6 +104,10 @@ public:
       * false, the reference's behaviour, keeps dmFASTER at the constant initial_FAST_threshold; true lets m_threshold[octave] follow
       * params_detect.target_feats_per_pixel on the device (svo_set_dyn_fast_threshold).  Set it, then applyParams(). */
     bool update_dyn_thresholds = false;
+    /** The context's opt-in to the adaptive NMS under dmFASTER (svo_set_faster_adaptive_nms).  The reference applies params_detect.nmsMethod =
+      * nmsmAdaptive to whatever detector ran (S2:599-606); here a dmFASTER + nmsmAdaptive configuration is refused by processNewImagePair
+      * unless this is true: it allocates scratch per stream and selects the most expensive selection kernel.  Set it, then applyParams(). */
+    bool faster_adaptive_nms = false;
     /** m_threshold and the GUI statistics of S2:548-549 (svo_faster_stats); only while update_dyn_thresholds is applied */
     void getFASTERStats(svo_faster_stats& out) { check(svo_get_faster_stats(m_ctx, 0, &out), "svo_get_faster_stats"); }
 
@@ -122,6 +126,7 @@ public:
     void applyParams() {
         check(svo_set_params(m_ctx, &params), "svo_set_params"); check(svo_set_klt_win(m_ctx, params_detect.KLT_win), "svo_set_klt_win");
         check(svo_set_dyn_fast_threshold(m_ctx, update_dyn_thresholds ? 1 : 0, params_detect.target_feats_per_pixel), "svo_set_dyn_fast_threshold");
+        check(svo_set_faster_adaptive_nms(m_ctx, faster_adaptive_nms ? 1 : 0), "svo_set_faster_adaptive_nms");
     }
     /** Loads configuration from an INI file from its name (H:665-672); sections in the order RECTIFY, DETECT, MATCH, IF-MATCH,
       * LEAST_SQUARES, GUI, GENERAL (H:551-553), an empty name skips the group */

@@ -117,6 +117,9 @@ struct svo_ctx {
     // svo_set_dyn_fast_threshold: dmFASTER's m_threshold[octave] of every lane (the `next` member) with its statistics; nullptr until first enabled.
     // Persistent detector scratch: read and written by detect calls alone, ordered on the stream they run on, like fast_th_dyn
     bool dyn_fast; double dyn_target; svo_faster_stats* d_fstats;
+    // svo_set_faster_adaptive_nms: the opt-in, and the scratch of k_faster_anms (3 x n_img x cand_total 64-bit words), allocated by the setter.
+    // svo_adaptive_nms has buffers of its own (keys, scratch, positions out), allocated by its first call: it touches nothing a frame uses
+    bool faster_anms; unsigned long long* d_fanms; unsigned long long* d_anms_list; uint32_t* d_anms_pos;
     unsigned long long* d_cand64;                      // dmFASTER's 64-bit candidate keys (n_img x cand_total), allocated by the first svo_process made while it is selected
     // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
     // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
@@ -381,6 +384,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->fast_th = 20; ctx->orb_th = 60;                  // common.cpp:35-36
     ctx->klt_win = 4; ctx->d_cand64 = nullptr;            // stage2_detect.cpp:47
     ctx->dyn_fast = false; ctx->dyn_target = 10. / 1000.; ctx->d_fstats = nullptr;      // stage2_detect.cpp:46; update_dyn_thresholds = false (H:1020)
+    ctx->faster_anms = false; ctx->d_fanms = nullptr; ctx->d_anms_list = nullptr; ctx->d_anms_pos = nullptr;
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
@@ -703,6 +707,64 @@ extern "C" int svo_get_faster_stats(svo_ctx* ctx, int lane, svo_faster_stats* ou
     return SVO_OK;
 }
 // (svo_faster_threshold_step, the rule as a host function, is in frame_call.cpp: it needs no device)
+
+// The adaptive NMS under dmFASTER (stage2_detect.cpp:599-606 behind S2:519-576; svo_hip.h at svo_set_faster_adaptive_nms): an opt-in of
+// the context.  While it is off a call that selects the combination is refused as it always was (frame_call.cpp).
+extern "C" int svo_set_faster_adaptive_nms(svo_ctx* ctx, int enable)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    const bool on = enable != 0;
+    if (on == ctx->faster_anms) return SVO_OK;
+    if (on) {
+        if (std::max(1024, ctx->cfg.max_cand) > faster_anms_max_candidates()) {
+            char msg[160]; snprintf(msg, sizeof(msg), "max_cand %d: the adaptive NMS under dmFASTER ranks at most %d candidates per image", ctx->cfg.max_cand, faster_anms_max_candidates());
+            ctx->last_error = msg; return SVO_ERR_UNSUPPORTED;
+        }
+        // allocated here, not at the first frame: before any capture (as d_fstats), and so that a context that cannot afford it learns so now
+        if (!ctx->d_fanms) HIPCHECK(dev_alloc(ctx, &ctx->d_fanms, faster_anms_scratch_words(2 * ctx->cfg.n_lanes, ctx->cand_total_alloc)));
+        HIPCHECK(configure_faster_anms(ctx->dc.max_kps));
+    }
+    drop_graphs(ctx);                                        // the launches of a detect call under dmFASTER + nmsmAdaptive change
+    ctx->faster_anms = on;
+    return SVO_OK;
+}
+extern "C" int svo_get_faster_adaptive_nms(const svo_ctx* ctx) { return ctx ? (ctx->faster_anms ? 1 : 0) : SVO_ERR_ARG; }
+
+// m_adaptive_non_max_sup on caller arrays: the device code of k_faster_anms on one list, so that it can be held to a reference on
+// hand-built inputs.  The keys are built here as k_faster publishes them; strictly ascending raster order makes position order index order.
+extern "C" int svo_adaptive_nms(svo_ctx* ctx, const svo_keypoint* kps, int n, int num_out_points, int img_w, int img_h, int32_t* out_order, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    const int n_cap = std::min(std::max(1024, ctx->cfg.max_cand), faster_anms_max_candidates());
+    { std::string why; const int rc = check_adaptive_nms_args(kps, n, num_out_points, img_w, img_h, out_order, cap, n_cap, ctx->dc.max_kps, why); if (rc) { ctx->last_error = why; return rc; } }
+    const int actual = std::min(num_out_points, n);                               // S2:151
+    if (actual <= 0) return 0;                                                   // S2:152
+    if (!ctx->d_anms_list) {
+        HIPCHECK(dev_alloc(ctx, &ctx->d_anms_list, (size_t)n_cap + faster_anms_scratch_words(1, n_cap)));
+        HIPCHECK(dev_alloc(ctx, &ctx->d_anms_pos, (size_t)ctx->dc.max_kps));
+    }
+    HIPCHECK(configure_faster_anms(ctx->dc.max_kps));
+    std::vector<unsigned long long> keys((size_t)n);
+    std::vector<uint32_t> pos_of((size_t)n);
+    for (int i = 0; i < n; i++) {
+        uint32_t u; memcpy(&u, &kps[i].response, 4);
+        const uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);         // ord32 (svo_device.h)
+        pos_of[(size_t)i] = (uint32_t)((int)kps[i].y * img_w + (int)kps[i].x);
+        keys[(size_t)i] = ((unsigned long long)ord << 32) | (unsigned long long)(0xFFFFFFFFu - pos_of[(size_t)i]);
+    }
+    const hipStream_t st = ctx->stream;
+    HIPCHECK(hipMemcpyAsync(ctx->d_anms_list, keys.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    launch_anms_list(ctx->d_anms_list, n, img_w, img_h, actual, ctx->dc.max_kps, ctx->d_anms_list + n_cap, n_cap, ctx->d_anms_pos, st);
+    std::vector<uint32_t> out((size_t)actual);
+    HIPCHECK(hipMemcpyAsync(out.data(), ctx->d_anms_pos, (size_t)actual * 4, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    for (int o = 0; o < actual && o < cap; o++)
+        out_order[o] = (int32_t)(std::lower_bound(pos_of.begin(), pos_of.end(), out[(size_t)o]) - pos_of.begin());
+    return actual;
+}
 
 extern "C" int svo_set_stream(svo_ctx* ctx, void* stream)
 {
@@ -1240,6 +1302,13 @@ static void enqueue_detect(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
                             // constant initial_FAST_threshold (m_threshold never moves: processNewImagePair passes no update_dyn_thresholds) unless
                             // svo_set_dyn_fast_threshold is on: then the lane's own m_threshold[octave], moved on the device (S2:537-546)
         { Span s(ctx, KT_RESIZE); for (int l = 1; l < d.n_levels; l++) launch_half(d, l, st); }
+        if (call.faster_anms) {     // svo_set_faster_adaptive_nms + nmsmAdaptive (S2:599-606 on this detector's output): the same detector launches, then
+                                    // k_faster_anms where the grid NMS would go -- it commits the dynamic thresholds itself when those are on
+            if (ctx->dyn_fast) { Span s(ctx, KT_FASTER); launch_faster_dyn(d, ctx->d_cand64, ctx->d_fstats, ctx->dyn_target, ctx->klt_win, st); }
+            else { Span s(ctx, KT_FASTER); launch_faster(d, ctx->d_cand64, p.initial_FAST_threshold, ctx->klt_win, st); }
+            { Span s(ctx, KT_FASTER_NMS); launch_faster_anms(d, ctx->d_cand64, ctx->d_fanms, ctx->dyn_fast ? ctx->d_fstats : nullptr, ctx->dyn_target, st); }
+            return;
+        }
         if (ctx->dyn_fast) {
             { Span s(ctx, KT_FASTER); launch_faster_dyn(d, ctx->d_cand64, ctx->d_fstats, ctx->dyn_target, ctx->klt_win, st); }      // two launches under one name
             { Span s(ctx, KT_FASTER_NMS); launch_faster_nms_dyn(d, ctx->d_cand64, p.non_maximal_suppression, p.min_distance, ctx->d_fstats, ctx->dyn_target, st); }
@@ -1366,7 +1435,7 @@ static int finish_call(svo_ctx* ctx, const FrameCall& call)
 static int process_lanes_body(svo_ctx* ctx, const uint64_t* lanes, bool masked, const svo_frame* frames, uint32_t flags)
 {
     const svo_params& p = ctx->params;
-    const FrameCall call = make_frame_call(flags, p);
+    const FrameCall call = make_frame_call(flags, p, ctx->faster_anms);
     // the mask first, without leaving: who is active, who sits out, and whether the mask itself is acceptable
     LaneMask active, idle; std::string why;
     const bool mask_ok = parse_lane_mask(lanes, masked, ctx->cfg.n_lanes, active, idle, why);

@@ -180,6 +180,14 @@ extern "C" int svo_batch_set_dyn_fast_threshold(svo_batch* b, int enable, double
     return SVO_OK;
 }
 
+extern "C" int svo_batch_set_faster_adaptive_nms(svo_batch* b, int enable)
+{
+    if (!b) return SVO_ERR_ARG;
+    int rc = svo_batch_synchronize(b); if (rc) return rc;
+    for (svo_ctx* c : b->ctx) BSVO(b, c, svo_set_faster_adaptive_nms(c, enable));
+    return SVO_OK;
+}
+
 extern "C" int svo_batch_set_camera(svo_batch* b, int lane, const svo_stereo_camera* cam)
 {
     if (!b || !cam || lane < -1 || lane >= b->B) return SVO_ERR_ARG;
@@ -448,6 +456,13 @@ extern "C" int svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable)
 {
     if (!f) return SVO_ERR_ARG;
     for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_pose_covariance(c, enable));
+    return SVO_OK;
+}
+
+extern "C" int svo_fpstream_set_faster_adaptive_nms(svo_fpstream* f, int enable)
+{
+    if (!f) return SVO_ERR_ARG;
+    for (svo_ctx* c : f->ctx) BSVO(f, c, svo_set_faster_adaptive_nms(c, enable));
     return SVO_OK;
 }
 

@@ -20,7 +20,8 @@ struct GNParams {
 // test_kernel_launch_knobs_do_not_change_results); the launchers pick the product form unless a debug knob says otherwise.
 //   product, many lanes (> 8 lane-octaves):  k_hamming_f4, k_ransac_hyp_thread, k_ransac_count_mfma16
 //   product, few lanes (one stream alone):   k_hamming_f4, k_ransac_hyp (16 lanes per sample), k_ransac_count<4> (VALU, for latency)
-//   product, other entry points:             k_hamming_plain (svo_hamming_match), k_track_gate (multi-octave contexts), k_project_points
+//   product, other entry points:             k_hamming_plain (svo_hamming_match), k_track_gate (multi-octave contexts), k_project_points,
+//                                            k_faster_anms (svo_set_faster_adaptive_nms) and k_anms_list (svo_adaptive_nms), one body
 //   A/B only (never launched by default):    k_hamming + k_gather_mdesc (the int8 matcher, SVO_HAM_FP4=0), k_ransac_count_mfma (4 x 4 tiles,
 //                                            SVO_DEBUG_MODE=52), k_ransac_count<16> (SVO_DEBUG_MODE=14).  Since round 6 these are compiled only
 //                                            under -DSVO_AB_KERNELS: the product libsvo_hip.so does not contain them (svo_create refuses the
@@ -71,6 +72,14 @@ void launch_faster_nms(const DevCtx& c, const unsigned long long* cand64, int do
 // (left images, then right images) read it; the NMS launch behind them commits the new thresholds and the statistics
 void launch_faster_dyn(const DevCtx& c, unsigned long long* cand64, const svo_faster_stats* stats, double target, int klt_win, hipStream_t st);
 void launch_faster_nms_dyn(const DevCtx& c, const unsigned long long* cand64, int do_nms, int min_distance, svo_faster_stats* stats, double target, hipStream_t st);
+// ... under svo_set_faster_adaptive_nms with nmsmAdaptive: k_faster_anms in place of k_faster_nms(_dyn).  scratch = faster_anms_scratch_words()
+// 64-bit words; stats = nullptr, or the records above (the launch then commits them as launch_faster_nms_dyn does).  A level holds at most
+// faster_anms_max_candidates() candidates.  launch_anms_list: the same device code on one list of keys (svo_adaptive_nms)
+hipError_t configure_faster_anms(int max_kps);
+size_t faster_anms_scratch_words(int n_img, int cand_total);
+int faster_anms_max_candidates();
+void launch_faster_anms(const DevCtx& c, const unsigned long long* cand64, unsigned long long* scratch, svo_faster_stats* stats, double target, hipStream_t st);
+void launch_anms_list(const unsigned long long* keys, int n, int w, int h, int actual, int max_kps, unsigned long long* scratch, int n_cap, uint32_t* out_pos, hipStream_t st);
 void launch_hamming(const DevCtx& c, const Knobs& k, int mode, int nsplit, hipStream_t st);
 void launch_match_lr_filter(const DevCtx& c, int one_to_one, double max_y_diff, hipStream_t st);
 void launch_track_filter(const DevCtx& c, hipStream_t st);

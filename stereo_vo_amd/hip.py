@@ -23,6 +23,7 @@ EXPORTS = [
     "svo_set_params", "svo_get_params", "svo_params_load_ini", "svo_set_fast_threshold", "svo_set_orb_threshold", "svo_get_fast_threshold",
     "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini",
     "svo_set_dyn_fast_threshold", "svo_get_dyn_fast_threshold", "svo_dyn_fast_load_ini", "svo_get_faster_stats", "svo_faster_stats_size", "svo_faster_threshold_step",
+    "svo_set_faster_adaptive_nms", "svo_get_faster_adaptive_nms", "svo_adaptive_nms",
     "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_set_pose_covariance", "svo_get_pose_covariance", "svo_get_pose_covariances", "svo_copy_pose_covariances_async", "svo_pose_cov_size",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
@@ -42,6 +43,7 @@ BATCH_EXPORTS = [
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
     "svo_batch_set_pose_covariance", "svo_batch_pose_covariances", "svo_fpstream_set_pose_covariance",
     "svo_batch_set_dyn_fast_threshold", "svo_batch_faster_stats", "svo_fpstream_set_dyn_fast_threshold",
+    "svo_batch_set_faster_adaptive_nms", "svo_fpstream_set_faster_adaptive_nms",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
     "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
 ]
@@ -111,6 +113,12 @@ def lib():
             L.svo_batch_set_dyn_fast_threshold.argtypes = [C.c_void_p, C.c_int, C.c_double]
             L.svo_batch_faster_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.svo_fpstream_set_dyn_fast_threshold.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        if hasattr(L, "svo_set_faster_adaptive_nms"):          # (as above: absent from a library of an earlier commit)
+            L.svo_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
+            L.svo_get_faster_adaptive_nms.argtypes = [C.c_void_p]
+            L.svo_adaptive_nms.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+            L.svo_batch_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
+            L.svo_fpstream_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -295,6 +303,25 @@ class Context:
         r = FasterStats()
         self._ck(self.L.svo_get_faster_stats(self.h, lane, C.byref(r)), "svo_get_faster_stats")
         return r
+
+    def set_faster_adaptive_nms(self, enable=True):
+        """opt in to (or out of) the adaptive NMS under dmFASTER (svo_set_faster_adaptive_nms); allocates its scratch at once"""
+        self._ck(self.L.svo_set_faster_adaptive_nms(self.h, 1 if enable else 0), "svo_set_faster_adaptive_nms")
+
+    def faster_adaptive_nms(self) -> bool:
+        return bool(self.L.svo_get_faster_adaptive_nms(self.h))
+
+    def adaptive_nms(self, kps, num_out_points, img_w, img_h, cap=None):
+        """m_adaptive_non_max_sup on one list (svo_adaptive_nms): the kernel of the adaptive NMS under dmFASTER on caller keypoints, for
+        holding it to a reference.  kps: keypoint_dtype records in strictly ascending raster order with integer coordinates.  Returns
+        (number kept, the first min(kept, cap) indices in radius-descending order); cap defaults to len(kps)."""
+        kps = np.ascontiguousarray(kps, dtype=keypoint_dtype)
+        cap = len(kps) if cap is None else int(cap)
+        out = np.zeros(max(1, cap), np.int32)
+        n = self.L.svo_adaptive_nms(self.h, _vp(kps) if len(kps) else None, len(kps), int(num_out_points), int(img_w), int(img_h), _vp(out), cap)
+        if n < 0:
+            self._ck(n, "svo_adaptive_nms")
+        return n, out[:min(n, cap)].copy()
 
     def orb_threshold(self):
         return self.L.svo_get_orb_threshold(self.h)

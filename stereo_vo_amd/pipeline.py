@@ -171,6 +171,11 @@ class StreamBatch:
         torch.cuda.synchronize(self.dev)
         self._ck(self.L.svo_batch_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_batch_set_dyn_fast_threshold")
 
+    def set_faster_adaptive_nms(self, enable=True):
+        """svo_batch_set_faster_adaptive_nms: the opt-in to the adaptive NMS under dmFASTER on every context"""
+        torch.cuda.synchronize(self.dev)
+        self._ck(self.L.svo_batch_set_faster_adaptive_nms(self.h, 1 if enable else 0), "svo_batch_set_faster_adaptive_nms")
+
     def faster_stats(self):
         """the FasterStats record of every stream, global lane order (waits for the steps in flight)"""
         arr = (FasterStats * self.B)()
@@ -246,6 +251,10 @@ class FrameParallelStream:
     def set_dyn_fast_threshold(self, enable=True, target=10. / 1000.):
         """refused when enable is set (svo_fpstream_set_dyn_fast_threshold): frame t's detection would need frame t - 1's corner count"""
         self._ck(self.L.svo_fpstream_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_fpstream_set_dyn_fast_threshold")
+
+    def set_faster_adaptive_nms(self, enable=True):
+        """svo_fpstream_set_faster_adaptive_nms: the opt-in to the adaptive NMS under dmFASTER on every context"""
+        self._ck(self.L.svo_fpstream_set_faster_adaptive_nms(self.h, 1 if enable else 0), "svo_fpstream_set_faster_adaptive_nms")
 
     def push(self, ptrs, stride=None):
         """Enqueue the next frame (ptrs[lane] = (left, right) device addresses).  Returns the context that owns it."""
