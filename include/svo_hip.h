@@ -226,6 +226,29 @@ int svo_set_camera(svo_ctx* ctx, int lane, const svo_stereo_camera* cam);
  * camera's images (bilinear, constant-0 border, S1:70-72) before detection.  map_x = map_y = NULL clears the map
  * (areImagesRectified(), S1:61-65). */
 int svo_set_rectify_map(svo_ctx* ctx, int lane, int side, const float* map_x, const float* map_y, int w, int h);
+/* The same maps from a calibration, built on the device: what setFromCamParams (S1:66-68) does itself, without OpenCV and without
+ * host arrays.
+ * svo_stereo_rectify: Bouguet's rectification as cv::stereoRectify does it for alpha = -1 -- a pure host function, no context and no
+ *   device.  Half of the rotation goes to each camera, the half-rotated baseline is aligned with the x axis (R1, R2); the common
+ *   focal length is the smaller fy, shrunk where k1 < 0; each principal point centres the four undistorted image corners (five
+ *   fixed-point iterations each); zero_disparity averages both coordinates of the two principal points, otherwise only y.
+ *   Refused with a text in `why` (when why_cap > 0) and nothing written to `out`: SVO_ERR_UNSUPPORTED for alpha >= 0 and for a rig
+ *   whose half-rotated baseline is more vertical than horizontal (or whose rotation is a half turn); SVO_ERR_ARG for a right camera
+ *   that is not to the right (-tx <= 0), a non-finite field, |R^T R - I| > 1e-6 in any entry, T = 0, w or h <= 0, a NULL pointer.
+ * svo_set_undistort_rectify: cv::initUndistortRectifyMap(cam, dist, R, P) + svo_set_rectify_map of one camera: the table is computed
+ *   by k_rectify_map in double from (A R)^-1 and is, entry for entry, what svo_set_rectify_map makes of the float maps of the same
+ *   closed form (csrc/rectify_model.hpp).  P = fx' fy' cx' cy' of the rectified camera.  lane = -1 builds the table ONCE and points
+ *   every lane at that one buffer; a later per-lane set (by either setter) or clear detaches that lane only.  Arguments, the rule
+ *   that all maps of a context share w and h, and the synchronisation are those of svo_set_rectify_map; a non-finite value is SVO_ERR_ARG.
+ * svo_set_stereo_calibration: svo_stereo_rectify + both cameras in ONE launch.  set_camera != 0 also hands out->cam to
+ *   svo_set_camera(lane): the reference leaves stereo_cam to its caller (0 is its literal behaviour), but the rectified intrinsics
+ *   are what stage 5 must work with (1 is the useful one).  out may be NULL.  On a refusal nothing changes, the text is in svo_last_error.
+ * svo_debug_get_rectify_map: the fixed-point entries in force for one camera, whichever setter made them: xy[i] = (sx + 1) | (sy + 1) << 16
+ *   (0xFFFFFFFF: wholly outside), frac[i] = fx | fy << 8.  Returns the count w * h (0: the camera has no map) and copies min(count, cap). */
+int svo_stereo_rectify(const svo_stereo_calibration* calib, svo_stereo_rectification* out, char* why, size_t why_cap);
+int svo_set_undistort_rectify(svo_ctx* ctx, int lane, int side, const svo_camera_model* cam, const double* R, const double* P, int w, int h);
+int svo_set_stereo_calibration(svo_ctx* ctx, int lane, const svo_stereo_calibration* calib, int set_camera, svo_stereo_rectification* out);
+int svo_debug_get_rectify_map(svo_ctx* ctx, int lane, int side, uint32_t* xy, uint32_t* frac, int cap);
 /* forget both frames, the warm start and the match-ID counters of one lane (a freshly constructed estimator, C:28-50); -1 = all.
  * The FAST / ORB thresholds belong to the context (all its lanes share svo_params) and stay as they are: svo_set_*_threshold.
  * dmFASTER's dynamic thresholds belong to the lane and start over (svo_set_dyn_fast_threshold). */

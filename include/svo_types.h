@@ -172,6 +172,37 @@ typedef struct svo_faster_stats {
     int32_t frame, reserved[3];
 } svo_faster_stats;
 
+/* The calibration of an unrectified stereo rig: what mrpt::vision::CStereoRectifyMap::setFromCamParams reads from the observation's
+ * TStereoCamera (stage1_rectify.cpp:66-68) -- intrinsics, distortion and the pose of the right camera -- in OpenCV's conventions.
+ *   dist            k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order; mrpt's TCamera::dist holds the first five, the rest 0).  Thin-prism and
+ *                   tilt terms are not built.
+ *   R, T            x_right = R x_left + T, R row-major: a right camera to the right of the left one has T[0] < 0
+ *   zero_disparity  1: CALIB_ZERO_DISPARITY, both rectified principal points are the mean of the two; 0: only their y is (mrpt's default)
+ *   alpha           must be negative (cv::stereoRectify's alpha = -1: no scaling to the inner / outer rectangle) */
+typedef struct svo_camera_model {
+    double fx, fy, cx, cy;
+    double dist[8];
+} svo_camera_model;
+typedef struct svo_stereo_calibration {
+    svo_camera_model left, right;
+    double R[9];
+    double T[3];
+    int32_t w, h;
+    int32_t zero_disparity;
+    int32_t reserved;
+    double alpha;
+} svo_stereo_calibration;
+/* what svo_stereo_rectify makes of it: the rotations that rectify each camera, the rectified intrinsics P = fx' fy' cx' cy' of each
+ * (fx' = fy'), tx = (R2 T)[0], the translation between the rectified cameras (negative for a right camera to the right; the fourth
+ * column of cv::stereoRectify's P2 is tx * fx'), and the record stage 5 works with: cam has the intrinsics of P1 / P2, baseline = -tx
+ * and ncols / nrows = w / h */
+typedef struct svo_stereo_rectification {
+    double R1[9], R2[9];
+    double P1[4], P2[4];
+    double tx;
+    svo_stereo_camera cam;
+} svo_stereo_rectification;
+
 #ifdef __cplusplus
 }
 #endif

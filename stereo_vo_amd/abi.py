@@ -94,6 +94,43 @@ class FasterStats(C.Structure):
 
 assert C.sizeof(FasterStats) == 96
 
+class CameraModel(C.Structure):
+    """svo_camera_model (include/svo_types.h): intrinsics and k1 k2 p1 p2 k3 k4 k5 k6 of one unrectified camera"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8)]
+
+    @classmethod
+    def make(cls, fx, fy, cx, cy, dist=()):
+        d = [float(v) for v in dist] + [0.0] * (8 - len(dist))
+        return cls(float(fx), float(fy), float(cx), float(cy), (C.c_double * 8)(*d))
+
+
+class StereoCalibration(C.Structure):
+    """svo_stereo_calibration: x_right = R x_left + T (OpenCV's convention, R row-major); alpha must be negative"""
+    _fields_ = [("left", CameraModel), ("right", CameraModel), ("R", C.c_double * 9), ("T", C.c_double * 3),
+                ("w", C.c_int32), ("h", C.c_int32), ("zero_disparity", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double)]
+
+    @classmethod
+    def make(cls, left, right, R, T, w, h, zero_disparity=False, alpha=-1.0):
+        """left / right: CameraModel or (fx, fy, cx, cy, dist); R: 3 x 3; T: 3"""
+        cams = [c if isinstance(c, CameraModel) else CameraModel.make(*c) for c in (left, right)]
+        R = np.asarray(R, np.float64).reshape(9); T = np.asarray(T, np.float64).reshape(3)
+        return cls(cams[0], cams[1], (C.c_double * 9)(*R), (C.c_double * 3)(*T), int(w), int(h), int(bool(zero_disparity)), 0, float(alpha))
+
+
+class StereoRectification(C.Structure):
+    """svo_stereo_rectification: R1 R2 (3 x 3 row-major), P1 P2 = fx' fy' cx' cy', tx, and the StereoCamera stage 5 works with"""
+    _fields_ = [("R1", C.c_double * 9), ("R2", C.c_double * 9), ("P1", C.c_double * 4), ("P2", C.c_double * 4),
+                ("tx", C.c_double), ("cam", StereoCamera)]
+
+    def rotation(self, side):
+        return np.array(self.R2 if side else self.R1).reshape(3, 3)
+
+    def intrinsics(self, side):
+        return np.array(self.P2 if side else self.P1)
+
+
+assert C.sizeof(CameraModel) == 96 and C.sizeof(StereoCalibration) == 312 and C.sizeof(StereoRectification) == 296
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

@@ -63,3 +63,43 @@ void launch_prepare(const PrepArgs& a, int n_img, hipStream_t st)
 {
     hipLaunchKernelGGL(k_prepare, dim3((a.w + 255) / 256, (a.h + 3) / 4, n_img), dim3(256), 0, st, a);
 }
+
+// The maps k_prepare reads, built from a calibration (svo_set_undistort_rectify, svo_set_stereo_calibration; rectify_model.hpp holds
+// the arithmetic, in double, one operation per operator).  Launched by those setters alone, never by a frame.  No LDS, no scratch.
+// grid = (ceil(w / 256), ceil(h / 4), image), as k_prepare; one thread = 4 adjacent entries = 32 bytes of dst[y * w + x].
+// A row starts 16-byte aligned only when y * w is even (hipMalloc aligns dst itself): such a thread stores two 16-byte pieces, the
+// others 8 + 16 + 8; the tail of a row (w % 4 entries) is cut entry by entry.  Write-bound at 8 bytes per pixel by design.
+__device__ __forceinline__ void store_entry(uint2* p, const RectifyEntry& a) { *p = make_uint2(a.x, a.y); }
+__device__ __forceinline__ void store_pair(uint2* p, const RectifyEntry& a, const RectifyEntry& b) { *(uint4*)p = make_uint4(a.x, a.y, b.x, b.y); }   // p is 16-byte aligned
+
+__global__ void __launch_bounds__(256) k_rectify_map(const RectifyImage* __restrict__ models, int w, int h)
+{
+    const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x4 >= w || y >= h) return;
+    const RectifyImage& im = models[blockIdx.z];
+    const int n = min(4, w - x4);                     // entries of this thread inside the row
+    RectifyEntry e[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        e[k].x = 0xFFFFFFFFu; e[k].y = 0;
+        if (k < n) {
+            double u, v;
+            rectify_source(im.m, x4 + k, y, &u, &v);
+            e[k] = rectify_fixed(u, v, w, h);
+        }
+    }
+    uint2* row = im.dst + ((long long)y * w + x4);
+    if (((unsigned long long)row & 8ull) == 0) {
+        if (n >= 2) store_pair(row, e[0], e[1]); else store_entry(row, e[0]);
+        if (n == 4) store_pair(row + 2, e[2], e[3]); else if (n == 3) store_entry(row + 2, e[2]);
+    } else {
+        store_entry(row, e[0]);
+        if (n >= 3) store_pair(row + 1, e[1], e[2]); else if (n == 2) store_entry(row + 1, e[1]);
+        if (n == 4) store_entry(row + 3, e[3]);
+    }
+}
+
+void launch_rectify_map(const RectifyImage* d_models, int n_img, int w, int h, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_rectify_map, dim3((w + 255) / 256, (h + 3) / 4, n_img), dim3(256), 0, st, d_models, w, h);
+}

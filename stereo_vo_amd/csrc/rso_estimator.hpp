@@ -265,6 +265,14 @@ public:
         const bool clear = map_x.empty();
         check(svo_set_rectify_map(m_ctx, 0, side, clear ? NULL : map_x.data(), clear ? NULL : map_y.data(), w, h), "svo_set_rectify_map");
     }
+    /** m_stereo_rectifier.setFromCamParams() itself (S1:66-68): the calibration of the unrectified rig in, both maps built on the
+     *  device.  As in the reference, request_data.stereo_cam stays the caller's (processNewImagePair hands it over with every frame):
+     *  the returned record holds the rectified camera, .cam, that stage 5 must be given there, with the rectifying rotations. */
+    svo_stereo_rectification setFromCamParams(const svo_stereo_calibration& calib) {
+        svo_stereo_rectification out;
+        check(svo_set_stereo_calibration(m_ctx, 0, &calib, 0, &out), "svo_set_stereo_calibration");
+        return out;
+    }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

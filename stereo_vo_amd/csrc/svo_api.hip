@@ -106,7 +106,10 @@ struct svo_ctx {
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
     uint2** d_map_ptrs; std::vector<uint2*> map_ptrs;  // per image: fixed-point map on the device or nullptr
     int map_w, map_h, n_maps;
-    std::vector<uint2*> map_bufs;                      // per image: the allocation behind map_ptrs (kept across clear / set cycles)
+    std::vector<uint2*> map_bufs;                      // per image: the allocation of its own behind map_ptrs (kept across clear / set cycles)
+    // maps from a calibration (svo_set_undistort_rectify, svo_set_stereo_calibration): the table of a side that lane = -1 built ONCE and
+    // every lane's map_ptrs entry points at until the lane is set or cleared on its own; the models k_rectify_map reads.  First use.
+    uint2* map_shared[2]; RectifyImage* d_rect_models;
     // getChangeInPose works on temporaries (common.cpp:362-400): a one-lane scratch view of the device context
     DevCtx cip; bool cip_ready;
     // svo_get_values: device packing buffer and its page-locked host mirror
@@ -389,6 +392,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
+    ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
     ctx->sad.cur.assign((size_t)cfg->n_lanes, 1); ctx->sad.prev.assign((size_t)cfg->n_lanes, 1); ctx->sad.drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
@@ -819,10 +823,11 @@ extern "C" int svo_set_rectify_map(svo_ctx* ctx, int lane, int side, const float
         if (lane >= 0 && lane != l) continue;
         uint2*& mp = ctx->map_ptrs[2 * l + side];
         if (map_x) {
-            if (!mp) {                                       // a cleared camera's buffer is reused, not allocated again
+            if (mp != ctx->map_bufs[2 * l + side] || !mp) {   // a cleared camera's buffer is reused, not allocated again; a lane that shared a calibration's table gets its own
                 uint2*& buf = ctx->map_bufs[2 * l + side];
                 if (!buf) HIPCHECK(dev_alloc(ctx, &buf, (size_t)ctx->cfg.max_w * ctx->cfg.max_h));
-                mp = buf; ctx->n_maps++;
+                if (!mp) ctx->n_maps++;
+                mp = buf;
             }
             HIPCHECK(hipMemcpy(mp, fixed.data(), fixed.size() * sizeof(uint2), hipMemcpyHostToDevice));
             ctx->map_w = w; ctx->map_h = h;
@@ -830,6 +835,109 @@ extern "C" int svo_set_rectify_map(svo_ctx* ctx, int lane, int side, const float
     }
     HIPCHECK(hipMemcpy(ctx->d_map_ptrs, ctx->map_ptrs.data(), sizeof(uint2*) * NI, hipMemcpyHostToDevice));
     return SVO_OK;
+}
+
+// ---- maps from a calibration (svo_hip.h at svo_stereo_rectify; setFromCamParams, stage1_rectify.cpp:66-68) -----------------------
+// What the two setters below share: the argument rules of svo_set_rectify_map, then ONE k_rectify_map launch for the n (1 or 2)
+// cameras in sides[] / models[], into the lane's own buffers or, with lane = -1, into the context's shared table of each side.
+static int rectify_map_args(svo_ctx* ctx, int lane, int w, int h)
+{
+    if (lane < -1 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    if (w <= 0 || h <= 0 || w > ctx->cfg.max_w || h > ctx->cfg.max_h || (ctx->n_maps > 0 && (w != ctx->map_w || h != ctx->map_h))) {
+        char msg[200];
+        if (ctx->n_maps > 0) snprintf(msg, sizeof(msg), "map size %d x %d: the context holds maps of %d x %d (all maps of a context share one size, within max_w x max_h = %d x %d)", w, h, ctx->map_w, ctx->map_h, ctx->cfg.max_w, ctx->cfg.max_h);
+        else snprintf(msg, sizeof(msg), "map size %d x %d: 1 x 1 .. max_w x max_h = %d x %d is expected", w, h, ctx->cfg.max_w, ctx->cfg.max_h);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    return SVO_OK;
+}
+static bool model_finite(const RectifyModel& m)
+{
+    const double* v = m.ir;                              // ir, k, fx fy cx cy: 21 doubles in a row
+    static_assert(sizeof(RectifyModel) == 21 * sizeof(double), "RectifyModel is 21 doubles");
+    for (int i = 0; i < 21; i++) if (!(fabs(v[i]) <= 1.7976931348623157e308)) return false;
+    return true;
+}
+static RectifyModel make_model(const svo_camera_model& cam, const double* R, const double* P)
+{
+    RectifyModel m;
+    rectify_inverse(P, R, m.ir);
+    for (int i = 0; i < 8; i++) m.k[i] = cam.dist[i];
+    m.fx = cam.fx; m.fy = cam.fy; m.cx = cam.cx; m.cy = cam.cy;
+    return m;
+}
+static int build_rectify_maps(svo_ctx* ctx, int lane, int n, const int* sides, const RectifyModel* models, int w, int h)
+{
+    const int NI = 2 * ctx->cfg.n_lanes;
+    HIPCHECK(sync_all(ctx));
+    if (ctx->map_ptrs.empty()) {
+        ctx->map_ptrs.assign(NI, nullptr); ctx->map_bufs.assign(NI, nullptr);
+        HIPCHECK(dev_alloc(ctx, (uint2***)&ctx->d_map_ptrs, (size_t)NI));
+        HIPCHECK(hipMemset(ctx->d_map_ptrs, 0, sizeof(uint2*) * NI));
+    }
+    if (!ctx->d_rect_models) HIPCHECK(dev_alloc(ctx, &ctx->d_rect_models, (size_t)2));
+    RectifyImage im[2];
+    for (int k = 0; k < n; k++) {
+        uint2*& buf = lane < 0 ? ctx->map_shared[sides[k]] : ctx->map_bufs[2 * lane + sides[k]];
+        if (!buf) HIPCHECK(dev_alloc(ctx, &buf, (size_t)ctx->cfg.max_w * ctx->cfg.max_h));
+        im[k].m = models[k]; im[k].dst = buf;
+    }
+    HIPCHECK(hipMemcpy(ctx->d_rect_models, im, sizeof(RectifyImage) * n, hipMemcpyHostToDevice));
+    launch_rectify_map(ctx->d_rect_models, n, w, h, ctx->stream);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++)
+        for (int l = 0; l < ctx->cfg.n_lanes; l++) {
+            if (lane >= 0 && lane != l) continue;
+            uint2*& mp = ctx->map_ptrs[2 * l + sides[k]];
+            if (!mp) ctx->n_maps++;
+            mp = im[k].dst;
+        }
+    ctx->map_w = w; ctx->map_h = h;
+    HIPCHECK(hipMemcpy(ctx->d_map_ptrs, ctx->map_ptrs.data(), sizeof(uint2*) * NI, hipMemcpyHostToDevice));
+    return SVO_OK;
+}
+
+extern "C" int svo_set_undistort_rectify(svo_ctx* ctx, int lane, int side, const svo_camera_model* cam, const double* R, const double* P, int w, int h)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !cam || !R || !P || side < 0 || side > 1) return SVO_ERR_ARG;
+    { const int rc = rectify_map_args(ctx, lane, w, h); if (rc) return rc; }
+    const RectifyModel m = make_model(*cam, R, P);
+    if (!model_finite(m)) { ctx->last_error = "svo_set_undistort_rectify: a value of the model or of (A R)^-1 is not finite"; return SVO_ERR_ARG; }
+    return build_rectify_maps(ctx, lane, 1, &side, &m, w, h);
+}
+
+extern "C" int svo_set_stereo_calibration(svo_ctx* ctx, int lane, const svo_stereo_calibration* calib, int set_camera, svo_stereo_rectification* out)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !calib || lane < -1 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    svo_stereo_rectification rect;
+    char why[320];
+    { const int rc = svo_stereo_rectify(calib, &rect, why, sizeof(why)); if (rc) { ctx->last_error = why; return rc; } }
+    { const int rc = rectify_map_args(ctx, lane, calib->w, calib->h); if (rc) return rc; }
+    const RectifyModel m[2] = { make_model(calib->left, rect.R1, rect.P1), make_model(calib->right, rect.R2, rect.P2) };
+    if (!model_finite(m[0]) || !model_finite(m[1])) { ctx->last_error = "svo_set_stereo_calibration: (A R)^-1 of a rectified camera is not finite"; return SVO_ERR_ARG; }
+    const int sides[2] = { 0, 1 };
+    { const int rc = build_rectify_maps(ctx, lane, 2, sides, m, calib->w, calib->h); if (rc) return rc; }
+    if (set_camera) { const int rc = svo_set_camera(ctx, lane, &rect.cam); if (rc) return rc; }
+    if (out) *out = rect;
+    return SVO_OK;
+}
+
+extern "C" int svo_debug_get_rectify_map(svo_ctx* ctx, int lane, int side, uint32_t* xy, uint32_t* frac, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || side < 0 || side > 1 || cap < 0 || (cap > 0 && (!xy || !frac))) return SVO_ERR_ARG;
+    if (ctx->map_ptrs.empty() || !ctx->map_ptrs[2 * lane + side]) return 0;
+    const int count = ctx->map_w * ctx->map_h, n = count < cap ? count : cap;      // max_w * max_h < 2^24 (svo_create)
+    if (n > 0) {
+        HIPCHECK(sync_all(ctx));
+        std::vector<uint2> e((size_t)n);
+        HIPCHECK(hipMemcpy(e.data(), ctx->map_ptrs[2 * lane + side], (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) { xy[i] = e[(size_t)i].x; frac[i] = e[(size_t)i].y; }
+    }
+    return count;
 }
 
 extern "C" int svo_reset(svo_ctx* ctx, int lane)

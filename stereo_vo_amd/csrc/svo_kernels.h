@@ -2,6 +2,7 @@
 // run-time knob take the context's Knobs (svo_knobs.hpp); none reads the environment.
 #pragma once
 #include "svo_device.h"
+#include "rectify_model.hpp"
 
 struct GNParams {
     int use_robust_kernel, max_iters, initial_max_iters, max_incr_cost;
@@ -42,6 +43,9 @@ struct PrepArgs {
     LaneMask idle;                    // lanes that sit the call out (DevCtx.idle): their images are neither read nor written
 };
 void launch_prepare(const PrepArgs& a, int n_img, hipStream_t st);
+// the fixed-point map of one image from its calibration (rectify_model.hpp): what k_rectify_map reads per image.  dst holds w * h entries.
+struct RectifyImage { RectifyModel m; uint2* dst; };
+void launch_rectify_map(const RectifyImage* d_models, int n_img, int w, int h, hipStream_t st);   // d_models: device memory; only the map setters launch it
 // frame hand-over between contexts (k_handover.hip)
 size_t handover_record_bytes(const DevCtx& c);                  // of the context's kind (DevCtx.carry_win)
 size_t handover_record_bytes(const DevCtx& c, bool windows);    // version 2 (false) / version 3 with the SAD windows (true)

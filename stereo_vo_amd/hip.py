@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import FasterStats, Params, PoseCov, Result, StereoCamera, keypoint_dtype, dmatch_dtype, index_pair_dtype
+from .abi import (CameraModel, FasterStats, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -24,7 +24,8 @@ EXPORTS = [
     "svo_get_orb_threshold", "svo_set_klt_win", "svo_get_klt_win", "svo_klt_win_load_ini",
     "svo_set_dyn_fast_threshold", "svo_get_dyn_fast_threshold", "svo_dyn_fast_load_ini", "svo_get_faster_stats", "svo_faster_stats_size", "svo_faster_threshold_step",
     "svo_set_faster_adaptive_nms", "svo_get_faster_adaptive_nms", "svo_adaptive_nms",
-    "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
+    "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map",
+    "svo_stereo_rectify", "svo_set_undistort_rectify", "svo_set_stereo_calibration", "svo_debug_get_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_set_pose_covariance", "svo_get_pose_covariance", "svo_get_pose_covariances", "svo_copy_pose_covariances_async", "svo_pose_cov_size",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
@@ -119,6 +120,11 @@ def lib():
             L.svo_adaptive_nms.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
             L.svo_batch_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
             L.svo_fpstream_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "svo_stereo_rectify"):          # (as above: absent from a library of an earlier commit)
+            L.svo_stereo_rectify.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+            L.svo_set_undistort_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.svo_set_stereo_calibration.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+            L.svo_debug_get_rectify_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -167,6 +173,19 @@ def load_dyn_fast_ini(path, detect_section, target=10. / 1000.) -> float:
 def faster_threshold_step(T, n, w, h, target) -> int:
     """the rule that moves dmFASTER's threshold after a detection that found n corners in a w x h image (host only)"""
     return int(lib().svo_faster_threshold_step(int(T), int(n), int(w), int(h), float(target)))
+
+
+def stereo_rectify(calib: StereoCalibration) -> StereoRectification:
+    """svo_stereo_rectify: Bouguet's rectification of a calibrated rig as cv::stereoRectify does it for alpha = -1 (host only, no
+    device).  SvoError with the library's text when the calibration is refused; .status holds the code."""
+    out = StereoRectification()
+    why = C.create_string_buffer(320)
+    rc = lib().svo_stereo_rectify(C.byref(calib), C.byref(out), why, len(why))
+    if rc != 0:
+        e = SvoError("svo_stereo_rectify: %s [%s]" % (lib().svo_strerror(rc).decode(), why.value.decode()))
+        e.status = rc
+        raise e
+    return out
 
 
 def _vp(a):
@@ -471,6 +490,28 @@ class Context:
         mx = np.ascontiguousarray(map_x, np.float32); my = np.ascontiguousarray(map_y, np.float32)
         assert mx.ndim == 2 and mx.shape == my.shape
         self._ck(self.L.svo_set_rectify_map(self.h, lane, side, C.c_void_p(mx.ctypes.data), C.c_void_p(my.ctypes.data), mx.shape[1], mx.shape[0]), "svo_set_rectify_map")
+
+    def set_undistort_rectify(self, lane, side, cam: CameraModel, R, P, w, h):
+        """cv::initUndistortRectifyMap(cam, R, P) + set_rectify_map of one camera, built on the device (svo_set_undistort_rectify).
+        R: 3 x 3 rectifying rotation, P: fx' fy' cx' cy' of the rectified camera.  lane = -1: one table shared by every lane."""
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9)); P = np.ascontiguousarray(np.asarray(P, np.float64).reshape(4))
+        self._ck(self.L.svo_set_undistort_rectify(self.h, int(lane), int(side), C.byref(cam), _vp(R), _vp(P), int(w), int(h)), "svo_set_undistort_rectify")
+
+    def set_stereo_calibration(self, calib: StereoCalibration, lane=-1, set_camera=True) -> StereoRectification:
+        """setFromCamParams: rectify the rig, build both maps on the device in one launch and (set_camera) hand the rectified camera to
+        stage 5 (svo_set_stereo_calibration).  Returns the rectification; on a refusal nothing has changed."""
+        out = StereoRectification()
+        self._ck(self.L.svo_set_stereo_calibration(self.h, int(lane), C.byref(calib), 1 if set_camera else 0, C.byref(out)), "svo_set_stereo_calibration")
+        return out
+
+    def rectify_map_fixed(self, lane, side):
+        """the fixed-point map in force for one camera, whichever setter made it: (xy, frac) flat uint32 arrays of w * h entries,
+        xy = (sx + 1) | (sy + 1) << 16 (0xFFFFFFFF: wholly outside), frac = fx | fy << 8; empty arrays when the camera has no map"""
+        n = self._ck(self.L.svo_debug_get_rectify_map(self.h, int(lane), int(side), None, None, 0), "svo_debug_get_rectify_map")
+        xy, frac = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        if n:
+            self._ck(self.L.svo_debug_get_rectify_map(self.h, int(lane), int(side), _vp(xy), _vp(frac), n), "svo_debug_get_rectify_map")
+        return xy, frac
 
     def projected_coords(self, pre_matches, pre_left, pre_right, tracked_first, cam, change_pose):
         """getProjectedCoords (common.cpp:415-466): (B, 4) float32 pixels of the pairings whose tracked_first is -1."""
