@@ -37,9 +37,26 @@ def c_round(v):
     return int(math.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
 
 
-def match_lr_sad(img_l, img_r, kl, kr, idx_l, idx_r, sad_max_distance, max_y_diff, one_to_one, minimum_response=0.0, sad_max_ratio=0.5):
+MUTANTS_S3 = ("ge_threshold", "and_ff", "le_min", "le_claim", "round_pt", "py_round", "no_flag", "round_disparity", "le_response")
+MUTANTS_S4 = ("ge_left", "ge_right", "and_ff", "le_min", "le_claim", "sum_gate", "lo0", "awx", "round_pt", "no_flag", "oct0_size")
+
+
+def _pt(v, mutant):
+    """(int)pt: towards zero.  (mutant round_pt: to nearest)"""
+    return int(math.floor(v + 0.5)) if mutant == "round_pt" else int(v)
+
+
+def flagged(k, W, H):
+    """the border rule of S3:289-295 on one keypoint: no 8 x 8 window inside a W x H image"""
+    return bool(k["x"] < 3 or k["y"] < 3 or k["x"] > W - 4 - 1 or k["y"] > H - 4 - 1)
+
+
+def match_lr_sad(img_l, img_r, kl, kr, idx_l, idx_r, sad_max_distance, max_y_diff, one_to_one, minimum_response=0.0, sad_max_ratio=0.5, mutant=None):
     """S3:185-419 with match_method == smSAD on one octave.  kl / kr: keypoint_dtype arrays (row-sorted), idx_l / idx_r: their
-    pyr_feats_index tables (one entry per image row).  Returns the DMatch list (dmatch_dtype, imgIdx = -1)."""
+    pyr_feats_index tables (one entry per image row).  Returns the DMatch list (dmatch_dtype, imgIdx = -1).
+    mutant (None: the walk as the reference has it): one of MUTANTS_S3, a walk that is wrong in exactly one rule; the hand-built
+    scenes of tests/sad_scenes.py must tell every one of them from the walk (tests/test_sad_scenes_cpu.py)."""
+    assert mutant is None or mutant in MUTANTS_S3, mutant
     H, W = img_l.shape
     max_ratio = sad_max_ratio                                                     # S3:200
     max_distance = effective_threshold(sad_max_distance)                          # S3:201 size_t(sad_max_distance)
@@ -49,7 +66,7 @@ def match_lr_sad(img_l, img_r, kl, kr, idx_l, idx_r, sad_max_distance, max_y_dif
     right_feat_assign = [[INVALID_IDX, UINT32_MAX] for _ in range(len(kr))]       # S3:229
     max_pt = (W - 4 - 1, H - 4 - 1)                                               # S3:235
     max_disparity = int(W * 0.7)                                                  # S3:247
-    d = c_round(max_y_diff)
+    d = c_round(max_y_diff) if mutant != "py_round" else round(max_y_diff)
     for y in range(n_rows_max - 1):                                               # S3:250
         l0, l1 = int(idx_l[y]), int(idx_l[y + 1])                                 # S3:253
         min_row_right = max(0, y - d)                                             # S3:254
@@ -65,16 +82,22 @@ def match_lr_sad(img_l, img_r, kl, kr, idx_l, idx_r, sad_max_distance, max_y_dif
                 fr = kr[ir]
                 if fl["response"] < minimum_response or fr["response"] < minimum_response:   # S3:279
                     continue
+                if mutant == "le_response" and (fl["response"] <= minimum_response or fr["response"] <= minimum_response):
+                    continue
                 disparity = int(fl["x"] - fr["x"])                                # S3:283 (float subtraction, truncated)
+                if mutant == "round_disparity":
+                    disparity = c_round(float(fl["x"] - fr["x"]))
                 if disparity < 1 or disparity > max_disparity:
                     continue
-                if (fl["x"] < 3 or fr["x"] < 3 or fl["y"] < 3 or fr["y"] < 3 or                    # S3:289-295
+                if mutant != "no_flag" and (fl["x"] < 3 or fr["x"] < 3 or fl["y"] < 3 or fr["y"] < 3 or                    # S3:289-295
                         fl["x"] > max_pt[0] or fr["x"] > max_pt[0] or fl["y"] > max_pt[1] or fr["y"] > max_pt[1]):
                     continue
-                dist = sad8(img_l, img_r, int(fl["x"]), int(fl["y"]), int(fr["x"]), int(fr["y"]))   # S3:309-313
-                if dist > max_distance:                                           # S3:334
+                dist = sad8(img_l, img_r, _pt(fl["x"], mutant), _pt(fl["y"], mutant), _pt(fr["x"], mutant), _pt(fr["y"], mutant))   # S3:309-313
+                if mutant == "and_ff":
+                    dist &= 0xFF
+                if dist > max_distance or (mutant == "ge_threshold" and dist == max_distance):   # S3:334
                     continue
-                if dist < min_1:                                                  # S3:338-345
+                if dist < min_1 or (mutant == "le_min" and dist == min_1):        # S3:338-345
                     min_2, min_1, min_idx = min_1, dist, ir
                 elif dist < min_2:
                     min_2 = dist
@@ -86,7 +109,7 @@ def match_lr_sad(img_l, img_r, kl, kr, idx_l, idx_r, sad_max_distance, max_y_dif
                     if a[0] == INVALID_IDX:
                         left_matches_idxs[il] = min_idx
                         a[0], a[1] = il, min_1
-                    elif min_1 < a[1]:
+                    elif min_1 < a[1] or (mutant == "le_claim" and min_1 == a[1]):
                         left_matches_idxs[a[0]] = INVALID_IDX
                         left_matches_idxs[il] = min_idx
                         a[0], a[1] = il, min_1
@@ -112,16 +135,23 @@ def matches_row_index(matches, kl, img_h):
     return ri
 
 
-def track_sad(prev, cur, win_w, win_h, ifm_sad_max_distance):
+def track_sad(prev, cur, win_w, win_h, ifm_sad_max_distance, skip_flagged=False, mutant=None):
     """S4:435-679 with use_SAD on one octave.  prev / cur: dicts with imgs (left, right), kl, kr, m (DMatch list), ri (its row
     index).  Returns potential_match_idxs as an index_pair_dtype array (previous pairing, current pairing), ascending in the
-    current index."""
+    current index.
+    skip_flagged: the library's documented deviation: a pairing of either frame with a keypoint that has no window
+    (`flagged`) is skipped, where the reference reads whatever lies there (`sad8` refuses that here).  Lists that stage 3 made hold
+    no such pairing, so the two forms differ on put lists only.
+    mutant: one of MUTANTS_S4 (see match_lr_sad); "no_flag" is the walk without the deviation."""
+    assert mutant is None or mutant in MUTANTS_S4, mutant
     H, W = prev["imgs"][0].shape
-    PATCHSIZE_L, PATCHSIZE_R = 3, 4                                               # S4:445-446
+    Wb, Hb = (2 * W, 2 * H) if mutant == "oct0_size" else (W, H)                  # (mutant: the borders of the octave-0 image)
+    skip_flagged = skip_flagged and mutant != "no_flag"
+    PATCHSIZE_L, PATCHSIZE_R = 0 if mutant == "lo0" else 3, 4                     # S4:445-446
     MAX_SAD = effective_threshold(ifm_sad_max_distance)                           # S4:448 (uint32_t)
     pm, cm = prev["m"], cur["m"]
-    absolute_wx_max = W - 1 - PATCHSIZE_R                                         # S4:489
-    absolute_wy_max = H - 1 - PATCHSIZE_R                                         # S4:490
+    absolute_wx_max = Wb - 1 - (0 if mutant == "awx" else PATCHSIZE_R)            # S4:489
+    absolute_wy_max = Hb - 1 - PATCHSIZE_R                                        # S4:490
     current_matches = [[INVALID_IDX, UINT32_MAX] for _ in range(len(cm))]         # S4:509
     for y in range(H - 1):                                                        # S4:514
         prev_idx0, prev_idx1 = int(prev["ri"][y]), int(prev["ri"][y + 1])         # S4:517-518
@@ -134,6 +164,8 @@ def track_sad(prev, cur, win_w, win_h, ifm_sad_max_distance):
             continue
         for pi in range(prev_idx0, prev_idx1):                                    # S4:537
             p_ft_l, p_ft_r = prev["kl"][pm[pi]["queryIdx"]], prev["kr"][pm[pi]["trainIdx"]]
+            if skip_flagged and (flagged(p_ft_l, Wb, Hb) or flagged(p_ft_r, Wb, Hb)):
+                continue
             best_pairing_in_curimg, best_pairing_sad = None, UINT32_MAX           # S4:543-544
             wx_min_l = max(PATCHSIZE_L, int(p_ft_l["x"] - np.float32(win_h)))     # S4:552-555
             wx_max_l = min(absolute_wx_max, int(p_ft_l["x"] + np.float32(win_h)))
@@ -143,20 +175,26 @@ def track_sad(prev, cur, win_w, win_h, ifm_sad_max_distance):
                 ft_l, ft_r = cur["kl"][cm[ci]["queryIdx"]], cur["kr"][cm[ci]["trainIdx"]]
                 if ft_l["x"] < wx_min_l or ft_l["x"] > wx_max_l or ft_r["x"] < wx_min_r or ft_r["x"] > wx_max_r:   # S4:567
                     continue
-                sad_l = sad8(prev["imgs"][0], cur["imgs"][0], int(p_ft_l["x"]), int(p_ft_l["y"]), int(ft_l["x"]), int(ft_l["y"]))   # S4:572
-                if sad_l > MAX_SAD:
+                if skip_flagged and (flagged(ft_l, Wb, Hb) or flagged(ft_r, Wb, Hb)):
                     continue
-                sad_r = sad8(prev["imgs"][1], cur["imgs"][1], int(p_ft_r["x"]), int(p_ft_r["y"]), int(ft_r["x"]), int(ft_r["y"]))   # S4:576
-                if sad_r > MAX_SAD:
+                sad_l = sad8(prev["imgs"][0], cur["imgs"][0], _pt(p_ft_l["x"], mutant), _pt(p_ft_l["y"], mutant), _pt(ft_l["x"], mutant), _pt(ft_l["y"], mutant))   # S4:572
+                if mutant != "sum_gate" and (sad_l > MAX_SAD or (mutant == "ge_left" and sad_l == MAX_SAD)):
+                    continue
+                sad_r = sad8(prev["imgs"][1], cur["imgs"][1], _pt(p_ft_r["x"], mutant), _pt(p_ft_r["y"], mutant), _pt(ft_r["x"], mutant), _pt(ft_r["y"], mutant))   # S4:576
+                if mutant != "sum_gate" and (sad_r > MAX_SAD or (mutant == "ge_right" and sad_r == MAX_SAD)):
                     continue
                 sad = sad_l + sad_r                                               # S4:580
-                if sad < best_pairing_sad:                                        # S4:583-587
+                if mutant == "sum_gate" and sad > MAX_SAD:
+                    continue
+                if mutant == "and_ff":
+                    sad &= 0xFF
+                if sad < best_pairing_sad or (mutant == "le_min" and sad == best_pairing_sad):   # S4:583-587
                     best_pairing_sad, best_pairing_in_curimg = sad, ci
             if best_pairing_in_curimg is not None:                                # S4:622-636
                 e = current_matches[best_pairing_in_curimg]
                 if e[0] == INVALID_IDX:
                     e[0], e[1] = pi, best_pairing_sad
-                if e[0] != INVALID_IDX and best_pairing_sad < e[1]:
+                if e[0] != INVALID_IDX and (best_pairing_sad < e[1] or (mutant == "le_claim" and best_pairing_sad == e[1])):
                     e[0], e[1] = pi, best_pairing_sad
     pot = [(e[0], ci) for ci, e in enumerate(current_matches) if e[0] != INVALID_IDX]   # S4:640-679
     return np.array(pot, index_pair_dtype)
