@@ -144,6 +144,11 @@ int  svo_fpstream_set_pose_covariance(svo_fpstream* f, int enable);
 /* dmFASTER's dynamic threshold cannot run frame-parallel: the detection of frame t needs the corner count of frame t - 1, the very
  * stage this schedule overlaps.  enable = 1 is SVO_ERR_UNSUPPORTED with a text; enable = 0 is accepted (the target is checked and ignored). */
 int  svo_fpstream_set_dyn_fast_threshold(svo_fpstream* f, int enable, double target_feats_per_pixel);
+/* The landmarks (svo_set_landmarks) are not available frame-parallel either: a frame's records live in the context that optimised it and
+ * the hand-over records do not carry them.  enable = 1 is SVO_ERR_UNSUPPORTED with a text; enable = 0 is accepted (std_noise_pixels is
+ * checked and ignored: negative or not finite is SVO_ERR_ARG).  The scheduler has no getter of its own: under svo_batch_* each context's
+ * svo_set_landmarks / svo_get_landmarks work (svo_batch_context). */
+int  svo_fpstream_set_landmarks(svo_fpstream* f, int enable, double std_noise_pixels);
 /* svo_set_faster_adaptive_nms on every context.  The selection reads and writes per-image scratch of the detect call alone and the
  * hand-over records carry nothing of it, so frame-parallel streams run it as they run the grid NMS. */
 int  svo_fpstream_set_faster_adaptive_nms(svo_fpstream* f, int enable);

@@ -357,6 +357,35 @@ int svo_get_pose_covariances(svo_ctx* ctx, svo_pose_cov* cov /* n_lanes entries 
 int svo_copy_pose_covariances_async(svo_ctx* ctx, void* dst_device, size_t bytes);
 size_t svo_pose_cov_size(void);
 
+/* THE LANDMARKS OF EVERY FRAME, WITH THEIR COVARIANCES (no reference counterpart: the reference triangulates them at S5:529-544 and keeps
+ * them; the record, its flags and the lane states are defined at svo_landmark / svo_landmarks_info in svo_types.h).  Off by default;
+ * while off a context allocates and launches nothing for it and every result is what it was.
+ * svo_set_landmarks(ctx, 1, std_noise_pixels) allocates, at once (before any graph capture), n_lanes x max_kps records of 176 bytes -- the
+ * one large allocation a context makes after svo_create (96 x 16384: 277 MB); when it fails the call is SVO_ERR_CAPACITY with the number
+ * in svo_last_error -- one info per lane (all SVO_LMK_NONE) and, unless the pose covariance made it, the array stage 5 leaves its final
+ * mask in.  std_noise_pixels is TLeastSquaresParams::std_noise_pixels (H:628), which the reference reads and never uses: 0 = its default
+ * of 1; negative or not finite is SVO_ERR_ARG with a text and the values in force stay.  It travels through this setter because
+ * svo_params' layout is frozen; svo_landmarks_load_ini reads it from the LEAST_SQUARES section of a file written for the reference
+ * (needs no device; the value is kept when the key is absent, SVO_ERR_ARG when the file holds a negative one).
+ * From then on every svo_process / svo_process_lanes with SVO_RUN_OPTIMIZE launches k_landmarks once behind k_gauss_newton -- behind
+ * k_pose_covariance when that is on, whose cov_delta then enters cov_cur -- ("landmarks" in svo_kernel_times, listed only while the feature is
+ * on), inside the captured graph under svo_use_graphs.  It rewrites the records and the info of every ACTIVE lane; an idle lane keeps both.
+ * A change of the switch or of the value drops the captured graphs.  svo_pose_cov is bit for bit what it is with the feature off.
+ * svo_reset sets the lane's info to SVO_LMK_NONE with n = 0.  svo_change_in_pose writes no records.  Hand-over records, state files and
+ * the RCCL companion do not carry them, and frame-parallel streams refuse the feature (svo_fpstream_set_landmarks, svo_batch.h).
+ * The getters imply svo_wait; with the feature off they and the copy return SVO_ERR_STATE with a text in svo_last_error.
+ * svo_get_landmarks returns the lane's count n and writes min(n, cap) records (one synchronisation).
+ * svo_copy_landmarks_async: n_lanes infos to dst_info and n_lanes x max_kps records (lane after lane; only the first info.n of a lane
+ * mean anything) to dst_records, device to device on the context's stream; either may be NULL; bytes = the size of dst_records.
+ * svo_landmark_abi_size() = sizeof(svo_landmark) as this library was compiled (176); callable without a device. */
+int svo_set_landmarks(svo_ctx* ctx, int enable, double std_noise_pixels);
+int svo_get_landmarks_enabled(const svo_ctx* ctx, int* enable, double* std_noise_pixels);   /* either pointer may be NULL */
+int svo_landmarks_load_ini(const char* path, const char* least_squares_section, double* std_noise_pixels);
+int svo_get_landmarks_info(svo_ctx* ctx, int lane, svo_landmarks_info* info);
+int svo_get_landmarks(svo_ctx* ctx, int lane, svo_landmark* out, int cap);
+int svo_copy_landmarks_async(svo_ctx* ctx, void* dst_info_device, void* dst_records_device, size_t bytes);
+size_t svo_landmark_abi_size(void);
+
 /* getValues (H:704-724) and friends.  which: 0 = current frame, 1 = previous frame; side: 0 left, 1 right.
  * Each returns the list length (possibly > cap; only min(len,cap) entries are written) or <0. */
 int svo_get_keypoints(svo_ctx* ctx, int lane, int which, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -410,7 +439,10 @@ int svo_put_features(svo_ctx* ctx, int lane, int which, int side, const svo_keyp
 /* (svo_put_matches also builds the list's matches_lr_row_index (S3:425-445) from the LEFT keypoints put before it: the reference builds that
  * index in stage 3 only, which this path skips (P:219-251), and its windowed tracker (S4:517-530) would read an index nobody built.) */
 int svo_put_matches(svo_ctx* ctx, int lane, int which, const svo_dmatch* m, int n);
-int svo_put_tracked(svo_ctx* ctx, int lane, const svo_index_pair* t, int n);
+int svo_put_tracked(svo_ctx* ctx, int lane, const svo_index_pair* t, int n);   /* octave 0; the lane's other octaves are emptied */
+/* the tracked pairs of one octave < svo_config.max_octaves; the lane's other octaves keep theirs.  (A caller that feeds stage 5 with
+ * the tracked pairs of several octaves, which it concatenates octave by octave, S5:419-461, and cuts at svo_config.max_kps.) */
+int svo_put_tracked_oct(svo_ctx* ctx, int lane, int octave, const svo_index_pair* t, int n);
 /* request_data.precomputed_matches_ID (H:218, P:233-244): the IDs of the octave-0 pairings put before; m_last_match_ID
  * becomes their maximum (P:236-243).  Honoured by the pipeline only when vo_use_matches_ids is set (P:246-250). */
 int svo_put_match_ids(svo_ctx* ctx, int lane, int which, const int32_t* ids, int n);
@@ -571,8 +603,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
 
 /* per-kernel HIP-event timing (svo_config.kernel_times = 1): names[i] points to static storage.
  * total_ms[i] / calls[i] accumulate since the last svo_kernel_times_reset. Returns number of kernels.
- * THE NUMBER RETURNED DEPENDS ON THE CONTEXT'S STATE in one respect: the last name, "pose_covariance", is listed only while
- * svo_set_pose_covariance is on, so a context that has it off returns the list (and the count) it always did.  Size arrays by the
+ * THE NUMBER RETURNED DEPENDS ON THE CONTEXT'S STATE in one respect: the last two names are listed only on request -- "pose_covariance"
+ * while svo_set_pose_covariance is on, and "landmarks" behind it while svo_set_landmarks is on (then with "pose_covariance" before it
+ * whatever that switch says) --, so a context that has both off returns the list (and the count) it always did.  Size arrays by the
  * value of the same call, or for the largest list (cap 64 always suffices). */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);

@@ -155,6 +155,60 @@ typedef struct svo_pose_cov {
     int32_t n_used, dof, state, reserved;
 } svo_pose_cov;
 
+/* One tracked left/right pairing of a frame as stage 5 sees it (svo_set_landmarks in svo_hip.h; no reference counterpart: the
+ * reference triangulates these points at S5:529-544 and keeps them to itself).  The records of a lane are in the order stage 5
+ * concatenates the tracked pairs, octave by octave (S5:419-461), cut at svo_config.max_kps as stage 5 cuts them.
+ *   xyz_prev   the point in the PREVIOUS left camera's frame: stage 5's own triangulation (S5:529-544) of the float pixels ul, vl
+ *              (previous left) and ur (previous right x), scaled by the octave's scale_norm (S5:422), with the lane's svo_stereo_camera:
+ *              den = l_fx (r_cx - ur) + r_fx (ul - l_cx);  X Y Z = baseline / den * (r_fx (ul - l_cx), r_fx (vl - l_cy), l_fx r_fx)
+ *   cov_prev   std_noise_pixels^2 * J J^T, J = d(X, Y, Z) / d(ul, vl, ur), analytic (vr does not enter the triangulation): independent
+ *              pixel noise of that standard deviation on the three coordinates.  Upper triangle xx xy xz yy yz zz, as cov_cur
+ *   xyz_cur    R(w) xyz_prev + t with (w, t) = svo_result.delta of the same call and R the exact Rodrigues rotation: the point in the
+ *              CURRENT left camera's frame, where m_evalRGN projects it (S5:180-195)
+ *   cov_cur    R cov_prev R^T, plus D cov_delta D^T with D = [d(R X)/dw | I3] when the lane's svo_pose_cov of the same call is
+ *              SVO_COV_OK or SVO_COV_DELTA_ONLY (SVO_LMK_POSE_TERM).  THE CROSS-COVARIANCE OF POSE AND LANDMARK IS NEGLECTED: stage 5
+ *              holds the landmarks fixed while it solves for the pose, so cov_delta carries no landmark uncertainty, and the pose was
+ *              estimated from these very pixels.  cov_cur is the sum of the two terms as if they were independent
+ *   residual   s_i = |r_i|^2 of the one more evaluation at delta that svo_pose_cov defines (over the mask stage 5 ended with, pixels
+ *              cast to float, float minus float); 0 where the pairing is not in that evaluation (SVO_LMK_USED clear)
+ *   match_id   the current frame's match ID of the pairing (H:794), -1 with vo_use_matches_ids off
+ *   prev_match, cur_match   the tracked pair's first / second: indices into the previous / current frame's pairings of `octave`
+ * flags:
+ *   SVO_LMK_FINITE     den != 0 and all of xyz_prev, cov_prev finite.  When clear EVERY double of the record is 0
+ *   SVO_LMK_INLIER     in the mask stage 5 ended with (the M of svo_pose_cov)
+ *   SVO_LMK_USED       in M and kept by that evaluation (finite Jacobian, S5:322): the U of svo_pose_cov
+ *   SVO_LMK_POSE       xyz_cur and cov_cur are set (the lane's state is SVO_LMK_OK and the record is finite)
+ *   SVO_LMK_POSE_TERM  cov_cur includes D cov_delta D^T */
+enum { SVO_LMK_FINITE = 1, SVO_LMK_INLIER = 2, SVO_LMK_USED = 4, SVO_LMK_POSE = 8, SVO_LMK_POSE_TERM = 16 };
+typedef struct svo_landmark {
+    double xyz_prev[3], cov_prev[6];
+    double xyz_cur[3], cov_cur[6];
+    double residual;
+    int32_t match_id, prev_match, cur_match, octave;
+    uint32_t flags;
+    int32_t reserved;
+} svo_landmark;
+/* per lane.  state:
+ *   SVO_LMK_NONE         the feature is off, the lane has no previous frame, was reset, or no call has reached stage 5 yet: n = 0
+ *   SVO_LMK_POINTS_ONLY  this call's stage 5 did not end with valid = 1 (bad tracking, fewer than 8 NMS survivors, every early return, a
+ *                        cost abort): xyz_prev, cov_prev, the indices, IDs, octave and SVO_LMK_FINITE are set, nothing of the pose is
+ *   SVO_LMK_OK           every field
+ * n = records of the lane, n_finite = those with SVO_LMK_FINITE, n_inliers = those with SVO_LMK_INLIER (0 unless SVO_LMK_OK),
+ * std_noise_pixels = the value cov_prev was scaled with */
+enum { SVO_LMK_NONE = 0, SVO_LMK_OK = 1, SVO_LMK_POINTS_ONLY = 2 };
+typedef struct svo_landmarks_info {
+    int32_t n, n_finite, n_inliers, state;
+    double std_noise_pixels;
+    int32_t reserved[2];
+} svo_landmarks_info;
+#ifdef __cplusplus
+static_assert(sizeof(svo_landmark) == 176 && sizeof(svo_landmark) % 16 == 0, "svo_landmark: 19 doubles, 6 words, 11 x 16 bytes");
+static_assert(sizeof(svo_landmarks_info) == 32, "svo_landmarks_info");
+#else
+_Static_assert(sizeof(svo_landmark) == 176 && sizeof(svo_landmark) % 16 == 0, "svo_landmark: 19 doubles, 6 words, 11 x 16 bytes");
+_Static_assert(sizeof(svo_landmarks_info) == 32, "svo_landmarks_info");
+#endif
+
 #define SVO_MAX_OCTAVES 4
 #define SVO_DESC_BYTES 32
 

@@ -80,6 +80,29 @@ class PoseCov(C.Structure):
 
 assert C.sizeof(PoseCov) == 888
 
+# svo_landmark (include/svo_types.h): one tracked pairing of a frame as stage 5 sees it; covariances as upper triangles xx xy xz yy yz zz
+LMK_FINITE, LMK_INLIER, LMK_USED, LMK_POSE, LMK_POSE_TERM = 1, 2, 4, 8, 16
+LMK_NONE, LMK_OK, LMK_POINTS_ONLY = range(3)
+Landmark = np.dtype([("xyz_prev", "<f8", (3,)), ("cov_prev", "<f8", (6,)), ("xyz_cur", "<f8", (3,)), ("cov_cur", "<f8", (6,)),
+                     ("residual", "<f8"), ("match_id", "<i4"), ("prev_match", "<i4"), ("cur_match", "<i4"), ("octave", "<i4"),
+                     ("flags", "<u4"), ("reserved", "<i4")])
+assert Landmark.itemsize == 176 and Landmark.itemsize % 16 == 0
+
+
+def cov3(tri):
+    """the symmetric 3 x 3 matrices of upper triangles (..., 6) as stored in Landmark.cov_prev / cov_cur"""
+    tri = np.asarray(tri)
+    return tri[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(tri.shape[:-1] + (3, 3))
+
+
+class LandmarksInfo(C.Structure):
+    """svo_landmarks_info: the lane's record count, how many are finite / inliers, its state and the std_noise_pixels used"""
+    _fields_ = [("n", C.c_int32), ("n_finite", C.c_int32), ("n_inliers", C.c_int32), ("state", C.c_int32),
+                ("std_noise_pixels", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(LandmarksInfo) == 32
+
 
 class FasterStats(C.Structure):
     """svo_faster_stats (include/svo_types.h): dmFASTER's dynamic thresholds of one lane and the corner counts that moved them, per octave"""

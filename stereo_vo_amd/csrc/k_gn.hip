@@ -262,8 +262,9 @@ static_assert(8 * LdsGaussNewton::n_keys(64) + 4 * (2 * LdsGaussNewton::n_hash(6
 static_assert(sizeof(GnShared) == 2424 && LdsGaussNewton{64}.total() == 4520 && LdsGaussNewton{1024}.total() == 33320 && LdsGaussNewton{16384}.total() == 33320, "k_gauss_newton LDS totals: 30 * min(pmax, 1024) + 160 + 2424 + 16");
 static_assert(LdsGaussNewton{64}.scratch_bytes_per_lane() == 30 * 64 && LdsGaussNewton{16384}.scratch_bytes_per_lane() == 30 * 16384, "k_gauss_newton scratch");
 static_assert(LdsGaussNewton{16384}.total() <= 160 * 1024, "gfx950: 160 KB of LDS per CU");
-// What k_gauss_newton leaves per lane in GNParams::mask_out for k_pose_covariance (svo_set_pose_covariance allocates it):
-// {int ended_valid, int T, pad to HEAD} | mask[pmax]
+// What k_gauss_newton leaves per lane in GNParams::mask_out for k_pose_covariance and k_landmarks (svo_set_pose_covariance or
+// svo_set_landmarks allocates it, whichever comes first): {int ended_valid, int T, pad to HEAD} | mask[pmax].  ended_valid is cleared
+// ("consumed") by the LAST kernel that reads the record: k_landmarks when it runs, else k_pose_covariance.
 struct GnMaskRecord {
     int pmax;
     static constexpr int HEAD = 16;
@@ -419,6 +420,17 @@ __device__ __forceinline__ bool gn_point(const svo_stereo_camera& cam, const Rot
     const float* o = obs + 8 * (long long)m;
     ri[0] = (double)(o[4] - pl_x); ri[1] = (double)(o[5] - pl_y); ri[2] = (double)(o[6] - pr_x); ri[3] = (double)(o[7] - pr_y);   // float subtraction, S5:335-338
     return true;
+}
+
+// One landmark of stage 5's triangulation (S5:529-544) from the previous frame's ul, vl, ur: xyz = baseline / den * (fr (ul - cul),
+// fr (vl - cvl), fl fr).  Returns den = fl (cur - ur) + fr (ul - cul).  Shared by k_gauss_newton and k_landmarks: one copy of the formula.
+__device__ __forceinline__ double gn_triangulate(double baseline, double fl, double fr, double cul, double cvl, double cur_,
+                                                 double ul, double vl, double ur, double* xyz)
+{
+    const double den = fl * (cur_ - ur) + fr * (ul - cul);
+    const double b_d = baseline / den;
+    xyz[0] = b_d * fr * (ul - cul); xyz[1] = b_d * fr * (vl - cvl); xyz[2] = b_d * fl * fr;
+    return den;
 }
 
 // Block reduction of the 28 sums: inside every wave on the permlane / DPP network (no LDS), then GN_NT / 64 x 28 doubles through
@@ -622,8 +634,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         for (int m = tid; m < T; m += blockDim.x) {
             if (!mask[m]) continue;
             const double ul = obs[8 * (long long)m], vl = obs[8 * (long long)m + 1], ur = obs[8 * (long long)m + 2];
-            const double b_d = baseline / (fl * (cur_ - ur) + fr * (ul - cul));
-            lmk[3 * m] = b_d * fr * (ul - cul); lmk[3 * m + 1] = b_d * fr * (vl - cvl); lmk[3 * m + 2] = b_d * fl * fr;
+            gn_triangulate(baseline, fl, fr, cul, cvl, cur_, ul, vl, ur, lmk + 3 * m);
         }
     };
     triangulate();
@@ -714,7 +725,7 @@ __global__ void __launch_bounds__(GN_NT) k_gauss_newton(DevCtx c, GNParams P, ui
         res.n_residual = n_res > T ? n_res : T; res.n_outliers = n_out;
         res.valid = !abort_;                                                                                         // S5:727
     }
-    // svo_set_pose_covariance: the final mask, T and whether this run ended valid, for k_pose_covariance (GnMaskRecord)
+    // svo_set_pose_covariance / svo_set_landmarks: the final mask, T and whether this run ended valid, for k_pose_covariance and k_landmarks (GnMaskRecord)
     if (P.mask_out) {
         uint8_t* mo = P.mask_out + (size_t)lane_id * GnMaskRecord{PM}.bytes();
         for (int m = tid; m < T; m += blockDim.x) mo[GnMaskRecord::HEAD + m] = mask[m];
@@ -821,7 +832,7 @@ __device__ void cov_rotation_derivs(const double* w, double* Rm, double* dR)
 }
 
 template <int NT>
-__global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, svo_pose_cov* out)
+__global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, svo_pose_cov* out, int consume)
 {
     SVO_TL_SCOPE(c, TL_GN, 1);
     SVO_LATENCY_CHAIN(c);
@@ -832,7 +843,7 @@ __global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, sv
     svo_pose_cov& o = out[lane_id];
     if (tid == 0) {
         sh.ended_valid = ((const int*)mo)[0]; sh.T = ((const int*)mo)[1];
-        ((int*)mo)[0] = 0;                                                   // consumed: a later call whose stage 5 returns early finds no mask
+        if (consume) ((int*)mo)[0] = 0;                                      // consumed: a later call whose stage 5 returns early finds no mask (k_landmarks does it when it follows)
         double d6[6];
         for (int k = 0; k < 6; k++) { d6[k] = c.results[lane_id].delta[k]; sh.delta[k] = d6[k]; }
         rodrigues_with_derivs(d6, sh.R);
@@ -934,9 +945,186 @@ __global__ void __launch_bounds__(NT) k_pose_covariance(DevCtx c, GNParams P, sv
     o.state = SVO_COV_OK;
 }
 
-void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, hipStream_t st)
+void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, bool consume, hipStream_t st)
 {
-    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_pose_covariance<NT>, dim3(c.n_lanes), dim3(NT), 0, st, c, P, out); });
+    gn_for_threads(k.gn_nt, [&](auto n) { constexpr int NT = decltype(n)::value; hipLaunchKernelGGL(k_pose_covariance<NT>, dim3(c.n_lanes), dim3(NT), 0, st, c, P, out, consume ? 1 : 0); });
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The landmarks of a frame (svo_set_landmarks, contract at svo_landmark in svo_types.h): no reference counterpart -- the reference
+// triangulates them (S5:529-544) and keeps them to itself.  One record per tracked pairing in stage 5's order: the point in the
+// previous and in the current left camera's frame, each with its covariance, the residual of the one more evaluation at the
+// returned delta (the evaluation of svo_pose_cov, through gn_point), the indices and the match ID.
+// Launched behind k_gauss_newton, and behind k_pose_covariance when that runs (its cov_delta enters cov_cur).  One thread per
+// pairing, a grid of (max_kps / 256, n_lanes) blocks of which those past a lane's T leave at once.  The kernel gathers from the
+// lists itself and does not read gn_obs / gn_lmk: k_gauss_newton returns before its gather on a lane with bad tracking, which
+// would leave them stale, and it triangulates only what its mask holds.  The final mask is k_gauss_newton's GnMaskRecord.
+// The lane's counts are summed over its blocks through three words of LmkArgs::cnt (zero between launches); the block that takes
+// the last ticket writes svo_landmarks_info, clears the words and consumes the mask record.
+// ------------------------------------------------------------------------------------------------------------
+#define LMK_NT 256
+// Static LDS of k_landmarks: ONE description.  The records of the block are staged here (a thread's 176-byte record would leave its
+// registers as stride-176 stores) and leave as contiguous 16-byte stores; delta, both rotations and cov_delta are read once per block.
+struct LmkShared {
+    svo_landmark stage[LMK_NT];   // 44 KB
+    double delta[6];
+    Rot R;                        // rodrigues_with_derivs: what gn_point evaluates with
+    double Rm[9], dR[27];         // cov_rotation_derivs: the exact rotation, for xyz_cur, cov_cur and D
+    double C[36];                 // cov_delta of the lane's svo_pose_cov (read only under pose_term)
+    int ended_valid, pose_term, n_finite, n_inliers;
+};
+static_assert(sizeof(svo_landmark) % 16 == 0 && offsetof(LmkShared, stage) == 0, "the staged records leave as uint4");
+static_assert(sizeof(LmkShared) == LMK_NT * 176 + 8 * (6 + 9 + 27 + 36) + sizeof(Rot) + 16 && sizeof(LmkShared) <= 64 * 1024, "k_landmarks LDS: 45 056 + 624 + 296 + 16");
+
+__global__ void __launch_bounds__(LMK_NT) k_landmarks(DevCtx c, GNParams P, LmkArgs A)
+{
+    SVO_TL_SCOPE(c, TL_GN, 2);
+    SVO_LATENCY_CHAIN(c);
+    __shared__ __attribute__((aligned(16))) LmkShared sh;
+    const int lane_id = blockIdx.y, tid = threadIdx.x, first = blockIdx.x * LMK_NT;
+    if (lane_idle(c, lane_id)) return;                                       // an idle lane keeps its records and its info
+    const LaneState& ls = c.lane[lane_id];
+    const int has_prev = ls.has_prev;
+    // tracked pairs of all octaves, concatenated octave by octave and cut at pmax, as k_gauss_newton does (S5:419-461)
+    const int cur = 1 - ls.prev_slot, prev = ls.prev_slot;
+    int toff[SVO_MAX_OCTAVES + 1];
+    toff[0] = 0;
+    for (int o = 0; o < SVO_MAX_OCTAVES; o++) toff[o + 1] = toff[o] + (o < c.n_oct ? c.n_tracked[lane_id * c.oct_cap + o] : 0);
+    int T = has_prev ? toff[SVO_MAX_OCTAVES] : 0;
+    const int cap = P.pmax < c.max_kps ? P.pmax : c.max_kps;                 // (the record array holds max_kps per lane)
+    if (T > cap) T = cap;
+    if (first >= T && blockIdx.x != 0) return;                               // block 0 stays: it writes the lane's info when T = 0
+    const int nblk = T > 0 ? (T + LMK_NT - 1) / LMK_NT : 1;                  // the blocks of this lane that take a ticket
+    uint8_t* mo = P.mask_out + (size_t)lane_id * GnMaskRecord{P.pmax}.bytes();
+    if (tid == 0) {
+        const int ev = has_prev && ((const int*)mo)[0] != 0 && ((const int*)mo)[1] == T;
+        sh.ended_valid = ev; sh.n_finite = 0; sh.n_inliers = 0;
+        int pt = 0;
+        if (ev) {
+            double d6[6];
+            for (int k = 0; k < 6; k++) { d6[k] = c.results[lane_id].delta[k]; sh.delta[k] = d6[k]; }
+            rodrigues_with_derivs(d6, sh.R);
+            cov_rotation_derivs(sh.delta, sh.Rm, sh.dR);
+            if (A.cov) { const int st = A.cov[lane_id].state; pt = st == SVO_COV_OK || st == SVO_COV_DELTA_ONLY; }
+        }
+        sh.pose_term = pt;
+    }
+    if (A.cov && tid >= 64 && tid < 64 + 36) sh.C[tid - 64] = A.cov[lane_id].cov_delta[tid - 64];
+    __syncthreads();
+    const int ev = sh.ended_valid, pose_term = sh.pose_term;
+    const int i = first + tid;
+    bool fin = false, inl = false;
+    if (i < T) {
+        int o = 0;
+        for (int q = 1; q < SVO_MAX_OCTAVES; q++) if (i >= toff[q] && q < c.n_oct) o = q;
+        const int vl = lane_id * c.oct_cap + o;
+        const svo_index_pair tp = c.tracked[(long long)vl * c.max_kps + (i - toff[o])];
+        const svo_dmatch a = c.matches[match_base(c, vl, prev) + tp.first], b = c.matches[match_base(c, vl, cur) + tp.second];
+        const svo_keypoint l1 = c.kps[feat_base(c, vl, prev, 0) + a.queryIdx], r1 = c.kps[feat_base(c, vl, prev, 1) + a.trainIdx];
+        const svo_keypoint l2 = c.kps[feat_base(c, vl, cur, 0) + b.queryIdx], r2 = c.kps[feat_base(c, vl, cur, 1) + b.trainIdx];
+        const float sn = (float)(size_t)(c.n_oct > 1 ? (1 << o) : 1);            // scale_norm, S5:422 (applied only when nOctaves > 1)
+        float ob[8];
+        if (c.n_oct > 1) { ob[0] = l1.x * sn; ob[1] = l1.y * sn; ob[2] = r1.x * sn; ob[3] = r1.y * sn; ob[4] = l2.x * sn; ob[5] = l2.y * sn; ob[6] = r2.x * sn; ob[7] = r2.y * sn; }
+        else { ob[0] = l1.x; ob[1] = l1.y; ob[2] = r1.x; ob[3] = r1.y; ob[4] = l2.x; ob[5] = l2.y; ob[6] = r2.x; ob[7] = r2.y; }
+        const svo_stereo_camera cam = c.cams[lane_id];
+        const double fl = cam.l_fx, fr = cam.r_fx;
+        svo_landmark rec;
+        double X[3];
+        const double den = gn_triangulate(cam.baseline, fl, fr, cam.l_cx, cam.l_cy, cam.r_cx, (double)ob[0], (double)ob[1], (double)ob[2], X);
+        // J = d(X, Y, Z) / d(ul, vl, ur): d den / d ul = fr, d den / d ur = -fl, and every coordinate is (a numerator) / den
+        const double id = 1.0 / den, bf = (cam.baseline / den) * fr, kl = fr * id, kr = fl * id;
+        const double J[3][3] = { { bf - X[0] * kl, 0.0, X[0] * kr }, { -X[1] * kl, bf, X[1] * kr }, { -X[2] * kl, 0.0, X[2] * kr } };
+        double Cp[3][3];
+        {
+            int h = 0;
+            for (int r = 0; r < 3; r++) for (int s = r; s < 3; s++) {
+                const double v = A.var_px * (J[r][0] * J[s][0] + J[r][1] * J[s][1] + J[r][2] * J[s][2]);
+                Cp[r][s] = v; Cp[s][r] = v; rec.cov_prev[h++] = v;
+            }
+        }
+        fin = den != 0.0;
+        for (int k = 0; k < 3; k++) { rec.xyz_prev[k] = X[k]; fin = fin && isfinite(X[k]); }
+        for (int k = 0; k < 6; k++) fin = fin && isfinite(rec.cov_prev[k]);
+        unsigned flags = fin ? SVO_LMK_FINITE : 0u;
+        for (int k = 0; k < 3; k++) rec.xyz_cur[k] = 0.0;
+        for (int k = 0; k < 6; k++) rec.cov_cur[k] = 0.0;
+        rec.residual = 0.0;
+        if (ev) {
+            inl = mo[GnMaskRecord::HEAD + i] != 0;
+            if (inl) {
+                flags |= SVO_LMK_INLIER;
+                double Jp[4][6], ri[4];
+                if (gn_point(cam, sh.R, sh.R.small_angle != 0, sh.delta[3], sh.delta[4], sh.delta[5], X, ob, 0, Jp, ri)) {
+                    flags |= SVO_LMK_USED;
+                    rec.residual = ri[0] * ri[0] + ri[1] * ri[1] + ri[2] * ri[2] + ri[3] * ri[3];
+                }
+            }
+            if (fin) {
+                flags |= SVO_LMK_POSE | (pose_term ? SVO_LMK_POSE_TERM : 0u);
+                const double* R = sh.Rm;
+                for (int r = 0; r < 3; r++) rec.xyz_cur[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + sh.delta[3 + r];
+                double M[3][3];                                                  // R cov_prev
+                for (int r = 0; r < 3; r++) for (int s = 0; s < 3; s++) M[r][s] = R[3 * r] * Cp[0][s] + R[3 * r + 1] * Cp[1][s] + R[3 * r + 2] * Cp[2][s];
+                double Dm[3][6], E[3][6];                                        // D = [d(R X)/dw | I3], E = D cov_delta
+                if (pose_term) {
+                    for (int k = 0; k < 3; k++) {
+                        const double* d = sh.dR + 9 * k;
+                        for (int r = 0; r < 3; r++) { Dm[r][k] = d[3 * r] * X[0] + d[3 * r + 1] * X[1] + d[3 * r + 2] * X[2]; Dm[r][3 + k] = r == k ? 1.0 : 0.0; }
+                    }
+                    for (int r = 0; r < 3; r++) for (int s = 0; s < 6; s++) {
+                        double v = 0;
+                        for (int k = 0; k < 6; k++) v += Dm[r][k] * sh.C[k * 6 + s];
+                        E[r][s] = v;
+                    }
+                }
+                int h = 0;
+                for (int r = 0; r < 3; r++) for (int s = r; s < 3; s++) {
+                    double v = M[r][0] * R[3 * s] + M[r][1] * R[3 * s + 1] + M[r][2] * R[3 * s + 2];
+                    if (pose_term) { double e = 0; for (int k = 0; k < 6; k++) e += E[r][k] * Dm[s][k]; v += e; }
+                    rec.cov_cur[h++] = v;
+                }
+            }
+        }
+        if (!fin) {                                                              // every double of the record is 0
+            for (int k = 0; k < 3; k++) rec.xyz_prev[k] = 0.0;
+            for (int k = 0; k < 6; k++) rec.cov_prev[k] = 0.0;
+            rec.residual = 0.0;
+        }
+        const int n_ids = A.ids_on ? c.n_ids[vl * 2 + cur] : 0;
+        rec.match_id = tp.second >= 0 && tp.second < n_ids ? c.ids[((long long)vl * 2 + cur) * c.max_kps + tp.second] : -1;
+        rec.prev_match = tp.first; rec.cur_match = tp.second; rec.octave = o; rec.flags = flags; rec.reserved = 0;
+        sh.stage[tid] = rec;
+    }
+    {
+        const unsigned long long bfin = __ballot(fin), binl = __ballot(inl);
+        if ((tid & 63) == 0) { atomicAdd(&sh.n_finite, (int)__popcll(bfin)); atomicAdd(&sh.n_inliers, (int)__popcll(binl)); }
+    }
+    __syncthreads();
+    {   // the block's records, contiguous in the lane's array: 16 bytes per thread and pass
+        const int nrec = T - first < LMK_NT ? (T - first > 0 ? T - first : 0) : LMK_NT;
+        const uint4* src = (const uint4*)sh.stage;
+        uint4* dst = (uint4*)(A.rec + (size_t)lane_id * c.max_kps + first);
+        for (int q = tid; q < nrec * (int)(sizeof(svo_landmark) / 16); q += LMK_NT) dst[q] = src[q];
+    }
+    if (tid == 0) {
+        int* cn = A.cnt + 4 * lane_id;
+        if (sh.n_finite) atomicAdd(cn, sh.n_finite);
+        if (sh.n_inliers) atomicAdd(cn + 1, sh.n_inliers);
+        __threadfence();
+        if (atomicAdd(cn + 2, 1) == nblk - 1) {                                  // the lane's last block
+            svo_landmarks_info& info = A.info[lane_id];
+            info.n = T; info.n_finite = atomicExch(cn, 0); info.n_inliers = atomicExch(cn + 1, 0);
+            info.state = !has_prev ? SVO_LMK_NONE : (ev ? SVO_LMK_OK : SVO_LMK_POINTS_ONLY);
+            info.std_noise_pixels = A.std_px; info.reserved[0] = 0; info.reserved[1] = 0;
+            atomicExch(cn + 2, 0);
+            ((int*)mo)[0] = 0;                                                   // consumed (see GnMaskRecord)
+        }
+    }
+}
+
+void launch_landmarks(const DevCtx& c, const GNParams& P, const LmkArgs& A, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_landmarks, dim3((c.max_kps + LMK_NT - 1) / LMK_NT, c.n_lanes), dim3(LMK_NT), 0, st, c, P, A);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -137,6 +137,7 @@ public:
         check(svo_params_load_ini(fileName.c_str(), names, &params), "svo_params_load_ini");
         { int32_t w = params_detect.KLT_win; check(svo_klt_win_load_ini(fileName.c_str(), names[1], &w), "svo_klt_win_load_ini"); params_detect.KLT_win = w; }
         check(svo_dyn_fast_load_ini(fileName.c_str(), names[1], &params_detect.target_feats_per_pixel), "svo_dyn_fast_load_ini");
+        check(svo_landmarks_load_ini(fileName.c_str(), names[4], &params_least_squares.std_noise_pixels), "svo_landmarks_load_ini");   // H:628
         applyParams();                                                                   // resetFASTThreshold / resetORBThreshold, H:662-663
     }
     void setVerbosityLevel(int level) { m_verbose_level = level; }                       // H:527
@@ -154,6 +155,20 @@ public:
         for (int i = 0; i < 36; i++) { out.info[i] = r.info[i]; out.cov_delta[i] = r.cov_delta[i]; out.cov_pose[i] = r.cov_pose[i]; }
         out.sigma2 = r.sigma2; out.n_used = r.n_used; out.dof = r.dof; out.state = r.state;
         return r.state == SVO_COV_OK;
+    }
+    /** The landmarks stage 5 triangulates, with their covariances (no reference counterpart; svo_landmark in svo_types.h).
+      * TLeastSquaresParams::std_noise_pixels (H:628) is read by loadParamsFromConfigFileName into params_least_squares and scales the
+      * covariances; enableLandmarks() before the frames; getLandmarks() after processNewImagePair fills one record per tracked pairing,
+      * in stage 5's order, and returns the lane's state (SVO_LMK_*).  getChangeInPose writes no records. */
+    struct TLeastSquaresParams { double std_noise_pixels; TLeastSquaresParams() : std_noise_pixels(1.0) {} } params_least_squares;
+    void enableLandmarks(bool enable = true) { check(svo_set_landmarks(m_ctx, enable ? 1 : 0, params_least_squares.std_noise_pixels), "svo_set_landmarks"); }
+    int getLandmarks(std::vector<svo_landmark>& out, svo_landmarks_info* info = nullptr) {
+        svo_landmarks_info li; check(svo_get_landmarks_info(m_ctx, 0, &li), "svo_get_landmarks_info");
+        out.resize((size_t)(li.n > 0 ? li.n : 0));
+        const int n = svo_get_landmarks(m_ctx, 0, out.empty() ? nullptr : out.data(), (int)out.size());
+        if (n < 0) check(n, "svo_get_landmarks");
+        if (info) *info = li;
+        return li.state;
     }
     int getFASTThreshold() { return svo_get_fast_threshold(m_ctx); }                     // H:530
     void setFASTThreshold(int v) { check(svo_set_fast_threshold(m_ctx, v), "svo_set_fast_threshold"); }   // H:531

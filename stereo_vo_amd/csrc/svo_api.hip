@@ -32,14 +32,16 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // svo_gather_windows: the slot-selecting window gather (only a caller of that entry point counts a call here)
        KT_GATHER_WIN,
        // svo_set_pose_covariance (only a context that enables it counts a call here)
-       KT_POSE_COV,      // keep it last: svo_kernel_times lists it only while the feature is on
+       KT_POSE_COV,      // keep these two last, in this order: svo_kernel_times lists each only while its feature is on (kt_listed)
+       // svo_set_landmarks (only a context that enables it counts a call here)
+       KT_LANDMARKS,
        KT_COUNT };
 static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
     "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
-    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance" };
+    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -116,7 +118,9 @@ struct svo_ctx {
     uint8_t* d_vals; uint8_t* h_vals; size_t vals_bytes;
     uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
     // svo_set_pose_covariance: one record per lane and the array k_gauss_newton leaves its final mask in; nullptr until first enabled
-    bool pose_cov; svo_pose_cov* d_cov; uint8_t* d_cov_mask;
+    bool pose_cov; svo_pose_cov* d_cov; uint8_t* d_cov_mask;      // (d_cov_mask: made by whichever of this feature and the next is enabled first)
+    // svo_set_landmarks: [n_lanes][max_kps] records, one info per lane, the 4 counter words per lane of k_landmarks; nullptr until first enabled
+    bool landmarks; double lmk_std; svo_landmark* d_lmk; svo_landmarks_info* d_lmk_info; int* d_lmk_cnt;
     // svo_set_dyn_fast_threshold: dmFASTER's m_threshold[octave] of every lane (the `next` member) with its statistics; nullptr until first enabled.
     // Persistent detector scratch: read and written by detect calls alone, ordered on the stream they run on, like fast_th_dyn
     bool dyn_fast; double dyn_target; svo_faster_stats* d_fstats;
@@ -394,6 +398,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
+    ctx->landmarks = false; ctx->lmk_std = 1.0; ctx->d_lmk = nullptr; ctx->d_lmk_info = nullptr; ctx->d_lmk_cnt = nullptr;
     ctx->sad.cur.assign((size_t)cfg->n_lanes, 1); ctx->sad.prev.assign((size_t)cfg->n_lanes, 1); ctx->sad.drop.assign((size_t)cfg->n_lanes, 0);
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
@@ -662,6 +667,97 @@ extern "C" int svo_copy_pose_covariances_async(svo_ctx* ctx, void* dst, size_t b
     { const int rc = pose_cov_ready(ctx); if (rc) return rc; }
     note_stream(ctx);
     HIPCHECK(hipMemcpyAsync(dst, ctx->d_cov, sizeof(svo_pose_cov) * ctx->cfg.n_lanes, hipMemcpyDeviceToDevice, ctx->stream));
+    mark_stream(ctx);
+    return SVO_OK;
+}
+
+// The landmarks of every frame (svo_types.h, svo_landmark).  Off: nothing is allocated, nothing launched.  As for the pose covariance the
+// buffers are made here, before any graph capture, and a change of the switch or of std_noise_pixels (a kernel argument) drops the
+// captured graphs.  The record array is the one large allocation a context makes after svo_create: refused with the number when it fails.
+extern "C" size_t svo_landmark_abi_size(void) { return sizeof(svo_landmark); }
+extern "C" int svo_set_landmarks(svo_ctx* ctx, int enable, double std_noise_pixels)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    if (!(std_noise_pixels >= 0.0 && std_noise_pixels <= 1.7976931348623157e308)) {
+        char msg[128]; snprintf(msg, sizeof(msg), "std_noise_pixels %g: a finite value >= 0 is expected (0 = the reference's default, 1)", std_noise_pixels);
+        ctx->last_error = msg; return SVO_ERR_ARG;
+    }
+    const bool on = enable != 0;
+    const double sd = std_noise_pixels == 0.0 ? 1.0 : std_noise_pixels;       // TLeastSquaresParams::std_noise_pixels defaults to 1
+    if (on == ctx->landmarks && (!on || sd == ctx->lmk_std)) return SVO_OK;
+    drop_graphs(ctx);
+    HIPCHECK(sync_all(ctx));
+    if (on) {
+        const size_t L = (size_t)ctx->cfg.n_lanes, MK = (size_t)ctx->dc.max_kps, mb = gn_mask_bytes_per_lane(ctx->dc.max_kps) * L;
+        if (!ctx->d_lmk) {
+            const hipError_t e = dev_alloc(ctx, &ctx->d_lmk, L * MK);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                char msg[200]; snprintf(msg, sizeof(msg), "svo_set_landmarks: %zu bytes for %zu lanes x %zu records of %zu bytes could not be allocated (%s)", L * MK * sizeof(svo_landmark), L, MK, sizeof(svo_landmark), hipGetErrorString(e));
+                ctx->last_error = msg; return SVO_ERR_CAPACITY;
+            }
+        }
+        if (!ctx->d_lmk_info) HIPCHECK(dev_alloc(ctx, &ctx->d_lmk_info, L));
+        if (!ctx->d_lmk_cnt) HIPCHECK(dev_alloc(ctx, &ctx->d_lmk_cnt, 4 * L));
+        if (!ctx->d_cov_mask) { HIPCHECK(dev_alloc(ctx, &ctx->d_cov_mask, mb)); }
+        else if (!ctx->pose_cov) HIPCHECK(hipMemset(ctx->d_cov_mask, 0, mb));      // (while the pose covariance is on the array is in use and consistent)
+        if (!ctx->landmarks) {                                                       // SVO_LMK_NONE until a stage 5 has run
+            HIPCHECK(hipMemset(ctx->d_lmk_info, 0, sizeof(svo_landmarks_info) * L));
+            HIPCHECK(hipMemset(ctx->d_lmk_cnt, 0, sizeof(int) * 4 * L));
+        }
+        ctx->lmk_std = sd;
+    }
+    ctx->landmarks = on;
+    return SVO_OK;
+}
+extern "C" int svo_get_landmarks_enabled(const svo_ctx* ctx, int* enable, double* std_noise_pixels)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (enable) *enable = ctx->landmarks ? 1 : 0;
+    if (std_noise_pixels) *std_noise_pixels = ctx->lmk_std;
+    return SVO_OK;
+}
+static int landmarks_ready(svo_ctx* ctx)
+{
+    if (ctx->landmarks) return SVO_OK;
+    ctx->last_error = "the landmarks are off: svo_set_landmarks(ctx, 1, std_noise_pixels) before the frame";
+    return SVO_ERR_STATE;
+}
+extern "C" int svo_get_landmarks_info(svo_ctx* ctx, int lane, svo_landmarks_info* info)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || !info || lane < 0 || lane >= ctx->cfg.n_lanes) return SVO_ERR_ARG;
+    int rc = landmarks_ready(ctx); if (rc) return rc;
+    rc = svo_wait(ctx); if (rc) return rc;
+    HIPCHECK(hipMemcpy(info, ctx->d_lmk_info + lane, sizeof(*info), hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+// One synchronisation (svo_wait), then the lane's count and min(count, cap) records.  Returns the count.
+extern "C" int svo_get_landmarks(svo_ctx* ctx, int lane, svo_landmark* out, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || cap < 0 || (cap > 0 && !out)) return SVO_ERR_ARG;
+    int rc = landmarks_ready(ctx); if (rc) return rc;
+    rc = svo_wait(ctx); if (rc) return rc;
+    svo_landmarks_info info;
+    HIPCHECK(hipMemcpy(&info, ctx->d_lmk_info + lane, sizeof(info), hipMemcpyDeviceToHost));
+    const int n = info.n < 0 ? 0 : (info.n > ctx->dc.max_kps ? ctx->dc.max_kps : info.n), m = n < cap ? n : cap;
+    if (m > 0) HIPCHECK(hipMemcpy(out, ctx->d_lmk + (size_t)lane * ctx->dc.max_kps, sizeof(svo_landmark) * (size_t)m, hipMemcpyDeviceToHost));
+    return n;
+}
+// dst_info: n_lanes svo_landmarks_info (or NULL); dst_records: n_lanes x max_kps svo_landmark, lane after lane (or NULL); bytes = the
+// size of the records' destination
+extern "C" int svo_copy_landmarks_async(svo_ctx* ctx, void* dst_info, void* dst_records, size_t bytes)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || (!dst_info && !dst_records)) return SVO_ERR_ARG;
+    const size_t L = (size_t)ctx->cfg.n_lanes, need = sizeof(svo_landmark) * L * (size_t)ctx->dc.max_kps;
+    if (dst_records && bytes < need) return SVO_ERR_ARG;
+    { const int rc = landmarks_ready(ctx); if (rc) return rc; }
+    note_stream(ctx);
+    if (dst_info) HIPCHECK(hipMemcpyAsync(dst_info, ctx->d_lmk_info, sizeof(svo_landmarks_info) * L, hipMemcpyDeviceToDevice, ctx->stream));
+    if (dst_records) HIPCHECK(hipMemcpyAsync(dst_records, ctx->d_lmk, need, hipMemcpyDeviceToDevice, ctx->stream));
     mark_stream(ctx);
     return SVO_OK;
 }
@@ -955,6 +1051,7 @@ extern "C" int svo_reset(svo_ctx* ctx, int lane)
             HIPCHECK(hipMemset(ctx->dc.n_ids + (size_t)l * OC * 2, 0, (size_t)OC * 2 * sizeof(int)));
             HIPCHECK(hipMemset(ctx->dc.results + l, 0, sizeof(svo_result)));
             if (ctx->pose_cov) HIPCHECK(hipMemset(ctx->d_cov + l, 0, sizeof(svo_pose_cov)));
+            if (ctx->landmarks) HIPCHECK(hipMemset(ctx->d_lmk_info + l, 0, sizeof(svo_landmarks_info)));      // SVO_LMK_NONE, n = 0
             if (ctx->dyn_fast) { const int rc = dyn_fast_init(ctx, l); if (rc) return rc; }     // a fresh estimator: m_threshold is empty (S2:522-523)
             HIPCHECK(hipMemset(ctx->dc.fast_th_dyn + (size_t)2 * l * SVO_MAX_LEVELS, 0, (size_t)2 * SVO_MAX_LEVELS * sizeof(uint32_t)));   // a fresh estimator speculates nothing
             ctx->sad.cur[l] = ctx->sad.prev[l] = 1; ctx->sad.drop[l] = 0;                       // no frames: nothing a SAD stage could miss
@@ -1134,8 +1231,9 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    // "pose_covariance" (the last name) is listed while svo_set_pose_covariance is on: a context that has it off reports the list it always did
-    const int n = ctx->pose_cov ? KT_COUNT : KT_POSE_COV;
+    // "pose_covariance" is listed while svo_set_pose_covariance is on, and "landmarks" (behind it, then with "pose_covariance" whatever its
+    // switch) while svo_set_landmarks is on: a context that has both off reports the list it always did
+    const int n = ctx->landmarks ? KT_COUNT : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
     for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
     return n;
 }
@@ -1511,9 +1609,15 @@ static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
     g.min_distance = p.min_distance; g.img_w = d.W; g.img_h = d.H; g.pmax = d.max_kps; g.standalone = 0;
     g.kernel_param = p.kernel_param; g.min_mod_out_vector = p.min_mod_out_vector; g.residual_threshold = p.residual_threshold;
     if (p.use_custom_initial_pose) g.use_custom_initial_pose = 1;        // deltaPose = initial_estimation = zeros (S5:504-505, default argument H:1045)
-    if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
+    if (ctx->pose_cov || ctx->landmarks) g.mask_out = ctx->d_cov_mask;
     { Span s(ctx, KT_GN); launch_gauss_newton(d, ctx->knobs, g, st); }
-    if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, ctx->knobs, g, ctx->d_cov, st); }
+    if (ctx->pose_cov) { Span s(ctx, KT_POSE_COV); launch_pose_covariance(d, ctx->knobs, g, ctx->d_cov, !ctx->landmarks, st); }
+    if (ctx->landmarks) {                                                        // behind k_pose_covariance: cov_cur takes its cov_delta
+        LmkArgs a; memset(&a, 0, sizeof(a));
+        a.rec = ctx->d_lmk; a.info = ctx->d_lmk_info; a.cnt = ctx->d_lmk_cnt; a.cov = ctx->pose_cov ? ctx->d_cov : nullptr;
+        a.std_px = ctx->lmk_std; a.var_px = ctx->lmk_std * ctx->lmk_std; a.ids_on = p.vo_use_matches_ids ? 1 : 0;
+        Span s(ctx, KT_LANDMARKS); launch_landmarks(d, g, a, st);
+    }
 }
 
 // Every lazily allocated buffer a frame may need exists BEFORE a capture begins: hipMalloc / hipMemset are refused on a capturing
@@ -2004,6 +2108,18 @@ extern "C" int svo_put_tracked(svo_ctx* ctx, int lane, const svo_index_pair* t, 
     HIPCHECK(hipMemcpy(ctx->dc.n_tracked + vl, &n, sizeof(int), hipMemcpyHostToDevice));
     return SVO_OK;
 }
+// the tracked pairs of ONE octave; the other octaves of the lane keep theirs (svo_put_tracked is octave 0 and empties the rest)
+extern "C" int svo_put_tracked_oct(svo_ctx* ctx, int lane, int octave, const svo_index_pair* t, int n)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || lane < 0 || lane >= ctx->cfg.n_lanes || octave < 0 || octave >= ctx->dc.oct_cap || n < 0 || (n > 0 && !t)) return SVO_ERR_ARG;
+    if (n > ctx->dc.max_kps) return SVO_ERR_CAPACITY;
+    int rc = svo_wait(ctx); if (rc) return rc;
+    const int vl = lane * ctx->dc.oct_cap + octave;
+    if (n > 0) HIPCHECK(hipMemcpy(ctx->dc.tracked + (long long)vl * ctx->dc.max_kps, t, sizeof(svo_index_pair) * n, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ctx->dc.n_tracked + vl, &n, sizeof(int), hipMemcpyHostToDevice));
+    return SVO_OK;
+}
 
 // ---- windows for frames the library did not detect --------------------------------------------------------------------
 // svo_gather_windows (svo_hip.h): the images of put / loaded lists arrive here, the x1/2 octave images are built from them as a detect
@@ -2383,7 +2499,8 @@ extern "C" int svo_change_in_pose(svo_ctx* ctx, const svo_index_pair* tracked, i
     // (the scratch lane's record of the covariance is lane 0's, and its mask goes through lane 0's part of the mask array: svo_wait above)
     if (ctx->pose_cov) g.mask_out = ctx->d_cov_mask;
     { Span sp(ctx, KT_GN); launch_gauss_newton(s, ctx->knobs, g, ctx->stream); }
-    if (ctx->pose_cov) { Span sp(ctx, KT_POSE_COV); launch_pose_covariance(s, ctx->knobs, g, ctx->d_cov, ctx->stream); }
+    // (svo_set_landmarks does not reach this entry point: no records are written here, and this launch consumes the mask itself)
+    if (ctx->pose_cov) { Span sp(ctx, KT_POSE_COV); launch_pose_covariance(s, ctx->knobs, g, ctx->d_cov, true, ctx->stream); }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(res, s.results, sizeof(*res), hipMemcpyDeviceToHost));

@@ -477,6 +477,17 @@ extern "C" int svo_fpstream_set_dyn_fast_threshold(svo_fpstream* f, int enable, 
     return SVO_OK;
 }
 
+extern "C" int svo_fpstream_set_landmarks(svo_fpstream* f, int enable, double std_noise_pixels)
+{
+    if (!f) return SVO_ERR_ARG;
+    if (!(std_noise_pixels >= 0.0 && std_noise_pixels <= 1.7976931348623157e308)) { f->last_error = "std_noise_pixels: a finite value >= 0 is expected"; return SVO_ERR_ARG; }
+    if (enable) {
+        f->last_error = "the landmarks are not available frame-parallel: a frame's records live in the context that optimised it, and the hand-over records do not carry them";
+        return SVO_ERR_UNSUPPORTED;
+    }
+    return SVO_OK;
+}
+
 extern "C" int svo_fpstream_set_camera(svo_fpstream* f, int lane, const svo_stereo_camera* cam)
 {
     if (!f || !cam) return SVO_ERR_ARG;

@@ -163,3 +163,20 @@ extern "C" int svo_dyn_fast_load_ini(const char* path, const char* detect_sectio
     }
     return SVO_OK;
 }
+
+// TLeastSquaresParams::std_noise_pixels (H:628, read_double; defaults to 1): the reference reads and prints it and uses it nowhere;
+// here it scales the landmarks' covariances.  Follow it with svo_set_landmarks.  *std_noise_pixels keeps its value when the section
+// or the key is absent; a negative or non-finite value in the file is SVO_ERR_ARG and the value stays (svo_set_landmarks would refuse it).
+extern "C" int svo_landmarks_load_ini(const char* path, const char* least_squares_section, double* std_noise_pixels)
+{
+    if (!path || !std_noise_pixels) return SVO_ERR_ARG;
+    Ini ini;
+    if (!parse_ini(path, ini)) return SVO_ERR_ARG;
+    if (least_squares_section && least_squares_section[0]) {
+        Reader r{ ini, lower(least_squares_section) };
+        const double v = r.read_double("std_noise_pixels", *std_noise_pixels);
+        if (!(v >= 0.0 && v <= 1.7976931348623157e308)) return SVO_ERR_ARG;
+        *std_noise_pixels = v;
+    }
+    return SVO_OK;
+}

@@ -13,7 +13,7 @@ struct GNParams {
     int pad;
     double kernel_param, min_mod_out_vector, residual_threshold;
     double init[6];
-    uint8_t* mask_out;                   // nullptr, or the array k_gauss_newton leaves its final mask in for k_pose_covariance (gn_mask_bytes_per_lane each)
+    uint8_t* mask_out;                   // nullptr, or the array k_gauss_newton leaves its final mask in for k_pose_covariance and k_landmarks (gn_mask_bytes_per_lane each)
 };
 
 // Which kernel forms are the PRODUCT and which are kept as A/B anchors only.  Every form below is compiled and run
@@ -102,4 +102,14 @@ void launch_project_points(const float* uvu, int n, const svo_stereo_camera& cam
 void launch_gauss_newton(const DevCtx& c, const Knobs& k, const GNParams& P, hipStream_t st);
 // svo_set_pose_covariance: P as handed to launch_gauss_newton just before (mask_out set), out = one record per lane
 size_t gn_mask_bytes_per_lane(int pmax);
-void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, hipStream_t st);
+// consume: the launch is the last reader of the mask record and clears its ended_valid (false when launch_landmarks follows)
+void launch_pose_covariance(const DevCtx& c, const Knobs& k, const GNParams& P, svo_pose_cov* out, bool consume, hipStream_t st);
+// svo_set_landmarks: P as handed to launch_gauss_newton just before (mask_out set).  rec = [n_lanes][max_kps] records, info = one per
+// lane, cnt = [n_lanes][4] ints that are zero between launches (the blocks of a lane add their counts and take a ticket there),
+// cov = the records launch_pose_covariance has just written, or nullptr while svo_set_pose_covariance is off
+struct LmkArgs {
+    svo_landmark* rec; svo_landmarks_info* info; int* cnt; const svo_pose_cov* cov;
+    double std_px, var_px;               // std_noise_pixels and its square
+    int ids_on, pad;                     // svo_params.vo_use_matches_ids
+};
+void launch_landmarks(const DevCtx& c, const GNParams& P, const LmkArgs& A, hipStream_t st);

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import (CameraModel, FasterStats, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
+from .abi import (CameraModel, FasterStats, Landmark, LandmarksInfo, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -27,9 +27,10 @@ EXPORTS = [
     "svo_set_stream", "svo_get_stream", "svo_get_device", "svo_set_camera", "svo_set_rectify_map",
     "svo_stereo_rectify", "svo_set_undistort_rectify", "svo_set_stereo_calibration", "svo_debug_get_rectify_map", "svo_reset", "svo_process", "svo_process_lanes", "svo_wait", "svo_get_result", "svo_get_results", "svo_copy_results_async",
     "svo_set_pose_covariance", "svo_get_pose_covariance", "svo_get_pose_covariances", "svo_copy_pose_covariances_async", "svo_pose_cov_size",
+    "svo_set_landmarks", "svo_get_landmarks_enabled", "svo_landmarks_load_ini", "svo_get_landmarks_info", "svo_get_landmarks", "svo_copy_landmarks_async", "svo_landmark_abi_size",
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
-    "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
+    "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_tracked_oct", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -44,7 +45,7 @@ BATCH_EXPORTS = [
     "svo_batch_wait_on_stream", "svo_batch_hold_for_event", "svo_batch_synchronize", "svo_batch_results", "svo_batch_reset",
     "svo_batch_set_pose_covariance", "svo_batch_pose_covariances", "svo_fpstream_set_pose_covariance",
     "svo_batch_set_dyn_fast_threshold", "svo_batch_faster_stats", "svo_fpstream_set_dyn_fast_threshold",
-    "svo_batch_set_faster_adaptive_nms", "svo_fpstream_set_faster_adaptive_nms",
+    "svo_batch_set_faster_adaptive_nms", "svo_fpstream_set_faster_adaptive_nms", "svo_fpstream_set_landmarks",
     "svo_fpstream_create", "svo_fpstream_destroy", "svo_fpstream_last_error", "svo_fpstream_contexts", "svo_fpstream_context",
     "svo_fpstream_last_owner", "svo_fpstream_set_params", "svo_fpstream_set_camera", "svo_fpstream_set_klt_win", "svo_fpstream_push", "svo_fpstream_synchronize",
 ]
@@ -120,6 +121,15 @@ def lib():
             L.svo_adaptive_nms.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
             L.svo_batch_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
             L.svo_fpstream_set_faster_adaptive_nms.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "svo_set_landmarks"):          # (as above: absent from a library of an earlier commit)
+            L.svo_set_landmarks.argtypes = [C.c_void_p, C.c_int, C.c_double]
+            L.svo_get_landmarks_enabled.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+            L.svo_landmarks_load_ini.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double)]
+            L.svo_get_landmarks_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            L.svo_get_landmarks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            L.svo_copy_landmarks_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+            L.svo_landmark_abi_size.restype = C.c_size_t; L.svo_landmark_abi_size.argtypes = []
+            L.svo_fpstream_set_landmarks.argtypes = [C.c_void_p, C.c_int, C.c_double]
         if hasattr(L, "svo_stereo_rectify"):          # (as above: absent from a library of an earlier commit)
             L.svo_stereo_rectify.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
             L.svo_set_undistort_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -167,6 +177,16 @@ def load_dyn_fast_ini(path, detect_section, target=10. / 1000.) -> float:
     rc = lib().svo_dyn_fast_load_ini(str(path).encode(), detect_section.encode() if detect_section else None, C.byref(v))
     if rc != 0:
         raise SvoError("svo_dyn_fast_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
+    return float(v.value)
+
+
+def load_landmarks_ini(path, least_squares_section, std_noise_pixels=1.0) -> float:
+    """TLeastSquaresParams::std_noise_pixels from the LEAST_SQUARES section of the reference's INI file; `std_noise_pixels` when the
+    section or key is absent; SvoError when the file holds a negative or non-finite value"""
+    v = C.c_double(float(std_noise_pixels))
+    rc = lib().svo_landmarks_load_ini(str(path).encode(), least_squares_section.encode() if least_squares_section else None, C.byref(v))
+    if rc != 0:
+        raise SvoError("svo_landmarks_load_ini(%s): %s" % (path, lib().svo_strerror(rc).decode()))
     return float(v.value)
 
 
@@ -566,6 +586,35 @@ class Context:
     def copy_pose_covariances_async(self, dst_ptr, nbytes):
         self._ck(self.L.svo_copy_pose_covariances_async(self.h, C.c_void_p(dst_ptr), C.c_size_t(nbytes)), "svo_copy_pose_covariances_async")
 
+    def set_landmarks(self, enable=True, std_noise_pixels=0.0):
+        """svo_set_landmarks: from now on every stage 5 leaves one Landmark record per tracked pairing of every active lane
+        (std_noise_pixels 0: the reference's default of 1)"""
+        self._ck(self.L.svo_set_landmarks(self.h, 1 if enable else 0, float(std_noise_pixels)), "svo_set_landmarks")
+
+    def landmarks_enabled(self):
+        """(enabled, std_noise_pixels in force)"""
+        e, s = C.c_int(0), C.c_double(0)
+        self._ck(self.L.svo_get_landmarks_enabled(self.h, C.byref(e), C.byref(s)), "svo_get_landmarks_enabled")
+        return bool(e.value), float(s.value)
+
+    def landmarks_info(self, lane=0) -> LandmarksInfo:
+        info = LandmarksInfo()
+        self._ck(self.L.svo_get_landmarks_info(self.h, lane, C.byref(info)), "svo_get_landmarks_info")
+        return info
+
+    def landmarks(self, lane=0):
+        """(LandmarksInfo, the lane's records as a numpy array of abi.Landmark) of the last stage 5 (waits)"""
+        info = self.landmarks_info(lane)
+        rec = np.zeros(max(0, info.n), Landmark)
+        if len(rec):
+            n = self._ck(self.L.svo_get_landmarks(self.h, lane, _vp(rec), len(rec)), "svo_get_landmarks")
+            assert n == len(rec), (n, len(rec))
+        return info, rec
+
+    def copy_landmarks_async(self, dst_info_ptr, dst_records_ptr, nbytes):
+        """svo_copy_landmarks_async: n_lanes infos and n_lanes x max_kps records into device memory, on the context's stream"""
+        self._ck(self.L.svo_copy_landmarks_async(self.h, C.c_void_p(dst_info_ptr), C.c_void_p(dst_records_ptr), C.c_size_t(nbytes)), "svo_copy_landmarks_async")
+
     def copy_results_async(self, dst_ptr, nbytes):
         self._ck(self.L.svo_copy_results_async(self.h, C.c_void_p(dst_ptr), C.c_size_t(nbytes)), "svo_copy_results_async")
 
@@ -695,9 +744,11 @@ class Context:
         ids = np.ascontiguousarray(ids, np.int32)
         self._ck(self.L.svo_put_match_ids_oct(self.h, lane, which, octave, _vp(ids), len(ids)), "svo_put_match_ids_oct")
 
-    def put_tracked(self, lane, t):
+    def put_tracked(self, lane, t, octave=None):
+        """octave None: svo_put_tracked (octave 0, the lane's other octaves emptied); else svo_put_tracked_oct (that octave alone)"""
         t = np.ascontiguousarray(t)
-        self._ck(self.L.svo_put_tracked(self.h, lane, _vp(t), len(t)), "svo_put_tracked")
+        if octave is None: self._ck(self.L.svo_put_tracked(self.h, lane, _vp(t), len(t)), "svo_put_tracked")
+        else: self._ck(self.L.svo_put_tracked_oct(self.h, lane, int(octave), _vp(t), len(t)), "svo_put_tracked_oct")
 
     def change_in_pose(self, tracked, pre_m, cur_m, pre_l, pre_r, cur_l, cur_r, cam, init6=None):
         n = len(tracked)

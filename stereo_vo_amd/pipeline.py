@@ -252,6 +252,10 @@ class FrameParallelStream:
         """refused when enable is set (svo_fpstream_set_dyn_fast_threshold): frame t's detection would need frame t - 1's corner count"""
         self._ck(self.L.svo_fpstream_set_dyn_fast_threshold(self.h, 1 if enable else 0, float(target)), "svo_fpstream_set_dyn_fast_threshold")
 
+    def set_landmarks(self, enable=True, std_noise_pixels=0.0):
+        """refused when enable is set (svo_fpstream_set_landmarks): a frame's records live in the context that optimised it"""
+        self._ck(self.L.svo_fpstream_set_landmarks(self.h, 1 if enable else 0, float(std_noise_pixels)), "svo_fpstream_set_landmarks")
+
     def set_faster_adaptive_nms(self, enable=True):
         """svo_fpstream_set_faster_adaptive_nms: the opt-in to the adaptive NMS under dmFASTER on every context"""
         self._ck(self.L.svo_fpstream_set_faster_adaptive_nms(self.h, 1 if enable else 0), "svo_fpstream_set_faster_adaptive_nms")
