@@ -1,6 +1,8 @@
 """Input lists built by hand for the pairing filters of stage 3 (k_match_lr_filter, k_match_lr_rbr<false>, lr_row_index) and the front end
 of stage 4 (k_track_filter<16|32|64>, k_track_win<false>), with k_hamming_f4 underneath (numpy only: no GPU, and the oracle is imported
-by the functions that need it).  In the style of tests/ransac_scenes.py, whose _kps / put_scene / run_case / check_case / oracle_track /
+by the functions that need it).  k_hamming_f4 is only "underneath" here -- planted matches are unique and far from every other candidate, and
+the pairing lists are identities --: its own edges (ties, tile / block / split boundaries, distances up to 256, indices past 8192, the gather
+through the pairing lists) live in tests/ham_scenes.py.  In the style of tests/ransac_scenes.py, whose _kps / put_scene / run_case / check_case / oracle_track /
 pairings_row_index are reused.
 
 Descriptors are made on purpose: every TARGET descriptor is random (redrawn until any two targets are 96 .. 160 bits apart), a QUERY is a
