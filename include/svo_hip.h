@@ -581,6 +581,44 @@ int svo_hamming_match(svo_ctx* ctx, const uint8_t* query, int nq, const uint8_t*
 int svo_adaptive_nms(svo_ctx* ctx, const svo_keypoint* kps, int n, int num_out_points, int img_w, int img_h,
                      int32_t* out_order, int cap);
 
+/* Pyramidal Lucas-Kanade tracking on caller lists, batched over many image pairs: the capability under the reference's ifmOpticalFlow
+ * (stage4_match_consecutive.cpp:333-431), offered like svo_hamming_match as a primitive -- SVO_IFM_OPTICAL_FLOW and SVO_DM_KLT stay
+ * SVO_ERR_UNSUPPORTED in svo_process.  Each job follows n points of `prev` into `next` with sub-pixel accuracy; nothing is detected or
+ * described in `next`.  The arithmetic is THIS PROJECT'S (tests/lk_ref.py is its definition and the device equals it bit for bit:
+ * fixed-point bilinear samples, integer Scharr derivatives, exact integer sums, one stated order for the double 2 x 2 solve).  It follows
+ * Bouguet's algorithm with the constants cv::calcOpticalFlowPyrLK documents, but equality with OpenCV is NOT claimed.
+ *   prev, next   8-bit grey images of the same w, h (strides may differ): host pointers, page-locked host pointers
+ *                (SVO_FLAG_PINNED_IMAGES) or device pointers read in place under the read contract of svo_image.stride
+ *                (SVO_FLAG_DEVICE_IMAGES, h * stride <= 2^31 - 1).  Any other flag bit is SVO_ERR_ARG.
+ *   pts, init    host arrays of n x 2 floats (x, y); init (may be NULL) is the first guess of each point in `next`, pts otherwise
+ *   next_pts     n x 2 floats: where each point ended (for a lost point: the guess it had when it was lost)
+ *   status       n bytes: 1 tracked, 0 lost (window outside the image at level 0, too little texture, a NaN or infinite coordinate, or
+ *                the forward-backward check)
+ *   err          NULL or n floats: mean |difference| of the window in grey levels; 0 for a point the forward pass lost
+ * Limits, refused up front with SVO_ERR_CAPACITY and the numbers in svo_last_error: n <= max_kps per job, n_jobs <= 4 * n_lanes *
+ * max_octaves, images within max_w x max_h.  SVO_ERR_ARG with a text: NULL pointers, win / max_level / max_iters outside their ranges,
+ * negative n or n_jobs, prev and next of different sizes, a stride smaller than a row, a device image that spans more than 2^31 - 1
+ * bytes.  Every refusal happens before anything is enqueued and leaves the outputs untouched.  n = 0 jobs (their images are still
+ * checked, and their pyramids built) and n_jobs = 0 are SVO_OK.
+ * The call synchronises.  It touches no lane state and none of the detector's scratch: its pyramids and point lists are buffers of their
+ * own, allocated by the first call, grown on demand and freed with the context.  It needs no svo_set_params and never runs inside a
+ * captured graph.  p == NULL: the defaults. */
+typedef struct svo_lk_job {
+    svo_image prev, next;
+    const float* pts;
+    const float* init;
+    int32_t n;
+    float* next_pts;
+    uint8_t* status;
+    float* err;
+} svo_lk_job;
+void svo_lk_default_params(svo_lk_params* p);
+int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* p, uint32_t flags);
+/* one pyramid level of the last svo_lk_track call: job, which = 0 prev / 1 next, level 0 = the image as the tracker read it.  Returns
+ * w * h (with out == NULL: the size only); 0 when the call built no such level (or no call was made); SVO_ERR_CAPACITY when cap < w * h.
+ * Level 0 of a device image is read from the caller's memory, which must still hold it. */
+int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -606,7 +644,8 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * THE NUMBER RETURNED DEPENDS ON THE CONTEXT'S STATE in one respect: the last two names are listed only on request -- "pose_covariance"
  * while svo_set_pose_covariance is on, and "landmarks" behind it while svo_set_landmarks is on (then with "pose_covariance" before it
  * whatever that switch says) --, so a context that has both off returns the list (and the count) it always did.  Size arrays by the
- * value of the same call, or for the largest list (cap 64 always suffices). */
+ * value of the same call, or for the largest list (cap 64 always suffices).
+ * "lk_pyrdown" and "lk_track" are appended behind whatever that rule lists, once the context has made a svo_lk_track call. */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

@@ -257,6 +257,21 @@ typedef struct svo_stereo_rectification {
     svo_stereo_camera cam;
 } svo_stereo_rectification;
 
+/* The parameters of svo_lk_track (svo_hip.h), the pyramidal Lucas-Kanade tracker on caller lists.  svo_lk_default_params fills in the
+ * defaults; the allowed ranges are checked by every call (SVO_ERR_ARG with a text).
+ *   win         side of the square window in pixels: odd, 5 .. 31 (default 21)
+ *   max_level   deepest pyramid level, 0 .. 5 (default 3); the pyramid of an image stops earlier, at the last level whose sides are
+ *               both at least win + 4
+ *   max_iters   iterations per level, 1 .. 100 (default 30)
+ *   eps         an iteration whose step is at most this long (pixels) ends the level (default 0.01)
+ *   min_eig     a window whose gradient matrix has a smaller minimum eigenvalue, per pixel, is not tracked at that level (default 1e-4)
+ *   fb_max      > 0: track the results back into the first image and drop the points whose round trip ends farther than this many
+ *               pixels from where they started (or is lost on the way); 0 (default): no such pass */
+typedef struct svo_lk_params {
+    int32_t win, max_level, max_iters;
+    float eps, min_eig, fb_max;
+} svo_lk_params;
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,26 @@ class StereoRectification(C.Structure):
 
 assert C.sizeof(CameraModel) == 96 and C.sizeof(StereoCalibration) == 312 and C.sizeof(StereoRectification) == 296
 
+class LkParams(C.Structure):
+    """svo_lk_params (include/svo_types.h): window side (odd, 5 .. 31), deepest level (0 .. 5), iterations per level (1 .. 100), the step
+    that ends a level, the minimum eigenvalue per pixel, and the forward-backward limit in pixels (0: no such pass)"""
+    _fields_ = [("win", C.c_int32), ("max_level", C.c_int32), ("max_iters", C.c_int32),
+                ("eps", C.c_float), ("min_eig", C.c_float), ("fb_max", C.c_float)]
+
+
+class LkImage(C.Structure):
+    """svo_image (include/svo_hip.h) as svo_lk_job holds it"""
+    _fields_ = [("data", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int64)]
+
+
+class LkJob(C.Structure):
+    """svo_lk_job (include/svo_hip.h): one image pair with its points (host arrays) and the arrays the results go to"""
+    _fields_ = [("prev", LkImage), ("next", LkImage), ("pts", C.c_void_p), ("init", C.c_void_p), ("n", C.c_int32),
+                ("next_pts", C.c_void_p), ("status", C.c_void_p), ("err", C.c_void_p)]
+
+
+assert C.sizeof(LkParams) == 24 and C.sizeof(LkJob) == 96
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

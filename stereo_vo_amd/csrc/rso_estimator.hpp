@@ -288,6 +288,29 @@ public:
         check(svo_set_stereo_calibration(m_ctx, 0, &calib, 0, &out), "svo_set_stereo_calibration");
         return out;
     }
+    /** Pyramidal Lucas-Kanade tracking of one image pair (svo_lk_track): the capability under the reference's ifmOpticalFlow branch
+     *  (S4:333-431), offered on caller lists -- ifm_method = ifmOpticalFlow itself stays unsupported.  Follows `points` of `prev` into
+     *  `next` (8-bit grey host images of one size; stride in bytes, 0 = w); next_points starts from `initial` when that has one entry
+     *  per point.  status[i] = 1 where the point was tracked; err[i]: mean |difference| of its window in grey levels.  The results are
+     *  this library's definition of the algorithm, not cv::calcOpticalFlowPyrLK's. */
+    void trackOpticalFlow(const uint8_t* prev, const uint8_t* next, int w, int h, const std::vector<TPixelCoordf>& points,
+                          std::vector<TPixelCoordf>& next_points, std::vector<uint8_t>& status, std::vector<float>& err,
+                          const svo_lk_params* lk_params = NULL, const std::vector<TPixelCoordf>& initial = std::vector<TPixelCoordf>(),
+                          long long prev_stride = 0, long long next_stride = 0) {
+        const size_t n = points.size();
+        std::vector<float> pts(2 * n), init, out(2 * n);
+        for (size_t i = 0; i < n; i++) { pts[2 * i] = points[i].x; pts[2 * i + 1] = points[i].y; }
+        if (n && initial.size() == n) { init.resize(2 * n); for (size_t i = 0; i < n; i++) { init[2 * i] = initial[i].x; init[2 * i + 1] = initial[i].y; } }
+        status.assign(n, 0); err.assign(n, 0.0f);
+        svo_lk_job job;
+        job.prev.data = prev; job.prev.w = w; job.prev.h = h; job.prev.stride = prev_stride ? prev_stride : w;
+        job.next.data = next; job.next.w = w; job.next.h = h; job.next.stride = next_stride ? next_stride : w;
+        job.pts = n ? pts.data() : NULL; job.init = init.empty() ? NULL : init.data(); job.n = (int32_t)n;
+        job.next_pts = n ? out.data() : NULL; job.status = n ? status.data() : NULL; job.err = n ? err.data() : NULL;
+        check(svo_lk_track(m_ctx, &job, 1, lk_params, 0), "svo_lk_track");
+        next_points.resize(n);
+        for (size_t i = 0; i < n; i++) next_points[i] = TPixelCoordf(out[2 * i], out[2 * i + 1]);
+    }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

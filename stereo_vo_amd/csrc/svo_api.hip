@@ -7,6 +7,7 @@
 #include "svo_kernels.h"
 #include "state_format.hpp"
 #include "frame_call.hpp"
+#include "lk_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -32,16 +33,19 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // svo_gather_windows: the slot-selecting window gather (only a caller of that entry point counts a call here)
        KT_GATHER_WIN,
        // svo_set_pose_covariance (only a context that enables it counts a call here)
-       KT_POSE_COV,      // keep these two last, in this order: svo_kernel_times lists each only while its feature is on (kt_listed)
+       KT_POSE_COV,      // keep these two in this order, behind every name a context always lists: svo_kernel_times lists each only while its feature is on
        // svo_set_landmarks (only a context that enables it counts a call here)
        KT_LANDMARKS,
+       // svo_lk_track: listed behind all of the above, and only once the context has made such a call (svo_kernel_times)
+       KT_LK_PYRDOWN, KT_LK_TRACK,
        KT_COUNT };
 static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
     "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
-    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks" };
+    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks",
+    "lk_pyrdown", "lk_track" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -104,6 +108,12 @@ struct svo_ctx {
     std::vector<TimedSpan> spans; std::vector<hipEvent_t> free_events;
     double kt_total[KT_COUNT]; long long kt_calls[KT_COUNT]; unsigned long long kt_mask;
     unsigned* d_ham_out; uint8_t* d_ham_q, *d_ham_t; int ham_cap_q, ham_cap_t;
+    // svo_lk_track: buffers of its own, made by its first call, grown on demand, freed with the context -- the pyramids of the call's
+    // images, the job records, the flat point arrays (pts, init, out: float2; status; err).  lk_jobs: the records of the last call, for
+    // svo_debug_lk_get_level.  lk_used: the context has made such a call (svo_kernel_times then lists its two names)
+    uint8_t* d_lk_pyr; size_t lk_pyr_cap; LkJobDev* d_lk_jobs; int lk_jobs_cap;
+    float2* d_lk_pts, *d_lk_init, *d_lk_out; uint8_t* d_lk_status; float* d_lk_err; int lk_pts_cap;
+    std::vector<LkJobDev> lk_jobs; bool lk_used;
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
     uint2** d_map_ptrs; std::vector<uint2*> map_ptrs;  // per image: fixed-point map on the device or nullptr
@@ -395,6 +405,8 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
+    ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0; ctx->lk_used = false;
+    ctx->d_lk_pts = ctx->d_lk_init = ctx->d_lk_out = nullptr; ctx->d_lk_status = nullptr; ctx->d_lk_err = nullptr;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -520,6 +532,7 @@ extern "C" void svo_destroy(svo_ctx* ctx)
     if (ctx->d_ham_out) hipFree(ctx->d_ham_out);
     if (ctx->d_ham_q) hipFree(ctx->d_ham_q);
     if (ctx->d_ham_t) hipFree(ctx->d_ham_t);
+    for (void* p : { (void*)ctx->d_lk_pyr, (void*)ctx->d_lk_jobs, (void*)ctx->d_lk_pts, (void*)ctx->d_lk_init, (void*)ctx->d_lk_out, (void*)ctx->d_lk_status, (void*)ctx->d_lk_err }) if (p) hipFree(p);
     if (ctx->up_ready) {
         hipStreamSynchronize(ctx->s_copy);
         for (int i = 0; i < 2; i++) { hipEventDestroy(ctx->ev_h2d[i]); hipEventDestroy(ctx->ev_det[i]); if (ctx->h_stage[i]) hipHostFree(ctx->h_stage[i]); }
@@ -1233,8 +1246,11 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     int rc = svo_wait(ctx); if (rc) return rc;
     // "pose_covariance" is listed while svo_set_pose_covariance is on, and "landmarks" (behind it, then with "pose_covariance" whatever its
     // switch) while svo_set_landmarks is on: a context that has both off reports the list it always did
-    const int n = ctx->landmarks ? KT_COUNT : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
+    int n = ctx->landmarks ? KT_LANDMARKS + 1 : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
     for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
+    // "lk_pyrdown" and "lk_track" behind whatever was listed, once the context has made a svo_lk_track call
+    for (int k = KT_LK_PYRDOWN; ctx->lk_used && k <= KT_LK_TRACK; k++, n++)
+        if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
     return n;
 }
 extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
@@ -2544,6 +2560,119 @@ extern "C" int svo_hamming_match(svo_ctx* ctx, const uint8_t* query, int nq, con
     HIPCHECK(hipStreamSynchronize(st));
     for (int i = 0; i < nq; i++) { idx[i] = (int)(out[i] & 0xFFFFu); dist[i] = (int)(out[i] >> 16); }
     return SVO_OK;
+}
+
+// ---- pyramidal Lucas-Kanade tracking on caller lists (svo_hip.h; the decisions: lk_call.hpp, the kernels: k_lk.hip) ---------------
+template <typename T>
+static hipError_t lk_realloc(T** p, size_t n)
+{
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    return hipMalloc((void**)p, n * sizeof(T));
+}
+
+extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_lk_params p;
+    if (params) p = *params; else svo_lk_default_params(&p);
+    const svo_lk::Caps caps{ ctx->dc.max_kps, 4 * ctx->cfg.n_lanes * ctx->dc.oct_cap, ctx->cfg.max_w, ctx->cfg.max_h };
+    { std::string why; const int rc = svo_lk::check_lk_call(jobs, n_jobs, p, flags, caps, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (n_jobs == 0) return SVO_OK;
+    const bool dev = (flags & SVO_FLAG_DEVICE_IMAGES) != 0;
+    const svo_lk::Plan plan = svo_lk::plan_lk_call(jobs, n_jobs, p, dev);
+    const size_t NP = (size_t)plan.n_pts;
+    // the buffers: a failed growth leaves the capacity at 0, so that the next call allocates afresh
+    ctx->lk_jobs.clear();
+    if ((size_t)plan.pyr_bytes > ctx->lk_pyr_cap) { ctx->lk_pyr_cap = 0; HIPCHECK(lk_realloc(&ctx->d_lk_pyr, (size_t)plan.pyr_bytes)); ctx->lk_pyr_cap = (size_t)plan.pyr_bytes; }
+    if (n_jobs > ctx->lk_jobs_cap) { ctx->lk_jobs_cap = 0; HIPCHECK(lk_realloc(&ctx->d_lk_jobs, (size_t)n_jobs)); ctx->lk_jobs_cap = n_jobs; }
+    if (plan.n_pts > ctx->lk_pts_cap) {
+        ctx->lk_pts_cap = 0;
+        HIPCHECK(lk_realloc(&ctx->d_lk_pts, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_init, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_out, NP));
+        HIPCHECK(lk_realloc(&ctx->d_lk_status, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_err, NP));
+        ctx->lk_pts_cap = plan.n_pts;
+    }
+    ctx->lk_used = true;
+    const hipStream_t st = ctx->stream;
+    // the job records; host images go to level 0 of their block, device images are read where they are
+    std::vector<LkJobDev> recs((size_t)n_jobs);
+    int lw[svo_lk::LK_MAX_LEVELS] = { 0 }, lh[svo_lk::LK_MAX_LEVELS] = { 0 };
+    for (int j = 0; j < n_jobs; j++) {
+        const svo_lk::Geometry& g = plan.geom[(size_t)j];
+        LkJobDev& r = recs[(size_t)j];
+        memset(&r, 0, sizeof(r));
+        r.nl = g.nl; r.pt0 = plan.pt0[(size_t)j]; r.n = jobs[j].n; r.has_init = (jobs[j].n > 0 && jobs[j].init) ? 1 : 0;
+        for (int l = 0; l < g.nl; l++) { r.w[l] = g.w[l]; r.h[l] = g.h[l]; if (g.w[l] > lw[l]) lw[l] = g.w[l]; if (g.h[l] > lh[l]) lh[l] = g.h[l]; }
+        for (int s = 0; s < 2; s++) {
+            const svo_image& im = s ? jobs[j].next : jobs[j].prev;
+            uint8_t* block = ctx->d_lk_pyr + plan.img_off[(size_t)(2 * j + s)];
+            for (int l = 1; l < g.nl; l++) { r.img[s][l] = block + g.off[l]; r.pitch[s][l] = g.w[l]; }
+            if (dev) { r.img[s][0] = im.data; r.pitch[s][0] = (int)im.stride; }
+            else {
+                r.img[s][0] = block; r.pitch[s][0] = g.w[0];
+                HIPCHECK(hipMemcpy2DAsync(block, (size_t)g.w[0], im.data, (size_t)im.stride, (size_t)g.w[0], (size_t)g.h[0], hipMemcpyHostToDevice, st));
+            }
+        }
+    }
+    HIPCHECK(hipMemcpyAsync(ctx->d_lk_jobs, recs.data(), sizeof(LkJobDev) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
+    std::vector<float> h_pts(2 * NP), h_init(plan.any_init ? 2 * NP : 0);
+    for (int j = 0; j < n_jobs; j++) {
+        if (jobs[j].n <= 0) continue;
+        const size_t o = 2 * (size_t)plan.pt0[(size_t)j], nb = sizeof(float) * 2 * (size_t)jobs[j].n;
+        memcpy(h_pts.data() + o, jobs[j].pts, nb);
+        if (jobs[j].init) memcpy(h_init.data() + o, jobs[j].init, nb);
+    }
+    if (NP) HIPCHECK(hipMemcpyAsync(ctx->d_lk_pts, h_pts.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
+    if (NP && plan.any_init) HIPCHECK(hipMemcpyAsync(ctx->d_lk_init, h_init.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
+    { Span s(ctx, KT_LK_PYRDOWN); for (int l = 1; l < plan.max_nl; l++) launch_lk_pyrdown(ctx->d_lk_jobs, n_jobs, l, lw[l], lh[l], st); }
+    LkTrackArgs a;
+    a.jobs = ctx->d_lk_jobs; a.n_jobs = n_jobs; a.n_pts = plan.n_pts;
+    a.pts = ctx->d_lk_pts; a.aux = ctx->d_lk_init;
+    a.out = ctx->d_lk_out; a.status = ctx->d_lk_status; a.err = ctx->d_lk_err;
+    a.p = p; a.backward = 0;
+    {
+        Span s(ctx, KT_LK_TRACK);
+        const int ppl = svo_lk::lk_pixels_per_lane(p.win);
+        launch_lk_track(a, ppl, st);
+        if (p.fb_max > 0.0f) {                               // the same kernel with the image roles swapped, from the results back
+            LkTrackArgs b = a;
+            b.pts = ctx->d_lk_out; b.aux = ctx->d_lk_pts; b.out = nullptr; b.err = nullptr; b.backward = 1;
+            launch_lk_track(b, ppl, st);
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    std::vector<float> h_out(2 * NP), h_err(NP);
+    std::vector<uint8_t> h_status(NP);
+    if (NP) {
+        HIPCHECK(hipMemcpyAsync(h_out.data(), ctx->d_lk_out, sizeof(float) * 2 * NP, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(h_status.data(), ctx->d_lk_status, NP, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(h_err.data(), ctx->d_lk_err, sizeof(float) * NP, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHECK(hipStreamSynchronize(st));
+    ctx->lk_jobs = recs;
+    for (int j = 0; j < n_jobs; j++) {
+        if (jobs[j].n <= 0) continue;
+        const size_t o = (size_t)plan.pt0[(size_t)j], n = (size_t)jobs[j].n;
+        memcpy(jobs[j].next_pts, h_out.data() + 2 * o, sizeof(float) * 2 * n);
+        memcpy(jobs[j].status, h_status.data() + o, n);
+        if (jobs[j].err) memcpy(jobs[j].err, h_err.data() + o, sizeof(float) * n);
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || which < 0 || which > 1 || job < 0 || level < 0) return SVO_ERR_ARG;
+    if ((size_t)job >= ctx->lk_jobs.size() || level >= ctx->lk_jobs[(size_t)job].nl) return 0;
+    int rc = svo_wait(ctx); if (rc) return rc;
+    const LkJobDev& r = ctx->lk_jobs[(size_t)job];
+    if (w) *w = r.w[level]; if (h) *h = r.h[level];
+    if (!out) return r.w[level] * r.h[level];
+    if (cap < r.w[level] * r.h[level]) return SVO_ERR_CAPACITY;
+    HIPCHECK(hipMemcpy2D(out, (size_t)r.w[level], r.img[which][level], (size_t)r.pitch[which][level], (size_t)r.w[level], (size_t)r.h[level], hipMemcpyDeviceToHost));
+    return r.w[level] * r.h[level];
 }
 
 // ---- probes ------------------------------------------------------------------------------------------------

@@ -113,3 +113,21 @@ struct LmkArgs {
     int ids_on, pad;                     // svo_params.vo_use_matches_ids
 };
 void launch_landmarks(const DevCtx& c, const GNParams& P, const LmkArgs& A, hipStream_t st);
+// svo_lk_track (k_lk.hip).  One record per job, in device memory: the levels of its two images (img[0] prev, img[1] next; level 0 is the
+// caller's device image or its copy in the context's pyramid buffer, the others lie in that buffer), the level sizes (lk_call.hpp), the
+// job's first index in the flat point arrays and its point count
+struct LkJobDev {
+    const uint8_t* img[2][6]; int pitch[2][6];
+    int w[6], h[6];
+    int nl, pt0, n, has_init;
+};
+// backward = 0: the forward pass (pts -> out, status, err; aux = the first guesses, read for jobs with has_init).  backward = 1: the
+// forward-backward check with the image roles swapped: pts = the forward results, aux = the points they came from; only status is written
+struct LkTrackArgs {
+    const LkJobDev* jobs; int n_jobs, n_pts;
+    const float2* pts; const float2* aux;
+    float2* out; uint8_t* status; float* err;
+    svo_lk_params p; int backward;
+};
+void launch_lk_pyrdown(const LkJobDev* jobs, int n_jobs, int level, int max_w, int max_h, hipStream_t st);   // max_w x max_h: the largest level `level` of the call
+void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);                             // pixels_per_lane: lk_pixels_per_lane(win)

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import (CameraModel, FasterStats, Landmark, LandmarksInfo, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
+from .abi import (CameraModel, FasterStats, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -31,6 +31,7 @@ EXPORTS = [
     "svo_get_keypoints", "svo_get_matches", "svo_get_tracked", "svo_get_residuals", "svo_get_outliers",
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_tracked_oct", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
+    "svo_lk_default_params", "svo_lk_track", "svo_debug_lk_get_level",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -135,6 +136,10 @@ def lib():
             L.svo_set_undistort_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
             L.svo_set_stereo_calibration.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
             L.svo_debug_get_rectify_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "svo_lk_track"):          # (as above: absent from a library of an earlier commit)
+            L.svo_lk_default_params.restype = None; L.svo_lk_default_params.argtypes = [C.c_void_p]
+            L.svo_lk_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+            L.svo_debug_lk_get_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -206,6 +211,12 @@ def stereo_rectify(calib: StereoCalibration) -> StereoRectification:
         e.status = rc
         raise e
     return out
+
+
+def default_lk_params() -> LkParams:
+    p = LkParams()
+    lib().svo_lk_default_params(C.byref(p))
+    return p
 
 
 def _vp(a):
@@ -771,12 +782,57 @@ class Context:
         self._ck(self.L.svo_hamming_match(self.h, _vp(q), len(q), _vp(t), len(t), _vp(idx), _vp(dist)), "svo_hamming_match")
         return idx[:len(q)], dist[:len(q)]
 
+    # -- pyramidal Lucas-Kanade tracking on caller lists (svo_lk_track) ------------------------------------------
+    def lk_track(self, jobs, params=None, device=False, pinned=False):
+        """jobs: a list of (prev, next, pts[, init]) -- prev / next uint8 [h, w] numpy arrays (any row stride; the last axis must be
+        contiguous), pts / init [n, 2] float32 (x, y).  With device=True prev / next are (device address, w, h, stride) tuples, read in
+        place; pinned=True declares the host arrays page-locked.  params: an LkParams (None: the defaults).  Returns a
+        (next_pts [n, 2] float32, status [n] uint8, err [n] float32) triple per job.  Synchronises."""
+        recs = (LkJob * max(1, len(jobs)))()
+        keep, out = [], []
+        for i, job in enumerate(jobs):
+            prev, nxt, pts = job[0], job[1], np.ascontiguousarray(job[2], np.float32).reshape(-1, 2)
+            init = None if len(job) < 4 or job[3] is None else np.ascontiguousarray(job[3], np.float32).reshape(-1, 2)
+            if init is not None and len(init) != len(pts):
+                raise ValueError("job %d: %d points but %d first guesses" % (i, len(pts), len(init)))
+            for s, im in enumerate((prev, nxt)):
+                if device:
+                    rec = LkImage(int(im[0]), int(im[1]), int(im[2]), int(im[3]))
+                else:
+                    if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                        raise ValueError("job %d: uint8 [h, w] images with contiguous rows are expected" % i)
+                    keep.append(im)
+                    rec = LkImage(im.ctypes.data, im.shape[1], im.shape[0], im.strides[0])
+                if s: recs[i].next = rec
+                else: recs[i].prev = rec
+            n = len(pts)
+            res = (np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.float32))
+            keep += [pts, init]
+            recs[i].pts, recs[i].init, recs[i].n = _vp(pts) if n else None, _vp(init) if (n and init is not None) else None, n
+            recs[i].next_pts, recs[i].status, recs[i].err = (_vp(a) if n else None for a in res)
+            out.append(res)
+        flags = FLAG_DEVICE_IMAGES if device else (FLAG_PINNED_IMAGES if pinned else 0)
+        self._ck(self.L.svo_lk_track(self.h, recs, len(jobs), C.byref(params) if params is not None else None, C.c_uint32(flags)), "svo_lk_track")
+        return out
+
+    def lk_level(self, job, which, level):
+        """pyramid level `level` of image `which` (0 prev, 1 next) of job `job` of the last lk_track call as a uint8 [h, w] array; None
+        when that call built no such level"""
+        w, h = C.c_int(0), C.c_int(0)
+        n = self._ck(self.L.svo_debug_lk_get_level(self.h, int(job), int(which), int(level), None, 0, C.byref(w), C.byref(h)), "svo_debug_lk_get_level")
+        if n == 0:
+            return None
+        out = np.zeros((h.value, w.value), np.uint8)
+        self._ck(self.L.svo_debug_lk_get_level(self.h, int(job), int(which), int(level), _vp(out), n, C.byref(w), C.byref(h)), "svo_debug_lk_get_level")
+        return out
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
     def kernel_times(self, appended=False):
         """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
-        hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows) and are
+        hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
+        "lk_pyrdown", "lk_track": svo_lk_track, listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
