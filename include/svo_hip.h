@@ -619,6 +619,47 @@ int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_
  * Level 0 of a device image is read from the caller's memory, which must still hold it. */
 int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h);
 
+/* Shi-Tomasi corner detection on caller images, batched over many images: the capability under the reference's dmKLT
+ * (stage2_detect.cpp:444-449: cv::goodFeaturesToTrack with quality 0.01, minimum distance 20, block 3), offered like svo_lk_track as a
+ * primitive -- SVO_DM_KLT stays SVO_ERR_UNSUPPORTED in svo_process.  The arithmetic is THIS PROJECT'S (tests/gftt_ref.py is its
+ * definition and the device equals it bit for bit): integer Sobel derivatives and block sums with reflect-101 borders, the smaller
+ * eigenvalue 0.5 * ((a + c) - sqrt((a - c)^2 + 4 b^2)) in double with one operation per operator, rounded to float32; the threshold
+ * float32(quality * the image's largest response); candidates = pixels off the border ring above the threshold and not below any of
+ * their eight neighbours; candidates walked by descending response (ties: raster order) and accepted unless a corner accepted before
+ * (integer dx^2 + dy^2 < min_distance^2) or a seed (the same in float32) is closer than min_distance.  Equality with OpenCV is NOT
+ * claimed.
+ *   img        8-bit grey image with both sides >= 8: a host pointer, a page-locked host pointer (SVO_FLAG_PINNED_IMAGES) or a device
+ *              pointer read in place under the read contract of svo_image.stride (SVO_FLAG_DEVICE_IMAGES, h * stride <= 2^31 - 1).
+ *              Any other flag bit is SVO_ERR_ARG.
+ *   seeds      NULL or n_seeds x 2 floats (x, y), a host array: points the caller already follows.  New corners keep min_distance from
+ *              them; they are never output.  A seed that is not finite or lies outside [0, w) x [0, h) is ignored.
+ *   cap        room in pts / response (may be 0)
+ *   pts        cap x 2 floats: the corners (x, y) in walk order; response (NULL or cap floats): their responses
+ *   info       3 ints: corners written = min(accepted, cap, max_corners if > 0); the number of candidates before the distance rule;
+ *              status: 0, or 1 when the job had more candidates than max(1024, svo_config.max_cand) -- then no corner is written,
+ *              the count is still the true one and the other jobs of the call are unaffected.
+ * Limits, refused up front with SVO_ERR_CAPACITY and the numbers in svo_last_error: cap, n_seeds, max_corners <= max_kps, n_jobs <=
+ * 4 * n_lanes * max_octaves, images within max_w x max_h, and a response-map buffer (4 bytes per pixel of the call) that cannot be
+ * allocated; a context whose max_cand exceeds 2^24 is refused too.  SVO_ERR_ARG with a text: NULL pointers, parameters outside their ranges (svo_types.h), negative counts, a side below 8,
+ * a stride smaller than a row, a device image that spans more than 2^31 - 1 bytes.  Every refusal happens before anything is enqueued
+ * and leaves the outputs untouched.  n_jobs = 0 is SVO_OK.
+ * The call synchronises.  It touches no lane state and none of the detector's scratch: its buffers are its own, allocated by the first
+ * call, grown on demand and freed with the context.  It needs no svo_set_params and never runs inside a captured graph.  p == NULL: the
+ * defaults. */
+typedef struct svo_gftt_job {
+    svo_image img;
+    const float* seeds;
+    int32_t n_seeds, cap;
+    float* pts;
+    float* response;
+    int32_t* info;
+} svo_gftt_job;
+void svo_gftt_default_params(svo_gftt_params* p);
+int svo_gftt_detect(svo_ctx* ctx, const svo_gftt_job* jobs, int n_jobs, const svo_gftt_params* p, uint32_t flags);
+/* the response map of one job of the last svo_gftt_detect call, w * h floats in raster order.  Returns w * h (with out == NULL: the size
+ * only); 0 when the last call had no such job (or no call was made); SVO_ERR_CAPACITY when cap < w * h. */
+int svo_debug_gftt_get_response(svo_ctx* ctx, int job, float* out, int cap, int* w, int* h);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -645,7 +686,8 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * while svo_set_pose_covariance is on, and "landmarks" behind it while svo_set_landmarks is on (then with "pose_covariance" before it
  * whatever that switch says) --, so a context that has both off returns the list (and the count) it always did.  Size arrays by the
  * value of the same call, or for the largest list (cap 64 always suffices).
- * "lk_pyrdown" and "lk_track" are appended behind whatever that rule lists, once the context has made a svo_lk_track call. */
+ * "gftt_response", "gftt_candidates" and "gftt_select" are appended behind whatever that rule lists, once the context has made a
+ * svo_gftt_detect call; "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call. */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

@@ -272,6 +272,17 @@ typedef struct svo_lk_params {
     float eps, min_eig, fb_max;
 } svo_lk_params;
 
+/* The parameters of svo_gftt_detect (svo_hip.h), the Shi-Tomasi corner detector on caller images.  svo_gftt_default_params fills in the
+ * defaults; the allowed ranges are checked by every call (SVO_ERR_ARG with a text).
+ *   max_corners   at most this many corners per job, 0 .. max_kps; 0 (default): as many as the job's `cap` holds
+ *   block         side of the window the structure tensor is summed over: 3 (default), 5 or 7
+ *   min_distance  no two corners, and no corner and seed, closer than this many pixels: 0 .. 255 (default 20; 0: no such rule)
+ *   quality       a corner's response exceeds this fraction of the image's largest: finite, in (0, 1] (default 0.01) */
+typedef struct svo_gftt_params {
+    int32_t max_corners, block, min_distance;
+    float quality;
+} svo_gftt_params;
+
 #ifdef __cplusplus
 }
 #endif

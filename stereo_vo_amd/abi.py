@@ -174,6 +174,22 @@ class LkJob(C.Structure):
 
 assert C.sizeof(LkParams) == 24 and C.sizeof(LkJob) == 96
 
+
+class GfttParams(C.Structure):
+    """svo_gftt_params (include/svo_types.h): the most corners per job (0: as many as cap holds), the block side (3, 5 or 7), the minimum
+    distance in pixels (0 .. 255) and the quality level in (0, 1]"""
+    _fields_ = [("max_corners", C.c_int32), ("block", C.c_int32), ("min_distance", C.c_int32), ("quality", C.c_float)]
+
+
+class GfttJob(C.Structure):
+    """svo_gftt_job (include/svo_hip.h): one image, the seeds new corners keep their distance from (a host array) and the arrays the
+    results go to"""
+    _fields_ = [("img", LkImage), ("seeds", C.c_void_p), ("n_seeds", C.c_int32), ("cap", C.c_int32),
+                ("pts", C.c_void_p), ("response", C.c_void_p), ("info", C.c_void_p)]
+
+
+assert C.sizeof(GfttParams) == 16 and C.sizeof(GfttJob) == 64
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

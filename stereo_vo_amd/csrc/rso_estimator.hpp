@@ -311,6 +311,28 @@ public:
         next_points.resize(n);
         for (size_t i = 0; i < n; i++) next_points[i] = TPixelCoordf(out[2 * i], out[2 * i + 1]);
     }
+    /** Shi-Tomasi corners of one image (svo_gftt_detect): the capability under the reference's dmKLT (S2:444-449), offered on a caller
+     *  image -- detect_method = dmKLT itself stays unsupported.  `corners` receives at most max_corners points (at most the context's
+     *  max_kps) by descending response, none closer than min_distance to another or to one of `seeds` (points already followed: the
+     *  way to top up a thinning track list).  Returns the number of candidates before the distance rule.  The results are this
+     *  library's definition of the algorithm, not cv::goodFeaturesToTrack's. */
+    int detectGoodFeatures(const uint8_t* img, int w, int h, int max_corners, std::vector<TPixelCoordf>& corners, std::vector<float>& response,
+                           const svo_gftt_params* gftt_params = NULL, const std::vector<TPixelCoordf>& seeds = std::vector<TPixelCoordf>(),
+                           long long stride = 0) {
+        const size_t ns = seeds.size();
+        std::vector<float> sd(2 * ns), out(2 * (size_t)(max_corners > 0 ? max_corners : 0));
+        for (size_t i = 0; i < ns; i++) { sd[2 * i] = seeds[i].x; sd[2 * i + 1] = seeds[i].y; }
+        response.assign(out.size() / 2, 0.0f);
+        int32_t info[3] = { 0, 0, 0 };
+        svo_gftt_job job;
+        job.img.data = img; job.img.w = w; job.img.h = h; job.img.stride = stride ? stride : w;
+        job.seeds = ns ? sd.data() : NULL; job.n_seeds = (int32_t)ns; job.cap = (int32_t)(out.size() / 2);
+        job.pts = out.empty() ? NULL : out.data(); job.response = response.empty() ? NULL : response.data(); job.info = info;
+        check(svo_gftt_detect(m_ctx, &job, 1, gftt_params, 0), "svo_gftt_detect");
+        corners.resize((size_t)info[0]); response.resize((size_t)info[0]);
+        for (size_t i = 0; i < corners.size(); i++) corners[i] = TPixelCoordf(out[2 * i], out[2 * i + 1]);
+        return info[1];
+    }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

@@ -8,6 +8,7 @@
 #include "state_format.hpp"
 #include "frame_call.hpp"
 #include "lk_call.hpp"
+#include "gftt_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -37,6 +38,8 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // svo_set_landmarks (only a context that enables it counts a call here)
        KT_LANDMARKS,
        // svo_lk_track: listed behind all of the above, and only once the context has made such a call (svo_kernel_times)
+       // svo_gftt_detect: listed behind the frame's names and before the LK ones, and only once the context has made such a call
+       KT_GFTT_RESPONSE, KT_GFTT_CANDIDATES, KT_GFTT_SELECT,
        KT_LK_PYRDOWN, KT_LK_TRACK,
        KT_COUNT };
 static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
@@ -45,6 +48,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
     "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
     "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks",
+    "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
 
 struct TimedSpan { int id; hipEvent_t a, b; };
@@ -114,6 +118,13 @@ struct svo_ctx {
     uint8_t* d_lk_pyr; size_t lk_pyr_cap; LkJobDev* d_lk_jobs; int lk_jobs_cap;
     float2* d_lk_pts, *d_lk_init, *d_lk_out; uint8_t* d_lk_status; float* d_lk_err; int lk_pts_cap;
     std::vector<LkJobDev> lk_jobs; bool lk_used;
+    // svo_gftt_detect: buffers of its own as well -- the response maps, the copies of host images, the job records, per job the
+    // candidate keys, the cell lists and the decision states, the flat seed and result arrays, four counters per job.  gftt_jobs: the
+    // records of the last call, for svo_debug_gftt_get_response.  gftt_used: the context has made such a call (svo_kernel_times)
+    float* d_gftt_map; size_t gftt_map_cap; uint8_t* d_gftt_img; size_t gftt_img_cap; GfttJobDev* d_gftt_jobs; int gftt_jobs_cap;
+    unsigned long long* d_gftt_keys; int* d_gftt_items; uint8_t* d_gftt_state; int* d_gftt_info;
+    float2* d_gftt_seeds; int gftt_seeds_cap; float2* d_gftt_pts; float* d_gftt_resp; int gftt_pts_cap;
+    std::vector<GfttJobDev> gftt_jobs; bool gftt_used;
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
     uint2** d_map_ptrs; std::vector<uint2*> map_ptrs;  // per image: fixed-point map on the device or nullptr
@@ -407,6 +418,9 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
     ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0; ctx->lk_used = false;
     ctx->d_lk_pts = ctx->d_lk_init = ctx->d_lk_out = nullptr; ctx->d_lk_status = nullptr; ctx->d_lk_err = nullptr;
+    ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
+    ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
+    ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -533,6 +547,8 @@ extern "C" void svo_destroy(svo_ctx* ctx)
     if (ctx->d_ham_q) hipFree(ctx->d_ham_q);
     if (ctx->d_ham_t) hipFree(ctx->d_ham_t);
     for (void* p : { (void*)ctx->d_lk_pyr, (void*)ctx->d_lk_jobs, (void*)ctx->d_lk_pts, (void*)ctx->d_lk_init, (void*)ctx->d_lk_out, (void*)ctx->d_lk_status, (void*)ctx->d_lk_err }) if (p) hipFree(p);
+    for (void* p : { (void*)ctx->d_gftt_map, (void*)ctx->d_gftt_img, (void*)ctx->d_gftt_jobs, (void*)ctx->d_gftt_keys, (void*)ctx->d_gftt_items, (void*)ctx->d_gftt_state,
+                     (void*)ctx->d_gftt_info, (void*)ctx->d_gftt_seeds, (void*)ctx->d_gftt_pts, (void*)ctx->d_gftt_resp }) if (p) hipFree(p);
     if (ctx->up_ready) {
         hipStreamSynchronize(ctx->s_copy);
         for (int i = 0; i < 2; i++) { hipEventDestroy(ctx->ev_h2d[i]); hipEventDestroy(ctx->ev_det[i]); if (ctx->h_stage[i]) hipHostFree(ctx->h_stage[i]); }
@@ -1248,7 +1264,10 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     // switch) while svo_set_landmarks is on: a context that has both off reports the list it always did
     int n = ctx->landmarks ? KT_LANDMARKS + 1 : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
     for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
-    // "lk_pyrdown" and "lk_track" behind whatever was listed, once the context has made a svo_lk_track call
+    // the three names of svo_gftt_detect behind whatever was listed, once the context has made such a call
+    for (int k = KT_GFTT_RESPONSE; ctx->gftt_used && k <= KT_GFTT_SELECT; k++, n++)
+        if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
+    // "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call
     for (int k = KT_LK_PYRDOWN; ctx->lk_used && k <= KT_LK_TRACK; k++, n++)
         if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
     return n;
@@ -2673,6 +2692,113 @@ extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int leve
     if (cap < r.w[level] * r.h[level]) return SVO_ERR_CAPACITY;
     HIPCHECK(hipMemcpy2D(out, (size_t)r.w[level], r.img[which][level], (size_t)r.pitch[which][level], (size_t)r.w[level], (size_t)r.h[level], hipMemcpyDeviceToHost));
     return r.w[level] * r.h[level];
+}
+
+// ---- Shi-Tomasi corner detection on caller images (svo_hip.h; the decisions: gftt_call.hpp, the kernels: k_gftt.hip) --------------
+extern "C" int svo_gftt_detect(svo_ctx* ctx, const svo_gftt_job* jobs, int n_jobs, const svo_gftt_params* params, uint32_t flags)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_gftt_params p;
+    if (params) p = *params; else svo_gftt_default_params(&p);
+    const svo_gftt::Caps caps{ ctx->dc.max_kps, 4 * ctx->cfg.n_lanes * ctx->dc.oct_cap, ctx->cfg.max_w, ctx->cfg.max_h, ctx->cfg.max_cand };
+    { std::string why; const int rc = svo_gftt::check_gftt_call(jobs, n_jobs, p, flags, caps, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (n_jobs == 0) return SVO_OK;
+    const bool dev = (flags & SVO_FLAG_DEVICE_IMAGES) != 0;
+    const svo_gftt::Plan plan = svo_gftt::plan_gftt_call(jobs, n_jobs, p, dev);
+    const int cand_cap = svo_gftt::gftt_cand_cap(ctx->cfg.max_cand), key_stride = svo_gftt::gftt_key_stride(cand_cap), seed_cap = ctx->dc.max_kps;
+    const long long items_stride = (5ll * cand_cap + 2ll * seed_cap + 3) / 4 * 4;
+    // the buffers: a failed growth leaves the capacity at 0, so that the next call allocates afresh.  The map buffer is the large one
+    // (4 bytes per pixel of the call): failing to get it is a capacity refusal, before anything is enqueued
+    ctx->gftt_jobs.clear();
+    if ((size_t)plan.map_floats > ctx->gftt_map_cap) {
+        ctx->gftt_map_cap = 0;
+        if (lk_realloc(&ctx->d_gftt_map, (size_t)plan.map_floats) != hipSuccess) {
+            (void)hipGetLastError(); ctx->d_gftt_map = nullptr;
+            char msg[200]; snprintf(msg, sizeof(msg), "%d jobs need a response-map buffer of %lld bytes, which the device could not provide", n_jobs, plan.map_floats * 4ll);
+            ctx->last_error = msg; return SVO_ERR_CAPACITY;
+        }
+        ctx->gftt_map_cap = (size_t)plan.map_floats;
+    }
+    if ((size_t)plan.img_bytes > ctx->gftt_img_cap) { ctx->gftt_img_cap = 0; HIPCHECK(lk_realloc(&ctx->d_gftt_img, (size_t)plan.img_bytes)); ctx->gftt_img_cap = (size_t)plan.img_bytes; }
+    if (n_jobs > ctx->gftt_jobs_cap) {
+        ctx->gftt_jobs_cap = 0;
+        HIPCHECK(lk_realloc(&ctx->d_gftt_jobs, (size_t)n_jobs)); HIPCHECK(lk_realloc(&ctx->d_gftt_info, 4 * (size_t)n_jobs));
+        HIPCHECK(lk_realloc(&ctx->d_gftt_keys, (size_t)n_jobs * (size_t)key_stride)); HIPCHECK(lk_realloc(&ctx->d_gftt_state, (size_t)n_jobs * (size_t)cand_cap));
+        HIPCHECK(lk_realloc(&ctx->d_gftt_items, (size_t)n_jobs * (size_t)items_stride));
+        ctx->gftt_jobs_cap = n_jobs;
+    }
+    if (plan.n_seeds > ctx->gftt_seeds_cap) { ctx->gftt_seeds_cap = 0; HIPCHECK(lk_realloc(&ctx->d_gftt_seeds, (size_t)plan.n_seeds)); ctx->gftt_seeds_cap = plan.n_seeds; }
+    if (plan.n_pts > ctx->gftt_pts_cap) {
+        ctx->gftt_pts_cap = 0;
+        HIPCHECK(lk_realloc(&ctx->d_gftt_pts, (size_t)plan.n_pts)); HIPCHECK(lk_realloc(&ctx->d_gftt_resp, (size_t)plan.n_pts));
+        ctx->gftt_pts_cap = plan.n_pts;
+    }
+    ctx->gftt_used = true;
+    const hipStream_t st = ctx->stream;
+    // the job records; host images are copied tightly packed, device images are read where they are
+    std::vector<GfttJobDev> recs((size_t)n_jobs);
+    std::vector<float> h_seeds(2 * (size_t)plan.n_seeds);
+    for (int j = 0; j < n_jobs; j++) {
+        const svo_image& im = jobs[j].img;
+        GfttJobDev& r = recs[(size_t)j];
+        memset(&r, 0, sizeof(r));
+        r.w = im.w; r.h = im.h; r.map = ctx->d_gftt_map + plan.map_off[(size_t)j];
+        r.seed0 = plan.seed0[(size_t)j]; r.n_seeds = jobs[j].n_seeds; r.pts0 = plan.pts0[(size_t)j]; r.cap = jobs[j].cap;
+        r.cell = plan.cells[(size_t)j].cell; r.gw = plan.cells[(size_t)j].gw; r.gh = plan.cells[(size_t)j].gh;
+        if (dev) { r.img = im.data; r.pitch = (int)im.stride; }
+        else {
+            uint8_t* copy = ctx->d_gftt_img + plan.img_off[(size_t)j];
+            r.img = copy; r.pitch = im.w;
+            HIPCHECK(hipMemcpy2DAsync(copy, (size_t)im.w, im.data, (size_t)im.stride, (size_t)im.w, (size_t)im.h, hipMemcpyHostToDevice, st));
+        }
+        if (jobs[j].n_seeds > 0) memcpy(h_seeds.data() + 2 * (size_t)r.seed0, jobs[j].seeds, sizeof(float) * 2 * (size_t)jobs[j].n_seeds);
+    }
+    HIPCHECK(hipMemcpyAsync(ctx->d_gftt_jobs, recs.data(), sizeof(GfttJobDev) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
+    if (plan.n_seeds) HIPCHECK(hipMemcpyAsync(ctx->d_gftt_seeds, h_seeds.data(), sizeof(float) * 2 * (size_t)plan.n_seeds, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(ctx->d_gftt_info, 0, sizeof(int) * 4 * (size_t)n_jobs, st));
+    GfttArgs a;
+    a.jobs = ctx->d_gftt_jobs; a.n_jobs = n_jobs; a.cand_cap = cand_cap; a.key_stride = key_stride; a.seed_cap = seed_cap; a.items_stride = (int)items_stride;
+    a.keys = ctx->d_gftt_keys; a.items = ctx->d_gftt_items; a.state = ctx->d_gftt_state;
+    a.seeds = ctx->d_gftt_seeds; a.pts = ctx->d_gftt_pts; a.resp = ctx->d_gftt_resp; a.info = ctx->d_gftt_info; a.p = p;
+    { Span s(ctx, KT_GFTT_RESPONSE); launch_gftt_response(a, plan.max_w, plan.max_h, st); }
+    { Span s(ctx, KT_GFTT_CANDIDATES); launch_gftt_candidates(a, plan.max_w, plan.max_h, st); }
+    { Span s(ctx, KT_GFTT_SELECT); launch_gftt_select(a, st); }
+    HIPCHECK(hipGetLastError());
+    std::vector<int> h_info(4 * (size_t)n_jobs);
+    std::vector<float> h_pts(2 * (size_t)plan.n_pts), h_resp((size_t)plan.n_pts);
+    HIPCHECK(hipMemcpyAsync(h_info.data(), ctx->d_gftt_info, sizeof(int) * 4 * (size_t)n_jobs, hipMemcpyDeviceToHost, st));
+    if (plan.n_pts) {
+        HIPCHECK(hipMemcpyAsync(h_pts.data(), ctx->d_gftt_pts, sizeof(float) * 2 * (size_t)plan.n_pts, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(h_resp.data(), ctx->d_gftt_resp, sizeof(float) * (size_t)plan.n_pts, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHECK(hipStreamSynchronize(st));
+    ctx->gftt_jobs = recs;
+    for (int j = 0; j < n_jobs; j++) {
+        const int* inf = h_info.data() + 4 * (size_t)j;
+        const size_t o = (size_t)plan.pts0[(size_t)j], n = (size_t)(inf[0] < jobs[j].cap ? inf[0] : jobs[j].cap);
+        if (n) {
+            memcpy(jobs[j].pts, h_pts.data() + 2 * o, sizeof(float) * 2 * n);
+            if (jobs[j].response) memcpy(jobs[j].response, h_resp.data() + o, sizeof(float) * n);
+        }
+        jobs[j].info[0] = (int32_t)n; jobs[j].info[1] = inf[1]; jobs[j].info[2] = inf[2];
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_debug_gftt_get_response(svo_ctx* ctx, int job, float* out, int cap, int* w, int* h)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx || job < 0) return SVO_ERR_ARG;
+    if ((size_t)job >= ctx->gftt_jobs.size()) return 0;
+    int rc = svo_wait(ctx); if (rc) return rc;
+    const GfttJobDev& r = ctx->gftt_jobs[(size_t)job];
+    if (w) *w = r.w; if (h) *h = r.h;
+    if (!out) return r.w * r.h;
+    if (cap < r.w * r.h) return SVO_ERR_CAPACITY;
+    HIPCHECK(hipMemcpy(out, r.map, sizeof(float) * (size_t)r.w * (size_t)r.h, hipMemcpyDeviceToHost));
+    return r.w * r.h;
 }
 
 // ---- probes ------------------------------------------------------------------------------------------------

@@ -131,3 +131,25 @@ struct LkTrackArgs {
 };
 void launch_lk_pyrdown(const LkJobDev* jobs, int n_jobs, int level, int max_w, int max_h, hipStream_t st);   // max_w x max_h: the largest level `level` of the call
 void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);                             // pixels_per_lane: lk_pixels_per_lane(win)
+// svo_gftt_detect (k_gftt.hip).  One record per job, in device memory: its image (the caller's device image or its copy in the context's
+// buffer), its response map, where its seeds and its results lie in the flat arrays, and the cell grid of the distance rule
+// (gftt_call.hpp: cell side >= min_distance, at most 64 x 64 cells)
+struct GfttJobDev {
+    const uint8_t* img; float* map;
+    int pitch, w, h;
+    int seed0, n_seeds, pts0, cap;
+    int cell, gw, gh;
+};
+// cand_cap: candidates a job may collect; key_stride: keys per job in `keys` (cand_cap rounded up to a power of two, the sort pads to
+// one); items: items_stride = 5 * cand_cap + 2 * seed_cap ints per job, rounded up to a multiple of 4; state: cand_cap bytes per job; info: 4 ints per job (corners written, candidates
+// counted, status, the bit pattern of the largest response), zeroed before the first kernel
+struct GfttArgs {
+    const GfttJobDev* jobs; int n_jobs;
+    int cand_cap, key_stride, seed_cap, items_stride;
+    unsigned long long* keys; int* items; uint8_t* state;
+    const float2* seeds; float2* pts; float* resp; int* info;
+    svo_gftt_params p;
+};
+void launch_gftt_response(const GfttArgs& a, int max_w, int max_h, hipStream_t st);      // max_w x max_h: the largest image of the call
+void launch_gftt_candidates(const GfttArgs& a, int max_w, int max_h, hipStream_t st);
+void launch_gftt_select(const GfttArgs& a, hipStream_t st);

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import (CameraModel, FasterStats, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
+from .abi import (CameraModel, FasterStats, GfttJob, GfttParams, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -32,6 +32,7 @@ EXPORTS = [
     "svo_get_keypoints_oct", "svo_get_matches_oct", "svo_get_tracked_oct", "svo_get_row_index", "svo_get_matches_row_index", "svo_get_match_ids", "svo_reset_ids", "svo_set_this_frame_as_kf",
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_tracked_oct", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
     "svo_lk_default_params", "svo_lk_track", "svo_debug_lk_get_level",
+    "svo_gftt_default_params", "svo_gftt_detect", "svo_debug_gftt_get_response",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -140,6 +141,10 @@ def lib():
             L.svo_lk_default_params.restype = None; L.svo_lk_default_params.argtypes = [C.c_void_p]
             L.svo_lk_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
             L.svo_debug_lk_get_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "svo_gftt_detect"):       # (as above)
+            L.svo_gftt_default_params.restype = None; L.svo_gftt_default_params.argtypes = [C.c_void_p]
+            L.svo_gftt_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+            L.svo_debug_gftt_get_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -216,6 +221,12 @@ def stereo_rectify(calib: StereoCalibration) -> StereoRectification:
 def default_lk_params() -> LkParams:
     p = LkParams()
     lib().svo_lk_default_params(C.byref(p))
+    return p
+
+
+def default_gftt_params() -> GfttParams:
+    p = GfttParams()
+    lib().svo_gftt_default_params(C.byref(p))
     return p
 
 
@@ -826,13 +837,52 @@ class Context:
         self._ck(self.L.svo_debug_lk_get_level(self.h, int(job), int(which), int(level), _vp(out), n, C.byref(w), C.byref(h)), "svo_debug_lk_get_level")
         return out
 
+    # -- Shi-Tomasi corner detection on caller images (svo_gftt_detect) ------------------------------------------
+    def gftt_detect(self, jobs, params=None, device=False, pinned=False):
+        """jobs: a list of (image, seeds or None[, cap]) -- image a uint8 [h, w] numpy array (any row stride; the last axis must be
+        contiguous), seeds [n, 2] float32 (x, y): points new corners keep min_distance from; cap: room for corners (default: the
+        context's max_kps).  With device=True image is an (address, w, h, stride) tuple, read in place; pinned=True declares the host
+        arrays page-locked.  params: a GfttParams (None: the defaults).  Returns a (pts [n, 2] float32, response [n] float32, n_cand,
+        status) tuple per job.  Synchronises."""
+        recs = (GfttJob * max(1, len(jobs)))()
+        keep, bufs = [], []
+        for i, job in enumerate(jobs):
+            im = job[0]
+            seeds = None if len(job) < 2 or job[1] is None else np.ascontiguousarray(job[1], np.float32).reshape(-1, 2)
+            cap = int(job[2]) if len(job) > 2 and job[2] is not None else int(self.max_kps)
+            if device:
+                recs[i].img = LkImage(int(im[0]), int(im[1]), int(im[2]), int(im[3]))
+            else:
+                if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                    raise ValueError("job %d: a uint8 [h, w] image with contiguous rows is expected" % i)
+                recs[i].img = LkImage(im.ctypes.data, im.shape[1], im.shape[0], im.strides[0])
+            res = (np.zeros((max(cap, 0), 2), np.float32), np.zeros(max(cap, 0), np.float32), np.zeros(3, np.int32))
+            keep += [im, seeds]
+            recs[i].seeds, recs[i].n_seeds, recs[i].cap = _vp(seeds) if seeds is not None else None, 0 if seeds is None else len(seeds), cap
+            recs[i].pts, recs[i].response, recs[i].info = (_vp(res[0]) if cap > 0 else None), (_vp(res[1]) if cap > 0 else None), _vp(res[2])
+            bufs.append(res)
+        flags = FLAG_DEVICE_IMAGES if device else (FLAG_PINNED_IMAGES if pinned else 0)
+        self._ck(self.L.svo_gftt_detect(self.h, recs, len(jobs), C.byref(params) if params is not None else None, C.c_uint32(flags)), "svo_gftt_detect")
+        return [(pts[:info[0]].copy(), resp[:info[0]].copy(), int(info[1]), int(info[2])) for pts, resp, info in bufs]
+
+    def gftt_response(self, job):
+        """the response map of job `job` of the last gftt_detect call as a float32 [h, w] array; None when that call had no such job"""
+        w, h = C.c_int(0), C.c_int(0)
+        n = self._ck(self.L.svo_debug_gftt_get_response(self.h, int(job), None, 0, C.byref(w), C.byref(h)), "svo_debug_gftt_get_response")
+        if n == 0:
+            return None
+        out = np.zeros((h.value, w.value), np.float32)
+        self._ck(self.L.svo_debug_gftt_get_response(self.h, int(job), _vp(out), n, C.byref(w), C.byref(h)), "svo_debug_gftt_get_response")
+        return out
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
     def kernel_times(self, appended=False):
         """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
         hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
-        "lk_pyrdown", "lk_track": svo_lk_track, listed once the context has made such a call) and are
+        "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, and "lk_pyrdown", "lk_track": svo_lk_track, each listed once
+        the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
