@@ -660,6 +660,58 @@ int svo_gftt_detect(svo_ctx* ctx, const svo_gftt_job* jobs, int n_jobs, const sv
  * only); 0 when the last call had no such job (or no call was made); SVO_ERR_CAPACITY when cap < w * h. */
 int svo_debug_gftt_get_response(svo_ctx* ctx, int job, float* out, int cap, int* w, int* h);
 
+/* A KLT FRONT END RESIDENT ON THE DEVICE: a per-context track table and one call per frame that follows every lane's tracks into the
+ * new stereo pair with the tracker of svo_lk_track, gates and compacts them, writes the lane's current-frame lists as the
+ * precomputed-data bypass would, and optionally runs stage 5.  Nothing synchronises inside a step.  The selectors SVO_DM_KLT and
+ * SVO_IFM_OPTICAL_FLOW stay refused by svo_process.  Detection of new points stays with the caller: top up with svo_klt_get_tracks,
+ * svo_gftt_detect (the tracks as seeds), svo_lk_track (left to right) and svo_klt_add_points.
+ * THE CONTRACT: after a step every getter of the lane -- keypoints, pairings, tracked pairs, pairing IDs, both row tables, the values
+ * record, the result with residuals and outliers -- returns, byte for byte, what this host recipe leaves: a call that only shifts
+ * (svo_process_lanes with no run bit), svo_lk_track with svo_klt_params.lk on the lane's (left[t-1], left[t], left points) and
+ * (right[t-1], right[t], right points), the gate below on the host, then svo_put_features_oct (both sides, descriptors NULL),
+ * svo_put_matches_oct, svo_put_match_ids_oct, svo_put_tracked_oct for octave 0 of the current frame, and svo_process_lanes with
+ * SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT.  tests/klt_ref.py holds that recipe and the walk of the selection.
+ * A lane's table holds up to `cap` tracks: left point, right point, ID, age, its index in the list of the last step and its index p in
+ * the list of the lane's PREVIOUS slot (-1: none).  svo_klt_step, for every lane of the mask (an idle lane keeps its table, its
+ * pyramids, its lists and its record, as if the call had not been made):
+ *   1. the prev/cur shift of svo_process, its recovery rule included (a lane whose last call ended in voecBadTracking or
+ *      voecBadCondNumber keeps its previous frame);
+ *   2. level 0 of both images is copied into the front end's own buffers and the pyramid levels are built; the pyramid of the lane's
+ *      last pair is still there and is not rebuilt.  HOST images (with or without SVO_FLAG_PINNED_IMAGES) are free once the call returns
+ *      unless they are pinned, DEVICE images (SVO_FLAG_DEVICE_IMAGES) and pinned ones once the enqueued work has run (svo_wait);
+ *   3. both lists are tracked from the lane's last pair into the new one (forward-backward as well when lk.fb_max > 0).  A lane without
+ *      a last pair -- its first step, or the first after svo_klt_reset -- tracks nothing: its points stand as they are, status 1;
+ *   4. a slot survives when both statuses are 1, all four coordinates are finite, |yl - yr| <= max_dy and min_disp <= xl - xr <=
+ *      max_disp (float32 compares as written).  Survivors keep their order and become keypoint i of both lists (size = lk.win, angle
+ *      -1, response 0, octave 0, class_id = the track's ID), pairing i -> i (imgIdx 0, distance 0), pairing ID i = the track's ID, and
+ *      one tracked pair (p, i) per survivor that has a p: the index the track had in the list of the last step when the lane shifted
+ *      in 1, its old p when the lane held its previous frame.  The compacted table (age + 1) replaces the old one;
+ *   5. stage 5 with SVO_RUN_OPTIMIZE, as svo_process enqueues it (pose covariance and landmarks included while they are on).
+ * flags: SVO_RUN_OPTIMIZE, SVO_FLAG_DEVICE_IMAGES or SVO_FLAG_PINNED_IMAGES; any other bit is SVO_ERR_ARG, SVO_FLAG_BGR_IMAGES included.
+ * svo_klt_enable allocates (NULL: the defaults, cap = min(1024, max_kps)); called again with other parameters it returns SVO_ERR_STATE
+ * unless every table is empty.  A context that never calls it allocates and launches nothing for the front end.
+ * svo_klt_add_points appends behind the lane's live count: fresh IDs (the lane's last ID + 1 ..., from 0), age 0, no indices; points
+ * beyond cap are dropped and the number appended is returned.  It and svo_klt_get_tracks (returns the live count, writes min(count, cap)
+ * entries; any array may be NULL) synchronise.  svo_klt_reset empties the tables of the lanes of the mask (NULL: all), forgets
+ * their last pairs and starts their IDs over from 0: such a lane is a fresh stream.
+ * svo_debug_klt_select runs 1 and 4 on ONE lane with the caller's arrays in place of the tracker's results (n must be the live count,
+ * else SVO_ERR_ARG): the selection on inputs no image could produce.
+ * Refusals, all before anything is enqueued, with the outputs untouched and a text in svo_last_error: SVO_ERR_STATE when the front end
+ * is not enabled, when svo_set_params has not been called, inside a captured graph, or for a member context of a frame-parallel
+ * stream (svo_batch.h; svo_klt_enable refuses it already); SVO_ERR_ARG / SVO_ERR_CAPACITY for parameters out
+ * of range (cap > max_kps: capacity), a mask bit at or above n_lanes, NULL images, images not of one size, below 64 x 64 or above
+ * max_w x max_h (capacity), strides below a row, device spans above 2^31 - 1 bytes; and whatever svo_process refuses for a
+ * SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT call under the parameters in force.
+ * Not carried by state files, hand-over records or the RCCL companion; no svo_batch / frame-parallel form; octave 0 only. */
+void svo_klt_default_params(svo_klt_params* p);
+int svo_klt_enable(svo_ctx* ctx, const svo_klt_params* p);
+int svo_klt_reset(svo_ctx* ctx, const uint64_t lanes[2] /* NULL = all lanes */);
+int svo_klt_add_points(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, int n);
+int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t lanes[2] /* NULL = all lanes */);
+int svo_klt_get_tracks(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, int32_t* ids, int32_t* age, int cap);
+int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy,
+                         const uint8_t* status_l, const uint8_t* status_r, int n);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -687,7 +739,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * whatever that switch says) --, so a context that has both off returns the list (and the count) it always did.  Size arrays by the
  * value of the same call, or for the largest list (cap 64 always suffices).
  * "gftt_response", "gftt_candidates" and "gftt_select" are appended behind whatever that rule lists, once the context has made a
- * svo_gftt_detect call; "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call. */
+ * svo_gftt_detect call; "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call or a svo_klt_step
+ * (whose pyramid and tracking launches count there); "klt_select" behind the lk names, once the context has made a svo_klt_step or a
+ * svo_debug_klt_select. */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

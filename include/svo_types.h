@@ -272,6 +272,18 @@ typedef struct svo_lk_params {
     float eps, min_eig, fb_max;
 } svo_lk_params;
 
+/* The parameters of the resident KLT front end (svo_klt_enable, svo_hip.h).  svo_klt_default_params fills in the defaults.
+ *   lk          the tracker's parameters, as svo_lk_track takes them and with the same ranges, fb_max included
+ *   cap         tracks per lane, 1 .. max_kps (default 1024; svo_klt_enable(ctx, NULL) uses min(1024, max_kps))
+ *   max_dy      a pair survives while |yl - yr| <= max_dy (default 1.5; >= 0)
+ *   min_disp, max_disp   ... and min_disp <= xl - xr <= max_disp (defaults 0.5 and +infinity: no upper gate) */
+typedef struct svo_klt_params {
+    svo_lk_params lk;
+    int32_t cap;
+    float max_dy;
+    float min_disp, max_disp;
+} svo_klt_params;
+
 /* The parameters of svo_gftt_detect (svo_hip.h), the Shi-Tomasi corner detector on caller images.  svo_gftt_default_params fills in the
  * defaults; the allowed ranges are checked by every call (SVO_ERR_ARG with a text).
  *   max_corners   at most this many corners per job, 0 .. max_kps; 0 (default): as many as the job's `cap` holds

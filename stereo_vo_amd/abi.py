@@ -175,6 +175,15 @@ class LkJob(C.Structure):
 assert C.sizeof(LkParams) == 24 and C.sizeof(LkJob) == 96
 
 
+class KltParams(C.Structure):
+    """svo_klt_params (include/svo_types.h): the tracker's parameters, the tracks per lane, and the gates of the selection --
+    |yl - yr| <= max_dy and min_disp <= xl - xr <= max_disp"""
+    _fields_ = [("lk", LkParams), ("cap", C.c_int32), ("max_dy", C.c_float), ("min_disp", C.c_float), ("max_disp", C.c_float)]
+
+
+assert C.sizeof(KltParams) == 40
+
+
 class GfttParams(C.Structure):
     """svo_gftt_params (include/svo_types.h): the most corners per job (0: as many as cap holds), the block side (3, 5 or 7), the minimum
     distance in pixels (0 .. 255) and the quality level in (0, 1]"""

@@ -1,0 +1,58 @@
+// klt_call.hpp -- what the calls of the resident KLT front end ARE, decided on the host without a device: the parameter ranges of
+// svo_klt_params, every refusal of svo_klt_enable / svo_klt_step / svo_klt_add_points / svo_klt_get_tracks / svo_klt_reset /
+// svo_debug_klt_select in the order they are made, and the buffer plan (pyramid ping-pong, table ping-pong, job records).
+// Host only, no HIP: svo_api.hip acts on these decisions, k_klt.hip reads the buffers they size, and tools/klt_check.cpp drives them
+// under the sanitizers on the CPU (`make hostcheck`).
+#pragma once
+#include "../../include/svo_hip.h"
+#include "frame_call.hpp"
+#include "lk_call.hpp"
+#include <stdint.h>
+#include <string>
+
+namespace svo_klt {
+
+// what the context can take (svo_config) and what it is doing
+struct Caps { int n_lanes, max_kps, max_w, max_h; };
+struct State {
+    bool enabled;         // svo_klt_enable has succeeded
+    bool params_set;      // svo_set_params has been called
+    bool capturing;       // the context's stream is capturing a graph
+    bool frame_parallel;  // the context is a member of a frame-parallel stream (svo_batch.h): its frames travel between contexts, a table would not
+};
+
+// NULL parameters of svo_klt_enable: the defaults with cap = min(1024, max_kps)
+svo_klt_params klt_resolve_params(const svo_klt_params* p, int max_kps);
+// the ranges of svo_klt_params: SVO_OK, SVO_ERR_ARG, or SVO_ERR_CAPACITY (cap > max_kps), with the numbers in `why`
+int check_klt_params(const svo_klt_params& p, const Caps& caps, std::string& why);
+// svo_klt_enable: the parameters, then -- for a context that is enabled already -- other parameters than those in force while a table
+// holds tracks (SVO_ERR_STATE); a member of a frame-parallel stream is refused first (SVO_ERR_STATE).  realloc: the call must (re)make the buffers
+int check_klt_enable(const svo_klt_params& p, const Caps& caps, bool enabled, const svo_klt_params& in_force, bool tables_empty, bool frame_parallel, bool& realloc, std::string& why);
+// what every other entry point asks first: enabled, parameters set, not inside a capture
+int check_klt_ready(const State& s, const char* entry, std::string& why);
+// svo_klt_step, in order: ready, flags, frames, the mask, then the images of the active lanes (NULL data, one size, the 64 x 64 floor,
+// max_w x max_h, strides, device spans).  active / idle: the parsed mask.  w, h: the size of the call's images
+int check_klt_step(const svo_frame* frames, uint32_t flags, const uint64_t* lanes, const Caps& caps, const State& s,
+                   LaneMask& active, LaneMask& idle, int& w, int& h, std::string& why);
+// svo_klt_add_points / svo_klt_get_tracks / svo_debug_klt_select: ready, the lane, the arrays and the count
+int check_klt_lane_call(const State& s, const char* entry, int lane, int n, bool arrays_ok, const Caps& caps, std::string& why);
+
+// the buffers of an enabled context, sized for max_w x max_h images:
+//   pyramids   [2 parities][n_lanes][2 sides] blocks of img_stride bytes, the levels of one image tightly packed (lk_geometry with
+//              level 0).  A lane's new pair goes to the parity its last pair did NOT go to: the other parity still holds frame t - 1
+//   table      [2 halves] x ( points [n_lanes][2 sides][cap] float2 + meta [n_lanes][4][cap] int32: id, age, index in the list of the
+//              last step, index in the lane's previous-slot list ).  k_klt_select reads one half and writes the other
+//   results    the tracker's out / status / err, [n_lanes][2 sides][cap]: job 2 * lane + side owns slots [job * cap, (job + 1) * cap)
+//   jobs       n_lanes pyramid records (left and right image of the NEW pair) and 2 * n_lanes tracking records
+struct Plan {
+    long long img_stride, pyr_bytes;
+    long long n_slots;              // n_lanes * 2 * cap
+    long long meta_ints;            // n_lanes * 4 * cap
+    int n_pyr_jobs, n_trk_jobs;
+    long long select_lds_bytes;     // dynamic LDS of k_klt_select: three row tables of max_h + 1 ints
+};
+Plan plan_klt(const svo_klt_params& p, const Caps& caps);
+// the geometry of a step's images (every lane has the same size)
+svo_lk::Geometry klt_geometry(const svo_klt_params& p, int w, int h);
+
+}

@@ -333,6 +333,34 @@ public:
         for (size_t i = 0; i < corners.size(); i++) corners[i] = TPixelCoordf(out[2 * i], out[2 * i + 1]);
         return info[1];
     }
+    /** The KLT front end resident on the device (svo_klt_enable / svo_klt_step, include/svo_hip.h): a track table per estimator that
+     *  one call per frame follows into the new stereo pair, gates, turns into the current frame's lists and hands to stage 5 -- what a
+     *  caller would otherwise assemble from trackOpticalFlow and the precomputed-data bypass, without leaving the device.
+     *  enableKLT allocates it (NULL: the defaults); addKLTPoints appends (left, right) pairs and returns how many went in; stepKLT takes
+     *  the new 8-bit grey host images (stride in bytes, 0 = w), runs stage 5 when `optimize` is set and leaves the increment where
+     *  processNewImagePair leaves it (svo_get_result); getKLTTracks returns the live tracks, the seeds of a detectGoodFeatures top-up. */
+    void enableKLT(const svo_klt_params* klt_params = NULL) { check(svo_klt_enable(m_ctx, klt_params), "svo_klt_enable"); }
+    int addKLTPoints(const std::vector<TPixelCoordf>& left, const std::vector<TPixelCoordf>& right) {
+        const size_t n = left.size() < right.size() ? left.size() : right.size();
+        std::vector<float> l(2 * n), r(2 * n);
+        for (size_t i = 0; i < n; i++) { l[2 * i] = left[i].x; l[2 * i + 1] = left[i].y; r[2 * i] = right[i].x; r[2 * i + 1] = right[i].y; }
+        return check(svo_klt_add_points(m_ctx, 0, n ? l.data() : NULL, n ? r.data() : NULL, (int)n), "svo_klt_add_points");
+    }
+    void stepKLT(const uint8_t* left, const uint8_t* right, int w, int h, bool optimize = true, long long left_stride = 0, long long right_stride = 0) {
+        svo_frame f;
+        f.left.data = left; f.left.w = w; f.left.h = h; f.left.stride = left_stride ? left_stride : w;
+        f.right.data = right; f.right.w = w; f.right.h = h; f.right.stride = right_stride ? right_stride : w;
+        check(svo_klt_step(m_ctx, &f, optimize ? SVO_RUN_OPTIMIZE : 0, NULL), "svo_klt_step");
+    }
+    int getKLTTracks(std::vector<TPixelCoordf>& left, std::vector<TPixelCoordf>& right, std::vector<int32_t>& ids, std::vector<int32_t>& age) {
+        const int n = check(svo_klt_get_tracks(m_ctx, 0, NULL, NULL, NULL, NULL, 0), "svo_klt_get_tracks");
+        std::vector<float> l(2 * (size_t)n), r(l.size());
+        ids.assign((size_t)n, 0); age.assign(ids.size(), 0);
+        if (n > 0) check(svo_klt_get_tracks(m_ctx, 0, l.data(), r.data(), ids.data(), age.data(), n), "svo_klt_get_tracks");
+        left.resize(ids.size()); right.resize(ids.size());
+        for (size_t i = 0; i < ids.size(); i++) { left[i] = TPixelCoordf(l[2 * i], l[2 * i + 1]); right[i] = TPixelCoordf(r[2 * i], r[2 * i + 1]); }
+        return n;
+    }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

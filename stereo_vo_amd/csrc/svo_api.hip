@@ -9,6 +9,7 @@
 #include "frame_call.hpp"
 #include "lk_call.hpp"
 #include "gftt_call.hpp"
+#include "klt_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -41,8 +42,11 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // svo_gftt_detect: listed behind the frame's names and before the LK ones, and only once the context has made such a call
        KT_GFTT_RESPONSE, KT_GFTT_CANDIDATES, KT_GFTT_SELECT,
        KT_LK_PYRDOWN, KT_LK_TRACK,
-       KT_COUNT };
-static_assert(KT_COUNT <= 64, "kt_mask is one 64-bit word");
+       KT_COUNT,
+       // the resident KLT front end: "klt_select", listed behind the LK names once the context has made a step.  Behind KT_COUNT: the
+       // name lives outside kt_names (kt_name below), whose last entries stay the LK ones
+       KT_KLT_SELECT = KT_COUNT, KT_ALL };
+static_assert(KT_ALL <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
@@ -50,6 +54,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks",
     "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
+static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -110,7 +115,7 @@ struct svo_ctx {
     std::vector<void*> allocs;
     std::string last_error;
     std::vector<TimedSpan> spans; std::vector<hipEvent_t> free_events;
-    double kt_total[KT_COUNT]; long long kt_calls[KT_COUNT]; unsigned long long kt_mask;
+    double kt_total[KT_ALL]; long long kt_calls[KT_ALL]; unsigned long long kt_mask;
     unsigned* d_ham_out; uint8_t* d_ham_q, *d_ham_t; int ham_cap_q, ham_cap_t;
     // svo_lk_track: buffers of its own, made by its first call, grown on demand, freed with the context -- the pyramids of the call's
     // images, the job records, the flat point arrays (pts, init, out: float2; status; err).  lk_jobs: the records of the last call, for
@@ -125,6 +130,16 @@ struct svo_ctx {
     unsigned long long* d_gftt_keys; int* d_gftt_items; uint8_t* d_gftt_state; int* d_gftt_info;
     float2* d_gftt_seeds; int gftt_seeds_cap; float2* d_gftt_pts; float* d_gftt_resp; int gftt_pts_cap;
     std::vector<GfttJobDev> gftt_jobs; bool gftt_used;
+    // the resident KLT front end (svo_klt_enable; the plan: klt_call.hpp): nothing is allocated until it is enabled.  Host side: the
+    // parameters in force, the table half that is live (every lane's: k_klt_select moves idle lanes along), per lane the pyramid parity
+    // its last pair went to and whether it has a last pair, the image size of the last step.  used: svo_kernel_times lists "klt_select"
+    struct Klt {
+        bool enabled, used; svo_klt_params p; svo_klt::Plan plan;
+        KltDev dev; uint8_t* d_pyr; LkJobDev* d_pyr_jobs, * d_trk_jobs; float2* d_stage;
+        int half, w, h; LaneMask parity, has_img;
+    } klt;
+    bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
+    bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
     uint2** d_map_ptrs; std::vector<uint2*> map_ptrs;  // per image: fixed-point map on the device or nullptr
@@ -174,6 +189,7 @@ struct svo_ctx {
 
 using namespace svo_call;
 static void drop_graphs(svo_ctx* ctx);
+static void klt_free(svo_ctx* ctx);
 static int dyn_fast_init(svo_ctx* ctx, int lane);
 static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
@@ -421,6 +437,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
     ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
+    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -429,7 +446,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
-    for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_ALL; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     ctx->kt_mask = ~0ull;
     *out = ctx;                                           // so that the caller can read last_error and destroy
     knobs_read(&ctx->knobs, knobs_env);
@@ -549,6 +566,7 @@ extern "C" void svo_destroy(svo_ctx* ctx)
     for (void* p : { (void*)ctx->d_lk_pyr, (void*)ctx->d_lk_jobs, (void*)ctx->d_lk_pts, (void*)ctx->d_lk_init, (void*)ctx->d_lk_out, (void*)ctx->d_lk_status, (void*)ctx->d_lk_err }) if (p) hipFree(p);
     for (void* p : { (void*)ctx->d_gftt_map, (void*)ctx->d_gftt_img, (void*)ctx->d_gftt_jobs, (void*)ctx->d_gftt_keys, (void*)ctx->d_gftt_items, (void*)ctx->d_gftt_state,
                      (void*)ctx->d_gftt_info, (void*)ctx->d_gftt_seeds, (void*)ctx->d_gftt_pts, (void*)ctx->d_gftt_resp }) if (p) hipFree(p);
+    klt_free(ctx);
     if (ctx->up_ready) {
         hipStreamSynchronize(ctx->s_copy);
         for (int i = 0; i < 2; i++) { hipEventDestroy(ctx->ev_h2d[i]); hipEventDestroy(ctx->ev_det[i]); if (ctx->h_stage[i]) hipHostFree(ctx->h_stage[i]); }
@@ -600,7 +618,7 @@ extern "C" int svo_set_params(svo_ctx* ctx, const svo_params* p)
     if (!ctx || !p) return SVO_ERR_ARG;
     { const int rc = params_fit(ctx, *p); if (rc) return rc; }
     const bool dyn_reinit = ctx->dyn_fast && dyn_fast_octaves_changed(ctx->params, *p);
-    ctx->params = *p;
+    ctx->params = *p; ctx->params_set = true;
     if (dyn_reinit) { const int rc = dyn_fast_init(ctx, -1); if (rc) return rc; }      // S2:522-523: m_threshold.assign(nOctaves, initial_FAST_threshold)
     // a context that has once selected a SAD method hands its frames over with their 8 x 8 windows (k_handover.hip, version 3), for good:
     // svo_handover_bytes grows here and never shrinks again
@@ -1268,8 +1286,13 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     for (int k = KT_GFTT_RESPONSE; ctx->gftt_used && k <= KT_GFTT_SELECT; k++, n++)
         if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
     // "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call
-    for (int k = KT_LK_PYRDOWN; ctx->lk_used && k <= KT_LK_TRACK; k++, n++)
+    for (int k = KT_LK_PYRDOWN; (ctx->lk_used || ctx->klt.used) && k <= KT_LK_TRACK; k++, n++)
         if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
+    // "klt_select" behind the LK names (which a step counts its pyramid and tracking launches under), once the context has made a step
+    if (ctx->klt.used) {
+        if (n < cap) { if (names) names[n] = kt_name(KT_KLT_SELECT); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_SELECT]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_SELECT]; }
+        n++;
+    }
     return n;
 }
 extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
@@ -1277,7 +1300,7 @@ extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     if (!name || !*name) { ctx->kt_mask = ~0ull; return SVO_OK; }
-    for (int i = 0; i < KT_COUNT; i++) if (!strcmp(name, kt_names[i])) { ctx->kt_mask = 1ull << i; return SVO_OK; }
+    for (int i = 0; i < KT_ALL; i++) if (!strcmp(name, kt_name(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
     return SVO_ERR_ARG;
 }
 
@@ -1286,7 +1309,7 @@ extern "C" int svo_kernel_times_reset(svo_ctx* ctx)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_ALL; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     return SVO_OK;
 }
 
@@ -2692,6 +2715,267 @@ extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int leve
     if (cap < r.w[level] * r.h[level]) return SVO_ERR_CAPACITY;
     HIPCHECK(hipMemcpy2D(out, (size_t)r.w[level], r.img[which][level], (size_t)r.pitch[which][level], (size_t)r.w[level], (size_t)r.h[level], hipMemcpyDeviceToHost));
     return r.w[level] * r.h[level];
+}
+
+// ---- the resident KLT front end (svo_hip.h; the decisions: klt_call.hpp, the kernels: k_klt.hip and k_lk.hip) ----------------------
+static void klt_free(svo_ctx* ctx)
+{
+    svo_ctx::Klt& k = ctx->klt;
+    for (void* p : { (void*)k.dev.pts[0], (void*)k.dev.pts[1], (void*)k.dev.meta[0], (void*)k.dev.meta[1], (void*)k.dev.lane, (void*)k.dev.out, (void*)k.dev.status,
+                     (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage }) if (p) (void)hipFree(p);
+    memset(&k, 0, sizeof(k));
+}
+static svo_klt::Caps klt_caps(const svo_ctx* ctx) { return { ctx->cfg.n_lanes, ctx->dc.max_kps, ctx->cfg.max_w, ctx->cfg.max_h }; }
+static svo_klt::State klt_state(svo_ctx* ctx)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    return { ctx->klt.enabled, ctx->params_set, ctx->capturing || cs != hipStreamCaptureStatusNone, ctx->frame_parallel };
+}
+static LaneMask klt_all_lanes(const svo_ctx* ctx)
+{
+    LaneMask a, i; std::string why;
+    parse_lane_mask(nullptr, false, ctx->cfg.n_lanes, a, i, why);
+    return a;
+}
+
+// svo_fpstream_create tells its member contexts what they are (svo_batch.cpp; not part of the public interface)
+extern "C" void svo_internal_mark_frame_parallel(svo_ctx* ctx) { if (ctx) ctx->frame_parallel = true; }
+
+extern "C" int svo_klt_enable(svo_ctx* ctx, const svo_klt_params* params)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    const svo_klt::Caps caps = klt_caps(ctx);
+    const svo_klt_params p = svo_klt::klt_resolve_params(params, caps.max_kps);
+    bool empty = true;
+    if (k.enabled && memcmp(&p, &k.p, sizeof(p)) != 0) {                // other parameters: only while no lane holds a track
+        { const int rc = svo_wait(ctx); if (rc) return rc; }
+        std::vector<KltLaneDev> lanes((size_t)caps.n_lanes);
+        HIPCHECK(hipMemcpy(lanes.data(), k.dev.lane, sizeof(KltLaneDev) * lanes.size(), hipMemcpyDeviceToHost));
+        for (const KltLaneDev& l : lanes) if (l.n > 0) empty = false;
+    }
+    bool realloc = false;
+    { std::string why; const int rc = svo_klt::check_klt_enable(p, caps, k.enabled, k.p, empty, ctx->frame_parallel, realloc, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (!realloc) return SVO_OK;
+    const svo_klt::Plan plan = svo_klt::plan_klt(p, caps);
+    if (plan.select_lds_bytes > 60 * 1024) {
+        char msg[160]; snprintf(msg, sizeof(msg), "max_h = %d: the selection keeps three row tables of max_h + 1 words in 60 KB of LDS", caps.max_h);
+        ctx->last_error = msg; return SVO_ERR_UNSUPPORTED;
+    }
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    klt_free(ctx);
+    k.p = p; k.plan = plan;
+    k.dev.n_lanes = caps.n_lanes; k.dev.cap = p.cap;
+    const size_t NS = (size_t)plan.n_slots;
+    for (int hf = 0; hf < 2; hf++) { HIPCHECK(lk_realloc(&k.dev.pts[hf], NS)); HIPCHECK(lk_realloc(&k.dev.meta[hf], (size_t)plan.meta_ints)); }
+    HIPCHECK(lk_realloc(&k.dev.lane, (size_t)caps.n_lanes)); HIPCHECK(lk_realloc(&k.dev.appended, (size_t)1));
+    HIPCHECK(lk_realloc(&k.dev.out, NS)); HIPCHECK(lk_realloc(&k.dev.status, NS)); HIPCHECK(lk_realloc(&k.dev.err, NS));
+    HIPCHECK(lk_realloc(&k.d_pyr, (size_t)plan.pyr_bytes));
+    HIPCHECK(lk_realloc(&k.d_pyr_jobs, (size_t)plan.n_pyr_jobs)); HIPCHECK(lk_realloc(&k.d_trk_jobs, (size_t)plan.n_trk_jobs));
+    HIPCHECK(lk_realloc(&k.d_stage, 2 * (size_t)p.cap));
+    HIPCHECK(hipMemsetAsync(k.dev.status, 0, NS, ctx->stream));
+    HIPCHECK(hipMemsetAsync(k.dev.out, 0, sizeof(float2) * NS, ctx->stream));
+    const LaneMask all = klt_all_lanes(ctx);
+    note_stream(ctx);
+    launch_klt_clear(ctx->dc, k.dev, 0, all, ctx->stream);
+    launch_klt_clear(ctx->dc, k.dev, 1, all, ctx->stream);
+    mark_stream(ctx);
+    HIPCHECK(hipGetLastError());
+    k.enabled = true;
+    return SVO_OK;
+}
+
+extern "C" int svo_klt_reset(svo_ctx* ctx, const uint64_t lanes[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_klt_ready(klt_state(ctx), "svo_klt_reset", why); if (rc) { ctx->last_error = why; return rc; } }
+    LaneMask active, idle; std::string why;
+    if (!parse_lane_mask(lanes, false, ctx->cfg.n_lanes, active, idle, why)) { ctx->last_error = why; return SVO_ERR_ARG; }
+    note_stream(ctx);
+    launch_klt_clear(ctx->dc, k.dev, k.half, active, ctx->stream);
+    mark_stream(ctx);
+    for (int wd = 0; wd < 2; wd++) k.has_img.w[wd] &= ~active.w[wd];
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_klt_add_points(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, int n)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_klt_add_points", lane, n, n <= 0 || (left_xy && right_xy), klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    if (n == 0) return 0;
+    const int m = n < k.p.cap ? n : k.p.cap;                             // (what lies beyond cap cannot go in whatever the live count is)
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    HIPCHECK(hipMemcpyAsync(k.d_stage, left_xy, sizeof(float2) * (size_t)m, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(k.d_stage + k.p.cap, right_xy, sizeof(float2) * (size_t)m, hipMemcpyHostToDevice, st));
+    launch_klt_append(k.dev, k.half, lane, k.d_stage, k.d_stage + k.p.cap, m, st);
+    int appended = 0;
+    HIPCHECK(hipMemcpyAsync(&appended, k.dev.appended, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    return appended;
+}
+
+extern "C" int svo_klt_get_tracks(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, int32_t* ids, int32_t* age, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_klt_get_tracks", lane, cap, true, klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    KltLaneDev kl;
+    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
+    const int n = kl.n, m = n < cap ? n : cap, C = k.p.cap;
+    if (m <= 0) return n;
+    const float2* pts = k.dev.pts[k.half] + (size_t)lane * 2 * C;
+    const int* meta = k.dev.meta[k.half] + (size_t)lane * KLT_META * C;
+    if (left_xy) HIPCHECK(hipMemcpy(left_xy, pts, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
+    if (right_xy) HIPCHECK(hipMemcpy(right_xy, pts + C, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
+    if (ids) HIPCHECK(hipMemcpy(ids, meta + KLT_ID * C, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+    if (age) HIPCHECK(hipMemcpy(age, meta + KLT_AGE * C, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+    return n;
+}
+
+// steps 1 and 4 of a step for the lanes of `active`: the shift (k_begin_frame as a svo_process call without a run bit launches it, with
+// that call's host bookkeeping) and the selection.  fresh: the lanes whose points stand as they are
+static int klt_shift(svo_ctx* ctx, const LaneMask& active, const LaneMask& idle, hipStream_t st)
+{
+    DevCtx& d = ctx->dc;
+    const FrameCall shift = make_frame_call(0, ctx->params, ctx->faster_anms);
+    SadStep step = sad_window_step(ctx->sad, idle, shift);              // (no SAD stage runs: never a bad lane)
+    ctx->sad = std::move(step.next);
+    ctx->frame_active = active; ctx->frame_active_set = true;
+    for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];
+    d.fast_th = ctx->fast_th; d.orb_th = ctx->orb_th; d.det_ahead = 0;
+    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, nullptr, 0, step.drop_prev, st); }
+    return SVO_OK;
+}
+static void klt_select(svo_ctx* ctx, const LaneMask& active, const LaneMask& fresh, hipStream_t st)
+{
+    svo_ctx::Klt& k = ctx->klt; const DevCtx& d = ctx->dc;
+    KltSelectArgs a; memset(&a, 0, sizeof(a));
+    a.t = k.dev; a.half = k.half; a.fresh = fresh;
+    a.max_dy = k.p.max_dy; a.min_disp = k.p.min_disp; a.max_disp = k.p.max_disp; a.kp_size = (float)k.p.lk.win;
+    a.H = std::max(0, std::min(d.oh[0], d.max_h));
+    { Span s(ctx, KT_KLT_SELECT); launch_klt_select(d, a, st); }
+    k.half ^= 1; k.used = true;
+    for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) ctx->sad.cur[(size_t)l] = 0;      // lists without an image behind them: no SAD windows
+}
+
+extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t lanes[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    const svo_klt::Caps caps = klt_caps(ctx);
+    LaneMask active, idle; int w = 0, h = 0;
+    { std::string why; const int rc = svo_klt::check_klt_step(frames, flags, lanes, caps, klt_state(ctx), active, idle, w, h, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (!lane_any(active)) return SVO_OK;                   // nobody takes part: nothing is enqueued
+    const FrameCall opt = make_frame_call(SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT, ctx->params, ctx->faster_anms);
+    { std::string why; const int rc = check_frame_call(opt, ctx->params, active, nullptr, why); if (rc) { ctx->last_error = why; return rc; } }
+    { const int rc = ensure_geometry(ctx, w, h); if (rc) return rc; }
+    DevCtx& d = ctx->dc;
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    d.idle = idle;
+    IdleGuard idle_guard{ &d };
+    // 1. the shift
+    { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
+    // 2. the new pair of every active lane into the parity its last pair did not go to; images of another size than the last step's
+    //    cannot be tracked from it
+    if (w != k.w || h != k.h) { memset(&k.has_img, 0, sizeof(k.has_img)); k.w = w; k.h = h; }
+    const svo_lk::Geometry g = svo_klt::klt_geometry(k.p, w, h);
+    const hipMemcpyKind kind = (flags & SVO_FLAG_DEVICE_IMAGES) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    LaneMask fresh, empty = idle;
+    bool any_tracks = false;
+    for (int wd = 0; wd < 2; wd++) { k.parity.w[wd] ^= active.w[wd]; fresh.w[wd] = active.w[wd] & ~k.has_img.w[wd]; empty.w[wd] |= fresh.w[wd]; any_tracks |= (active.w[wd] & k.has_img.w[wd]) != 0; }
+    for (int l = 0; l < d.n_lanes; l++) {
+        if (!lane_in(active, l)) continue;
+        for (int sd = 0; sd < 2; sd++) {
+            const svo_image& im = sd ? frames[l].right : frames[l].left;
+            uint8_t* block = k.d_pyr + ((long long)((lane_in(k.parity, l) ? 1 : 0) * d.n_lanes + l) * 2 + sd) * k.plan.img_stride;
+            HIPCHECK(hipMemcpy2DAsync(block, (size_t)w, im.data, (size_t)im.stride, (size_t)w, (size_t)h, kind, st));
+        }
+    }
+    KltJobArgs ja; memset(&ja, 0, sizeof(ja));
+    ja.pyr_jobs = k.d_pyr_jobs; ja.trk_jobs = k.d_trk_jobs; ja.pyr = k.d_pyr; ja.img_stride = k.plan.img_stride;
+    ja.n_lanes = d.n_lanes; ja.cap = k.p.cap; ja.nl = g.nl;
+    for (int l = 0; l < g.nl; l++) { ja.w[l] = g.w[l]; ja.h[l] = g.h[l]; ja.off[l] = g.off[l]; }
+    ja.parity = k.parity; ja.empty = empty; ja.idle = idle;
+    { Span s(ctx, KT_LK_PYRDOWN); launch_klt_jobs(ja, st); for (int l = 1; l < g.nl; l++) launch_lk_pyrdown(k.d_pyr_jobs, d.n_lanes, l, g.w[l], g.h[l], st); }
+    // 3. one tracking launch over every lane's two jobs (and the way back under fb_max); no lane has a last pair: nothing to track
+    if (any_tracks) {
+        LkTrackArgs a;
+        a.jobs = k.d_trk_jobs; a.n_jobs = 2 * d.n_lanes; a.n_pts = 2 * d.n_lanes * k.p.cap;
+        a.pts = k.dev.pts[k.half]; a.aux = nullptr;
+        a.out = k.dev.out; a.status = k.dev.status; a.err = k.dev.err;
+        a.p = k.p.lk; a.backward = 0;
+        Span s(ctx, KT_LK_TRACK);
+        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
+        launch_lk_track(a, ppl, st);
+        if (k.p.lk.fb_max > 0.0f) {
+            LkTrackArgs b = a;
+            b.pts = k.dev.out; b.aux = k.dev.pts[k.half]; b.out = nullptr; b.err = nullptr; b.backward = 1;
+            launch_lk_track(b, ppl, st);
+        }
+    }
+    // 4. the selection
+    klt_select(ctx, active, fresh, st);
+    for (int wd = 0; wd < 2; wd++) k.has_img.w[wd] |= active.w[wd];
+    // 5. stage 5
+    if (flags & SVO_RUN_OPTIMIZE) enqueue_optimize(ctx, opt, st);
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status_l, const uint8_t* status_r, int n)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_debug_klt_select", lane, n, n <= 0 || (left_xy && right_xy && status_l && status_r), klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    if (!ctx->geom_ready) { ctx->last_error = "svo_debug_klt_select: no geometry yet: the row tables need the image size of a step or of put lists"; return SVO_ERR_STATE; }
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    KltLaneDev kl;
+    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
+    if (n != kl.n) { char msg[128]; snprintf(msg, sizeof(msg), "svo_debug_klt_select: n = %d, the lane's table holds %d tracks", n, kl.n); ctx->last_error = msg; return SVO_ERR_ARG; }
+    const uint64_t words[2] = { lane < 64 ? 1ull << lane : 0ull, lane >= 64 ? 1ull << (lane - 64) : 0ull };
+    LaneMask active, idle, fresh; std::string why;
+    parse_lane_mask(words, true, ctx->cfg.n_lanes, active, idle, why);
+    memset(&fresh, 0, sizeof(fresh));
+    DevCtx& d = ctx->dc;
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    const size_t C = (size_t)k.p.cap, o = (size_t)(2 * lane) * C;
+    if (n > 0) {
+        HIPCHECK(hipMemcpyAsync(k.dev.out + o, left_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(k.dev.out + o + C, right_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(k.dev.status + o, status_l, (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(k.dev.status + o + C, status_r, (size_t)n, hipMemcpyHostToDevice, st));
+    }
+    d.idle = idle;
+    IdleGuard idle_guard{ &d };
+    { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
+    klt_select(ctx, active, fresh, st);
+    HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays are free
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
 }
 
 // ---- Shi-Tomasi corner detection on caller images (svo_hip.h; the decisions: gftt_call.hpp, the kernels: k_gftt.hip) --------------

@@ -25,6 +25,8 @@
 #include <string>
 #include <vector>
 
+extern "C" void svo_internal_mark_frame_parallel(svo_ctx* ctx);      // svo_api.hip: not part of the public interface
+
 namespace {
 struct Err { std::string text; };
 int hip_fail(std::string& dst, const char* what, hipError_t e) { dst = std::string(what) + ": " + hipGetErrorString(e); return SVO_ERR_HIP; }
@@ -402,6 +404,7 @@ extern "C" int svo_fpstream_create(const svo_config* cfg, int n_contexts, svo_fp
         const int rc = svo_create(&c, &x);
         if (rc != SVO_OK) { f->last_error = std::string("svo_create: ") + svo_strerror(rc) + (x ? std::string(" [") + svo_last_error(x) + "]" : std::string()); if (x) svo_destroy(x); return rc; }
         f->ctx.push_back(x);
+        svo_internal_mark_frame_parallel(x);              // (svo_api.hip: the resident KLT front end refuses such a context)
         hipEvent_t e; BHIP(f, hipEventCreateWithFlags(&e, hipEventDisableTiming)); f->exported.push_back(e);
     }
     f->nbytes = svo_handover_bytes(f->ctx[0]);

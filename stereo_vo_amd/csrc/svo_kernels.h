@@ -153,3 +153,42 @@ struct GfttArgs {
 void launch_gftt_response(const GfttArgs& a, int max_w, int max_h, hipStream_t st);      // max_w x max_h: the largest image of the call
 void launch_gftt_candidates(const GfttArgs& a, int max_w, int max_h, hipStream_t st);
 void launch_gftt_select(const GfttArgs& a, hipStream_t st);
+// the resident KLT front end (k_klt.hip; the buffer plan: klt_call.hpp).  The table of a lane: cap slots, the first n of them live.
+struct KltLaneDev {
+    int n;                // live tracks
+    int next_id;          // the ID the next appended track gets
+    int seen_slot;        // LaneState::prev_slot as the front end saw it last: another value after k_begin_frame means the lane shifted
+    int pad;
+};
+enum { KLT_ID = 0, KLT_AGE, KLT_IDX, KLT_PIDX, KLT_META };     // the rows of a lane's meta block
+struct KltDev {
+    int n_lanes, cap;
+    float2* pts[2];       // [half][n_lanes][2 sides][cap]: NaN behind the live count
+    int* meta[2];         // [half][n_lanes][KLT_META][cap]: ID, age, index in the list of the last step, index in the previous slot's list (-1: none)
+    KltLaneDev* lane;     // [n_lanes]
+    float2* out; uint8_t* status; float* err;      // the tracker's results (or svo_debug_klt_select's arrays): [n_lanes][2 sides][cap]
+    int* appended;        // what the last k_klt_append launch appended
+};
+struct KltSelectArgs {
+    KltDev t; int half;   // the half that is read; the other one is written
+    LaneMask fresh;       // lanes without a last pair: their points stand as they are, status 1
+    float max_dy, min_disp, max_disp, kp_size;
+    int H;                // rows of the two row tables: min(octave-0 image height, DevCtx.max_h)
+};
+// the job records of a step, built on the device from the step's geometry: n_lanes pyramid records (img[0] / img[1] = the left / right
+// image of the NEW pair) and 2 * n_lanes tracking records (job 2 * lane + side: img[0] the side's last image, img[1] its new one).
+// parity: the pyramid buffer the lane's new pair is in; empty: lanes that track nothing (idle, or without a last pair) -- their
+// tracking records describe a 0 x 0 image, on which the tracker retires every point before it reads a pixel
+struct KltJobArgs {
+    LkJobDev* pyr_jobs; LkJobDev* trk_jobs;
+    uint8_t* pyr; long long img_stride;
+    int n_lanes, cap, nl;
+    int w[6], h[6]; long long off[6];
+    LaneMask parity, empty, idle;
+};
+size_t klt_select_lds_bytes(int H);
+void launch_klt_jobs(const KltJobArgs& a, hipStream_t st);
+void launch_klt_select(const DevCtx& c, const KltSelectArgs& a, hipStream_t st);
+void launch_klt_append(const KltDev& t, int half, int lane, const float2* left, const float2* right, int n, hipStream_t st);
+// empties the tables of the lanes of the mask in `half` and starts their IDs over
+void launch_klt_clear(const DevCtx& c, const KltDev& t, int half, const LaneMask& lanes, hipStream_t st);

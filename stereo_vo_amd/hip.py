@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import (CameraModel, FasterStats, GfttJob, GfttParams, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
+from .abi import (CameraModel, FasterStats, GfttJob, GfttParams, KltParams, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -33,6 +33,7 @@ EXPORTS = [
     "svo_put_features", "svo_put_matches", "svo_put_tracked", "svo_put_tracked_oct", "svo_put_match_ids", "svo_save_state", "svo_load_state", "svo_change_in_pose", "svo_projected_coords", "svo_hamming_match",
     "svo_lk_default_params", "svo_lk_track", "svo_debug_lk_get_level",
     "svo_gftt_default_params", "svo_gftt_detect", "svo_debug_gftt_get_response",
+    "svo_klt_default_params", "svo_klt_enable", "svo_klt_reset", "svo_klt_add_points", "svo_klt_step", "svo_klt_get_tracks", "svo_debug_klt_select",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -145,6 +146,14 @@ def lib():
             L.svo_gftt_default_params.restype = None; L.svo_gftt_default_params.argtypes = [C.c_void_p]
             L.svo_gftt_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
             L.svo_debug_gftt_get_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "svo_klt_step"):          # (as above)
+            L.svo_klt_default_params.restype = None; L.svo_klt_default_params.argtypes = [C.c_void_p]
+            L.svo_klt_enable.argtypes = [C.c_void_p, C.c_void_p]
+            L.svo_klt_reset.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            L.svo_klt_add_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+            L.svo_klt_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+            L.svo_klt_get_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.svo_debug_klt_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -221,6 +230,12 @@ def stereo_rectify(calib: StereoCalibration) -> StereoRectification:
 def default_lk_params() -> LkParams:
     p = LkParams()
     lib().svo_lk_default_params(C.byref(p))
+    return p
+
+
+def default_klt_params() -> KltParams:
+    p = KltParams()
+    lib().svo_klt_default_params(C.byref(p))
     return p
 
 
@@ -875,14 +890,78 @@ class Context:
         self._ck(self.L.svo_debug_gftt_get_response(self.h, int(job), _vp(out), n, C.byref(w), C.byref(h)), "svo_debug_gftt_get_response")
         return out
 
+    # -- the resident KLT front end (svo_klt_step) -----------------------------------------------------------------
+    def _words(self, active):
+        if active is None:
+            return None
+        w = list(lane_mask_words(active, self.n_lanes)) + [0]
+        return (C.c_uint64 * 2)(w[0], w[1])
+
+    def klt_enable(self, params=None):
+        """allocates the front end; params: a KltParams (None: the defaults, cap = min(1024, max_kps))"""
+        self._ck(self.L.svo_klt_enable(self.h, C.byref(params) if params is not None else None), "svo_klt_enable")
+
+    def klt_reset(self, active=None):
+        """empties the tables of the lanes of `active` (None: all) and forgets their last image pairs"""
+        self._ck(self.L.svo_klt_reset(self.h, self._words(active)), "svo_klt_reset")
+
+    def klt_add_points(self, lane, left_xy, right_xy):
+        """appends (left, right) point pairs ([n, 2] float32 each) to the lane's table; returns how many went in"""
+        l = np.ascontiguousarray(left_xy, np.float32).reshape(-1, 2)
+        r = np.ascontiguousarray(right_xy, np.float32).reshape(-1, 2)
+        if len(l) != len(r):
+            raise ValueError("%d left points but %d right points" % (len(l), len(r)))
+        return self._ck(self.L.svo_klt_add_points(self.h, int(lane), _vp(l), _vp(r), len(l)), "svo_klt_add_points")
+
+    def klt_step(self, frames, flags=RUN_OPTIMIZE, active=None, device=False, pinned=False):
+        """frames: one (left, right) pair per lane -- uint8 [h, w] numpy arrays (any row stride), or with device=True / pinned=True
+        (address, w, h, stride) tuples; the entries of lanes outside `active` are not read and may be None.  flags: RUN_OPTIMIZE or 0."""
+        assert len(frames) == self.n_lanes
+        fr = (Frame * self.n_lanes)()
+        keep = []
+        _, idle = self._mask(active)
+        for i, pr in enumerate(frames):
+            if i in idle:
+                continue
+            for s, im in enumerate(pr):
+                if device or pinned:
+                    rec = Image(int(im[0]), int(im[1]), int(im[2]), int(im[3]))
+                else:
+                    if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                        raise ValueError("lane %d: uint8 [h, w] images with contiguous rows are expected" % i)
+                    keep.append(im)
+                    rec = Image(im.ctypes.data, im.shape[1], im.shape[0], im.strides[0])
+                if s: fr[i].right = rec
+                else: fr[i].left = rec
+        flags = (flags & ~(FLAG_DEVICE_IMAGES | FLAG_PINNED_IMAGES)) | (FLAG_DEVICE_IMAGES if device else (FLAG_PINNED_IMAGES if pinned else 0))
+        self._ck(self.L.svo_klt_step(self.h, fr, C.c_uint32(flags), self._words(active)), "svo_klt_step")
+
+    def klt_tracks(self, lane=0):
+        """(left [n, 2] float32, right [n, 2] float32, ids [n] int32, age [n] int32) of the lane's live tracks.  Synchronises."""
+        n = self._ck(self.L.svo_klt_get_tracks(self.h, int(lane), None, None, None, None, 0), "svo_klt_get_tracks")
+        l, r = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        ids, age = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        if n:
+            self._ck(self.L.svo_klt_get_tracks(self.h, int(lane), _vp(l), _vp(r), _vp(ids), _vp(age), n), "svo_klt_get_tracks")
+        return l, r, ids, age
+
+    def klt_debug_select(self, lane, left_xy, right_xy, status_l, status_r):
+        """the shift and the selection of a step on one lane, with these arrays in place of the tracker's results (svo_debug_klt_select)"""
+        l = np.ascontiguousarray(left_xy, np.float32).reshape(-1, 2)
+        r = np.ascontiguousarray(right_xy, np.float32).reshape(-1, 2)
+        sl, sr = np.ascontiguousarray(status_l, np.uint8), np.ascontiguousarray(status_r, np.uint8)
+        if not (len(l) == len(r) == len(sl) == len(sr)):
+            raise ValueError("four arrays of one length are expected")
+        self._ck(self.L.svo_debug_klt_select(self.h, int(lane), _vp(l), _vp(r), _vp(sl), _vp(sr), len(l)), "svo_debug_klt_select")
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
     def kernel_times(self, appended=False):
         """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
         hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
-        "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, and "lk_pyrdown", "lk_track": svo_lk_track, each listed once
-        the context has made such a call) and are
+        "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, "lk_pyrdown", "lk_track": svo_lk_track and svo_klt_step, and
+        "klt_select": svo_klt_step, each listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
