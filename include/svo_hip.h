@@ -663,8 +663,8 @@ int svo_debug_gftt_get_response(svo_ctx* ctx, int job, float* out, int cap, int*
 /* A KLT FRONT END RESIDENT ON THE DEVICE: a per-context track table and one call per frame that follows every lane's tracks into the
  * new stereo pair with the tracker of svo_lk_track, gates and compacts them, writes the lane's current-frame lists as the
  * precomputed-data bypass would, and optionally runs stage 5.  Nothing synchronises inside a step.  The selectors SVO_DM_KLT and
- * SVO_IFM_OPTICAL_FLOW stay refused by svo_process.  Detection of new points stays with the caller: top up with svo_klt_get_tracks,
- * svo_gftt_detect (the tracks as seeds), svo_lk_track (left to right) and svo_klt_add_points.
+ * SVO_IFM_OPTICAL_FLOW stay refused by svo_process.  Tracks only die in a step: svo_klt_topup (below) replaces them on the device; the host
+ * recipe it equals is svo_klt_get_tracks, svo_gftt_detect (the tracks as seeds), svo_lk_track (left to right) and svo_klt_add_points.
  * THE CONTRACT: after a step every getter of the lane -- keypoints, pairings, tracked pairs, pairing IDs, both row tables, the values
  * record, the result with residuals and outliers -- returns, byte for byte, what this host recipe leaves: a call that only shifts
  * (svo_process_lanes with no run bit), svo_lk_track with svo_klt_params.lk on the lane's (left[t-1], left[t], left points) and
@@ -712,6 +712,46 @@ int svo_klt_get_tracks(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, 
 int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy,
                          const uint8_t* status_l, const uint8_t* status_r, int n);
 
+/* THE TOP-UP OF THE KLT FRONT END, RESIDENT ON THE DEVICE: tracks only die in svo_klt_step; svo_klt_topup replaces them without a host
+ * round trip.  One call looks at every lane of the mask, decides ON THE DEVICE which of them have thinned, detects new corners there
+ * with the detector of svo_gftt_detect (the live tracks as seeds), finds their partners in the right image with the tracker of
+ * svo_lk_track, gates the pairs and appends the survivors to the lane's table.  Nothing synchronises inside the call and the host
+ * reads nothing back.
+ * THE CONTRACT: after a svo_klt_topup call and svo_wait, svo_klt_get_tracks (points, IDs, ages, count) of every lane, and every getter
+ * after any later svo_klt_step, return byte for byte what this host recipe leaves, lane by lane for the lanes of the mask that have a
+ * last pair in the front end, n being the lane's live count:
+ *   1. n >= below: nothing happens.  Otherwise want = max(min(target, cap) - n, 0);
+ *   2. svo_gftt_detect with one job: the left level-0 image of the lane's last pair, tightly packed, as the last svo_klt_step copied
+ *      it; seeds = the n live left points; the job's cap = want; the parameters `gftt`;
+ *   3. svo_lk_track with one job: (left, right) of that last pair, pts = the new corners, init = the corners shifted by
+ *      (-init_disp, 0) in float32, the parameters svo_klt_params.lk as enabled (fb_max included: the left-right-left check);
+ *   4. the gate of svo_klt_step item 4 on (corner, partner): status 1, four finite coordinates, |yl - yr| <= max_dy and
+ *      min_disp <= xl - xr <= max_disp (float32 compares as written);
+ *   5. svo_klt_add_points with the survivors in walk order: fresh IDs from the lane's next ID, age 0, no indices; what lies beyond cap
+ *      is dropped.
+ * A lane outside the mask, at or above `below`, or without a last pair (never stepped, or reset since) keeps its table bit for bit,
+ * the NaN tail included.  Lane lists, records, results, stage 5 outputs and the pyramids are never touched.  tests/klt_topup_ref.py
+ * holds the recipe.
+ * svo_klt_topup_info (synchronises): info[0] corners detected, info[1] candidates before the distance rule, info[2] tracks appended,
+ * info[3] why, for the lane in the last call: 0 topped up; 1 more candidates than max(1024, svo_config.max_cand), nothing is written,
+ * as in svo_gftt_detect; 2 not below the threshold; 3 no last pair; 4 not in the mask.
+ * svo_klt_topup_enable allocates the top-up's own buffers (NULL: the defaults), the response maps among them: 4 bytes per pixel for
+ * n_lanes images of max_w x max_h; a context that never calls it allocates and launches nothing for the top-up.  svo_gftt_detect and
+ * svo_lk_track calls made in between are undisturbed, and their debug getters keep answering for the caller's last call.  A
+ * svo_klt_enable that re-makes the front end's buffers (other parameters, empty tables) drops the top-up: enable it again.
+ * svo_debug_klt_topup_append runs items 4 and 5 alone on ONE lane with the caller's arrays in place of the detector's corners and the
+ * tracker's results (0 <= n <= cap; no threshold applies); it synchronises.
+ * Refusals, all before anything is enqueued, with the outputs untouched and a text in svo_last_error: SVO_ERR_STATE when the front end
+ * or the top-up is not enabled, inside a captured graph, or when svo_klt_topup_enable is called again with other parameters after a
+ * top-up has run while a table holds tracks; SVO_ERR_ARG / SVO_ERR_CAPACITY for parameters out of range (the gftt ranges of
+ * svo_types.h, below or target outside 1 .. cap, a non-finite init_disp), a mask bit at or above n_lanes, a context whose max_cand
+ * exceeds 2^24 (capacity), and a response-map buffer the device cannot provide (capacity). */
+void svo_klt_topup_default_params(const svo_ctx* ctx, svo_klt_topup_params* p);   /* needs cap: after svo_klt_enable (before: cap = min(1024, max_kps)) */
+int svo_klt_topup_enable(svo_ctx* ctx, const svo_klt_topup_params* p);
+int svo_klt_topup(svo_ctx* ctx, const uint64_t lanes[2] /* NULL = all lanes */);
+int svo_klt_topup_info(svo_ctx* ctx, int lane, int32_t info[4]);
+int svo_debug_klt_topup_append(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status, int n);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -741,7 +781,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * "gftt_response", "gftt_candidates" and "gftt_select" are appended behind whatever that rule lists, once the context has made a
  * svo_gftt_detect call; "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call or a svo_klt_step
  * (whose pyramid and tracking launches count there); "klt_select" behind the lk names, once the context has made a svo_klt_step or a
- * svo_debug_klt_select. */
+ * svo_debug_klt_select; "klt_topup" behind that, once the context has made a svo_klt_topup or svo_debug_klt_topup_append call (its
+ * three kernels count there, its detector and tracker launches under the gftt and lk names, which are then listed as well, and
+ * "klt_select" with them). */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

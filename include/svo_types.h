@@ -295,6 +295,19 @@ typedef struct svo_gftt_params {
     float quality;
 } svo_gftt_params;
 
+/* The parameters of the resident top-up of the KLT front end (svo_klt_topup_enable, svo_hip.h).  svo_klt_topup_default_params fills in
+ * the defaults, which depend on the front end's cap.
+ *   gftt        the detector's parameters, as svo_gftt_detect takes them and with the same ranges
+ *   below       a lane is topped up only while its live count < below: 1 .. cap (default (cap + 1) / 2)
+ *   target      ... up to this many tracks: 1 .. cap (default cap)
+ *   init_disp   the first guess of a new corner (x, y) in the right image is (x - init_disp, y): finite (default 0) */
+typedef struct svo_klt_topup_params {
+    svo_gftt_params gftt;
+    int32_t below;
+    int32_t target;
+    float init_disp;
+} svo_klt_topup_params;
+
 #ifdef __cplusplus
 }
 #endif

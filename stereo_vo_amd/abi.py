@@ -199,6 +199,18 @@ class GfttJob(C.Structure):
 
 assert C.sizeof(GfttParams) == 16 and C.sizeof(GfttJob) == 64
 
+
+class KltTopupParams(C.Structure):
+    """svo_klt_topup_params (include/svo_types.h): the detector's parameters, the live count below which a lane is topped up, the count
+    it is topped up to, and the disparity of a new corner's first guess in the right image"""
+    _fields_ = [("gftt", GfttParams), ("below", C.c_int32), ("target", C.c_int32), ("init_disp", C.c_float)]
+
+
+assert C.sizeof(KltTopupParams) == 28
+
+# svo_klt_topup_info: info[3]
+TOPUP_OK, TOPUP_OVERFLOW, TOPUP_ENOUGH, TOPUP_NO_PAIR, TOPUP_NOT_ASKED = range(5)
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

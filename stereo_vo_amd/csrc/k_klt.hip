@@ -1,6 +1,8 @@
 // k_klt.hip -- the resident KLT front end on the device (svo_hip.h: svo_klt_step): the job records of a step (k_klt_jobs), the gate and
 // stable compaction that turn the tracker's results into a lane's current-frame lists (k_klt_select), the append behind
 // svo_klt_add_points (k_klt_append) and the table reset (k_klt_clear).  The tracker itself is k_lk.hip's, launched as it is.
+// Behind them the top-up of svo_klt_topup: the detector's records decided on the device (k_klt_topup_jobs), the tracker's records and
+// first guesses (k_klt_topup_prepare), the gate and the append (k_klt_topup_append), around k_gftt.hip's and k_lk.hip's kernels.
 //
 // k_klt_select is the walk of tests/klt_ref.py and leaves what svo_put_features_oct / svo_put_matches_oct / svo_put_match_ids_oct /
 // svo_put_tracked_oct leave for the same lists (svo_api.hip), row tables included.
@@ -236,4 +238,131 @@ void launch_klt_jobs(const KltJobArgs& a, hipStream_t st)
 {
     if (a.n_lanes <= 0) return;
     hipLaunchKernelGGL(k_klt_jobs, dim3((unsigned)((3 * a.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a);
+}
+
+// ---- svo_klt_topup ------------------------------------------------------------------------------------------------------------
+// The detector (k_gftt.hip) and the tracker (k_lk.hip) are launched as they are, on records these kernels write: which lanes take part
+// is decided here from KltLaneDev.n, never on the host.
+//
+// k_klt_topup_jobs: thread l writes lane l's detector record and the reason the lane sits out, if it does.  Such a lane gets a 0 x 0
+// image and cap 0: its blocks of k_gftt_response and k_gftt_candidates leave on their first lines, and k_gftt_select finds no candidate
+// and writes a count of 0.  The seeds are the lane's live left points where they lie in the table.
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_topup_jobs(const KltTopupArgs a)
+{
+    const int lane = blockIdx.x * KLT_BLOCK + threadIdx.x;
+    if (lane >= a.t.n_lanes) return;
+    const int cap = a.t.cap;
+    int n = a.t.lane[lane].n;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    const int reason = !lane_bit(a.lanes, lane) ? KLT_TOPUP_NOT_ASKED : !lane_bit(a.has_img, lane) ? KLT_TOPUP_NO_PAIR : n >= a.below ? KLT_TOPUP_ENOUGH : KLT_TOPUP_OK;
+    const bool run = reason == KLT_TOPUP_OK;
+    const int goal = a.target < cap ? a.target : cap, want = goal > n ? goal - n : 0;
+    const int par = lane_bit(a.parity, lane) ? 1 : 0;
+    GfttJobDev& J = a.gjobs[lane];
+    J.img = run ? a.pyr + ((long long)(par * a.t.n_lanes + lane) * 2 + 0) * a.img_stride + a.off[0] : nullptr;
+    J.map = a.map + (long long)lane * a.map_stride;
+    J.pitch = run ? a.w[0] : 0; J.w = run ? a.w[0] : 0; J.h = run ? a.h[0] : 0;
+    J.seed0 = lane * 2 * cap; J.n_seeds = run ? n : 0; J.pts0 = lane * cap; J.cap = run ? want : 0;
+    J.cell = a.cell; J.gw = run ? a.gw : 0; J.gh = run ? a.gh : 0;
+    for (int k = 0; k < 4; k++) { a.ginfo[4 * lane + k] = 0; a.tinfo[4 * lane + k] = k == 3 ? reason : 0; }
+}
+
+void launch_klt_topup_jobs(const KltTopupArgs& a, hipStream_t st)
+{
+    if (a.t.n_lanes <= 0) return;
+    hipLaunchKernelGGL(k_klt_topup_jobs, dim3((unsigned)((a.t.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a);
+}
+
+// k_klt_topup_prepare, behind k_gftt_select: one thread per slot writes the slot's first guess -- the corner shifted by (-init_disp, 0),
+// NaN behind the detector's count, on which the tracker retires the slot before it reads a pixel --, and the thread of a lane's slot 0
+// writes the lane's tracking record (left -> right of the lane's last pair), in place
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_topup_prepare(const KltTopupArgs a)
+{
+    const int cap = a.t.cap;
+    const int g = blockIdx.x * KLT_BLOCK + threadIdx.x;
+    if (g >= a.t.n_lanes * cap) return;
+    const int lane = g / cap, slot = g - lane * cap;
+    const bool run = a.tinfo[4 * lane + 3] == KLT_TOPUP_OK && a.ginfo[4 * lane + 2] == 0;
+    const int cnt = run ? a.ginfo[4 * lane + 0] : 0;
+    float2 q = make_float2(NAN, NAN);
+    if (slot < cnt) { const float2 p = a.corners[g]; q = make_float2(__fsub_rn(p.x, a.init_disp), p.y); }
+    a.init[g] = q;
+    if (slot != 0) return;
+    const int par = lane_bit(a.parity, lane) ? 1 : 0;
+    LkJobDev& J = a.lk_jobs[lane];
+    for (int s = 0; s < 2; s++) for (int l = 0; l < 6; l++) { J.img[s][l] = nullptr; J.pitch[s][l] = 0; }
+    for (int l = 0; l < 6; l++) { J.w[l] = 0; J.h[l] = 0; }
+    J.pt0 = lane * cap; J.n = cnt; J.has_init = 1;
+    J.nl = cnt > 0 ? a.nl : 1;
+    if (cnt <= 0) return;
+    for (int l = 0; l < a.nl; l++) {
+        J.w[l] = a.w[l]; J.h[l] = a.h[l]; J.pitch[0][l] = a.w[l]; J.pitch[1][l] = a.w[l];
+        for (int s = 0; s < 2; s++) J.img[s][l] = a.pyr + ((long long)(par * a.t.n_lanes + lane) * 2 + s) * a.img_stride + a.off[l];
+    }
+}
+
+void launch_klt_topup_prepare(const KltTopupArgs& a, hipStream_t st)
+{
+    const long long n = (long long)a.t.n_lanes * a.t.cap;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_klt_topup_prepare, dim3((unsigned)((n + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a);
+}
+
+// k_klt_topup_append, behind the tracker: one block per lane.  The gate of k_klt_select on (corner, partner), the stable compaction of
+// its scheme -- chunks of 256 in slot order, ballot + popcount inside a wave, the wave totals through LDS --, and the append of
+// k_klt_append behind the live count: fresh IDs, age 0, no indices, nothing beyond cap.  Thread 0 writes the lane words and the record
+// of svo_klt_topup_info.  A lane that sits out is not touched.
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_topup_append(const KltTopupArgs a, int only_lane)
+{
+    __shared__ int wsurv[KLT_WAVES];
+    const int lane = only_lane >= 0 ? only_lane : blockIdx.x, tid = threadIdx.x, wave = tid >> 6, wl = tid & 63;
+    const int cap = a.t.cap;
+    int* tinfo = a.tinfo + 4 * lane;
+    const int* ginfo = a.ginfo + 4 * lane;
+    if (tinfo[3] != KLT_TOPUP_OK) return;                              // block-uniform
+    if (ginfo[2] != 0) { if (tid == 0) { tinfo[0] = 0; tinfo[1] = ginfo[1]; tinfo[2] = 0; tinfo[3] = KLT_TOPUP_OVERFLOW; } return; }
+    const KltLaneDev kl = a.t.lane[lane];
+    const int n0 = kl.n < cap ? (kl.n < 0 ? 0 : kl.n) : cap;
+    const int cnt = ginfo[0] < cap ? ginfo[0] : cap;
+    float2* pts = a.t.pts[a.half] + (size_t)lane * 2 * cap;
+    int* meta = a.t.meta[a.half] + (size_t)lane * KLT_META * cap;
+    const float2* __restrict__ cl = a.corners + (size_t)lane * cap, * __restrict__ cr = a.out + (size_t)lane * cap;
+    const uint8_t* __restrict__ st = a.status + (size_t)lane * cap;
+    int n_surv = 0;                                                    // the running base: block-uniform
+    for (int base = 0; base < cnt; base += KLT_BLOCK) {
+        const int slot = base + tid;
+        float2 pl = make_float2(0.0f, 0.0f), pr = pl;
+        bool ok = false;
+        if (slot < cnt) {
+            pl = cl[slot]; pr = cr[slot];
+            const float disp = pl.x - pr.x;
+            ok = st[slot] == 1 && klt_finite(pl.x) && klt_finite(pl.y) && klt_finite(pr.x) && klt_finite(pr.y)
+                 && fabsf(pl.y - pr.y) <= a.max_dy && disp >= a.min_disp && disp <= a.max_disp;
+        }
+        const unsigned long long bs = __ballot(ok);
+        if (wl == 63) wsurv[wave] = __popcll(bs);
+        __syncthreads();
+        int i = n_surv + __popcll(bs & ((1ull << wl) - 1ull)), tot = 0;
+#pragma unroll
+        for (int w = 0; w < KLT_WAVES; w++) { if (w < wave) i += wsurv[w]; tot += wsurv[w]; }
+        if (ok && n0 + i < cap) {
+            pts[n0 + i] = pl; pts[cap + n0 + i] = pr;
+            meta[KLT_ID * cap + n0 + i] = kl.next_id + i; meta[KLT_AGE * cap + n0 + i] = 0;
+            meta[KLT_IDX * cap + n0 + i] = -1; meta[KLT_PIDX * cap + n0 + i] = -1;
+        }
+        n_surv += tot;
+        __syncthreads();                       // the per-wave words are free for the next chunk; every thread has read the lane words
+    }
+    __syncthreads();                           // (a lane without corners ran no chunk: every thread has read the lane words here too)
+    if (tid == 0) {
+        const int m = n_surv < cap - n0 ? n_surv : cap - n0;
+        a.t.lane[lane].n = n0 + m; a.t.lane[lane].next_id = kl.next_id + m;
+        tinfo[0] = cnt; tinfo[1] = ginfo[1]; tinfo[2] = m; tinfo[3] = KLT_TOPUP_OK;
+    }
+}
+
+void launch_klt_topup_append(const KltTopupArgs& a, int only_lane, hipStream_t st)
+{
+    if (a.t.n_lanes <= 0) return;
+    hipLaunchKernelGGL(k_klt_topup_append, dim3(only_lane >= 0 ? 1u : (unsigned)a.t.n_lanes), dim3(KLT_BLOCK), 0, st, a, only_lane);
 }

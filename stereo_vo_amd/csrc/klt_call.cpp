@@ -1,11 +1,13 @@
 // klt_call.cpp -- the decisions of the resident KLT front end that need no device (klt_call.hpp).  Host only, built with g++.
 #include "klt_call.hpp"
+#include "gftt_call.hpp"
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
 static_assert(sizeof(svo_klt_params) == 40, "svo_klt_params: svo_lk_params (24 bytes), cap and three floats");
+static_assert(sizeof(svo_klt_topup_params) == 28, "svo_klt_topup_params: svo_gftt_params (16 bytes), two counts and a float");
 
 namespace svo_klt {
 
@@ -116,6 +118,91 @@ Plan plan_klt(const svo_klt_params& p, const Caps& caps)
     pl.meta_ints = (long long)caps.n_lanes * 4 * p.cap;
     pl.n_pyr_jobs = caps.n_lanes; pl.n_trk_jobs = 2 * caps.n_lanes;
     pl.select_lds_bytes = 3ll * (caps.max_h + 1) * (long long)sizeof(int32_t);
+    return pl;
+}
+
+// ---- the resident top-up ----
+svo_klt_topup_params topup_default_params(int cap)
+{
+    svo_klt_topup_params r;
+    svo_gftt_default_params(&r.gftt);
+    r.below = (cap + 1) / 2; r.target = cap; r.init_disp = 0.0f;
+    return r;
+}
+
+int check_topup_params(const svo_klt_topup_params& p, const Caps& caps, const TopupCaps& tc, std::string& why)
+{
+    char msg[200]; msg[0] = 0;
+    if (const int rc = svo_gftt::check_gftt_params(p.gftt, why)) return rc;
+    why.clear();
+    int rc = SVO_ERR_ARG;
+    if (p.gftt.max_corners > caps.max_kps) { snprintf(msg, sizeof(msg), "max_corners %d, svo_config.max_kps is %d", p.gftt.max_corners, caps.max_kps); rc = SVO_ERR_CAPACITY; }
+    else if (p.below < 1 || p.below > tc.cap) snprintf(msg, sizeof(msg), "below %d: 1 .. cap = %d is expected", p.below, tc.cap);
+    else if (p.target < 1 || p.target > tc.cap) snprintf(msg, sizeof(msg), "target %d: 1 .. cap = %d is expected", p.target, tc.cap);
+    else if (!isfinite(p.init_disp)) snprintf(msg, sizeof(msg), "init_disp %g: a finite value is expected", (double)p.init_disp);
+    else if (tc.max_cand > svo_gftt::GFTT_MAX_CAND_CAP) {
+        snprintf(msg, sizeof(msg), "svo_config.max_cand %d: the detector sorts at most %d candidates per lane", tc.max_cand, (int)svo_gftt::GFTT_MAX_CAND_CAP);
+        rc = SVO_ERR_CAPACITY;
+    }
+    if (!msg[0]) return SVO_OK;
+    why = msg; return rc;
+}
+
+int check_topup_enable(const svo_klt_topup_params& p, const Caps& caps, const TopupCaps& tc, const State& s, bool topup_enabled,
+                       const svo_klt_topup_params& in_force, bool has_run, bool tables_empty, bool& realloc, bool& adopt, std::string& why)
+{
+    realloc = adopt = false;
+    why.clear();
+    if (!s.enabled) { why = "svo_klt_topup_enable: the KLT front end is not enabled (svo_klt_enable)"; return SVO_ERR_STATE; }
+    if (s.capturing) { why = "svo_klt_topup_enable: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (const int rc = check_topup_params(p, caps, tc, why)) return rc;
+    if (!topup_enabled) { realloc = true; return SVO_OK; }
+    if (memcmp(&p, &in_force, sizeof(p)) == 0) return SVO_OK;
+    if (has_run && !tables_empty) { why = "the top-up has run with other parameters and a lane's table holds tracks: svo_klt_reset every lane first"; return SVO_ERR_STATE; }
+    adopt = true;                                 // (no buffer is sized by these parameters)
+    return SVO_OK;
+}
+
+int check_topup_ready(const State& s, bool topup_enabled, const char* entry, std::string& why)
+{
+    char msg[200];
+    why.clear();
+    if (!s.enabled) { snprintf(msg, sizeof(msg), "%s: the KLT front end is not enabled (svo_klt_enable)", entry); why = msg; return SVO_ERR_STATE; }
+    if (!topup_enabled) { snprintf(msg, sizeof(msg), "%s: the top-up is not enabled (svo_klt_topup_enable)", entry); why = msg; return SVO_ERR_STATE; }
+    if (s.capturing) { snprintf(msg, sizeof(msg), "%s: the context's stream is capturing a graph: the call cannot run inside one", entry); why = msg; return SVO_ERR_STATE; }
+    return SVO_OK;
+}
+
+int check_topup_call(const State& s, bool topup_enabled, const uint64_t* lanes, const Caps& caps, LaneMask& active, std::string& why)
+{
+    LaneMask idle;
+    memset(&active, 0, sizeof(active));
+    if (const int rc = check_topup_ready(s, topup_enabled, "svo_klt_topup", why)) return rc;
+    if (!svo_call::parse_lane_mask(lanes, false, caps.n_lanes, active, idle, why)) return SVO_ERR_ARG;
+    return SVO_OK;
+}
+
+int check_topup_lane_call(const State& s, bool topup_enabled, const char* entry, int lane, int n, bool arrays_ok, const Caps& caps, const TopupCaps& tc, std::string& why)
+{
+    char msg[200];
+    if (const int rc = check_topup_ready(s, topup_enabled, entry, why)) return rc;
+    if (lane < 0 || lane >= caps.n_lanes) { snprintf(msg, sizeof(msg), "%s: lane %d of %d", entry, lane, caps.n_lanes); why = msg; return SVO_ERR_ARG; }
+    if (n < 0 || !arrays_ok) { snprintf(msg, sizeof(msg), "%s: %d entries at %s", entry, n, arrays_ok ? "an address" : "NULL"); why = msg; return SVO_ERR_ARG; }
+    if (n > tc.cap) { snprintf(msg, sizeof(msg), "%s: %d entries, a lane's table holds cap = %d", entry, n, tc.cap); why = msg; return SVO_ERR_ARG; }
+    return SVO_OK;
+}
+
+TopupPlan plan_topup(const svo_klt_params& kp, const Caps& caps, const TopupCaps& tc)
+{
+    TopupPlan pl;
+    pl.map_stride = ((long long)caps.max_w * caps.max_h + 63) / 64 * 64;
+    pl.map_floats = pl.map_stride * caps.n_lanes;
+    pl.cand_cap = svo_gftt::gftt_cand_cap(tc.max_cand); pl.key_stride = svo_gftt::gftt_key_stride(pl.cand_cap);
+    pl.items_stride = (5ll * pl.cand_cap + 2ll * kp.cap + 3) / 4 * 4;
+    pl.n_keys = (long long)caps.n_lanes * pl.key_stride; pl.n_items = (long long)caps.n_lanes * pl.items_stride;
+    pl.n_state = (long long)caps.n_lanes * pl.cand_cap;
+    pl.n_pts = (long long)caps.n_lanes * kp.cap;
+    pl.n_jobs = caps.n_lanes;
     return pl;
 }
 

@@ -55,4 +55,39 @@ Plan plan_klt(const svo_klt_params& p, const Caps& caps);
 // the geometry of a step's images (every lane has the same size)
 svo_lk::Geometry klt_geometry(const svo_klt_params& p, int w, int h);
 
+// ---- the resident top-up (svo_klt_topup_enable / svo_klt_topup / svo_klt_topup_info / svo_debug_klt_topup_append) ----
+// what the top-up asks of the context besides Caps: the front end's cap and svo_config.max_cand
+struct TopupCaps { int cap, max_cand; };
+// the defaults for a front end of `cap` tracks per lane: the detector's defaults, below = (cap + 1) / 2, target = cap, init_disp = 0
+svo_klt_topup_params topup_default_params(int cap);
+// the ranges of svo_klt_topup_params: the gftt ranges (max_corners against max_kps is a capacity), below and target in 1 .. cap, a
+// finite init_disp (SVO_ERR_ARG), a context whose max_cand exceeds 2^24 (SVO_ERR_CAPACITY, as svo_gftt_detect has it)
+int check_topup_params(const svo_klt_topup_params& p, const Caps& caps, const TopupCaps& tc, std::string& why);
+// svo_klt_topup_enable, in order: the front end enabled and no capture (SVO_ERR_STATE), the parameters, then -- for a top-up that is
+// enabled already -- other parameters than those in force after a top-up has run while a table holds tracks (SVO_ERR_STATE).
+// realloc: the call must make the buffers; adopt: only the parameters change
+int check_topup_enable(const svo_klt_topup_params& p, const Caps& caps, const TopupCaps& tc, const State& s, bool topup_enabled,
+                       const svo_klt_topup_params& in_force, bool has_run, bool tables_empty, bool& realloc, bool& adopt, std::string& why);
+// what svo_klt_topup, svo_klt_topup_info and svo_debug_klt_topup_append ask first: both enabled, not inside a capture
+int check_topup_ready(const State& s, bool topup_enabled, const char* entry, std::string& why);
+// svo_klt_topup: ready, then the mask (NULL = all lanes)
+int check_topup_call(const State& s, bool topup_enabled, const uint64_t* lanes, const Caps& caps, LaneMask& active, std::string& why);
+// svo_klt_topup_info / svo_debug_klt_topup_append: ready, the lane, the arrays, 0 <= n <= cap
+int check_topup_lane_call(const State& s, bool topup_enabled, const char* entry, int lane, int n, bool arrays_ok, const Caps& caps, const TopupCaps& tc, std::string& why);
+
+// the buffers of an enabled top-up, its own (svo_gftt_detect's and svo_lk_track's are not touched):
+//   maps       n_lanes response maps of map_stride floats (max_w x max_h rounded up to 64 floats): the large one
+//   detector   per lane cand_cap candidates in a row of key_stride 64-bit keys, items_stride ints of cell lists (seed capacity = cap),
+//              cand_cap state bytes, 4 counters
+//   points     corners, responses, first guesses, tracked points, status, error: n_lanes * cap each
+//   jobs       n_lanes detector records and n_lanes tracking records; 4 ints of svo_klt_topup_info per lane
+struct TopupPlan {
+    long long map_stride, map_floats;
+    int cand_cap, key_stride; long long items_stride;
+    long long n_keys, n_items, n_state;
+    long long n_pts;
+    int n_jobs;
+};
+TopupPlan plan_topup(const svo_klt_params& kp, const Caps& caps, const TopupCaps& tc);
+
 }

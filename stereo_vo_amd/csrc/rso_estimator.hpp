@@ -338,7 +338,7 @@ public:
      *  caller would otherwise assemble from trackOpticalFlow and the precomputed-data bypass, without leaving the device.
      *  enableKLT allocates it (NULL: the defaults); addKLTPoints appends (left, right) pairs and returns how many went in; stepKLT takes
      *  the new 8-bit grey host images (stride in bytes, 0 = w), runs stage 5 when `optimize` is set and leaves the increment where
-     *  processNewImagePair leaves it (svo_get_result); getKLTTracks returns the live tracks, the seeds of a detectGoodFeatures top-up. */
+     *  processNewImagePair leaves it (svo_get_result); getKLTTracks returns the live tracks, the seeds of a detectGoodFeatures top-up by hand (topUpKLT below does it on the device). */
     void enableKLT(const svo_klt_params* klt_params = NULL) { check(svo_klt_enable(m_ctx, klt_params), "svo_klt_enable"); }
     int addKLTPoints(const std::vector<TPixelCoordf>& left, const std::vector<TPixelCoordf>& right) {
         const size_t n = left.size() < right.size() ? left.size() : right.size();
@@ -361,6 +361,14 @@ public:
         for (size_t i = 0; i < ids.size(); i++) { left[i] = TPixelCoordf(l[2 * i], l[2 * i + 1]); right[i] = TPixelCoordf(r[2 * i], r[2 * i + 1]); }
         return n;
     }
+    /** The top-up of the resident front end (svo_klt_topup_enable / svo_klt_topup): tracks only die in stepKLT; topUpKLT replaces them
+     *  on the device -- new corners where the live tracks leave room, their partners in the right image, the gate, the append -- when
+     *  the table has thinned below topup_params->below, without synchronising.  enableKLTTopUp allocates (NULL: below = (cap + 1) / 2,
+     *  target = cap, the detector's defaults, init_disp 0); getKLTTopUpInfo waits and returns what the last topUpKLT did: corners
+     *  detected, candidates, tracks appended, and why (0 topped up, 1 candidate overflow, 2 not below the threshold, 3 no last pair). */
+    void enableKLTTopUp(const svo_klt_topup_params* topup_params = NULL) { check(svo_klt_topup_enable(m_ctx, topup_params), "svo_klt_topup_enable"); }
+    void topUpKLT() { check(svo_klt_topup(m_ctx, NULL), "svo_klt_topup"); }
+    void getKLTTopUpInfo(int32_t info[4]) { check(svo_klt_topup_info(m_ctx, 0, info), "svo_klt_topup_info"); }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

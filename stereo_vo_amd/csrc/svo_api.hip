@@ -45,7 +45,8 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        KT_COUNT,
        // the resident KLT front end: "klt_select", listed behind the LK names once the context has made a step.  Behind KT_COUNT: the
        // name lives outside kt_names (kt_name below), whose last entries stay the LK ones
-       KT_KLT_SELECT = KT_COUNT, KT_ALL };
+       // ... and "klt_topup" behind it, once the context has topped up (the three kernels of k_klt.hip around the detector and the tracker)
+       KT_KLT_SELECT = KT_COUNT, KT_KLT_TOPUP, KT_ALL };
 static_assert(KT_ALL <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
@@ -55,6 +56,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
 static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
+static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : kt_name(i); }
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -137,6 +139,12 @@ struct svo_ctx {
         bool enabled, used; svo_klt_params p; svo_klt::Plan plan;
         KltDev dev; uint8_t* d_pyr; LkJobDev* d_pyr_jobs, * d_trk_jobs; float2* d_stage;
         int half, w, h; LaneMask parity, has_img;
+        // the resident top-up (svo_klt_topup_enable; the plan: klt_call.hpp), buffers of its own: the response maps, the detector's job
+        // records, keys, cell lists, states and counters, the corners with their responses, the first guesses, the tracker's records and
+        // results, four ints per lane for svo_klt_topup_info.  topup_used: a top-up has run (svo_kernel_times, svo_klt_topup_enable)
+        bool topup_enabled, topup_used; svo_klt_topup_params tp; svo_klt::TopupPlan tplan;
+        float* d_tmap; GfttJobDev* d_tgjobs; unsigned long long* d_tkeys; int* d_titems; uint8_t* d_tstate; int* d_tginfo, * d_tinfo;
+        float2* d_tcorners, * d_tinit, * d_tout; float* d_tresp, * d_terr; uint8_t* d_tstatus; LkJobDev* d_tlk_jobs;
     } klt;
     bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
     bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
@@ -1283,14 +1291,19 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     int n = ctx->landmarks ? KT_LANDMARKS + 1 : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
     for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
     // the three names of svo_gftt_detect behind whatever was listed, once the context has made such a call
-    for (int k = KT_GFTT_RESPONSE; ctx->gftt_used && k <= KT_GFTT_SELECT; k++, n++)
+    for (int k = KT_GFTT_RESPONSE; (ctx->gftt_used || ctx->klt.topup_used) && k <= KT_GFTT_SELECT; k++, n++)
         if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
     // "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call
-    for (int k = KT_LK_PYRDOWN; (ctx->lk_used || ctx->klt.used) && k <= KT_LK_TRACK; k++, n++)
+    for (int k = KT_LK_PYRDOWN; (ctx->lk_used || ctx->klt.used || ctx->klt.topup_used) && k <= KT_LK_TRACK; k++, n++)
         if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
     // "klt_select" behind the LK names (which a step counts its pyramid and tracking launches under), once the context has made a step
-    if (ctx->klt.used) {
+    if (ctx->klt.used || ctx->klt.topup_used) {
         if (n < cap) { if (names) names[n] = kt_name(KT_KLT_SELECT); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_SELECT]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_SELECT]; }
+        n++;
+    }
+    // "klt_topup" behind it, once the context has topped up (the detector and tracker launches of a top-up count under their own names)
+    if (ctx->klt.topup_used) {
+        if (n < cap) { if (names) names[n] = kt_name_all(KT_KLT_TOPUP); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_TOPUP]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_TOPUP]; }
         n++;
     }
     return n;
@@ -1300,7 +1313,7 @@ extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     if (!name || !*name) { ctx->kt_mask = ~0ull; return SVO_OK; }
-    for (int i = 0; i < KT_ALL; i++) if (!strcmp(name, kt_name(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
+    for (int i = 0; i < KT_ALL; i++) if (!strcmp(name, kt_name_all(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
     return SVO_ERR_ARG;
 }
 
@@ -2722,7 +2735,9 @@ static void klt_free(svo_ctx* ctx)
 {
     svo_ctx::Klt& k = ctx->klt;
     for (void* p : { (void*)k.dev.pts[0], (void*)k.dev.pts[1], (void*)k.dev.meta[0], (void*)k.dev.meta[1], (void*)k.dev.lane, (void*)k.dev.out, (void*)k.dev.status,
-                     (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage }) if (p) (void)hipFree(p);
+                     (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage,
+                     (void*)k.d_tmap, (void*)k.d_tgjobs, (void*)k.d_tkeys, (void*)k.d_titems, (void*)k.d_tstate, (void*)k.d_tginfo, (void*)k.d_tinfo, (void*)k.d_tcorners,
+                     (void*)k.d_tinit, (void*)k.d_tout, (void*)k.d_tresp, (void*)k.d_terr, (void*)k.d_tstatus, (void*)k.d_tlk_jobs }) if (p) (void)hipFree(p);
     memset(&k, 0, sizeof(k));
 }
 static svo_klt::Caps klt_caps(const svo_ctx* ctx) { return { ctx->cfg.n_lanes, ctx->dc.max_kps, ctx->cfg.max_w, ctx->cfg.max_h }; }
@@ -2974,6 +2989,186 @@ extern "C" int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy
     { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
     klt_select(ctx, active, fresh, st);
     HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays are free
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
+
+// ---- the resident top-up of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernels: k_klt.hip around k_gftt.hip and k_lk.hip) ----
+static svo_klt::TopupCaps topup_caps(const svo_ctx* ctx)
+{
+    const int cap = ctx->klt.enabled ? ctx->klt.p.cap : std::min(1024, ctx->dc.max_kps);
+    return { cap, ctx->cfg.max_cand };
+}
+static void topup_free(svo_ctx::Klt& k)
+{
+    void** all[] = { (void**)&k.d_tmap, (void**)&k.d_tgjobs, (void**)&k.d_tkeys, (void**)&k.d_titems, (void**)&k.d_tstate, (void**)&k.d_tginfo, (void**)&k.d_tinfo,
+                     (void**)&k.d_tcorners, (void**)&k.d_tinit, (void**)&k.d_tout, (void**)&k.d_tresp, (void**)&k.d_terr, (void**)&k.d_tstatus, (void**)&k.d_tlk_jobs };
+    for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    k.topup_enabled = false;
+}
+
+extern "C" void svo_klt_topup_default_params(const svo_ctx* ctx, svo_klt_topup_params* p)
+{
+    if (!p) return;
+    *p = svo_klt::topup_default_params(ctx ? topup_caps(ctx).cap : 1024);
+}
+
+extern "C" int svo_klt_topup_enable(svo_ctx* ctx, const svo_klt_topup_params* params)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    const svo_klt::Caps caps = klt_caps(ctx);
+    const svo_klt::TopupCaps tc = topup_caps(ctx);
+    const svo_klt_topup_params p = params ? *params : svo_klt::topup_default_params(tc.cap);
+    bool empty = true;
+    if (k.enabled && k.topup_enabled && k.topup_used && memcmp(&p, &k.tp, sizeof(p)) != 0) {      // other parameters after a top-up: only while no lane holds a track
+        { const int rc = svo_wait(ctx); if (rc) return rc; }
+        std::vector<KltLaneDev> lanes((size_t)caps.n_lanes);
+        HIPCHECK(hipMemcpy(lanes.data(), k.dev.lane, sizeof(KltLaneDev) * lanes.size(), hipMemcpyDeviceToHost));
+        for (const KltLaneDev& l : lanes) if (l.n > 0) empty = false;
+    }
+    bool realloc = false, adopt = false;
+    { std::string why; const int rc = svo_klt::check_topup_enable(p, caps, tc, klt_state(ctx), k.topup_enabled, k.tp, k.topup_used, empty, realloc, adopt, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (adopt) { k.tp = p; return SVO_OK; }
+    if (!realloc) return SVO_OK;
+    const svo_klt::TopupPlan plan = svo_klt::plan_topup(k.p, caps, tc);
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    // the response maps are the large buffer (4 bytes per pixel of n_lanes images of max_w x max_h): failing to get them is a capacity refusal
+    if (lk_realloc(&k.d_tmap, (size_t)plan.map_floats) != hipSuccess) {
+        (void)hipGetLastError(); k.d_tmap = nullptr;
+        char msg[200]; snprintf(msg, sizeof(msg), "%d lanes of %d x %d need a response-map buffer of %lld bytes, which the device could not provide", caps.n_lanes, caps.max_w, caps.max_h, plan.map_floats * 4ll);
+        ctx->last_error = msg; return SVO_ERR_CAPACITY;
+    }
+    const size_t NP = (size_t)plan.n_pts, NJ = (size_t)plan.n_jobs;
+    hipError_t e = hipSuccess;
+    auto grow = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    grow(lk_realloc(&k.d_tgjobs, NJ)); grow(lk_realloc(&k.d_tginfo, 4 * NJ)); grow(lk_realloc(&k.d_tinfo, 4 * NJ)); grow(lk_realloc(&k.d_tlk_jobs, NJ));
+    grow(lk_realloc(&k.d_tkeys, (size_t)plan.n_keys)); grow(lk_realloc(&k.d_titems, (size_t)plan.n_items)); grow(lk_realloc(&k.d_tstate, (size_t)plan.n_state));
+    grow(lk_realloc(&k.d_tcorners, NP)); grow(lk_realloc(&k.d_tinit, NP)); grow(lk_realloc(&k.d_tout, NP));
+    grow(lk_realloc(&k.d_tresp, NP)); grow(lk_realloc(&k.d_terr, NP)); grow(lk_realloc(&k.d_tstatus, NP));
+    if (e != hipSuccess) { (void)hipGetLastError(); topup_free(k); HIPCHECK(e); }
+    // before the first call every lane's record says "not in the mask"
+    std::vector<int> none(4 * NJ, 0);
+    for (size_t l = 0; l < NJ; l++) none[4 * l + 3] = KLT_TOPUP_NOT_ASKED;
+    HIPCHECK(hipMemcpy(k.d_tinfo, none.data(), sizeof(int) * none.size(), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(k.d_tginfo, 0, sizeof(int) * 4 * NJ));
+    k.tp = p; k.tplan = plan; k.topup_enabled = true;
+    return SVO_OK;
+}
+
+// the arguments of the three kernels for the front end's state as it is
+static KltTopupArgs topup_args(svo_ctx* ctx, const LaneMask& lanes)
+{
+    svo_ctx::Klt& k = ctx->klt;
+    KltTopupArgs a; memset(&a, 0, sizeof(a));
+    a.t = k.dev; a.half = k.half;
+    a.gjobs = k.d_tgjobs; a.ginfo = k.d_tginfo; a.tinfo = k.d_tinfo;
+    a.map = k.d_tmap; a.map_stride = k.tplan.map_stride;
+    a.lk_jobs = k.d_tlk_jobs; a.pyr = k.d_pyr; a.img_stride = k.plan.img_stride;
+    a.cell = 1;
+    if (k.w > 0 && k.h > 0) {
+        const svo_lk::Geometry g = svo_klt::klt_geometry(k.p, k.w, k.h);
+        a.nl = g.nl;
+        for (int l = 0; l < g.nl; l++) { a.w[l] = g.w[l]; a.h[l] = g.h[l]; a.off[l] = g.off[l]; }
+        const svo_gftt::Cells cells = svo_gftt::gftt_cells(k.w, k.h, k.tp.gftt.min_distance);
+        a.cell = cells.cell; a.gw = cells.gw; a.gh = cells.gh;
+    }
+    a.below = k.tp.below; a.target = k.tp.target; a.init_disp = k.tp.init_disp;
+    a.max_dy = k.p.max_dy; a.min_disp = k.p.min_disp; a.max_disp = k.p.max_disp;
+    a.lanes = lanes; a.has_img = k.has_img; a.parity = k.parity;
+    a.corners = k.d_tcorners; a.init = k.d_tinit; a.out = k.d_tout; a.status = k.d_tstatus;
+    return a;
+}
+
+extern "C" int svo_klt_topup(svo_ctx* ctx, const uint64_t lanes[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    LaneMask active;
+    { std::string why; const int rc = svo_klt::check_topup_call(klt_state(ctx), k.topup_enabled, lanes, klt_caps(ctx), active, why); if (rc) { ctx->last_error = why; return rc; } }
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    const KltTopupArgs a = topup_args(ctx, active);
+    const int n_lanes = k.dev.n_lanes;
+    bool any = false;                                        // a lane of the mask has a last pair: only then is there an image to look at
+    for (int wd = 0; wd < 2; wd++) any |= (active.w[wd] & k.has_img.w[wd]) != 0;
+    k.topup_used = true;
+    // 1. the detector's records, decided on the device from the live counts
+    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_jobs(a, st); }
+    if (any && a.nl > 0) {
+        // 2 .. 4. the detector as svo_gftt_detect launches it, on the top-up's own buffers; the seeds are the table's left points
+        GfttArgs g;
+        g.jobs = k.d_tgjobs; g.n_jobs = n_lanes; g.cand_cap = k.tplan.cand_cap; g.key_stride = k.tplan.key_stride; g.seed_cap = k.p.cap; g.items_stride = (int)k.tplan.items_stride;
+        g.keys = k.d_tkeys; g.items = k.d_titems; g.state = k.d_tstate;
+        g.seeds = k.dev.pts[k.half]; g.pts = k.d_tcorners; g.resp = k.d_tresp; g.info = k.d_tginfo; g.p = k.tp.gftt;
+        { Span s(ctx, KT_GFTT_RESPONSE); launch_gftt_response(g, k.w, k.h, st); }
+        { Span s(ctx, KT_GFTT_CANDIDATES); launch_gftt_candidates(g, k.w, k.h, st); }
+        { Span s(ctx, KT_GFTT_SELECT); launch_gftt_select(g, st); }
+        // 5. the tracking records and the first guesses
+        { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_prepare(a, st); }
+        // 6. left -> right over every lane (and the way back under fb_max), as svo_lk_track launches it
+        LkTrackArgs t;
+        t.jobs = k.d_tlk_jobs; t.n_jobs = n_lanes; t.n_pts = n_lanes * k.p.cap;
+        t.pts = k.d_tcorners; t.aux = k.d_tinit;
+        t.out = k.d_tout; t.status = k.d_tstatus; t.err = k.d_terr;
+        t.p = k.p.lk; t.backward = 0;
+        Span s(ctx, KT_LK_TRACK);
+        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
+        launch_lk_track(t, ppl, st);
+        if (k.p.lk.fb_max > 0.0f) {
+            LkTrackArgs b = t;
+            b.pts = k.d_tout; b.aux = k.d_tcorners; b.out = nullptr; b.err = nullptr; b.backward = 1;
+            launch_lk_track(b, ppl, st);
+        }
+    }
+    // 7. the gate and the append
+    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_append(a, -1, st); }
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_klt_topup_info(svo_ctx* ctx, int lane, int32_t info[4])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_topup_lane_call(klt_state(ctx), k.topup_enabled, "svo_klt_topup_info", lane, 0, info != nullptr, klt_caps(ctx), topup_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    HIPCHECK(hipMemcpy(info, k.d_tinfo + 4 * lane, sizeof(int32_t) * 4, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
+extern "C" int svo_debug_klt_topup_append(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status, int n)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_topup_lane_call(klt_state(ctx), k.topup_enabled, "svo_debug_klt_topup_append", lane, n, n <= 0 || (left_xy && right_xy && status), klt_caps(ctx), topup_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    LaneMask none; memset(&none, 0, sizeof(none));
+    const KltTopupArgs a = topup_args(ctx, none);
+    const size_t o = (size_t)lane * (size_t)k.p.cap;
+    if (n > 0) {
+        HIPCHECK(hipMemcpyAsync(k.d_tcorners + o, left_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(k.d_tout + o, right_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(k.d_tstatus + o, status, (size_t)n, hipMemcpyHostToDevice, st));
+    }
+    // the records the kernel reads: n corners, no overflow, the lane takes part
+    const int ginfo[4] = { n, n, 0, 0 }, tinfo[4] = { 0, 0, 0, KLT_TOPUP_OK };
+    HIPCHECK(hipMemcpyAsync(k.d_tginfo + 4 * lane, ginfo, sizeof(ginfo), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(k.d_tinfo + 4 * lane, tinfo, sizeof(tinfo), hipMemcpyHostToDevice, st));
+    k.topup_used = true;
+    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_append(a, lane, st); }
+    HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays (and the two records above) are free
     HIPCHECK(hipGetLastError());
     return SVO_OK;
 }

@@ -192,3 +192,23 @@ void launch_klt_select(const DevCtx& c, const KltSelectArgs& a, hipStream_t st);
 void launch_klt_append(const KltDev& t, int half, int lane, const float2* left, const float2* right, int n, hipStream_t st);
 // empties the tables of the lanes of the mask in `half` and starts their IDs over
 void launch_klt_clear(const DevCtx& c, const KltDev& t, int half, const LaneMask& lanes, hipStream_t st);
+// svo_klt_topup: what its three kernels read.  One detector job and one tracking job (left -> right) per lane; lane l owns slots
+// [l * cap, (l + 1) * cap) of the flat arrays.  ginfo: the detector's four ints per job; tinfo: four ints per lane (svo_klt_topup_info)
+enum { KLT_TOPUP_OK = 0, KLT_TOPUP_OVERFLOW, KLT_TOPUP_ENOUGH, KLT_TOPUP_NO_PAIR, KLT_TOPUP_NOT_ASKED };
+struct KltTopupArgs {
+    KltDev t; int half;
+    GfttJobDev* gjobs; int* ginfo; int* tinfo;
+    float* map; long long map_stride;             // one response map of map_stride floats per lane
+    LkJobDev* lk_jobs;
+    const uint8_t* pyr; long long img_stride;     // the front end's pyramid buffer (KltJobArgs)
+    int nl, w[6], h[6]; long long off[6];         // the geometry of the last step's images
+    int cell, gw, gh;                             // gftt_cells of level 0
+    int below, target;
+    float init_disp, max_dy, min_disp, max_disp;
+    LaneMask lanes, has_img, parity;              // the call's mask; the lanes with a last pair; the parity that pair is in
+    float2* corners; float2* init; float2* out; uint8_t* status;     // the detector's corners, the first guesses, the tracker's results
+};
+void launch_klt_topup_jobs(const KltTopupArgs& a, hipStream_t st);
+void launch_klt_topup_prepare(const KltTopupArgs& a, hipStream_t st);
+// one block per lane, or with only_lane >= 0 that lane alone (svo_debug_klt_topup_append)
+void launch_klt_topup_append(const KltTopupArgs& a, int only_lane, hipStream_t st);

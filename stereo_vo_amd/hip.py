@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .abi import (CameraModel, FasterStats, GfttJob, GfttParams, KltParams, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
+from .abi import (CameraModel, FasterStats, GfttJob, GfttParams, KltParams, KltTopupParams, Landmark, LandmarksInfo, LkImage, LkJob, LkParams, Params, PoseCov, Result, StereoCalibration, StereoCamera, StereoRectification, keypoint_dtype, dmatch_dtype, index_pair_dtype)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVO_HIP_LIB") or os.path.join(_HERE, "libsvo_hip.so")      # SVO_HIP_LIB: a library built from another commit, for A/B runs (tools/prof.sh abbench)
@@ -34,6 +34,7 @@ EXPORTS = [
     "svo_lk_default_params", "svo_lk_track", "svo_debug_lk_get_level",
     "svo_gftt_default_params", "svo_gftt_detect", "svo_debug_gftt_get_response",
     "svo_klt_default_params", "svo_klt_enable", "svo_klt_reset", "svo_klt_add_points", "svo_klt_step", "svo_klt_get_tracks", "svo_debug_klt_select",
+    "svo_klt_topup_default_params", "svo_klt_topup_enable", "svo_klt_topup", "svo_klt_topup_info", "svo_debug_klt_topup_append",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -154,6 +155,12 @@ def lib():
             L.svo_klt_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
             L.svo_klt_get_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
             L.svo_debug_klt_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "svo_klt_topup"):         # (as above)
+            L.svo_klt_topup_default_params.restype = None; L.svo_klt_topup_default_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.svo_klt_topup_enable.argtypes = [C.c_void_p, C.c_void_p]
+            L.svo_klt_topup.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            L.svo_klt_topup_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            L.svo_debug_klt_topup_append.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -954,6 +961,46 @@ class Context:
             raise ValueError("four arrays of one length are expected")
         self._ck(self.L.svo_debug_klt_select(self.h, int(lane), _vp(l), _vp(r), _vp(sl), _vp(sr), len(l)), "svo_debug_klt_select")
 
+    # -- the resident top-up of the front end (svo_klt_topup) -------------------------------------------------------
+    def klt_topup_default_params(self) -> KltTopupParams:
+        """the defaults for this context's front end: below = (cap + 1) / 2, target = cap"""
+        p = KltTopupParams()
+        self.L.svo_klt_topup_default_params(self.h, C.byref(p))
+        return p
+
+    def klt_topup_enable(self, params=None, **fields):
+        """allocates the top-up's buffers.  params: a KltTopupParams (None: the defaults); keyword arguments override single fields --
+        below, target, init_disp, and max_corners, block, min_distance, quality of the detector.  Returns the parameters in force."""
+        p = self.klt_topup_default_params() if params is None else params
+        if fields:
+            q = KltTopupParams()
+            C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
+            p = q
+            for k, v in fields.items():
+                setattr(p.gftt if k in ("max_corners", "block", "min_distance", "quality") else p, k, v)
+        self._ck(self.L.svo_klt_topup_enable(self.h, C.byref(p) if (params is not None or fields) else None), "svo_klt_topup_enable")
+        return p
+
+    def klt_topup(self, active=None):
+        """tops up the thinned lanes of `active` (None: all) on the device; enqueues only"""
+        self._ck(self.L.svo_klt_topup(self.h, self._words(active)), "svo_klt_topup")
+
+    def klt_topup_info(self, lane=0):
+        """(corners detected, candidates, tracks appended, reason) of the lane in the last top-up; reason: abi.TOPUP_*.  Synchronises."""
+        info = np.zeros(4, np.int32)
+        self._ck(self.L.svo_klt_topup_info(self.h, int(lane), _vp(info)), "svo_klt_topup_info")
+        return tuple(int(v) for v in info)
+
+    def klt_debug_topup_append(self, lane, left_xy, right_xy, status):
+        """the gate and the append of a top-up on one lane, with these arrays in place of the detector's corners and the tracker's
+        results (svo_debug_klt_topup_append)"""
+        l = np.ascontiguousarray(left_xy, np.float32).reshape(-1, 2)
+        r = np.ascontiguousarray(right_xy, np.float32).reshape(-1, 2)
+        st = np.ascontiguousarray(status, np.uint8)
+        if not (len(l) == len(r) == len(st)):
+            raise ValueError("three arrays of one length are expected")
+        self._ck(self.L.svo_debug_klt_topup_append(self.h, int(lane), _vp(l), _vp(r), _vp(st), len(l)), "svo_debug_klt_topup_append")
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
@@ -961,7 +1008,7 @@ class Context:
         """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
         hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
         "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, "lk_pyrdown", "lk_track": svo_lk_track and svo_klt_step, and
-        "klt_select": svo_klt_step, each listed once the context has made such a call) and are
+        "klt_select": svo_klt_step, "klt_topup": svo_klt_topup, each listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
