@@ -752,6 +752,52 @@ int svo_klt_topup(svo_ctx* ctx, const uint64_t lanes[2] /* NULL = all lanes */);
 int svo_klt_topup_info(svo_ctx* ctx, int lane, int32_t info[4]);
 int svo_debug_klt_topup_append(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status, int n);
 
+/* STAGE 4'S RANSAC ON THE TRACKED PAIRS A LANE HOLDS, AND AS A GATE INSIDE svo_klt_step.  The detect-match-track path verifies its
+ * tracked pairs with cv::findFundamentalMat(FM_RANSAC, 1.0, 0.99) on the left and on the right point pairs (stage4_match_consecutive.cpp:
+ * 202-255, 684-699); lists that arrive through the precomputed-data bypass (svo_put_tracked_oct) and the lists of the resident KLT front
+ * end had no such verification.  svo_ransac_tracked runs the same device RANSAC -- the sampler of cv::RNG, the LMedS registrator for 8 to
+ * 14 pairs, the direct path for 7 -- on what the lanes hold.  It enqueues on the context's stream and never synchronises.
+ * For every lane of the mask (NULL: all) and every octave below n_octaves:
+ *   candidates   the lane-octave's tracked pairs (first, second) in list order; first indexes the pairings of the lane's PREVIOUS slot,
+ *                second those of its current slot.  The left point pair is the previous left keypoint of pairing `first` (queryIdx) and
+ *                the current left keypoint of pairing `second`; the right pair the same through trainIdx.  A pair with an index outside
+ *                its pairing list, or whose pairings point outside their keypoint lists, is no candidate and never reaches the output
+ *                (the puts validate nothing; this call does);
+ *   the rule     one RANSAC per side on the candidates (oracle: svo_oracle_ransac_fundamental); use_f = both inlier counts >= 8.  With
+ *                use_f a candidate survives iff both masks hold it; without it -- 0 to 7 candidates, the 7-pair direct path, a side that
+ *                finds no model -- every candidate survives.  There is no consistency check, no bad-tracking gate and no min_pairs rule;
+ *   the output   the survivors keep their order and replace the list (svo_get_tracked_oct); nothing else of the lists changes;
+ *   track_stats  the lane's eight counters describe THIS call alone, summed over the octaves: SVO_TS_THRESHOLD = pairs in the list before
+ *                the call, SVO_TS_COLLISION = candidates, SVO_TS_INLIERS_L / _R and SVO_TS_HYP_L / _R = each side's inlier count and
+ *                hypotheses visited, SVO_TS_BOTH_MASKS = SVO_TS_TRACKED = survivors.  No other field of the record is written.
+ * A lane of the mask without a previous frame gets empty lists and zero counters (no error code is written); a lane outside the mask is
+ * untouched.  Refusals, before anything is enqueued, with a text in svo_last_error: SVO_ERR_STATE before svo_set_params, before the
+ * context has a geometry (put or load lists, or process a frame, first) and inside a captured graph; SVO_ERR_ARG for a mask bit at or
+ * above n_lanes.  tests/ransac_tracked_ref.py holds the walk.
+ * ONE BEHAVIOUR OF THE REFERENCE'S ARITHMETIC TO KNOW: with 8 to 14 candidates OpenCV's LMedS path runs, and it can reject half of a
+ * clean list (the oracle, on synthetic stereo tracks: 9 of 14 pairs rejected, 2 of them planted outliers).  With 15 or more clean pairs
+ * it rejected none; with 40 to 1024 pairs and 15-20 % planted outliers it rejected 85-100 % of those and at most 2 % of the good pairs.
+ *
+ * svo_klt_set_ransac(ctx, mode) makes the same sequence a gate inside svo_klt_step and svo_debug_klt_select, between the selection
+ * (item 4) and stage 5, for the step's active lanes.  It is accepted once svo_klt_enable has succeeded (SVO_ERR_STATE before, and inside
+ * a captured graph; SVO_ERR_ARG for another mode); svo_klt_get_ransac returns the mode.
+ *   0 (default)  a step allocates, launches and returns exactly what it did without this call;
+ *   1            the tracked pairs are filtered and the lane's track_stats filled; the current-frame lists and the table stay as the
+ *                selection wrote them;
+ *   2            as 1, and the tracks whose pair was rejected leave the table: the live tracks are compacted in order, the slots behind
+ *                the new count become empty, the survivors keep the index they have in the step's lists, no ID is given out again.  A
+ *                lane that rejected nothing writes nothing.  Under the LMedS behaviour above a lane with 8 to 14 tracked pairs can lose
+ *                half of them in a step; svo_klt_topup then finds a thinner table and refills it.
+ * THE CONTRACT is svo_klt_step's with public calls added: after a step every getter and svo_klt_get_tracks return byte for byte what
+ * this leaves: the recipe of svo_klt_step up to and including its puts; svo_ransac_tracked on the step's lanes; for mode 2
+ * svo_get_tracked, and every track that had a tracked pair and lost it removed from the host's table; then svo_process_lanes with
+ * SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT.  That last call starts the lane's record afresh, track_stats included, so the gate's counters
+ * are there to read after a step WITHOUT SVO_RUN_OPTIMIZE (and after svo_debug_klt_select) and are zero after a step with it: to have
+ * both, step without the flag, read them, and make the svo_process_lanes call of the recipe.  svo_klt_topup is unchanged.  No svo_batch, frame-parallel or graph-captured form. */
+int svo_ransac_tracked(svo_ctx* ctx, const uint64_t lanes[2] /* NULL = all lanes */);
+int svo_klt_set_ransac(svo_ctx* ctx, int mode);
+int svo_klt_get_ransac(const svo_ctx* ctx);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -783,7 +829,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * (whose pyramid and tracking launches count there); "klt_select" behind the lk names, once the context has made a svo_klt_step or a
  * svo_debug_klt_select; "klt_topup" behind that, once the context has made a svo_klt_topup or svo_debug_klt_topup_append call (its
  * three kernels count there, its detector and tracker launches under the gftt and lk names, which are then listed as well, and
- * "klt_select" with them). */
+ * "klt_select" with them); "ransac_feed" behind all of those, once the context has made a svo_ransac_tracked call or a step under
+ * svo_klt_set_ransac (the RANSAC launches behind it count under "ransac_hyp" .. "track_finalize"), and "klt_prune" last, once a step
+ * in mode 2 has run. */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

@@ -211,6 +211,9 @@ assert C.sizeof(KltTopupParams) == 28
 # svo_klt_topup_info: info[3]
 TOPUP_OK, TOPUP_OVERFLOW, TOPUP_ENOUGH, TOPUP_NO_PAIR, TOPUP_NOT_ASKED = range(5)
 
+# svo_klt_set_ransac: the RANSAC gate of svo_klt_step
+KLT_RANSAC_OFF, KLT_RANSAC_FILTER, KLT_RANSAC_PRUNE = range(3)
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

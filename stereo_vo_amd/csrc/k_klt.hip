@@ -209,6 +209,74 @@ void launch_klt_clear(const DevCtx& c, const KltDev& t, int half, const LaneMask
     hipLaunchKernelGGL(k_klt_clear, dim3((unsigned)t.n_lanes), dim3(KLT_BLOCK), 0, st, c, t, half, lanes);
 }
 
+// svo_klt_set_ransac(2), behind k_track_finalize: the tracks whose pair the RANSAC rejected leave the table.  One block per lane, on
+// the LIVE half (the one k_klt_select has just written: slot j is list index j).  The candidates of the lane's octave 0 are still where
+// k_ransac_feed put them (block 1 of bf_idx holds their current indices, trk_nk their count) and c.tracked holds the survivors: a slot is
+// dropped iff it is the `second` of a candidate and of no survivor -- one bit per slot in LDS, set by the candidates, cleared by the
+// survivors.  The points and the four meta rows are compacted stably IN PLACE in chunks of 256: a chunk is read, then a barrier, then
+// written (a slot moves to a lower or the same index, never into a later chunk).  KLT_IDX keeps the list index -- the lists are not
+// touched --, the slots behind the new count become what k_klt_select leaves behind a count, and no ID is given out again.
+// A lane whose candidates all survived (no use_f, or a clean list) writes nothing; an idle lane is not touched.
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_prune(const DevCtx c, const KltDev t, int half)
+{
+    extern __shared__ unsigned klt_drop[];
+    __shared__ int wkeep[KLT_WAVES];
+    const int lane = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, wl = tid & 63;
+    if (lane_idle(c, lane)) return;
+    const int cap = t.cap, vl = lane * c.oct_cap;
+    auto count = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
+    const int n_cand = count(c.trk_nk[vl], c.max_kps), n_keep = count(c.n_tracked[vl], c.max_kps);
+    if (n_keep >= n_cand) return;                                      // block-uniform: nothing was rejected
+    const int n = count(t.lane[lane].n, cap);
+    for (int i = tid; i < (cap + 31) / 32; i += KLT_BLOCK) klt_drop[i] = 0u;
+    __syncthreads();
+    const int* __restrict__ cand = c.bf_idx + ((long long)vl * 3 + 1) * c.max_kps;
+    const svo_index_pair* __restrict__ kept = c.tracked + (long long)vl * c.max_kps;
+    for (int i = tid; i < n_cand; i += KLT_BLOCK) { const int s = cand[i]; if ((unsigned)s < (unsigned)n) atomicOr(&klt_drop[s >> 5], 1u << (s & 31)); }
+    __syncthreads();
+    for (int i = tid; i < n_keep; i += KLT_BLOCK) { const int s = kept[i].second; if ((unsigned)s < (unsigned)n) atomicAnd(&klt_drop[s >> 5], ~(1u << (s & 31))); }
+    __syncthreads();
+    float2* pts = t.pts[half] + (size_t)lane * 2 * cap;
+    int* meta = t.meta[half] + (size_t)lane * KLT_META * cap;
+    int n_new = 0;                                                     // the running base: block-uniform
+    for (int base = 0; base < n; base += KLT_BLOCK) {
+        const int slot = base + tid;
+        float2 pl = make_float2(0.0f, 0.0f), pr = pl;
+        int m[KLT_META] = { 0, 0, 0, 0 };
+        bool keep = false;
+        if (slot < n) {
+            pl = pts[slot]; pr = pts[cap + slot];
+#pragma unroll
+            for (int r = 0; r < KLT_META; r++) m[r] = meta[r * cap + slot];
+            keep = !((klt_drop[slot >> 5] >> (slot & 31)) & 1u);
+        }
+        const unsigned long long b = __ballot(keep);
+        if (wl == 63) wkeep[wave] = __popcll(b);
+        __syncthreads();                       // the chunk is read: its slots may be written
+        int o = n_new + __popcll(b & ((1ull << wl) - 1ull)), tot = 0;
+#pragma unroll
+        for (int w = 0; w < KLT_WAVES; w++) { if (w < wave) o += wkeep[w]; tot += wkeep[w]; }
+        if (keep && o != slot) {
+            pts[o] = pl; pts[cap + o] = pr;
+#pragma unroll
+            for (int r = 0; r < KLT_META; r++) meta[r * cap + o] = m[r];
+        }
+        n_new += tot;
+        __syncthreads();                       // the per-wave words are free for the next chunk
+    }
+    for (int i = n_new + tid; i < n; i += KLT_BLOCK) {
+        pts[i] = make_float2(NAN, NAN); pts[cap + i] = make_float2(NAN, NAN);
+        meta[KLT_ID * cap + i] = -1; meta[KLT_AGE * cap + i] = 0; meta[KLT_IDX * cap + i] = -1; meta[KLT_PIDX * cap + i] = -1;
+    }
+    if (tid == 0) t.lane[lane].n = n_new;
+}
+
+void launch_klt_prune(const DevCtx& c, const KltDev& t, int half, hipStream_t st)
+{
+    if (t.n_lanes <= 0) return;
+    hipLaunchKernelGGL(k_klt_prune, dim3((unsigned)t.n_lanes), dim3(KLT_BLOCK), (size_t)((t.cap + 31) / 32) * sizeof(unsigned), st, c, t, half);
+}
+
 // the job records of a step (KltJobArgs, svo_kernels.h): thread l < n_lanes writes lane l's pyramid record, thread n_lanes + j the
 // tracking record of job j = 2 * lane + side
 __global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a)

@@ -2152,6 +2152,80 @@ __global__ void k_track_gate(DevCtx c, int bad_tracking_th)
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// svo_ransac_tracked: stage 4's RANSAC on the tracked pairs a lane HOLDS (svo_put_tracked_oct, or the selection of the resident KLT
+// front end), where a tracker kernel would stand.  A pair (first, second) is a candidate when first indexes the previous slot's
+// pairings, second the current slot's, and all four keypoint indices of the two pairings lie in their lists (the puts validate
+// nothing, so this kernel does); the others are dropped here and never reach the output.  The candidates keep their order and become
+// the survivor list k_track_finalize reads under win_mode: trk_kq = first, block 1 of bf_idx = second, both sides' point pairs
+// previous -> current in trk_pts.  k_track_finalize then rewrites c.tracked from these copies, so the list is filtered in place.
+//   phase 0, one block of 64 threads per lane: the lane's eight track_stats are zeroed.  trk_publish and k_track_finalize add to them
+//            atomically from the blocks of every octave, so the zeroing cannot ride in one of those blocks.
+//   phase 1, one block of 256 threads per lane-octave: chunks of 256 pairs in list order; a chunk's candidates get consecutive indices
+//            behind the running base (ballot + popcount inside a wave, the wave totals through LDS), as k_klt_select compacts.
+// A lane without a previous frame hands over nothing (k_track_finalize empties its lists); an idle lane is not touched.
+// ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_ransac_feed(DevCtx c, int phase)
+{
+    SVO_TL_SCOPE(c, TL_TRK_FILTER, 3);
+    SVO_LATENCY_CHAIN(c);
+    __shared__ int scan[40];
+    __shared__ int wvalid[4];
+    const int tid = threadIdx.x;
+    if (phase == 0) {
+        const int lane_id = blockIdx.x;
+        if (lane_id >= c.n_lanes || lane_idle(c, lane_id)) return;
+        if (tid < 8) c.results[lane_id].track_stats[tid] = 0;
+        return;
+    }
+    const int vl = blockIdx.x, lane_id = vl / c.oct_cap, oct = vl % c.oct_cap, wave = tid >> 6, wl = tid & 63;
+    if (oct >= c.n_oct || lane_idle(c, lane_id)) return;
+    const LaneState& ls = c.lane[lane_id];
+    if (!ls.has_prev) { if (tid == 0) c.trk_nk[vl] = 0; return; }
+    const int cur = 1 - ls.prev_slot, prev = ls.prev_slot, cap = c.max_kps;
+    auto count = [cap](int v) { return v < 0 ? 0 : (v > cap ? cap : v); };                // a list holds at most max_kps entries
+    const int n_in = count(c.n_tracked[vl]);
+    const unsigned npm = (unsigned)count(c.n_matches[vl * 2 + prev]), ncm = (unsigned)count(c.n_matches[vl * 2 + cur]);
+    const unsigned npl = (unsigned)count(c.n_kps[feat_cnt_idx(vl, prev, 0)]), npr = (unsigned)count(c.n_kps[feat_cnt_idx(vl, prev, 1)]);
+    const unsigned ncl = (unsigned)count(c.n_kps[feat_cnt_idx(vl, cur, 0)]), ncr = (unsigned)count(c.n_kps[feat_cnt_idx(vl, cur, 1)]);
+    const svo_index_pair* trk = c.tracked + (long long)vl * cap;
+    const svo_dmatch* pm = c.matches + match_base(c, vl, prev), *cm = c.matches + match_base(c, vl, cur);
+    const svo_keypoint* pkl = c.kps + feat_base(c, vl, prev, 0), *pkr = c.kps + feat_base(c, vl, prev, 1);
+    const svo_keypoint* ckl = c.kps + feat_base(c, vl, cur, 0), *ckr = c.kps + feat_base(c, vl, cur, 1);
+    int* kq = c.trk_kq + (long long)vl * cap;                                             // previous pairing index of candidate i
+    int* cq = c.bf_idx + ((long long)vl * 3 + 1) * cap;                                   // current pairing index of candidate i
+    float* ptsL = c.trk_pts + ((long long)vl * 2 + 0) * cap * 4, *ptsR = c.trk_pts + ((long long)vl * 2 + 1) * cap * 4;
+    int n_valid = 0;                                                                      // the running base: block-uniform
+    for (int base = 0; base < n_in; base += 256) {
+        const int i = base + tid;
+        svo_index_pair p; p.first = 0; p.second = 0;
+        svo_dmatch mp, mc; mp.queryIdx = mp.trainIdx = mc.queryIdx = mc.trainIdx = 0;
+        bool ok = false;
+        if (i < n_in) {
+            p = trk[i];
+            if ((unsigned)p.first < npm && (unsigned)p.second < ncm) {                    // (a negative index is a large unsigned one)
+                mp = pm[p.first]; mc = cm[p.second];
+                ok = (unsigned)mp.queryIdx < npl && (unsigned)mp.trainIdx < npr && (unsigned)mc.queryIdx < ncl && (unsigned)mc.trainIdx < ncr;
+            }
+        }
+        const unsigned long long b = __ballot(ok);
+        if (wl == 63) wvalid[wave] = __popcll(b);
+        __syncthreads();
+        int o = n_valid + __popcll(b & ((1ull << wl) - 1ull)), tot = 0;
+#pragma unroll
+        for (int w = 0; w < 4; w++) { if (w < wave) o += wvalid[w]; tot += wvalid[w]; }
+        if (ok) {
+            kq[o] = p.first; cq[o] = p.second;
+            const svo_keypoint a = pkl[mp.queryIdx], d = ckl[mc.queryIdx], e = pkr[mp.trainIdx], f = ckr[mc.trainIdx];      // (all four loads first)
+            trk_write_pair(ptsL, o, a, d);
+            trk_write_pair(ptsR, o, e, f);
+        }
+        n_valid += tot;
+        __syncthreads();                                                                  // the per-wave words are free for the next chunk
+    }
+    trk_publish(c, vl, lane_id, n_in, n_valid, scan);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Match-ID bookkeeping (params_general.vo_use_matches_ids; H:735-742): IDs follow a pairing through time.
 //   reset (P:254-267): previous IDs renumbered 0..N-1, the frame becomes the key frame;
 //   first frame (S3:67, 172-173): every pairing receives a fresh ID, octave by octave;
@@ -2344,6 +2418,23 @@ void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, h
     const bool fold = c.oct_cap == 1;
     hipLaunchKernelGGL(k_track_finalize, dim3(c.n_lanes * c.oct_cap), dim3(256), LdsTrackFinalize{c.max_kps}.total(), st, c, win_mode, fold ? bad_tracking_th : -1);
     if (!fold) hipLaunchKernelGGL(k_track_gate, dim3((c.n_lanes + 63) / 64), dim3(64), 0, st, c, bad_tracking_th);
+}
+// phase 0 of k_ransac_feed alone: the track_stats of the lanes DevCtx.idle leaves in are zeroed
+void launch_ransac_stats_clear(const DevCtx& c, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_ransac_feed, dim3(c.n_lanes), dim3(64), 0, st, c, 0);
+}
+// svo_ransac_tracked: the held lists to the RANSAC (both phases of k_ransac_feed) ...
+void launch_ransac_feed(const DevCtx& c, hipStream_t st)
+{
+    launch_ransac_stats_clear(c, st);
+    hipLaunchKernelGGL(k_ransac_feed, dim3(c.n_lanes * c.oct_cap), dim3(256), 0, st, c, 1);
+}
+// ... and, behind the three RANSAC chunks, k_track_finalize on the survivor list without a bad-tracking gate and without k_track_gate:
+// no record's error code is written, a lane without a previous frame gets empty lists
+void launch_track_finalize_ungated(const DevCtx& c, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_track_finalize, dim3(c.n_lanes * c.oct_cap), dim3(256), LdsTrackFinalize{c.max_kps}.total(), st, c, 1, -1);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -105,6 +105,31 @@ int check_klt_lane_call(const State& s, const char* entry, int lane, int n, bool
     return SVO_OK;
 }
 
+// ---- the RANSAC gate ----
+int check_ransac_tracked(bool params_set, bool geom_ready, bool capturing, const uint64_t* lanes, int n_lanes, LaneMask& active, LaneMask& idle, std::string& why)
+{
+    memset(&active, 0, sizeof(active)); memset(&idle, 0, sizeof(idle));
+    why.clear();
+    if (!params_set) { why = "svo_ransac_tracked: no svo_set_params yet: the octaves of the lists are not known"; return SVO_ERR_STATE; }
+    if (!geom_ready) { why = "svo_ransac_tracked: no geometry yet: put or load the lists first (svo_set_params clears the geometry of the lists before it)"; return SVO_ERR_STATE; }
+    if (capturing) { why = "svo_ransac_tracked: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (!svo_call::parse_lane_mask(lanes, false, n_lanes, active, idle, why)) return SVO_ERR_ARG;
+    return SVO_OK;
+}
+
+int check_klt_set_ransac(const State& s, int mode, std::string& why)
+{
+    char msg[200];
+    why.clear();
+    if (!s.enabled) { why = "svo_klt_set_ransac: the KLT front end is not enabled (svo_klt_enable)"; return SVO_ERR_STATE; }
+    if (s.capturing) { why = "svo_klt_set_ransac: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (mode < KLT_RANSAC_OFF || mode > KLT_RANSAC_PRUNE) {
+        snprintf(msg, sizeof(msg), "svo_klt_set_ransac: mode %d: 0 (off), 1 (filter the tracked pairs) or 2 (and drop the rejected tracks) is expected", mode);
+        why = msg; return SVO_ERR_ARG;
+    }
+    return SVO_OK;
+}
+
 svo_lk::Geometry klt_geometry(const svo_klt_params& p, int w, int h) { return svo_lk::lk_geometry(w, h, p.lk.win, p.lk.max_level, true); }
 
 Plan plan_klt(const svo_klt_params& p, const Caps& caps)

@@ -37,6 +37,15 @@ int check_klt_step(const svo_frame* frames, uint32_t flags, const uint64_t* lane
 // svo_klt_add_points / svo_klt_get_tracks / svo_debug_klt_select: ready, the lane, the arrays and the count
 int check_klt_lane_call(const State& s, const char* entry, int lane, int n, bool arrays_ok, const Caps& caps, std::string& why);
 
+
+// ---- the RANSAC gate (svo_ransac_tracked / svo_klt_set_ransac; tools/klt_ransac_check.cpp drives these) ----
+enum { KLT_RANSAC_OFF = 0, KLT_RANSAC_FILTER = 1, KLT_RANSAC_PRUNE = 2 };
+// svo_ransac_tracked, in order: no svo_set_params yet, no geometry yet, a capturing stream (SVO_ERR_STATE), then the mask (NULL = all
+// lanes; a bit at or above n_lanes: SVO_ERR_ARG).  The front end need not be enabled.  active / idle: the parsed mask
+int check_ransac_tracked(bool params_set, bool geom_ready, bool capturing, const uint64_t* lanes, int n_lanes, LaneMask& active, LaneMask& idle, std::string& why);
+// svo_klt_set_ransac: the front end enabled and no capture (SVO_ERR_STATE), then the mode, 0 .. 2 (SVO_ERR_ARG)
+int check_klt_set_ransac(const State& s, int mode, std::string& why);
+
 // the buffers of an enabled context, sized for max_w x max_h images:
 //   pyramids   [2 parities][n_lanes][2 sides] blocks of img_stride bytes, the levels of one image tightly packed (lk_geometry with
 //              level 0).  A lane's new pair goes to the parity its last pair did NOT go to: the other parity still holds frame t - 1

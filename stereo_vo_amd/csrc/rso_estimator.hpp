@@ -369,6 +369,14 @@ public:
     void enableKLTTopUp(const svo_klt_topup_params* topup_params = NULL) { check(svo_klt_topup_enable(m_ctx, topup_params), "svo_klt_topup_enable"); }
     void topUpKLT() { check(svo_klt_topup(m_ctx, NULL), "svo_klt_topup"); }
     void getKLTTopUpInfo(int32_t info[4]) { check(svo_klt_topup_info(m_ctx, 0, info), "svo_klt_topup_info"); }
+    /** Stage 4's geometric verification for lists the tracker did not make (svo_ransac_tracked): filterTrackedRANSAC runs
+     *  findFundamentalMat's RANSAC on the left and on the right point pairs of the tracked pairs the estimator holds -- after
+     *  setPrecomputedData-style puts, before the optimisation -- and keeps what both masks keep; it does not synchronise.
+     *  setKLTRansac makes it a gate inside stepKLT: 0 off (default), 1 the tracked pairs are filtered, 2 the rejected tracks also
+     *  leave the table (with 8 to 14 pairs OpenCV's LMedS path can reject half of a clean list: see svo_hip.h). */
+    void filterTrackedRANSAC() { check(svo_ransac_tracked(m_ctx, NULL), "svo_ransac_tracked"); }
+    void setKLTRansac(int mode) { check(svo_klt_set_ransac(m_ctx, mode), "svo_klt_set_ransac"); }
+    int getKLTRansac() const { return svo_klt_get_ransac(m_ctx); }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

@@ -47,7 +47,10 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        // name lives outside kt_names (kt_name below), whose last entries stay the LK ones
        // ... and "klt_topup" behind it, once the context has topped up (the three kernels of k_klt.hip around the detector and the tracker)
        KT_KLT_SELECT = KT_COUNT, KT_KLT_TOPUP, KT_ALL };
-static_assert(KT_ALL <= 64, "kt_mask is one 64-bit word");
+// ... and "ransac_feed" (svo_ransac_tracked, or a step under svo_klt_set_ransac) and "klt_prune" (a step in mode 2) behind those, each
+// once the context has launched it.  The RANSAC launches between them count under their names of a frame
+enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_EVERY };
+static_assert(KT_EVERY <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
     "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
@@ -56,7 +59,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
 static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
-static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : kt_name(i); }
+static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : kt_name(i); }
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -117,7 +120,7 @@ struct svo_ctx {
     std::vector<void*> allocs;
     std::string last_error;
     std::vector<TimedSpan> spans; std::vector<hipEvent_t> free_events;
-    double kt_total[KT_ALL]; long long kt_calls[KT_ALL]; unsigned long long kt_mask;
+    double kt_total[KT_EVERY]; long long kt_calls[KT_EVERY]; unsigned long long kt_mask;
     unsigned* d_ham_out; uint8_t* d_ham_q, *d_ham_t; int ham_cap_q, ham_cap_t;
     // svo_lk_track: buffers of its own, made by its first call, grown on demand, freed with the context -- the pyramids of the call's
     // images, the job records, the flat point arrays (pts, init, out: float2; status; err).  lk_jobs: the records of the last call, for
@@ -139,6 +142,8 @@ struct svo_ctx {
         bool enabled, used; svo_klt_params p; svo_klt::Plan plan;
         KltDev dev; uint8_t* d_pyr; LkJobDev* d_pyr_jobs, * d_trk_jobs; float2* d_stage;
         int half, w, h; LaneMask parity, has_img;
+        int ransac;                                    // svo_klt_set_ransac: 0 off, 1 filter the tracked pairs, 2 and drop the rejected tracks
+        bool prune_used;                               // a step has launched k_klt_prune (svo_kernel_times)
         // the resident top-up (svo_klt_topup_enable; the plan: klt_call.hpp), buffers of its own: the response maps, the detector's job
         // records, keys, cell lists, states and counters, the corners with their responses, the first guesses, the tracker's records and
         // results, four ints per lane for svo_klt_topup_info.  topup_used: a top-up has run (svo_kernel_times, svo_klt_topup_enable)
@@ -147,6 +152,7 @@ struct svo_ctx {
         float2* d_tcorners, * d_tinit, * d_tout; float* d_tresp, * d_terr; uint8_t* d_tstatus; LkJobDev* d_tlk_jobs;
     } klt;
     bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
+    bool ransac_feed_used;                             // the context has launched k_ransac_feed (svo_kernel_times)
     bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
@@ -445,7 +451,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
     ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
-    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false;
+    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -454,7 +460,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
-    for (int i = 0; i < KT_ALL; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_EVERY; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     ctx->kt_mask = ~0ull;
     *out = ctx;                                           // so that the caller can read last_error and destroy
     knobs_read(&ctx->knobs, knobs_env);
@@ -1306,6 +1312,12 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
         if (n < cap) { if (names) names[n] = kt_name_all(KT_KLT_TOPUP); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_TOPUP]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_TOPUP]; }
         n++;
     }
+    // "ransac_feed" and "klt_prune" behind everything else, each once the context has launched the kernel
+    for (int k = KT_RANSAC_FEED; k <= KT_KLT_PRUNE; k++) {
+        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : ctx->klt.prune_used)) continue;
+        if (n < cap) { if (names) names[n] = kt_name_all(k); if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
+        n++;
+    }
     return n;
 }
 extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
@@ -1313,7 +1325,7 @@ extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     if (!name || !*name) { ctx->kt_mask = ~0ull; return SVO_OK; }
-    for (int i = 0; i < KT_ALL; i++) if (!strcmp(name, kt_name_all(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
+    for (int i = 0; i < KT_EVERY; i++) if (!strcmp(name, kt_name_all(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
     return SVO_ERR_ARG;
 }
 
@@ -1322,7 +1334,7 @@ extern "C" int svo_kernel_times_reset(svo_ctx* ctx)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    for (int i = 0; i < KT_ALL; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_EVERY; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     return SVO_OK;
 }
 
@@ -1637,29 +1649,21 @@ static void enqueue_match(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
         launch_match_lr_rbr(d, true, p.enable_robust_1to1_match, p.max_y_diff, call.minresp, call.max_sad_match, st);
     }
 }
-static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+// The chunks of the RANSAC's sample schedule (set before the tracker kernels: phase 0 of the schedule rides in them).  A handful of
+// lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
+// there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
+static void set_ransac_chunks(svo_ctx* ctx)
 {
-    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
-    Section sec("_stg4"), sec2("stg4.track");                                    // S4:76, 457
-    const int win = p.ifm_method == SVO_IFM_DESC_WIN || p.ifm_method == SVO_IFM_SAD;
-    // The chunks of the RANSAC's sample schedule (set before the tracker kernels: phase 0 of the schedule rides in them).  A handful of
-    // lanes (one stream on its own): chunk 0 takes chunk 1's samples and more -- a hypothesis + count launch pair is ~20 us of latency
-    // there, more than evaluating the samples an early bound might have saved.  SVO_RS_C0 = 32 | 160 | 320 forces a form (A/B, tests).
-    {
-        const int forced = ctx->knobs.rs_c0;
-        d.rs_c0 = forced ? forced : (d.n_lanes * d.n_oct > 8 ? SVO_RANSAC_CHUNK0 : SVO_RANSAC_FEW);
-        d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
-    }
-    if (!win) {
-        { Span s(ctx, wide_lists(d) ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, ctx->knobs, 1, hamming_splits(ctx), st); }
-        { Span s(ctx, wide_lists(d) ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
-    } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
-        Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
-    } else {                                                // ifmSAD
-        Span s(ctx, KT_TRK_SAD); launch_track_win(d, true, p.ifm_win_w, p.ifm_win_h, call.max_sad_track, st);
-    }
-    // F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
-    // as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
+    DevCtx& d = ctx->dc;
+    const int forced = ctx->knobs.rs_c0;
+    d.rs_c0 = forced ? forced : (d.n_lanes * d.n_oct > 8 ? SVO_RANSAC_CHUNK0 : SVO_RANSAC_FEW);
+    d.rs_c1 = d.rs_c0 > SVO_RANSAC_CHUNK1 ? d.rs_c0 : SVO_RANSAC_CHUNK1;
+}
+// F-matrix RANSAC: the first SVO_RANSAC_CHUNK0 hypotheses of the fixed schedule, then two more chunks, each only
+// as far as the 0.99-confidence stop of the sequential algorithm can still reach given what has been counted so far
+static void enqueue_ransac_chunks(svo_ctx* ctx, hipStream_t st)
+{
+    DevCtx& d = ctx->dc;
     { Span s(ctx, KT_RANSAC_HYP); launch_ransac_hyp(d, 0, st); }
     { Span s(ctx, KT_RANSAC_CNT); launch_ransac_count(d, ctx->knobs, 0, st); }
     if (d.rs_c0 < d.rs_c1) {
@@ -1668,7 +1672,34 @@ static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
     }
     { Span s(ctx, KT_RANSAC_HYP2); launch_ransac_hyp(d, 2, st); }
     { Span s(ctx, KT_RANSAC_CNT2); launch_ransac_count(d, ctx->knobs, 2, st); }
+}
+static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
+{
+    DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
+    Section sec("_stg4"), sec2("stg4.track");                                    // S4:76, 457
+    const int win = p.ifm_method == SVO_IFM_DESC_WIN || p.ifm_method == SVO_IFM_SAD;
+    set_ransac_chunks(ctx);
+    if (!win) {
+        { Span s(ctx, wide_lists(d) ? KT_HAM_TRK_WIDE : KT_HAM_TRK); launch_hamming(d, ctx->knobs, 1, hamming_splits(ctx), st); }
+        { Span s(ctx, wide_lists(d) ? KT_TRK_FILTER_64 : KT_TRK_FILTER); launch_track_filter(d, st); }
+    } else if (p.ifm_method == SVO_IFM_DESC_WIN) {          // ifmDescWin (stage4_match_consecutive.cpp:435-738)
+        Span s(ctx, KT_TRK_FILTER); launch_track_win(d, false, p.ifm_win_w, p.ifm_win_h, 0u, st);
+    } else {                                                // ifmSAD
+        Span s(ctx, KT_TRK_SAD); launch_track_win(d, true, p.ifm_win_w, p.ifm_win_h, call.max_sad_track, st);
+    }
+    enqueue_ransac_chunks(ctx, st);
     { Span s(ctx, KT_TRK_FINAL); launch_track_finalize(d, p.bad_tracking_th, win, st); }
+}
+// svo_ransac_tracked, and the gate of a step under svo_klt_set_ransac: the RANSAC of stage 4 on the tracked pairs the lanes hold, for
+// the lanes DevCtx.idle leaves in.  No bad-tracking gate: the precomputed-data bypass has none
+static void enqueue_ransac_tracked(svo_ctx* ctx, hipStream_t st)
+{
+    DevCtx& d = ctx->dc;
+    set_ransac_chunks(ctx);
+    { Span s(ctx, KT_RANSAC_FEED); launch_ransac_feed(d, st); }
+    enqueue_ransac_chunks(ctx, st);
+    { Span s(ctx, KT_TRK_FINAL); launch_track_finalize_ungated(d, st); }
+    ctx->ransac_feed_used = true;
 }
 static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
 {
@@ -2781,7 +2812,9 @@ extern "C" int svo_klt_enable(svo_ctx* ctx, const svo_klt_params* params)
         ctx->last_error = msg; return SVO_ERR_UNSUPPORTED;
     }
     { const int rc = svo_wait(ctx); if (rc) return rc; }
+    const int ransac = k.ransac;                            // (the mode outlives the buffers)
     klt_free(ctx);
+    k.ransac = ransac;
     k.p = p; k.plan = plan;
     k.dev.n_lanes = caps.n_lanes; k.dev.cap = p.cap;
     const size_t NS = (size_t)plan.n_slots;
@@ -2888,6 +2921,45 @@ static void klt_select(svo_ctx* ctx, const LaneMask& active, const LaneMask& fre
     k.half ^= 1; k.used = true;
     for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) ctx->sad.cur[(size_t)l] = 0;      // lists without an image behind them: no SAD windows
 }
+// between the selection and stage 5, under svo_klt_set_ransac: the RANSAC on the tracked pairs the selection wrote, for the step's active
+// lanes (DevCtx.idle is the step's); mode 2: the rejected tracks then leave the live half
+static void klt_ransac_gate(svo_ctx* ctx, hipStream_t st)
+{
+    svo_ctx::Klt& k = ctx->klt;
+    if (k.ransac == svo_klt::KLT_RANSAC_OFF) return;
+    enqueue_ransac_tracked(ctx, st);
+    if (k.ransac == svo_klt::KLT_RANSAC_PRUNE) { Span s(ctx, KT_KLT_PRUNE); launch_klt_prune(ctx->dc, k.dev, k.half, st); k.prune_used = true; }
+}
+
+extern "C" int svo_klt_set_ransac(svo_ctx* ctx, int mode)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    { std::string why; const int rc = svo_klt::check_klt_set_ransac(klt_state(ctx), mode, why); if (rc) { ctx->last_error = why; return rc; } }
+    ctx->klt.ransac = mode;
+    return SVO_OK;
+}
+extern "C" int svo_klt_get_ransac(const svo_ctx* ctx) { return ctx ? ctx->klt.ransac : SVO_ERR_ARG; }
+
+extern "C" int svo_ransac_tracked(svo_ctx* ctx, const uint64_t lanes[2])
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    LaneMask active, idle;
+    { std::string why; const int rc = svo_klt::check_ransac_tracked(ctx->params_set, ctx->geom_ready, klt_state(ctx).capturing, lanes, ctx->cfg.n_lanes, active, idle, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (!lane_any(active)) return SVO_OK;                   // nobody takes part: nothing is enqueued
+    DevCtx& d = ctx->dc;
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    d.idle = idle;
+    IdleGuard idle_guard{ &d };
+    enqueue_ransac_tracked(ctx, st);
+    HIPCHECK(hipGetLastError());
+    return SVO_OK;
+}
 
 extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t lanes[2])
 {
@@ -2950,9 +3022,14 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
     }
     // 4. the selection
     klt_select(ctx, active, fresh, st);
+    klt_ransac_gate(ctx, st);
     for (int wd = 0; wd < 2; wd++) k.has_img.w[wd] |= active.w[wd];
-    // 5. stage 5
-    if (flags & SVO_RUN_OPTIMIZE) enqueue_optimize(ctx, opt, st);
+    // 5. stage 5.  The recipe's stage-5 call starts the lane's record afresh (k_begin_frame), the gate's counters included: a gated
+    //    step that optimises leaves them at zero as well, one that does not leaves them standing
+    if (flags & SVO_RUN_OPTIMIZE) {
+        if (k.ransac != svo_klt::KLT_RANSAC_OFF) { Span s(ctx, KT_RANSAC_FEED); launch_ransac_stats_clear(d, st); }
+        enqueue_optimize(ctx, opt, st);
+    }
     HIPCHECK(hipGetLastError());
     return SVO_OK;
 }
@@ -2988,6 +3065,7 @@ extern "C" int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy
     IdleGuard idle_guard{ &d };
     { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
     klt_select(ctx, active, fresh, st);
+    klt_ransac_gate(ctx, st);
     HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays are free
     HIPCHECK(hipGetLastError());
     return SVO_OK;

@@ -90,6 +90,12 @@ void launch_track_filter(const DevCtx& c, hipStream_t st);
 void launch_ransac_hyp(const DevCtx& c, int chunk, hipStream_t st);
 void launch_ransac_count(const DevCtx& c, const Knobs& k, int chunk, hipStream_t st);
 void launch_track_finalize(const DevCtx& c, int bad_tracking_th, int win_mode, hipStream_t st);
+// svo_ransac_tracked (k_match.hip): k_ransac_feed hands the tracked pairs the lanes HOLD to the RANSAC -- set DevCtx.rs_c0 / rs_c1 first,
+// phase 0 of the sample schedule rides in it --, then the three chunks as a frame launches them, then k_track_finalize on the survivor
+// list with no bad-tracking gate and no k_track_gate
+void launch_ransac_feed(const DevCtx& c, hipStream_t st);
+void launch_ransac_stats_clear(const DevCtx& c, hipStream_t st);     // its zeroing phase alone (a gated svo_klt_step ahead of stage 5)
+void launch_track_finalize_ungated(const DevCtx& c, hipStream_t st);
 // sad = false: smDescRbR / ifmDescWin on the descriptors; sad = true: smSAD / ifmSAD on the windows of launch_sad_patch (max_sad: ifmSAD's threshold)
 void launch_match_lr_rbr(const DevCtx& c, bool sad, int one_to_one, double max_y_diff, double minimum_response, int max_distance, hipStream_t st);
 void launch_track_win(const DevCtx& c, bool sad, int win_w, int win_h, unsigned max_sad, hipStream_t st);
@@ -192,6 +198,8 @@ void launch_klt_select(const DevCtx& c, const KltSelectArgs& a, hipStream_t st);
 void launch_klt_append(const KltDev& t, int half, int lane, const float2* left, const float2* right, int n, hipStream_t st);
 // empties the tables of the lanes of the mask in `half` and starts their IDs over
 void launch_klt_clear(const DevCtx& c, const KltDev& t, int half, const LaneMask& lanes, hipStream_t st);
+// svo_klt_set_ransac(2): behind k_track_finalize, the tracks whose pair the RANSAC rejected leave the live half `half` (k_klt_prune)
+void launch_klt_prune(const DevCtx& c, const KltDev& t, int half, hipStream_t st);
 // svo_klt_topup: what its three kernels read.  One detector job and one tracking job (left -> right) per lane; lane l owns slots
 // [l * cap, (l + 1) * cap) of the flat arrays.  ginfo: the detector's four ints per job; tinfo: four ints per lane (svo_klt_topup_info)
 enum { KLT_TOPUP_OK = 0, KLT_TOPUP_OVERFLOW, KLT_TOPUP_ENOUGH, KLT_TOPUP_NO_PAIR, KLT_TOPUP_NOT_ASKED };

@@ -35,6 +35,7 @@ EXPORTS = [
     "svo_gftt_default_params", "svo_gftt_detect", "svo_debug_gftt_get_response",
     "svo_klt_default_params", "svo_klt_enable", "svo_klt_reset", "svo_klt_add_points", "svo_klt_step", "svo_klt_get_tracks", "svo_debug_klt_select",
     "svo_klt_topup_default_params", "svo_klt_topup_enable", "svo_klt_topup", "svo_klt_topup_info", "svo_debug_klt_topup_append",
+    "svo_ransac_tracked", "svo_klt_set_ransac", "svo_klt_get_ransac",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -161,6 +162,10 @@ def lib():
             L.svo_klt_topup.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
             L.svo_klt_topup_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
             L.svo_debug_klt_topup_append.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "svo_ransac_tracked"):    # (as above)
+            L.svo_ransac_tracked.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            L.svo_klt_set_ransac.argtypes = [C.c_void_p, C.c_int]
+            L.svo_klt_get_ransac.argtypes = [C.c_void_p]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -1001,6 +1006,21 @@ class Context:
             raise ValueError("three arrays of one length are expected")
         self._ck(self.L.svo_debug_klt_topup_append(self.h, int(lane), _vp(l), _vp(r), _vp(st), len(l)), "svo_debug_klt_topup_append")
 
+    # -- the RANSAC gate (svo_ransac_tracked, svo_klt_set_ransac) ---------------------------------------------------
+    def ransac_tracked(self, active=None):
+        """stage 4's fundamental-matrix RANSAC on the tracked pairs the lanes of `active` (None: all) hold, every octave: the pairs both
+        masks keep replace the list, the lane's track_stats describe the call.  Enqueues only (svo_ransac_tracked)"""
+        self._ck(self.L.svo_ransac_tracked(self.h, self._words(active)), "svo_ransac_tracked")
+
+    def klt_set_ransac(self, mode):
+        """the RANSAC gate of svo_klt_step: abi.KLT_RANSAC_OFF (0, the default), KLT_RANSAC_FILTER (1: the tracked pairs are filtered) or
+        KLT_RANSAC_PRUNE (2: and the rejected tracks leave the table).  After klt_enable."""
+        self._ck(self.L.svo_klt_set_ransac(self.h, int(mode)), "svo_klt_set_ransac")
+
+    def klt_ransac(self):
+        """the mode svo_klt_set_ransac left"""
+        return self._ck(self.L.svo_klt_get_ransac(self.h), "svo_klt_get_ransac")
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
@@ -1008,7 +1028,8 @@ class Context:
         """{name: (total ms, calls)} in the order of the C list.  Its first 32 names are the kernels of svo_process and of the
         hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
         "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, "lk_pyrdown", "lk_track": svo_lk_track and svo_klt_step, and
-        "klt_select": svo_klt_step, "klt_topup": svo_klt_topup, each listed once the context has made such a call) and are
+        "klt_select": svo_klt_step, "klt_topup": svo_klt_topup, "ransac_feed": svo_ransac_tracked and a step under klt_set_ransac,
+        "klt_prune": a step in mode 2, each listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
