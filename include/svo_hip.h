@@ -798,6 +798,52 @@ int svo_ransac_tracked(svo_ctx* ctx, const uint64_t lanes[2] /* NULL = all lanes
 int svo_klt_set_ransac(svo_ctx* ctx, int mode);
 int svo_klt_get_ransac(const svo_ctx* ctx);
 
+/* POSE-PREDICTED FIRST GUESSES FOR svo_klt_step.  A step starts the search for every track at the track's old position; the lane holds
+ * what a stereo front end predicts from instead: the depth of every track (xl, yl, xr and the camera stage 5 runs with) and the pose
+ * increment stage 5 estimated a frame ago (svo_result.delta).  svo_klt_set_prediction(ctx, 1) makes a step triangulate each track, move it
+ * by that increment (constant velocity), reproject it into both cameras and start the forward tracking pass there; nothing is read back
+ * and nothing synchronises.  It is accepted once svo_klt_enable has succeeded (SVO_ERR_STATE before, and inside a captured graph;
+ * SVO_ERR_ARG for a mode other than 0 and 1); svo_klt_get_prediction returns the mode.
+ *   0 (default)  a step allocates, launches and returns exactly what it did without this call;
+ *   1            the first call allocates the one buffer of the mode (a float2 per lane, side and slot, a byte per lane and slot).  A
+ *                svo_klt_enable that re-makes the front end's buffers drops it and returns to mode 0, as it drops the top-up.
+ * THE RULE, for a lane of the step's mask that tracks (it has a last pair) and slot s below its live count, (xl, yl), (xr, yr) the slot's
+ * float32 points.  The device's definition is k_project_points (k_gn.hip), its restatement svo_oracle_project; every compare is written
+ * as it is evaluated:
+ *   1  the lane predicts iff svo_result.valid != 0 and all six delta values are finite, the record taken as svo_get_result would
+ *      return it immediately before the step.  Nothing else is consulted, neither ages nor error codes: after a step without
+ *      SVO_RUN_OPTIMIZE, or one that ended invalid, the record says so and the lane does not predict;
+ *   2  triangulate in double, one operation per operator, with ul = xl, vl = yl, ur = xr: disparity = fl*(cur - ur) + fr*(ul - cul),
+ *      b_d = baseline/disparity, X = (b_d*fr*(ul - cul), b_d*fr*(vl - cvl), b_d*fl*fr);
+ *   3  move and project: the rotation R of delta's first three values (the reference's Rodrigues formula with its small-angle
+ *      branch), Xc = R X + t, and the four float32 pixels uL vL uR vR exactly as k_project_points stores them;
+ *   4  the slot is predicted (used = 1) iff the lane predicts, disparity > 0 and Z1c > 0 (compared in double), all four pixels are
+ *      finite, and both guesses lie inside the image: 0 <= x <= w - 1 and 0 <= y <= h - 1, compared in float32 against the level-0
+ *      size of the lane's last pair.  Then the left guess is (uL, vL) and the right guess (uR, vR); otherwise used = 0 and both
+ *      guesses are the slot's own points, bit for bit -- which tracks exactly as no guess does;
+ *   5  the slots behind the live count get NaN guesses and used = 0.
+ * Lanes that do not predict, lanes outside the mask and lanes without a last pair get their own points and used = 0.  Only the forward
+ * pass starts from the guesses: the forward-backward pass under fb_max, the gate, the RANSAC gate, svo_klt_topup and stage 5 are as
+ * they were.  A lost point reports the guess it had when it was lost (svo_lk_track): with the prediction on, the predicted one.
+ * THE CONTRACT is svo_klt_step's with public calls added: after a step in mode 1 every getter of the lane and svo_klt_get_tracks return
+ * byte for byte what the recipe of svo_klt_step leaves when svo_get_result and svo_klt_get_tracks are read before its shift call, the
+ * guesses are computed by the rule on the host, and they are passed as `init` of both svo_lk_track jobs of the lane
+ * (tests/klt_predict_ref.py holds the walk and the recipe).
+ * svo_klt_predicted synchronises and returns, for the lane's live tracks, the guesses the next svo_klt_step would start from as things
+ * stand now (the lane's record and table of this moment; a lane without a last pair does not predict): it returns the live count, like
+ * svo_klt_get_tracks, and writes min(count, cap) entries of left_xy / right_xy (x, y pairs) and `used`; any array may be NULL.
+ * svo_debug_klt_predict runs the same kernel on the lane's table with the caller's delta6 and valid in place of the lane's record:
+ * the rule on inputs no sequence could produce, the counterpart of svo_debug_klt_select.  Neither changes a table, a list or a record.
+ * Both are refused with SVO_ERR_STATE before svo_klt_enable, before svo_set_params, inside a captured graph and while the mode is 0,
+ * and with SVO_ERR_ARG for a lane outside the context, cap < 0 or delta6 == NULL, in that order.
+ * No constant-image-flow mode for lanes without a valid pose, no prediction from a caller's pose or an IMU, no automatic choice of the
+ * pyramid depth, no prediction inside svo_klt_topup; no svo_batch, frame-parallel or graph-captured form. */
+int svo_klt_set_prediction(svo_ctx* ctx, int mode);     /* 0 off (default), 1 constant-velocity pose prediction */
+int svo_klt_get_prediction(const svo_ctx* ctx);
+int svo_klt_predicted(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, uint8_t* used, int cap);
+int svo_debug_klt_predict(svo_ctx* ctx, int lane, const double* delta6, int valid,
+                          float* left_xy, float* right_xy, uint8_t* used, int cap);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -830,8 +876,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * svo_debug_klt_select; "klt_topup" behind that, once the context has made a svo_klt_topup or svo_debug_klt_topup_append call (its
  * three kernels count there, its detector and tracker launches under the gftt and lk names, which are then listed as well, and
  * "klt_select" with them); "ransac_feed" behind all of those, once the context has made a svo_ransac_tracked call or a step under
- * svo_klt_set_ransac (the RANSAC launches behind it count under "ransac_hyp" .. "track_finalize"), and "klt_prune" last, once a step
- * in mode 2 has run. */
+ * svo_klt_set_ransac (the RANSAC launches behind it count under "ransac_hyp" .. "track_finalize"), "klt_prune" behind it, once a step
+ * in mode 2 has run, and "klt_predict" last, once the context has made a step under svo_klt_set_prediction(1) or a svo_klt_predicted /
+ * svo_debug_klt_predict call. */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

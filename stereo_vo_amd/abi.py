@@ -214,6 +214,9 @@ TOPUP_OK, TOPUP_OVERFLOW, TOPUP_ENOUGH, TOPUP_NO_PAIR, TOPUP_NOT_ASKED = range(5
 # svo_klt_set_ransac: the RANSAC gate of svo_klt_step
 KLT_RANSAC_OFF, KLT_RANSAC_FILTER, KLT_RANSAC_PRUNE = range(3)
 
+# svo_klt_set_prediction: where the forward pass of svo_klt_step starts its search
+KLT_PREDICT_OFF, KLT_PREDICT_POSE = range(2)
+
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")
 

@@ -1134,29 +1134,117 @@ void launch_landmarks(const DevCtx& c, const GNParams& P, const LmkArgs& A, hipS
 // ------------------------------------------------------------------------------------------------------------
 struct Delta6 { double v[6]; };
 
+// One point: triangulated from (ul, vl, ur) as stage 5 does, moved by the rotation r (row-major 3 x 3) and the translation t, projected
+// into both cameras.  One IEEE operation per operator, in this order: k_project_points and k_klt_predict both evaluate exactly this.
+// Returns the disparity and the moved depth with the four pixels (uL vL uR vR)
+struct MovedPoint { double disparity, Z1c; float pix[4]; };
+__device__ __forceinline__ MovedPoint triangulate_move_project(double ul, double vl, double ur, const svo_stereo_camera& cam, const double* r, const double* t)
+{
+    MovedPoint m;
+    const double cul = cam.l_cx, cvl = cam.l_cy, fl = cam.l_fx, cur = cam.r_cx, fr = cam.r_fx;
+    const double disparity = fl * (cur - ur) + fr * (ul - cul);
+    const double b_d = cam.baseline / disparity;
+    const double X1p = b_d * fr * (ul - cul), Y1p = b_d * fr * (vl - cvl), Z1p = b_d * fl * fr;
+    const double X1c = r[0] * X1p + r[1] * Y1p + r[2] * Z1p + t[0];
+    const double Y1c = r[3] * X1p + r[4] * Y1p + r[5] * Z1p + t[1];
+    const double Z1c = r[6] * X1p + r[7] * Y1p + r[8] * Z1p + t[2];
+    const double X2c = X1c - cam.baseline;
+    m.disparity = disparity; m.Z1c = Z1c;
+    m.pix[0] = (float)(cam.l_fx * X1c / Z1c + cam.l_cx);
+    m.pix[1] = (float)(cam.l_fy * Y1c / Z1c + cam.l_cy);
+    m.pix[2] = (float)(cam.r_fx * X2c / Z1c + cam.r_cx);
+    m.pix[3] = (float)(cam.r_fy * Y1c / Z1c + cam.r_cy);
+    return m;
+}
+
 __global__ void __launch_bounds__(256) k_project_points(const float* uvu, int n, svo_stereo_camera cam, Delta6 dp, float* pix)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Rot R; rodrigues_with_derivs<false>(dp.v, R);
     const double ul = (double)uvu[3 * i], vl = (double)uvu[3 * i + 1], ur = (double)uvu[3 * i + 2];
-    const double cul = cam.l_cx, cvl = cam.l_cy, fl = cam.l_fx, cur = cam.r_cx, fr = cam.r_fx;
-    const double disparity = fl * (cur - ur) + fr * (ul - cul);
-    const double b_d = cam.baseline / disparity;
-    const double X1p = b_d * fr * (ul - cul), Y1p = b_d * fr * (vl - cvl), Z1p = b_d * fl * fr;
-    const double* r = R.r;
-    const double X1c = r[0] * X1p + r[1] * Y1p + r[2] * Z1p + dp.v[3];
-    const double Y1c = r[3] * X1p + r[4] * Y1p + r[5] * Z1p + dp.v[4];
-    const double Z1c = r[6] * X1p + r[7] * Y1p + r[8] * Z1p + dp.v[5];
-    const double X2c = X1c - cam.baseline;
-    pix[4 * i + 0] = (float)(cam.l_fx * X1c / Z1c + cam.l_cx);
-    pix[4 * i + 1] = (float)(cam.l_fy * Y1c / Z1c + cam.l_cy);
-    pix[4 * i + 2] = (float)(cam.r_fx * X2c / Z1c + cam.r_cx);
-    pix[4 * i + 3] = (float)(cam.r_fy * Y1c / Z1c + cam.r_cy);
+    const MovedPoint m = triangulate_move_project(ul, vl, ur, cam, R.r, dp.v + 3);
+    pix[4 * i + 0] = m.pix[0];
+    pix[4 * i + 1] = m.pix[1];
+    pix[4 * i + 2] = m.pix[2];
+    pix[4 * i + 3] = m.pix[3];
 }
 
 void launch_project_points(const float* uvu, int n, const svo_stereo_camera& cam, const double* delta6, float* pix, hipStream_t st)
 {
     Delta6 d; for (int k = 0; k < 6; k++) d.v[k] = delta6[k];
     if (n > 0) hipLaunchKernelGGL(k_project_points, dim3((n + 255) / 256), dim3(256), 0, st, uvu, n, cam, d, pix);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// svo_klt_set_prediction(1): the first guesses of a step of the resident KLT front end (svo_hip.h; the walk: tests/klt_predict_ref.py).
+// Grid (ceil(cap / 256), n_lanes), one thread per slot.  Thread 0 of a block decides whether the lane predicts -- it is one of
+// `tracks`, its record is valid, its six delta values are finite -- and builds the lane's rotation ONCE into LDS (section 7 of DESIGN.md:
+// what a rotation per thread cost k_landmarks); behind the barrier every thread triangulates its slot from the live half, moves it and
+// projects it with the expressions of k_project_points.  A slot whose guess cannot be used, and every slot of a lane that does not
+// predict, starts at its own points; the slots behind the live count get NaN.  Reads: the live half, the lane's count, its record and
+// camera.  Writes: the guesses and `used`, nothing else.
+// ------------------------------------------------------------------------------------------------------------
+// (the rotation is built in place in LDS: a Rot local to thread 0 leaves its two small-angle branches in scratch)
+struct KltPredictLds { Rot R; double t[3]; int predicts; };
+static __device__ __forceinline__ bool predict_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ void __launch_bounds__(256) k_klt_predict(const DevCtx c, const KltPredictArgs a)
+{
+    __shared__ KltPredictLds S;
+    const int lane = a.only_lane >= 0 ? a.only_lane : (int)blockIdx.y;
+    const int slot = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int cap = a.t.cap;
+    if (threadIdx.x == 0) {
+        int predicts = 0;
+        if (lane_bit(a.tracks, lane)) {
+            Delta6 d;
+            int valid;
+            if (a.forced) { valid = a.forced_valid; for (int k = 0; k < 6; k++) d.v[k] = a.forced_delta[k]; }
+            else { const svo_result& res = c.results[lane]; valid = res.valid; for (int k = 0; k < 6; k++) d.v[k] = res.delta[k]; }
+            bool finite = true;
+            for (int k = 0; k < 6; k++) finite = finite && isfinite(d.v[k]);
+            if (valid != 0 && finite) {
+                rodrigues_with_derivs<false>(d.v, S.R);
+                for (int k = 0; k < 3; k++) S.t[k] = d.v[3 + k];
+                predicts = 1;
+            }
+        }
+        S.predicts = predicts;
+    }
+    __syncthreads();
+    if (slot >= cap) return;
+    const float2* __restrict__ pts = a.t.pts[a.half] + (size_t)lane * 2 * cap;
+    const int n = a.t.lane[lane].n, n_live = n < cap ? n : cap;
+    float2 gl, gr;
+    bool used = false;
+    if (slot < n_live) {
+        const float2 pl = pts[slot], pr = pts[cap + slot];
+        gl = pl; gr = pr;
+        if (S.predicts) {
+            const svo_stereo_camera cam = c.cams[lane];
+            double r[9], t[3];
+            for (int k = 0; k < 9; k++) r[k] = S.R.r[k];
+            for (int k = 0; k < 3; k++) t[k] = S.t[k];
+            const MovedPoint m = triangulate_move_project((double)pl.x, (double)pl.y, (double)pr.x, cam, r, t);
+            used = m.disparity > 0.0 && m.Z1c > 0.0
+                && predict_finite(m.pix[0]) && predict_finite(m.pix[1]) && predict_finite(m.pix[2]) && predict_finite(m.pix[3])
+                && m.pix[0] >= 0.0f && m.pix[0] <= a.x_max && m.pix[1] >= 0.0f && m.pix[1] <= a.y_max
+                && m.pix[2] >= 0.0f && m.pix[2] <= a.x_max && m.pix[3] >= 0.0f && m.pix[3] <= a.y_max;
+            if (used) { gl = make_float2(m.pix[0], m.pix[1]); gr = make_float2(m.pix[2], m.pix[3]); }
+        }
+    } else {
+        const float nan = __uint_as_float(0x7fc00000u);
+        gl = make_float2(nan, nan); gr = gl;
+    }
+    a.guess[(size_t)(2 * lane) * cap + slot] = gl;
+    a.guess[(size_t)(2 * lane + 1) * cap + slot] = gr;
+    a.used[(size_t)lane * cap + slot] = used ? 1 : 0;
+}
+
+void launch_klt_predict(const DevCtx& c, const KltPredictArgs& a, hipStream_t st)
+{
+    if (a.t.n_lanes <= 0 || a.t.cap <= 0) return;
+    const dim3 grid((unsigned)((a.t.cap + 255) / 256), (unsigned)(a.only_lane >= 0 ? 1 : a.t.n_lanes));
+    hipLaunchKernelGGL(k_klt_predict, grid, dim3(256), 0, st, c, a);
 }

@@ -278,8 +278,9 @@ void launch_klt_prune(const DevCtx& c, const KltDev& t, int half, hipStream_t st
 }
 
 // the job records of a step (KltJobArgs, svo_kernels.h): thread l < n_lanes writes lane l's pyramid record, thread n_lanes + j the
-// tracking record of job j = 2 * lane + side
-__global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a)
+// tracking record of job j = 2 * lane + side.  has_init: 1 under svo_klt_set_prediction(1), where the forward launch starts from the
+// guesses of k_klt_predict (k_gn.hip)
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a, const int has_init)
 {
     const int t = blockIdx.x * KLT_BLOCK + threadIdx.x;
     if (t >= 3 * a.n_lanes) return;
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a)
     LkJobDev& J = pyr ? a.pyr_jobs[lane] : a.trk_jobs[2 * lane + side];      // written in place: a local record indexed by level would live in scratch
     for (int s = 0; s < 2; s++) for (int l = 0; l < 6; l++) { J.img[s][l] = nullptr; J.pitch[s][l] = 0; }
     for (int l = 0; l < 6; l++) { J.w[l] = 0; J.h[l] = 0; }
-    J.pt0 = pyr ? 0 : (2 * lane + side) * a.cap; J.n = pyr ? 0 : a.cap; J.has_init = 0;
+    J.pt0 = pyr ? 0 : (2 * lane + side) * a.cap; J.n = pyr ? 0 : a.cap; J.has_init = pyr ? 0 : has_init;
     auto block = [&](int parity, int sd) { return a.pyr + ((long long)(parity * a.n_lanes + lane) * 2 + sd) * a.img_stride; };
     // a lane that builds no pyramid has no level; a lane that tracks nothing has one level of 0 x 0 pixels
     const bool none = pyr ? lane_bit(a.idle, lane) : lane_bit(a.empty, lane);
@@ -302,10 +303,10 @@ __global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a)
     }
 }
 
-void launch_klt_jobs(const KltJobArgs& a, hipStream_t st)
+void launch_klt_jobs(const KltJobArgs& a, int has_init, hipStream_t st)
 {
     if (a.n_lanes <= 0) return;
-    hipLaunchKernelGGL(k_klt_jobs, dim3((unsigned)((3 * a.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_klt_jobs, dim3((unsigned)((3 * a.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a, has_init);
 }
 
 // ---- svo_klt_topup ------------------------------------------------------------------------------------------------------------

@@ -130,6 +130,42 @@ int check_klt_set_ransac(const State& s, int mode, std::string& why)
     return SVO_OK;
 }
 
+// ---- the pose prediction ----
+int check_klt_set_prediction(const State& s, int mode, bool have_buffer, bool& alloc, std::string& why)
+{
+    char msg[200];
+    alloc = false;
+    why.clear();
+    if (!s.enabled) { why = "svo_klt_set_prediction: the KLT front end is not enabled (svo_klt_enable)"; return SVO_ERR_STATE; }
+    if (s.capturing) { why = "svo_klt_set_prediction: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (mode < KLT_PREDICT_OFF || mode > KLT_PREDICT_POSE) {
+        snprintf(msg, sizeof(msg), "svo_klt_set_prediction: mode %d: 0 (off) or 1 (constant-velocity pose prediction) is expected", mode);
+        why = msg; return SVO_ERR_ARG;
+    }
+    alloc = mode == KLT_PREDICT_POSE && !have_buffer;
+    return SVO_OK;
+}
+
+int check_klt_predict_call(const State& s, const char* entry, int mode, int lane, int cap, bool delta_ok, const Caps& caps, std::string& why)
+{
+    char msg[200];
+    if (const int rc = check_klt_ready(s, entry, why)) return rc;
+    if (mode != KLT_PREDICT_POSE) { snprintf(msg, sizeof(msg), "%s: the prediction is off (svo_klt_set_prediction)", entry); why = msg; return SVO_ERR_STATE; }
+    if (lane < 0 || lane >= caps.n_lanes) { snprintf(msg, sizeof(msg), "%s: lane %d of %d", entry, lane, caps.n_lanes); why = msg; return SVO_ERR_ARG; }
+    if (cap < 0) { snprintf(msg, sizeof(msg), "%s: room for %d entries", entry, cap); why = msg; return SVO_ERR_ARG; }
+    if (!delta_ok) { snprintf(msg, sizeof(msg), "%s: delta6 == NULL", entry); why = msg; return SVO_ERR_ARG; }
+    return SVO_OK;
+}
+
+PredictPlan plan_predict(const svo_klt_params& p, const Caps& caps)
+{
+    PredictPlan pl;
+    pl.n_guess = (long long)caps.n_lanes * 2 * p.cap;
+    pl.n_used = (long long)caps.n_lanes * p.cap;
+    pl.blocks_x = (p.cap + 255) / 256;
+    return pl;
+}
+
 svo_lk::Geometry klt_geometry(const svo_klt_params& p, int w, int h) { return svo_lk::lk_geometry(w, h, p.lk.win, p.lk.max_level, true); }
 
 Plan plan_klt(const svo_klt_params& p, const Caps& caps)

@@ -1,6 +1,7 @@
 // klt_call.hpp -- what the calls of the resident KLT front end ARE, decided on the host without a device: the parameter ranges of
 // svo_klt_params, every refusal of svo_klt_enable / svo_klt_step / svo_klt_add_points / svo_klt_get_tracks / svo_klt_reset /
-// svo_debug_klt_select in the order they are made, and the buffer plan (pyramid ping-pong, table ping-pong, job records).
+// svo_debug_klt_select in the order they are made, and the buffer plan (pyramid ping-pong, table ping-pong, job records); the same for
+// the top-up, the RANSAC gate and the pose prediction.
 // Host only, no HIP: svo_api.hip acts on these decisions, k_klt.hip reads the buffers they size, and tools/klt_check.cpp drives them
 // under the sanitizers on the CPU (`make hostcheck`).
 #pragma once
@@ -46,8 +47,26 @@ int check_ransac_tracked(bool params_set, bool geom_ready, bool capturing, const
 // svo_klt_set_ransac: the front end enabled and no capture (SVO_ERR_STATE), then the mode, 0 .. 2 (SVO_ERR_ARG)
 int check_klt_set_ransac(const State& s, int mode, std::string& why);
 
+// ---- the pose prediction (svo_klt_set_prediction / svo_klt_get_prediction / svo_klt_predicted / svo_debug_klt_predict;
+//      tools/klt_predict_check.cpp drives these) ----
+enum { KLT_PREDICT_OFF = 0, KLT_PREDICT_POSE = 1 };
+// svo_klt_set_prediction: the front end enabled and no capture (SVO_ERR_STATE), then the mode, 0 .. 1 (SVO_ERR_ARG).  alloc: the call
+// must make the guess buffer (mode 1 and no buffer yet)
+int check_klt_set_prediction(const State& s, int mode, bool have_buffer, bool& alloc, std::string& why);
+// svo_klt_predicted / svo_debug_klt_predict, in order: ready (check_klt_ready), the prediction on (SVO_ERR_STATE), then the lane, a count
+// >= 0 and the arrays (SVO_ERR_ARG; delta_ok: svo_debug_klt_predict's delta6 is there)
+int check_klt_predict_call(const State& s, const char* entry, int mode, int lane, int cap, bool delta_ok, const Caps& caps, std::string& why);
+// the one buffer of the prediction: the guesses [n_lanes][2 sides][cap] float2, laid out as the tracker's results are (job 2 * lane + side
+// owns slots [job * cap, (job + 1) * cap)), and a byte per slot [n_lanes][cap]
+struct PredictPlan {
+    long long n_guess;              // float2: n_lanes * 2 * cap
+    long long n_used;               // bytes: n_lanes * cap
+    int blocks_x;                   // k_klt_predict's grid: (ceil(cap / 256), n_lanes)
+};
+PredictPlan plan_predict(const svo_klt_params& p, const Caps& caps);
+
 // the buffers of an enabled context, sized for max_w x max_h images:
-//   pyramids   [2 parities][n_lanes][2 sides] blocks of img_stride bytes, the levels of one image tightly packed (lk_geometry with
+//   pyramids  [2 parities][n_lanes][2 sides] blocks of img_stride bytes, the levels of one image tightly packed (lk_geometry with
 //              level 0).  A lane's new pair goes to the parity its last pair did NOT go to: the other parity still holds frame t - 1
 //   table      [2 halves] x ( points [n_lanes][2 sides][cap] float2 + meta [n_lanes][4][cap] int32: id, age, index in the list of the
 //              last step, index in the lane's previous-slot list ).  k_klt_select reads one half and writes the other

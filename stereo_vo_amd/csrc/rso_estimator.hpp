@@ -377,6 +377,10 @@ public:
     void filterTrackedRANSAC() { check(svo_ransac_tracked(m_ctx, NULL), "svo_ransac_tracked"); }
     void setKLTRansac(int mode) { check(svo_klt_set_ransac(m_ctx, mode), "svo_klt_set_ransac"); }
     int getKLTRansac() const { return svo_klt_get_ransac(m_ctx); }
+    /** Where stepKLT starts its search (svo_klt_set_prediction): 0 at every track's old position (default), 1 at the track
+     *  triangulated from its stereo pair, moved by the pose increment of the last optimised step (constant velocity) and reprojected
+     *  into both cameras.  A step that did not end valid predicts nothing for the next one. */
+    void setKltPrediction(int mode) { check(svo_klt_set_prediction(m_ctx, mode), "svo_klt_set_prediction"); }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

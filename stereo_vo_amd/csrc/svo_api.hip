@@ -49,7 +49,8 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
        KT_KLT_SELECT = KT_COUNT, KT_KLT_TOPUP, KT_ALL };
 // ... and "ransac_feed" (svo_ransac_tracked, or a step under svo_klt_set_ransac) and "klt_prune" (a step in mode 2) behind those, each
 // once the context has launched it.  The RANSAC launches between them count under their names of a frame
-enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_EVERY };
+// ... and "klt_predict" (a step under svo_klt_set_prediction(1), svo_klt_predicted, svo_debug_klt_predict) last of all
+enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_KLT_PREDICT, KT_EVERY };
 static_assert(KT_EVERY <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
@@ -59,7 +60,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
 static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
-static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : kt_name(i); }
+static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : i == KT_KLT_PREDICT ? "klt_predict" : kt_name(i); }
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -144,6 +145,9 @@ struct svo_ctx {
         int half, w, h; LaneMask parity, has_img;
         int ransac;                                    // svo_klt_set_ransac: 0 off, 1 filter the tracked pairs, 2 and drop the rejected tracks
         bool prune_used;                               // a step has launched k_klt_prune (svo_kernel_times)
+        // svo_klt_set_prediction: 0 off, 1 constant-velocity pose prediction.  The one buffer of mode 1 (klt_call.hpp: plan_predict), made
+        // by the first call with mode 1 and dropped with the front end's buffers: the guesses and a byte per slot
+        int predict; float2* d_guess; uint8_t* d_gused;
         // the resident top-up (svo_klt_topup_enable; the plan: klt_call.hpp), buffers of its own: the response maps, the detector's job
         // records, keys, cell lists, states and counters, the corners with their responses, the first guesses, the tracker's records and
         // results, four ints per lane for svo_klt_topup_info.  topup_used: a top-up has run (svo_kernel_times, svo_klt_topup_enable)
@@ -153,6 +157,7 @@ struct svo_ctx {
     } klt;
     bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
     bool ransac_feed_used;                             // the context has launched k_ransac_feed (svo_kernel_times)
+    bool klt_predict_used;                             // the context has launched k_klt_predict (svo_kernel_times)
     bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
@@ -451,7 +456,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
     ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
-    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false;
+    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false; ctx->klt_predict_used = false;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -1312,9 +1317,9 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
         if (n < cap) { if (names) names[n] = kt_name_all(KT_KLT_TOPUP); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_TOPUP]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_TOPUP]; }
         n++;
     }
-    // "ransac_feed" and "klt_prune" behind everything else, each once the context has launched the kernel
-    for (int k = KT_RANSAC_FEED; k <= KT_KLT_PRUNE; k++) {
-        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : ctx->klt.prune_used)) continue;
+    // "ransac_feed", "klt_prune" and "klt_predict" behind everything else, each once the context has launched the kernel
+    for (int k = KT_RANSAC_FEED; k <= KT_KLT_PREDICT; k++) {
+        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : k == KT_KLT_PRUNE ? ctx->klt.prune_used : ctx->klt_predict_used)) continue;
         if (n < cap) { if (names) names[n] = kt_name_all(k); if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
         n++;
     }
@@ -2768,7 +2773,8 @@ static void klt_free(svo_ctx* ctx)
     for (void* p : { (void*)k.dev.pts[0], (void*)k.dev.pts[1], (void*)k.dev.meta[0], (void*)k.dev.meta[1], (void*)k.dev.lane, (void*)k.dev.out, (void*)k.dev.status,
                      (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage,
                      (void*)k.d_tmap, (void*)k.d_tgjobs, (void*)k.d_tkeys, (void*)k.d_titems, (void*)k.d_tstate, (void*)k.d_tginfo, (void*)k.d_tinfo, (void*)k.d_tcorners,
-                     (void*)k.d_tinit, (void*)k.d_tout, (void*)k.d_tresp, (void*)k.d_terr, (void*)k.d_tstatus, (void*)k.d_tlk_jobs }) if (p) (void)hipFree(p);
+                     (void*)k.d_tinit, (void*)k.d_tout, (void*)k.d_tresp, (void*)k.d_terr, (void*)k.d_tstatus, (void*)k.d_tlk_jobs,
+                     (void*)k.d_guess, (void*)k.d_gused }) if (p) (void)hipFree(p);
     memset(&k, 0, sizeof(k));
 }
 static svo_klt::Caps klt_caps(const svo_ctx* ctx) { return { ctx->cfg.n_lanes, ctx->dc.max_kps, ctx->cfg.max_w, ctx->cfg.max_h }; }
@@ -2942,6 +2948,88 @@ extern "C" int svo_klt_set_ransac(svo_ctx* ctx, int mode)
 }
 extern "C" int svo_klt_get_ransac(const svo_ctx* ctx) { return ctx ? ctx->klt.ransac : SVO_ERR_ARG; }
 
+// ---- the pose prediction of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernel: k_klt_predict in k_gn.hip) ----
+// the guesses for the table as it stands: the lanes of `tracks` may predict; only_lane >= 0: that lane alone; delta6: the caller's
+// increment and `valid` in place of the lanes' records (svo_debug_klt_predict)
+static void klt_predict(svo_ctx* ctx, const LaneMask& tracks, int only_lane, const double* delta6, int valid, hipStream_t st)
+{
+    svo_ctx::Klt& k = ctx->klt;
+    KltPredictArgs a; memset(&a, 0, sizeof(a));
+    a.t = k.dev; a.half = k.half;
+    a.guess = k.d_guess; a.used = k.d_gused;
+    a.tracks = tracks;
+    a.x_max = (float)(k.w - 1); a.y_max = (float)(k.h - 1);
+    a.only_lane = only_lane;
+    if (delta6) { a.forced = 1; a.forced_valid = valid; for (int i = 0; i < 6; i++) a.forced_delta[i] = delta6[i]; }
+    { Span s(ctx, KT_KLT_PREDICT); launch_klt_predict(ctx->dc, a, st); }
+    ctx->klt_predict_used = true;
+}
+
+extern "C" int svo_klt_set_prediction(svo_ctx* ctx, int mode)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    bool alloc = false;
+    { std::string why; const int rc = svo_klt::check_klt_set_prediction(klt_state(ctx), mode, k.d_guess != nullptr, alloc, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (alloc) {
+        const svo_klt::PredictPlan plan = svo_klt::plan_predict(k.p, klt_caps(ctx));
+        hipError_t e = lk_realloc(&k.d_guess, (size_t)plan.n_guess);
+        if (e == hipSuccess) e = lk_realloc(&k.d_gused, (size_t)plan.n_used);
+        if (e != hipSuccess) {                              // the mode stays as it was
+            (void)hipGetLastError();
+            if (k.d_guess) { (void)hipFree(k.d_guess); k.d_guess = nullptr; }
+            if (k.d_gused) { (void)hipFree(k.d_gused); k.d_gused = nullptr; }
+            HIPCHECK(e);
+        }
+    }
+    k.predict = mode;
+    return SVO_OK;
+}
+extern "C" int svo_klt_get_prediction(const svo_ctx* ctx) { return ctx ? ctx->klt.predict : SVO_ERR_ARG; }
+
+// svo_klt_predicted and svo_debug_klt_predict: the kernel on one lane, then the lane's count and its guesses back
+static int klt_predict_lane(svo_ctx* ctx, const char* entry, int lane, const double* delta6, bool forced, int valid, float* left_xy, float* right_xy, uint8_t* used, int cap)
+{
+    svo_ctx::Klt& k = ctx->klt;
+    { std::string why; const int rc = svo_klt::check_klt_predict_call(klt_state(ctx), entry, k.predict, lane, cap, !forced || delta6 != nullptr, klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
+    { const int rc = svo_wait(ctx); if (rc) return rc; }
+    LaneMask tracks; memset(&tracks, 0, sizeof(tracks));
+    if (lane_in(k.has_img, lane)) tracks.w[lane >> 6] = 1ull << (lane & 63);
+    const hipStream_t st = ctx->stream;
+    note_stream(ctx);
+    MarkGuard mark_guard{ ctx };
+    klt_predict(ctx, tracks, lane, forced ? delta6 : nullptr, valid, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    KltLaneDev kl;
+    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
+    const int C = k.p.cap, n = kl.n < C ? kl.n : C, m = n < cap ? n : cap;
+    if (m <= 0) return n;
+    const float2* g = k.d_guess + (size_t)lane * 2 * C;
+    if (left_xy) HIPCHECK(hipMemcpy(left_xy, g, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
+    if (right_xy) HIPCHECK(hipMemcpy(right_xy, g + C, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
+    if (used) HIPCHECK(hipMemcpy(used, k.d_gused + (size_t)lane * C, (size_t)m, hipMemcpyDeviceToHost));
+    return n;
+}
+
+extern "C" int svo_klt_predicted(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, uint8_t* used, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    return klt_predict_lane(ctx, "svo_klt_predicted", lane, nullptr, false, 0, left_xy, right_xy, used, cap);
+}
+
+extern "C" int svo_debug_klt_predict(svo_ctx* ctx, int lane, const double* delta6, int valid, float* left_xy, float* right_xy, uint8_t* used, int cap)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    return klt_predict_lane(ctx, "svo_debug_klt_predict", lane, delta6, true, valid, left_xy, right_xy, used, cap);
+}
+
 extern "C" int svo_ransac_tracked(svo_ctx* ctx, const uint64_t lanes[2])
 {
     if (ctx) use_device(ctx);
@@ -2980,6 +3068,13 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
     MarkGuard mark_guard{ ctx };
     d.idle = idle;
     IdleGuard idle_guard{ &d };
+    // 0. under svo_klt_set_prediction(1): the first guesses of the lanes that will track, AHEAD of the shift -- k_begin_frame starts the
+    //    lanes' records afresh, and the prediction reads them as the last step left them (images of another size track nothing)
+    if (k.predict == svo_klt::KLT_PREDICT_POSE) {
+        LaneMask tracks; memset(&tracks, 0, sizeof(tracks));
+        if (w == k.w && h == k.h) for (int wd = 0; wd < 2; wd++) tracks.w[wd] = active.w[wd] & k.has_img.w[wd];
+        klt_predict(ctx, tracks, -1, nullptr, 0, st);
+    }
     // 1. the shift
     { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
     // 2. the new pair of every active lane into the parity its last pair did not go to; images of another size than the last step's
@@ -3003,12 +3098,12 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
     ja.n_lanes = d.n_lanes; ja.cap = k.p.cap; ja.nl = g.nl;
     for (int l = 0; l < g.nl; l++) { ja.w[l] = g.w[l]; ja.h[l] = g.h[l]; ja.off[l] = g.off[l]; }
     ja.parity = k.parity; ja.empty = empty; ja.idle = idle;
-    { Span s(ctx, KT_LK_PYRDOWN); launch_klt_jobs(ja, st); for (int l = 1; l < g.nl; l++) launch_lk_pyrdown(k.d_pyr_jobs, d.n_lanes, l, g.w[l], g.h[l], st); }
+    { Span s(ctx, KT_LK_PYRDOWN); launch_klt_jobs(ja, k.predict == svo_klt::KLT_PREDICT_POSE ? 1 : 0, st); for (int l = 1; l < g.nl; l++) launch_lk_pyrdown(k.d_pyr_jobs, d.n_lanes, l, g.w[l], g.h[l], st); }
     // 3. one tracking launch over every lane's two jobs (and the way back under fb_max); no lane has a last pair: nothing to track
     if (any_tracks) {
         LkTrackArgs a;
         a.jobs = k.d_trk_jobs; a.n_jobs = 2 * d.n_lanes; a.n_pts = 2 * d.n_lanes * k.p.cap;
-        a.pts = k.dev.pts[k.half]; a.aux = nullptr;
+        a.pts = k.dev.pts[k.half]; a.aux = k.predict == svo_klt::KLT_PREDICT_POSE ? k.d_guess : nullptr;      // (read for records with has_init)
         a.out = k.dev.out; a.status = k.dev.status; a.err = k.dev.err;
         a.p = k.p.lk; a.backward = 0;
         Span s(ctx, KT_LK_TRACK);

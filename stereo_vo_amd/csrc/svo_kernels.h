@@ -193,7 +193,21 @@ struct KltJobArgs {
     LaneMask parity, empty, idle;
 };
 size_t klt_select_lds_bytes(int H);
-void launch_klt_jobs(const KltJobArgs& a, hipStream_t st);
+// has_init: what every tracking record gets (1 under svo_klt_set_prediction(1): the forward launch then reads its first guesses from aux)
+void launch_klt_jobs(const KltJobArgs& a, int has_init, hipStream_t st);
+// svo_klt_set_prediction(1) (k_klt_predict in k_gn.hip, beside k_project_points): the first guesses of a step's forward tracking launch.
+// For lane l and slot s < cap: guess[(2 * l + side) * cap + s] and used[l * cap + s].  A lane of `tracks` whose record (DevCtx.results, or
+// forced_valid / forced_delta under `forced`) is valid with a finite delta moves its live slots by that increment; every other slot gets
+// its own points (NaN behind the live count) and used = 0.  only_lane >= 0: that lane alone (grid.y = 1)
+struct KltPredictArgs {
+    KltDev t; int half;               // the live half, read only
+    float2* guess; uint8_t* used;
+    LaneMask tracks;                  // the lanes of the step's mask that have a last pair
+    float x_max, y_max;               // w - 1 and h - 1 of level 0 of that pair
+    int only_lane;
+    int forced, forced_valid; double forced_delta[6];
+};
+void launch_klt_predict(const DevCtx& c, const KltPredictArgs& a, hipStream_t st);
 void launch_klt_select(const DevCtx& c, const KltSelectArgs& a, hipStream_t st);
 void launch_klt_append(const KltDev& t, int half, int lane, const float2* left, const float2* right, int n, hipStream_t st);
 // empties the tables of the lanes of the mask in `half` and starts their IDs over

@@ -36,6 +36,7 @@ EXPORTS = [
     "svo_klt_default_params", "svo_klt_enable", "svo_klt_reset", "svo_klt_add_points", "svo_klt_step", "svo_klt_get_tracks", "svo_debug_klt_select",
     "svo_klt_topup_default_params", "svo_klt_topup_enable", "svo_klt_topup", "svo_klt_topup_info", "svo_debug_klt_topup_append",
     "svo_ransac_tracked", "svo_klt_set_ransac", "svo_klt_get_ransac",
+    "svo_klt_set_prediction", "svo_klt_get_prediction", "svo_klt_predicted", "svo_debug_klt_predict",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -166,6 +167,11 @@ def lib():
             L.svo_ransac_tracked.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
             L.svo_klt_set_ransac.argtypes = [C.c_void_p, C.c_int]
             L.svo_klt_get_ransac.argtypes = [C.c_void_p]
+        if hasattr(L, "svo_klt_set_prediction"):    # (as above)
+            L.svo_klt_set_prediction.argtypes = [C.c_void_p, C.c_int]
+            L.svo_klt_get_prediction.argtypes = [C.c_void_p]
+            L.svo_klt_predicted.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.svo_debug_klt_predict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -1021,6 +1027,34 @@ class Context:
         """the mode svo_klt_set_ransac left"""
         return self._ck(self.L.svo_klt_get_ransac(self.h), "svo_klt_get_ransac")
 
+    # -- the pose prediction of the front end (svo_klt_set_prediction) ------------------------------------------------
+    def klt_set_prediction(self, mode):
+        """where the forward pass of svo_klt_step starts: abi.KLT_PREDICT_OFF (0, the default: at the track's old position) or
+        KLT_PREDICT_POSE (1: the track triangulated, moved by the lane's last pose increment and reprojected).  After klt_enable."""
+        self._ck(self.L.svo_klt_set_prediction(self.h, int(mode)), "svo_klt_set_prediction")
+
+    def klt_prediction(self):
+        """the mode svo_klt_set_prediction left"""
+        return self._ck(self.L.svo_klt_get_prediction(self.h), "svo_klt_get_prediction")
+
+    def _klt_guesses(self, what, call):
+        n = self._ck(call(None, None, None, 0), what)
+        l, r, used = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        if n:
+            self._ck(call(_vp(l), _vp(r), _vp(used), n), what)
+        return l, r, used
+
+    def klt_predicted(self, lane=0):
+        """(left [n, 2] float32, right [n, 2] float32, used [n] uint8): the guesses the next klt_step would start the lane's live tracks
+        from as things stand now; used = 0: the track's own points.  Needs mode 1.  Synchronises (svo_klt_predicted)."""
+        return self._klt_guesses("svo_klt_predicted", lambda l, r, u, cap: self.L.svo_klt_predicted(self.h, int(lane), l, r, u, cap))
+
+    def debug_klt_predict(self, lane, delta6, valid):
+        """klt_predicted with `delta6` (six float64: the rotation vector, the translation) and `valid` in place of the lane's result
+        record (svo_debug_klt_predict)"""
+        d = np.ascontiguousarray(delta6, np.float64).reshape(6)
+        return self._klt_guesses("svo_debug_klt_predict", lambda l, r, u, cap: self.L.svo_debug_klt_predict(self.h, int(lane), _vp(d), int(valid), l, r, u, cap))
+
     # -- timing ----------------------------------------------------------------------------------------
     FRAME_KERNEL_NAMES = 32
 
@@ -1029,7 +1063,8 @@ class Context:
         hand-over calls; the names appended behind them belong to other entry points ("gather_windows": svo_gather_windows;
         "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, "lk_pyrdown", "lk_track": svo_lk_track and svo_klt_step, and
         "klt_select": svo_klt_step, "klt_topup": svo_klt_topup, "ransac_feed": svo_ransac_tracked and a step under klt_set_ransac,
-        "klt_prune": a step in mode 2, each listed once the context has made such a call) and are
+        "klt_prune": a step in mode 2, "klt_predict": a step under klt_set_prediction(1), klt_predicted and debug_klt_predict,
+        each listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
         tot = (C.c_double * 64)()
