@@ -618,6 +618,19 @@ int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_
  * w * h (with out == NULL: the size only); 0 when the call built no such level (or no call was made); SVO_ERR_CAPACITY when cap < w * h.
  * Level 0 of a device image is read from the caller's memory, which must still hold it. */
 int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h);
+/* THE ROW TRACKER: svo_lk_track with one unknown.  The template of a point is taken from `prev` at pts, and its partner is searched in
+ * `next` ALONG THE ROW of the guess (init, else pts): x alone moves, with the gradient Ix alone, so it also follows a vertical edge, on
+ * which the two-dimensional tracker gives up.  For a rectified stereo pair prev is the left image and next the right one.  It takes the
+ * records, flags and limits of svo_lk_track, makes the same refusals in the same order, uses the same buffers and pyramid kernel,
+ * synchronises as it does, never runs inside a captured graph, and svo_debug_lk_get_level answers for it as for svo_lk_track.
+ * tests/lk_row_ref.py is its definition and the device equals it bit for bit; against svo_lk_track:
+ *   - the guess's y is never updated: next_pts[i].y is the guess's y (init's bit pattern, else the point's);
+ *   - A11 = sum Ix^2; a level is skipped (at level 0 the point is lost) when A11 / win^2 < min_eig;
+ *   - an iteration moves x by -b1 / A11, b1 = sum (J - I) Ix, and stops on |dx| <= eps, on the oscillation rule applied to dx, or
+ *     after max_iters;
+ *   - under fb_max the way back runs from next to prev along the row of the forward result, and the distance is |back.x - pts.x|.
+ * svo_lk_track itself is untouched by it. */
+int svo_lk_track_rows(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* p, uint32_t flags);
 
 /* Shi-Tomasi corner detection on caller images, batched over many images: the capability under the reference's dmKLT
  * (stage2_detect.cpp:444-449: cv::goodFeaturesToTrack with quality 0.01, minimum distance 20, block 3), offered like svo_lk_track as a
@@ -844,6 +857,32 @@ int svo_klt_predicted(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, u
 int svo_debug_klt_predict(svo_ctx* ctx, int lane, const double* delta6, int valid,
                           float* left_xy, float* right_xy, uint8_t* used, int cap);
 
+/* STEREO RE-ASSOCIATION FOR svo_klt_step.  A step follows a track's left and right point independently through time, and nothing ties
+ * the halves of a pair to each other again: each drifts on its own until the gate drops the pair.  svo_klt_set_stereo(ctx, 1) makes a
+ * step track the LEFT list through time only and find every right point afresh in the NEW pair, along the row of the new left point,
+ * with the row tracker of svo_lk_track_rows.  It is accepted once svo_klt_enable has succeeded (SVO_ERR_STATE before, and inside a
+ * captured graph; SVO_ERR_ARG for a mode other than 0 and 1); svo_klt_get_stereo returns the mode.
+ *   0 (default)  a step allocates, launches and returns exactly what it did without this call;
+ *   1            the first call allocates the buffers of the mode (a job record per lane, a float2 per lane, side and slot).  A
+ *                svo_klt_enable that re-makes the front end's buffers drops them and returns to mode 0, as it drops the top-up.
+ * In mode 1 item 3 of a step becomes, for every active lane:
+ *   3a  the left list is tracked through time exactly as in mode 0 (prediction guesses, fb_max; a lane without a last pair: its
+ *       points stand with status 1);
+ *   3b  for each slot the right point is found by svo_lk_track_rows' tracker on (left[t], right[t]) -- the pyramids the step has just
+ *       built -- with pts = the left results of 3a and init = (xl' - (xl - xr), yl') in float32 as written, (xl, xr) the table's old
+ *       points and (xl', yl') the result of 3a; svo_klt_params.lk applies, fb_max included (left, right and back along the row).  A
+ *       lane without a last pair runs 3b too: it needs the new pair only.  Right status and right point go where the pass through
+ *       time put them; the gate, the RANSAC gate, the prune, stage 5 and svo_klt_topup are as they were.  Every surviving pair has
+ *       yr == yl bit for bit.  The predicted right guesses of svo_klt_set_prediction(1) are not used; svo_klt_predicted is unchanged.
+ * Nothing synchronises, nothing is read back and nothing is allocated per step.
+ * THE CONTRACT is svo_klt_step's with public calls: after a step in mode 1 every getter of the lane and svo_klt_get_tracks return byte
+ * for byte what the recipe of svo_klt_step leaves when its second svo_lk_track job (the right list through time) is replaced by a
+ * svo_lk_track_rows job on (left[t], right[t], pts = the left job's next_pts, init as above) (tests/klt_stereo_ref.py holds it).
+ * No row association inside svo_klt_topup, no predicted disparity as the guess, no unrectified pairs, no bound on the row search; no
+ * svo_batch, frame-parallel or graph-captured form. */
+int svo_klt_set_stereo(svo_ctx* ctx, int mode);         /* 0 the right list through time (default), 1 the right partner along the row */
+int svo_klt_get_stereo(const svo_ctx* ctx);
+
 /* debugging / parity probes */
 int svo_debug_get_level(svo_ctx* ctx, int lane, int side, int level, uint8_t* out, int cap, int* w, int* h);
 int svo_debug_get_raw_keypoints(svo_ctx* ctx, int lane, int side, svo_keypoint* kps, uint8_t* desc, int cap);
@@ -877,8 +916,9 @@ int svo_debug_timeline(svo_ctx* ctx, uint64_t* out, int cap_records, int reset);
  * three kernels count there, its detector and tracker launches under the gftt and lk names, which are then listed as well, and
  * "klt_select" with them); "ransac_feed" behind all of those, once the context has made a svo_ransac_tracked call or a step under
  * svo_klt_set_ransac (the RANSAC launches behind it count under "ransac_hyp" .. "track_finalize"), "klt_prune" behind it, once a step
- * in mode 2 has run, and "klt_predict" last, once the context has made a step under svo_klt_set_prediction(1) or a svo_klt_predicted /
- * svo_debug_klt_predict call. */
+ * in mode 2 has run, "klt_predict" behind it, once the context has made a step under svo_klt_set_prediction(1) or a svo_klt_predicted /
+ * svo_debug_klt_predict call, and "lk_track_row" last, once the context has made a svo_lk_track_rows call or a step under
+ * svo_klt_set_stereo(1) (whose guess kernel counts there too). */
 int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_ms, int64_t* calls, int cap);
 int svo_kernel_times_reset(svo_ctx* ctx);
 /* time only the kernel of that name from now on (NULL or "": all again): two events per kernel cost a few percent of

@@ -216,6 +216,8 @@ KLT_RANSAC_OFF, KLT_RANSAC_FILTER, KLT_RANSAC_PRUNE = range(3)
 
 # svo_klt_set_prediction: where the forward pass of svo_klt_step starts its search
 KLT_PREDICT_OFF, KLT_PREDICT_POSE = range(2)
+# svo_klt_set_stereo: how svo_klt_step finds a track's right point
+KLT_STEREO_TEMPORAL, KLT_STEREO_ROW = range(2)
 
 # indices of Result.track_stats (include/svo_types.h SVO_TS_*)
 TS_NAMES = ("threshold", "collision", "inliers_left", "inliers_right", "hyp_left", "hyp_right", "both_masks", "tracked")

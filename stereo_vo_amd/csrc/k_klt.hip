@@ -283,18 +283,20 @@ void launch_klt_prune(const DevCtx& c, const KltDev& t, int half, hipStream_t st
 __global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a, const int has_init)
 {
     const int t = blockIdx.x * KLT_BLOCK + threadIdx.x;
-    if (t >= 3 * a.n_lanes) return;
-    const bool pyr = t < a.n_lanes;
-    const int lane = pyr ? t : (t - a.n_lanes) >> 1, side = pyr ? 0 : (t - a.n_lanes) & 1;
+    if (t >= (a.row_jobs ? 4 : 3) * a.n_lanes) return;
+    const bool row = t >= 3 * a.n_lanes;       // (only with row_jobs) a row record: the images of a pyramid record, the points of a tracking one
+    const bool pyr = t < a.n_lanes || row;
+    const int lane = row ? t - 3 * a.n_lanes : pyr ? t : (t - a.n_lanes) >> 1, side = pyr ? 0 : (t - a.n_lanes) & 1;
     const int par = lane_bit(a.parity, lane) ? 1 : 0;
-    LkJobDev& J = pyr ? a.pyr_jobs[lane] : a.trk_jobs[2 * lane + side];      // written in place: a local record indexed by level would live in scratch
+    LkJobDev& J = row ? a.row_jobs[lane] : pyr ? a.pyr_jobs[lane] : a.trk_jobs[2 * lane + side];      // written in place: a local record indexed by level would live in scratch
     for (int s = 0; s < 2; s++) for (int l = 0; l < 6; l++) { J.img[s][l] = nullptr; J.pitch[s][l] = 0; }
     for (int l = 0; l < 6; l++) { J.w[l] = 0; J.h[l] = 0; }
     J.pt0 = pyr ? 0 : (2 * lane + side) * a.cap; J.n = pyr ? 0 : a.cap; J.has_init = pyr ? 0 : has_init;
+    if (row) { J.pt0 = 2 * lane * a.cap; J.n = lane_bit(a.idle, lane) ? 0 : a.cap; J.has_init = 1; }
     auto block = [&](int parity, int sd) { return a.pyr + ((long long)(parity * a.n_lanes + lane) * 2 + sd) * a.img_stride; };
     // a lane that builds no pyramid has no level; a lane that tracks nothing has one level of 0 x 0 pixels
-    const bool none = pyr ? lane_bit(a.idle, lane) : lane_bit(a.empty, lane);
-    J.nl = none ? (pyr ? 0 : 1) : a.nl;
+    const bool none = pyr ? lane_bit(a.idle, lane) : (lane_bit(a.empty, lane) || (a.row_jobs && side == 1));
+    J.nl = none ? (pyr && !row ? 0 : 1) : a.nl;
     if (none) return;
     for (int l = 0; l < a.nl; l++) {
         J.w[l] = a.w[l]; J.h[l] = a.h[l]; J.pitch[0][l] = a.w[l]; J.pitch[1][l] = a.w[l];
@@ -306,7 +308,28 @@ __global__ __launch_bounds__(KLT_BLOCK) void k_klt_jobs(const KltJobArgs a, cons
 void launch_klt_jobs(const KltJobArgs& a, int has_init, hipStream_t st)
 {
     if (a.n_lanes <= 0) return;
-    hipLaunchKernelGGL(k_klt_jobs, dim3((unsigned)((3 * a.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a, has_init);
+    hipLaunchKernelGGL(k_klt_jobs, dim3((unsigned)(((a.row_jobs ? 4 : 3) * a.n_lanes + KLT_BLOCK - 1) / KLT_BLOCK)), dim3(KLT_BLOCK), 0, st, a, has_init);
+}
+
+// the first guesses of a step's row pass (KltRowGuessArgs, svo_kernels.h): grid (ceil(cap / 256), n_lanes), one thread per slot
+__global__ __launch_bounds__(KLT_BLOCK) void k_klt_row_guess(const KltRowGuessArgs a)
+{
+    const int lane = blockIdx.y, s = blockIdx.x * KLT_BLOCK + threadIdx.x, cap = a.t.cap;
+    if (s >= cap || !lane_bit(a.active, lane)) return;
+    const size_t o = (size_t)(2 * lane) * cap + s;
+    const float2 pl = a.t.pts[a.half][o], pr = a.t.pts[a.half][o + cap];
+    float2 nl = pl;
+    bool ok = true;
+    if (lane_bit(a.fresh, lane)) { a.t.out[o] = pl; a.t.status[o] = 1; a.t.err[o] = 0.0f; }
+    else { nl = a.t.out[o]; ok = a.t.status[o] == 1; }
+    const float nan = __uint_as_float(0x7fc00000u);
+    a.guess[o] = ok ? make_float2(nl.x - (pl.x - pr.x), nl.y) : make_float2(nan, nan);
+}
+
+void launch_klt_row_guess(const KltRowGuessArgs& a, hipStream_t st)
+{
+    if (a.t.n_lanes <= 0 || a.t.cap <= 0) return;
+    hipLaunchKernelGGL(k_klt_row_guess, dim3((unsigned)((a.t.cap + KLT_BLOCK - 1) / KLT_BLOCK), (unsigned)a.t.n_lanes), dim3(KLT_BLOCK), 0, st, a);
 }
 
 // ---- svo_klt_topup ------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// k_lk.hip -- svo_lk_track on the device: the pyramid (k_lk_pyrdown) and the pyramidal Lucas-Kanade tracker (k_lk_track).
+// k_lk.hip -- svo_lk_track on the device: the pyramid (k_lk_pyrdown) and the pyramidal Lucas-Kanade tracker (k_lk_track); behind them
+// the row tracker of svo_lk_track_rows (k_lk_track_row), a kernel of its own on the same helpers.
 //
 // The arithmetic is the walk of tests/lk_ref.py, operation for operation: integer pyramid, integer Scharr derivatives, bilinear samples
 // with 14-bit weights, exact integer sums, and the double 2 x 2 solve in the walk's order (-ffp-contract=off: one IEEE operation per
@@ -251,6 +252,187 @@ __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
     const float2 o = A.aux[gp];
     const double ddx = (double)gx - (double)o.x, ddy = (double)gy - (double)o.y;
     if (lost || ddx * ddx + ddy * ddy > (double)A.p.fb_max * (double)A.p.fb_max) A.status[gp] = 0;
+}
+
+// ---- row tracker (svo_lk_track_rows, step item 3b under svo_klt_set_stereo(1)) --------------------------------------------------
+// The walk of tests/lk_row_ref.py: the template from prev at pt, the partner searched in next along the row of the guess.  One unknown, so
+// a pixel keeps I and Ix (pk and gi), an iteration reduces one sum, and the update is one double division.  gy never moves inside a
+// level: the win + 1 rows an iteration reads are the same in all of them, and only the window's column moves.  So the wave stages a
+// STRIP of those rows once per level, S = min(LK_TILE_BYTES / (win + 1), win + 17, level width) columns wide with the first window in
+// its middle, and stages again only when a window leaves it (the bytes a sample reads are the image's either way: no bit depends on S).
+//
+// `rows` rows of S bytes of a level at (x0, y0) into the wave's slice; t / S by a multiplication that is exact for t < 1168, S <= 48
+static __device__ __forceinline__ void lk_stage_strip(uint8_t* tile, const uint8_t* __restrict__ img, int pitch, int x0, int y0, int S, int rows, int lane)
+{
+    const unsigned M = (65536u + (unsigned)S - 1u) / (unsigned)S;
+    const uint8_t* __restrict__ p = img + (y0 * pitch + x0);
+#pragma unroll 2
+    for (int t = lane; t < S * rows; t += 64) {
+        const int ty = (int)(((unsigned)t * M) >> 16), tx = t - ty * S;
+        tile[t] = p[ty * pitch + tx];
+    }
+    lk_wave_sync();
+}
+
+// NP, BACK: as k_lk_track.  BACK compares along x alone.  A point index behind its job's count leaves at once: the records of a step
+// (k_klt_jobs) give lane l the slots [2 l cap, 2 l cap + cap) and leave the cap slots behind them to nobody.
+template <int NP, bool BACK>
+__global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
+{
+    __shared__ uint8_t tiles[4][LK_TILE_BYTES];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int gp = (int)blockIdx.x * 4 + wave;
+    if (gp >= A.n_pts) return;
+    uint8_t* tile = tiles[wave];
+    int lo = 0, hi = A.n_jobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (A.jobs[mid].pt0 <= gp) lo = mid; else hi = mid - 1; }
+    const LkJobDev& J = A.jobs[lo];
+    if (gp - J.pt0 >= J.n) return;
+    const int sp = BACK ? 1 : 0, sn = 1 - sp;
+    if (BACK && !__builtin_amdgcn_readfirstlane((int)A.status[gp])) return;
+    const float2 pt = A.pts[gp];
+    float g0x = pt.x, g0y = pt.y;
+    if (!BACK && J.has_init) { const float2 t = A.aux[gp]; g0x = t.x; g0y = t.y; }
+    if (!(lk_finite(pt.x) && lk_finite(pt.y) && lk_finite(g0x) && lk_finite(g0y))) {
+        if (lane == 0) { A.out[gp] = make_float2(g0x, g0y); A.status[gp] = 0; A.err[gp] = 0.0f; }
+        return;
+    }
+    const int win = A.p.win, nwin = win * win;
+    const float half = (float)((win - 1) / 2);
+    // pk as in k_lk_track (offset y * (win + 1) + x, y, the window flag, I); gi: Ix
+    int pk[NP], gi[NP];
+    {
+        const unsigned M = (65536u + (unsigned)win - 1u) / (unsigned)win;
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            const int idx = k * 64 + lane;
+            const int y = (int)(((unsigned)idx * M) >> 16), x = idx - y * win;
+            pk[k] = idx < nwin ? ((y * (win + 1) + x) | (y << 10) | 0x8000) : 0;
+            gi[k] = 0;
+        }
+    }
+    const int top = J.nl - 1;
+    float gx = g0x * __uint_as_float((unsigned)(127 - top) << 23), gy = g0y * __uint_as_float((unsigned)(127 - top) << 23);
+    bool lost = false;
+    float err = 0.0f;
+#pragma unroll 1
+    for (int L = top; L >= 0; --L) {
+        const int w = J.w[L], h = J.h[L];
+        const float sc = __uint_as_float((unsigned)(127 - L) << 23);
+        int ix, iy, w00, w01, w10, w11;
+        bool ok = lk_window(pt.x * sc - half, pt.y * sc - half, w, h, win, ix, iy, w00, w01, w10, w11);
+        double A11 = 0.0;
+        if (ok) {
+            // 1. template: I and Ix
+            const int T = win + 3;
+            lk_stage(tile, J.img[sp][L], J.pitch[sp][L], ix - 1, iy - 1, T, lane);
+            int s11 = 0;
+#pragma unroll
+            for (int k = 0; k < NP; k++) {
+                const int q = pk[k] & 0xffff, m = (q << 16) >> 31;
+                const int base = (q & 1023) + 2 * ((q >> 10) & 31) + win + 4;
+                int P[4][4];
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+#pragma unroll
+                    for (int c = 0; c < 4; c++) P[r][c] = (int)tile[base + (r - 1) * T + (c - 1)];
+                int dx[2][2];
+#pragma unroll
+                for (int r = 0; r < 2; r++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+                        dx[r][c] = 3 * (P[r][c + 2] - P[r][c]) + 10 * (P[r + 1][c + 2] - P[r + 1][c]) + 3 * (P[r + 2][c + 2] - P[r + 2][c]);
+                const int I = (P[1][1] * w00 + P[1][2] * w01 + P[2][1] * w10 + P[2][2] * w11 + 256) >> 9;
+                const int Ix = ((dx[0][0] * w00 + dx[0][1] * w01 + dx[1][0] * w10 + dx[1][1] * w11 + 8192) >> 14) & m;
+                pk[k] = q | (I << 16); gi[k] = Ix;
+                s11 += Ix * Ix;
+            }
+            lk_wave_sync();                                        // every lane has read the tile before the strip overwrites it
+            // 2. the gradient sum
+            A11 = (double)lk_wave_sum(s11) * 0x1p-20;
+            if (A11 / (double)nwin < (double)A.p.min_eig || A11 < 0x1p-23) ok = false;
+        }
+        if (!ok) {
+            if (L == 0) { lost = true; break; }
+            gx = gx * 2.0f; gy = gy * 2.0f;
+            continue;
+        }
+        // 3. iterations along the row
+        const uint8_t* __restrict__ nimg = J.img[sn][L];
+        const int npitch = J.pitch[sn][L], T1 = win + 1;
+        int S = LK_TILE_BYTES / T1;
+        S = S < win + 17 ? S : win + 17; S = S < w ? S : w;                   // T1 <= S <= 48: an inside window needs w >= win + 3
+        const int dS = S - T1;
+        int x0 = -1;                                                          // the strip's first column; -1: the slice holds no strip
+        float pdx = 0.0f;
+        bool outside = false;
+        int jx, jy, v00, v01, v10, v11;
+        // the strip covers the window at jx: columns x0 .. x0 + S - 1 inside 0 .. w - 1, rows jy .. jy + win inside the level (lk_window)
+        auto cover = [&]() {
+            if (x0 >= 0 && jx >= x0 && jx + T1 <= x0 + S) return;
+            x0 = jx - (dS >> 1); x0 = x0 < w - S ? x0 : w - S; x0 = x0 > 0 ? x0 : 0;
+            lk_stage_strip(tile, nimg, npitch, x0, jy, S, T1, lane);
+        };
+#pragma unroll 1
+        for (int j = 0; j < A.p.max_iters; j++) {
+            if (!lk_window(gx - half, gy - half, w, h, win, jx, jy, v00, v01, v10, v11)) { outside = true; break; }
+            cover();
+            const int off = jx - x0;
+            int s1 = 0;
+#pragma unroll
+            for (int k = 0; k < NP; k++) {
+                int q = pk[k], g = gi[k];
+                asm volatile("" : "+v"(q), "+v"(g));               // unpack here, every iteration (as k_lk_track does)
+                const int base = (q & 1023) + ((q >> 10) & 31) * dS + off;
+                const int d = lk_sample(tile, base, S, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
+                s1 += d * g;
+            }
+            lk_wave_sync();
+            const double b1 = (double)lk_wave_sum(s1) * 0x1p-20;
+            const float dx = (float)(-b1 / A11);
+            gx = gx + dx;
+            if ((double)dx * (double)dx <= (double)A.p.eps * (double)A.p.eps) break;
+            if (j > 0 && fabs((double)(dx + pdx)) < 0.01) { gx = gx - 0.5f * dx; break; }
+            pdx = dx;
+        }
+        if (L == 0) {
+            if (outside) { lost = true; break; }
+            // 4. error at the final position
+            if (lk_window(gx - half, gy - half, w, h, win, jx, jy, v00, v01, v10, v11)) {
+                cover();
+                const int off = jx - x0;
+                int s = 0;
+#pragma unroll
+                for (int k = 0; k < NP; k++) {
+                    const int q = pk[k], base = (q & 1023) + ((q >> 10) & 31) * dS + off;
+                    const int d = lk_sample(tile, base, S, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
+                    s += (d < 0 ? -d : d) & ((q << 16) >> 31);
+                }
+                err = (float)((double)lk_wave_sum(s) / (double)(32 * nwin));
+            }
+            break;
+        }
+        gx = gx * 2.0f; gy = gy * 2.0f;
+    }
+    if (lane != 0) return;
+    if (!BACK) {
+        A.out[gp] = make_float2(gx, gy); A.status[gp] = lost ? 0 : 1;
+        A.err[gp] = lost ? 0.0f : err;
+        return;
+    }
+    // the round trip along the row: lost when this pass lost it or when it ends farther than fb_max in x from where the point started
+    const float2 o = A.aux[gp];
+    const double ddx = (double)gx - (double)o.x;
+    if (lost || ddx * ddx > (double)A.p.fb_max * (double)A.p.fb_max) A.status[gp] = 0;
+}
+
+void launch_lk_track_row(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st)
+{
+    if (a.n_pts <= 0) return;
+    const dim3 grid((unsigned)((a.n_pts + 3) / 4)), block(256);
+    if (pixels_per_lane <= 2) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<2, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<2, false>), grid, block, 0, st, a); }
+    else if (pixels_per_lane <= 7) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<7, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<7, false>), grid, block, 0, st, a); }
+    else { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<16, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<16, false>), grid, block, 0, st, a); }
 }
 
 void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st)

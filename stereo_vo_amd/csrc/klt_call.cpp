@@ -166,6 +166,31 @@ PredictPlan plan_predict(const svo_klt_params& p, const Caps& caps)
     return pl;
 }
 
+// ---- the stereo re-association ----
+int check_klt_set_stereo(const State& s, int mode, bool have_buffers, bool& alloc, std::string& why)
+{
+    char msg[200];
+    alloc = false;
+    why.clear();
+    if (!s.enabled) { why = "svo_klt_set_stereo: the KLT front end is not enabled (svo_klt_enable)"; return SVO_ERR_STATE; }
+    if (s.capturing) { why = "svo_klt_set_stereo: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (mode < KLT_STEREO_TEMPORAL || mode > KLT_STEREO_ROW) {
+        snprintf(msg, sizeof(msg), "svo_klt_set_stereo: mode %d: 0 (the right list through time) or 1 (the right partner along the row of the new pair) is expected", mode);
+        why = msg; return SVO_ERR_ARG;
+    }
+    alloc = mode == KLT_STEREO_ROW && !have_buffers;
+    return SVO_OK;
+}
+
+StereoPlan plan_stereo(const svo_klt_params& p, const Caps& caps)
+{
+    StereoPlan pl;
+    pl.n_jobs = caps.n_lanes;
+    pl.n_guess = (long long)caps.n_lanes * 2 * p.cap;
+    pl.n_pts = (2ll * caps.n_lanes - 1) * p.cap;
+    return pl;
+}
+
 svo_lk::Geometry klt_geometry(const svo_klt_params& p, int w, int h) { return svo_lk::lk_geometry(w, h, p.lk.win, p.lk.max_level, true); }
 
 Plan plan_klt(const svo_klt_params& p, const Caps& caps)

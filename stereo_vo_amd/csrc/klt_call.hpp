@@ -65,6 +65,21 @@ struct PredictPlan {
 };
 PredictPlan plan_predict(const svo_klt_params& p, const Caps& caps);
 
+// ---- the stereo re-association (svo_klt_set_stereo / svo_klt_get_stereo; tools/klt_stereo_check.cpp drives these) ----
+// 0: the right list is tracked through time; 1: the right partner is found along the row in the new pair (svo_lk_track_rows' kernel)
+enum { KLT_STEREO_TEMPORAL = 0, KLT_STEREO_ROW = 1 };
+// svo_klt_set_stereo: the front end enabled and no capture (SVO_ERR_STATE), then the mode, 0 .. 1 (SVO_ERR_ARG).  alloc: the call must
+// make the buffers of mode 1 (mode 1 and none yet)
+int check_klt_set_stereo(const State& s, int mode, bool have_buffers, bool& alloc, std::string& why);
+// the buffers of mode 1: one row record per lane, and the first guesses of the row pass laid out as the tracker's results are (lane l's
+// at [2 l cap, 2 l cap + cap): the row pass indexes its points, guesses and -- cap behind -- results with one number)
+struct StereoPlan {
+    int n_jobs;                     // LkJobDev: n_lanes
+    long long n_guess;              // float2: n_lanes * 2 * cap
+    long long n_pts;                // the point indices a row launch covers: (2 * n_lanes - 1) * cap
+};
+StereoPlan plan_stereo(const svo_klt_params& p, const Caps& caps);
+
 // the buffers of an enabled context, sized for max_w x max_h images:
 //   pyramids  [2 parities][n_lanes][2 sides] blocks of img_stride bytes, the levels of one image tightly packed (lk_geometry with
 //              level 0).  A lane's new pair goes to the parity its last pair did NOT go to: the other parity still holds frame t - 1

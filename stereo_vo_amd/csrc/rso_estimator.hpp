@@ -381,6 +381,10 @@ public:
      *  triangulated from its stereo pair, moved by the pose increment of the last optimised step (constant velocity) and reprojected
      *  into both cameras.  A step that did not end valid predicts nothing for the next one. */
     void setKltPrediction(int mode) { check(svo_klt_set_prediction(m_ctx, mode), "svo_klt_set_prediction"); }
+    /** How stepKLT finds a track's right point (svo_klt_set_stereo): 0 the right list is tracked through time (default), 1 the partner
+     *  of every new left point is found in the new pair along its row, so that the halves of a pair cannot drift apart. */
+    void setKltStereo(int mode) { check(svo_klt_set_stereo(m_ctx, mode), "svo_klt_set_stereo"); }
+    int getKltStereo() const { return svo_klt_get_stereo(m_ctx); }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }
     bool loadStateFromFile(const std::string& filename) { return svo_load_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

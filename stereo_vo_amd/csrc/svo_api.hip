@@ -50,7 +50,8 @@ enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, 
 // ... and "ransac_feed" (svo_ransac_tracked, or a step under svo_klt_set_ransac) and "klt_prune" (a step in mode 2) behind those, each
 // once the context has launched it.  The RANSAC launches between them count under their names of a frame
 // ... and "klt_predict" (a step under svo_klt_set_prediction(1), svo_klt_predicted, svo_debug_klt_predict) last of all
-enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_KLT_PREDICT, KT_EVERY };
+// ... and "lk_track_row" (svo_lk_track_rows, or a step under svo_klt_set_stereo(1)) behind that
+enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_KLT_PREDICT, KT_LK_TRACK_ROW, KT_EVERY };
 static_assert(KT_EVERY <= 64, "kt_mask is one 64-bit word");
 static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
     "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
@@ -60,7 +61,7 @@ static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "sele
     "gftt_response", "gftt_candidates", "gftt_select",
     "lk_pyrdown", "lk_track" };
 static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
-static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : i == KT_KLT_PREDICT ? "klt_predict" : kt_name(i); }
+static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : i == KT_KLT_PREDICT ? "klt_predict" : i == KT_LK_TRACK_ROW ? "lk_track_row" : kt_name(i); }
 
 struct TimedSpan { int id; hipEvent_t a, b; };
 
@@ -148,6 +149,9 @@ struct svo_ctx {
         // svo_klt_set_prediction: 0 off, 1 constant-velocity pose prediction.  The one buffer of mode 1 (klt_call.hpp: plan_predict), made
         // by the first call with mode 1 and dropped with the front end's buffers: the guesses and a byte per slot
         int predict; float2* d_guess; uint8_t* d_gused;
+        // svo_klt_set_stereo: 0 the right list is tracked through time, 1 it is found along the row in the new pair.  The buffers of mode 1
+        // (klt_call.hpp: plan_stereo), made by the first call with mode 1 and dropped with the front end's buffers
+        int stereo; LkJobDev* d_row_jobs; float2* d_row_guess;
         // the resident top-up (svo_klt_topup_enable; the plan: klt_call.hpp), buffers of its own: the response maps, the detector's job
         // records, keys, cell lists, states and counters, the corners with their responses, the first guesses, the tracker's records and
         // results, four ints per lane for svo_klt_topup_info.  topup_used: a top-up has run (svo_kernel_times, svo_klt_topup_enable)
@@ -158,6 +162,7 @@ struct svo_ctx {
     bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
     bool ransac_feed_used;                             // the context has launched k_ransac_feed (svo_kernel_times)
     bool klt_predict_used;                             // the context has launched k_klt_predict (svo_kernel_times)
+    bool lk_row_used;                                  // the context has launched k_lk_track_row (svo_kernel_times)
     bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
     // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
     uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
@@ -456,7 +461,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
     ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
-    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false; ctx->klt_predict_used = false;
+    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false; ctx->klt_predict_used = false; ctx->lk_row_used = false;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -1317,9 +1322,9 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
         if (n < cap) { if (names) names[n] = kt_name_all(KT_KLT_TOPUP); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_TOPUP]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_TOPUP]; }
         n++;
     }
-    // "ransac_feed", "klt_prune" and "klt_predict" behind everything else, each once the context has launched the kernel
-    for (int k = KT_RANSAC_FEED; k <= KT_KLT_PREDICT; k++) {
-        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : k == KT_KLT_PRUNE ? ctx->klt.prune_used : ctx->klt_predict_used)) continue;
+    // "ransac_feed", "klt_prune", "klt_predict" and "lk_track_row" behind everything else, each once the context has launched the kernel
+    for (int k = KT_RANSAC_FEED; k <= KT_LK_TRACK_ROW; k++) {
+        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : k == KT_KLT_PRUNE ? ctx->klt.prune_used : k == KT_KLT_PREDICT ? ctx->klt_predict_used : ctx->lk_row_used)) continue;
         if (n < cap) { if (names) names[n] = kt_name_all(k); if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
         n++;
     }
@@ -2661,7 +2666,8 @@ static hipError_t lk_realloc(T** p, size_t n)
     return hipMalloc((void**)p, n * sizeof(T));
 }
 
-extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
+// svo_lk_track and svo_lk_track_rows: one call, the tracker apart (rows: k_lk_track_row, counted under its own name)
+static int lk_track_call(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags, bool rows)
 {
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
@@ -2685,6 +2691,7 @@ extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, co
         ctx->lk_pts_cap = plan.n_pts;
     }
     ctx->lk_used = true;
+    if (rows) ctx->lk_row_used = true;
     const hipStream_t st = ctx->stream;
     // the job records; host images go to level 0 of their block, device images are read where they are
     std::vector<LkJobDev> recs((size_t)n_jobs);
@@ -2723,13 +2730,13 @@ extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, co
     a.out = ctx->d_lk_out; a.status = ctx->d_lk_status; a.err = ctx->d_lk_err;
     a.p = p; a.backward = 0;
     {
-        Span s(ctx, KT_LK_TRACK);
+        Span s(ctx, rows ? KT_LK_TRACK_ROW : KT_LK_TRACK);
         const int ppl = svo_lk::lk_pixels_per_lane(p.win);
-        launch_lk_track(a, ppl, st);
+        if (rows) launch_lk_track_row(a, ppl, st); else launch_lk_track(a, ppl, st);
         if (p.fb_max > 0.0f) {                               // the same kernel with the image roles swapped, from the results back
             LkTrackArgs b = a;
             b.pts = ctx->d_lk_out; b.aux = ctx->d_lk_pts; b.out = nullptr; b.err = nullptr; b.backward = 1;
-            launch_lk_track(b, ppl, st);
+            if (rows) launch_lk_track_row(b, ppl, st); else launch_lk_track(b, ppl, st);
         }
     }
     HIPCHECK(hipGetLastError());
@@ -2750,6 +2757,16 @@ extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, co
         if (jobs[j].err) memcpy(jobs[j].err, h_err.data() + o, sizeof(float) * n);
     }
     return SVO_OK;
+}
+
+extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
+{
+    return lk_track_call(ctx, jobs, n_jobs, params, flags, false);
+}
+
+extern "C" int svo_lk_track_rows(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
+{
+    return lk_track_call(ctx, jobs, n_jobs, params, flags, true);
 }
 
 extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h)
@@ -2774,7 +2791,7 @@ static void klt_free(svo_ctx* ctx)
                      (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage,
                      (void*)k.d_tmap, (void*)k.d_tgjobs, (void*)k.d_tkeys, (void*)k.d_titems, (void*)k.d_tstate, (void*)k.d_tginfo, (void*)k.d_tinfo, (void*)k.d_tcorners,
                      (void*)k.d_tinit, (void*)k.d_tout, (void*)k.d_tresp, (void*)k.d_terr, (void*)k.d_tstatus, (void*)k.d_tlk_jobs,
-                     (void*)k.d_guess, (void*)k.d_gused }) if (p) (void)hipFree(p);
+                     (void*)k.d_guess, (void*)k.d_gused, (void*)k.d_row_jobs, (void*)k.d_row_guess }) if (p) (void)hipFree(p);
     memset(&k, 0, sizeof(k));
 }
 static svo_klt::Caps klt_caps(const svo_ctx* ctx) { return { ctx->cfg.n_lanes, ctx->dc.max_kps, ctx->cfg.max_w, ctx->cfg.max_h }; }
@@ -2989,6 +3006,31 @@ extern "C" int svo_klt_set_prediction(svo_ctx* ctx, int mode)
 }
 extern "C" int svo_klt_get_prediction(const svo_ctx* ctx) { return ctx ? ctx->klt.predict : SVO_ERR_ARG; }
 
+// ---- the stereo re-association of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernels: k_lk_track_row, k_klt_row_guess) ----
+extern "C" int svo_klt_set_stereo(svo_ctx* ctx, int mode)
+{
+    if (ctx) use_device(ctx);
+    if (!ctx) return SVO_ERR_ARG;
+    ctx->last_error.clear();
+    svo_ctx::Klt& k = ctx->klt;
+    bool alloc = false;
+    { std::string why; const int rc = svo_klt::check_klt_set_stereo(klt_state(ctx), mode, k.d_row_jobs != nullptr, alloc, why); if (rc) { ctx->last_error = why; return rc; } }
+    if (alloc) {
+        const svo_klt::StereoPlan plan = svo_klt::plan_stereo(k.p, klt_caps(ctx));
+        hipError_t e = lk_realloc(&k.d_row_jobs, (size_t)plan.n_jobs);
+        if (e == hipSuccess) e = lk_realloc(&k.d_row_guess, (size_t)plan.n_guess);
+        if (e != hipSuccess) {                              // the mode stays as it was
+            (void)hipGetLastError();
+            if (k.d_row_jobs) { (void)hipFree(k.d_row_jobs); k.d_row_jobs = nullptr; }
+            if (k.d_row_guess) { (void)hipFree(k.d_row_guess); k.d_row_guess = nullptr; }
+            HIPCHECK(e);
+        }
+    }
+    k.stereo = mode;
+    return SVO_OK;
+}
+extern "C" int svo_klt_get_stereo(const svo_ctx* ctx) { return ctx ? ctx->klt.stereo : SVO_ERR_ARG; }
+
 // svo_klt_predicted and svo_debug_klt_predict: the kernel on one lane, then the lane's count and its guesses back
 static int klt_predict_lane(svo_ctx* ctx, const char* entry, int lane, const double* delta6, bool forced, int valid, float* left_xy, float* right_xy, uint8_t* used, int cap)
 {
@@ -3094,7 +3136,8 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
         }
     }
     KltJobArgs ja; memset(&ja, 0, sizeof(ja));
-    ja.pyr_jobs = k.d_pyr_jobs; ja.trk_jobs = k.d_trk_jobs; ja.pyr = k.d_pyr; ja.img_stride = k.plan.img_stride;
+    const bool rows = k.stereo == svo_klt::KLT_STEREO_ROW;
+    ja.pyr_jobs = k.d_pyr_jobs; ja.trk_jobs = k.d_trk_jobs; ja.row_jobs = rows ? k.d_row_jobs : nullptr; ja.pyr = k.d_pyr; ja.img_stride = k.plan.img_stride;
     ja.n_lanes = d.n_lanes; ja.cap = k.p.cap; ja.nl = g.nl;
     for (int l = 0; l < g.nl; l++) { ja.w[l] = g.w[l]; ja.h[l] = g.h[l]; ja.off[l] = g.off[l]; }
     ja.parity = k.parity; ja.empty = empty; ja.idle = idle;
@@ -3114,6 +3157,30 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
             b.pts = k.dev.out; b.aux = k.dev.pts[k.half]; b.out = nullptr; b.err = nullptr; b.backward = 1;
             launch_lk_track(b, ppl, st);
         }
+    }
+    // 3b. under svo_klt_set_stereo(1) the right records of 3 were empty: the right partner of every left result is found in the NEW pair
+    //     along the row (and back under fb_max), from guesses formed on the device.  A lane without a last pair takes part: its left
+    //     points stand (k_klt_row_guess writes them as results with status 1), so the selection has no fresh lane to treat apart
+    if (rows) {
+        KltRowGuessArgs ga; memset(&ga, 0, sizeof(ga));
+        ga.t = k.dev; ga.half = k.half; ga.guess = k.d_row_guess; ga.active = active; ga.fresh = fresh;
+        const int C = k.p.cap;
+        LkTrackArgs a;
+        a.jobs = k.d_row_jobs; a.n_jobs = d.n_lanes; a.n_pts = (2 * d.n_lanes - 1) * C;       // lane l: slots [2 l C, 2 l C + C), results C behind
+        a.pts = k.dev.out; a.aux = k.d_row_guess;
+        a.out = k.dev.out + C; a.status = k.dev.status + C; a.err = k.dev.err + C;
+        a.p = k.p.lk; a.backward = 0;
+        Span s(ctx, KT_LK_TRACK_ROW);
+        launch_klt_row_guess(ga, st);
+        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
+        launch_lk_track_row(a, ppl, st);
+        if (k.p.lk.fb_max > 0.0f) {
+            LkTrackArgs b = a;
+            b.pts = k.dev.out + C; b.aux = k.dev.out; b.out = nullptr; b.err = nullptr; b.backward = 1;
+            launch_lk_track_row(b, ppl, st);
+        }
+        ctx->lk_row_used = true;
+        memset(&fresh, 0, sizeof(fresh));
     }
     // 4. the selection
     klt_select(ctx, active, fresh, st);

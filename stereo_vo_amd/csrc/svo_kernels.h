@@ -137,6 +137,9 @@ struct LkTrackArgs {
 };
 void launch_lk_pyrdown(const LkJobDev* jobs, int n_jobs, int level, int max_w, int max_h, hipStream_t st);   // max_w x max_h: the largest level `level` of the call
 void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);                             // pixels_per_lane: lk_pixels_per_lane(win)
+// svo_lk_track_rows (k_lk_track_row in k_lk.hip): the same arguments; the search runs along the row of the guess, the backward pass compares
+// x alone.  A point index behind its job's count (gp - pt0 >= n) is nobody's and is left alone: a step's row records leave such gaps
+void launch_lk_track_row(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);
 // svo_gftt_detect (k_gftt.hip).  One record per job, in device memory: its image (the caller's device image or its copy in the context's
 // buffer), its response map, where its seeds and its results lie in the flat arrays, and the cell grid of the distance rule
 // (gftt_call.hpp: cell side >= min_distance, at most 64 x 64 cells)
@@ -185,8 +188,11 @@ struct KltSelectArgs {
 // image of the NEW pair) and 2 * n_lanes tracking records (job 2 * lane + side: img[0] the side's last image, img[1] its new one).
 // parity: the pyramid buffer the lane's new pair is in; empty: lanes that track nothing (idle, or without a last pair) -- their
 // tracking records describe a 0 x 0 image, on which the tracker retires every point before it reads a pixel
+// row_jobs (svo_klt_set_stereo(1), else NULL): n_lanes more records, lane l's with img[0] / img[1] = the left / right image of the NEW pair
+// and the slots [2 l cap, 2 l cap + cap) -- the left results are its points, the right results lie cap behind them; an idle lane's has
+// no point.  The tracking records of the right side then describe a 0 x 0 image: the right list is not tracked through time
 struct KltJobArgs {
-    LkJobDev* pyr_jobs; LkJobDev* trk_jobs;
+    LkJobDev* pyr_jobs; LkJobDev* trk_jobs; LkJobDev* row_jobs;
     uint8_t* pyr; long long img_stride;
     int n_lanes, cap, nl;
     int w[6], h[6]; long long off[6];
@@ -208,6 +214,16 @@ struct KltPredictArgs {
     int forced, forced_valid; double forced_delta[6];
 };
 void launch_klt_predict(const DevCtx& c, const KltPredictArgs& a, hipStream_t st);
+// svo_klt_set_stereo(1), behind the step's tracking launches (k_klt_row_guess in k_klt.hip): the first guesses of the row pass.  For an
+// active lane l and slot s < cap: guess[2 l cap + s] = (xl' - (xl - xr), yl') in float32 as written, (xl, xr) the table's old points and
+// (xl', yl') the left result; NaN where the left status is not 1 (the row pass then reads nothing for the slot).  A lane of `fresh` has
+// no last pair: its left points stand -- they are copied to the results with status 1 -- and are the (xl', yl') of its guesses
+struct KltRowGuessArgs {
+    KltDev t; int half;               // the live half, read only
+    float2* guess;                    // [n_lanes][2][cap], the first cap of a lane used
+    LaneMask active, fresh;
+};
+void launch_klt_row_guess(const KltRowGuessArgs& a, hipStream_t st);
 void launch_klt_select(const DevCtx& c, const KltSelectArgs& a, hipStream_t st);
 void launch_klt_append(const KltDev& t, int half, int lane, const float2* left, const float2* right, int n, hipStream_t st);
 // empties the tables of the lanes of the mask in `half` and starts their IDs over

@@ -37,6 +37,7 @@ EXPORTS = [
     "svo_klt_topup_default_params", "svo_klt_topup_enable", "svo_klt_topup", "svo_klt_topup_info", "svo_debug_klt_topup_append",
     "svo_ransac_tracked", "svo_klt_set_ransac", "svo_klt_get_ransac",
     "svo_klt_set_prediction", "svo_klt_get_prediction", "svo_klt_predicted", "svo_debug_klt_predict",
+    "svo_lk_track_rows", "svo_klt_set_stereo", "svo_klt_get_stereo",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -172,6 +173,10 @@ def lib():
             L.svo_klt_get_prediction.argtypes = [C.c_void_p]
             L.svo_klt_predicted.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
             L.svo_debug_klt_predict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "svo_lk_track_rows"):         # (as above)
+            L.svo_lk_track_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+            L.svo_klt_set_stereo.argtypes = [C.c_void_p, C.c_int]
+            L.svo_klt_get_stereo.argtypes = [C.c_void_p]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -827,7 +832,7 @@ class Context:
         return idx[:len(q)], dist[:len(q)]
 
     # -- pyramidal Lucas-Kanade tracking on caller lists (svo_lk_track) ------------------------------------------
-    def lk_track(self, jobs, params=None, device=False, pinned=False):
+    def lk_track(self, jobs, params=None, device=False, pinned=False, _entry="svo_lk_track"):
         """jobs: a list of (prev, next, pts[, init]) -- prev / next uint8 [h, w] numpy arrays (any row stride; the last axis must be
         contiguous), pts / init [n, 2] float32 (x, y).  With device=True prev / next are (device address, w, h, stride) tuples, read in
         place; pinned=True declares the host arrays page-locked.  params: an LkParams (None: the defaults).  Returns a
@@ -856,8 +861,14 @@ class Context:
             recs[i].next_pts, recs[i].status, recs[i].err = (_vp(a) if n else None for a in res)
             out.append(res)
         flags = FLAG_DEVICE_IMAGES if device else (FLAG_PINNED_IMAGES if pinned else 0)
-        self._ck(self.L.svo_lk_track(self.h, recs, len(jobs), C.byref(params) if params is not None else None, C.c_uint32(flags)), "svo_lk_track")
+        self._ck(getattr(self.L, _entry)(self.h, recs, len(jobs), C.byref(params) if params is not None else None, C.c_uint32(flags)), _entry)
         return out
+
+    def lk_track_rows(self, jobs, params=None, device=False, pinned=False):
+        """lk_track's records, flags and results with the row tracker (svo_lk_track_rows): the template of a point comes from prev at pts,
+        and its partner is searched in next along the row of the guess (init, else pts) -- x alone moves, the returned y is the guess's.
+        For a rectified stereo pair prev is the left image and next the right one.  Synchronises."""
+        return self.lk_track(jobs, params, device, pinned, _entry="svo_lk_track_rows")
 
     def lk_level(self, job, which, level):
         """pyramid level `level` of image `which` (0 prev, 1 next) of job `job` of the last lk_track call as a uint8 [h, w] array; None
@@ -1037,6 +1048,16 @@ class Context:
         """the mode svo_klt_set_prediction left"""
         return self._ck(self.L.svo_klt_get_prediction(self.h), "svo_klt_get_prediction")
 
+    # -- the stereo re-association of the front end (svo_klt_set_stereo) ----------------------------------------------
+    def klt_set_stereo(self, mode):
+        """how klt_step finds a track's right point: abi.KLT_STEREO_TEMPORAL (0, the default: the right list is tracked through time) or
+        KLT_STEREO_ROW (1: the partner of the new left point is found in the new pair along its row).  After klt_enable."""
+        self._ck(self.L.svo_klt_set_stereo(self.h, int(mode)), "svo_klt_set_stereo")
+
+    def klt_get_stereo(self):
+        """the mode svo_klt_set_stereo left"""
+        return self._ck(self.L.svo_klt_get_stereo(self.h), "svo_klt_get_stereo")
+
     def _klt_guesses(self, what, call):
         n = self._ck(call(None, None, None, 0), what)
         l, r, used = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
@@ -1064,6 +1085,7 @@ class Context:
         "gftt_response", "gftt_candidates", "gftt_select": svo_gftt_detect, "lk_pyrdown", "lk_track": svo_lk_track and svo_klt_step, and
         "klt_select": svo_klt_step, "klt_topup": svo_klt_topup, "ransac_feed": svo_ransac_tracked and a step under klt_set_ransac,
         "klt_prune": a step in mode 2, "klt_predict": a step under klt_set_prediction(1), klt_predicted and debug_klt_predict,
+        "lk_track_row": lk_track_rows and a step under klt_set_stereo(1),
         each listed once the context has made such a call) and are
         included with appended=True, so that a reader of the frame's launches finds the list it always found."""
         names = (C.c_char_p * 64)()
