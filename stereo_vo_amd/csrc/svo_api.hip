@@ -3,67 +3,15 @@
 // svo_process enqueues one frame of every lane on the context's stream as a fixed sequence of ~20 kernel
 // launches; every data-dependent size (keypoint, pairing, track counts) stays in device memory, so there is no
 // host synchronisation inside a frame and frames can be enqueued back to back.
-#include "svo_device.h"
-#include "svo_kernels.h"
+#include "svo_ctx.hpp"
 #include "state_format.hpp"
-#include "frame_call.hpp"
-#include "lk_call.hpp"
-#include "gftt_call.hpp"
-#include "klt_call.hpp"
 #include <math.h>
-#include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string>
-#include <vector>
 #include <mutex>
 #include <map>
 #include <memory>
 #include <condition_variable>
-
-#define HIPCHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e); return SVO_ERR_HIP; } } while (0)
-
-enum { KT_BEGIN, KT_RESIZE, KT_FAST, KT_SELECT, KT_DESCRIBE, KT_NMS, KT_HAM_LR, KT_LR_FILTER, KT_HAM_TRK, KT_TRK_FILTER,
-       KT_RANSAC_HYP, KT_RANSAC_CNT, KT_TRK_FINAL, KT_GN, KT_RANSAC_HYP1, KT_RANSAC_CNT1, KT_RANSAC_HYP2, KT_RANSAC_CNT2,
-       KT_SAD_PATCH, KT_LR_SAD, KT_TRK_SAD,
-       // the instantiations that only a 16384-entry context launches, under names of their own (a context with max_kps <= 8192 never counts a call here)
-       KT_SELECT_8192, KT_NMS_16, KT_HAM_LR_WIDE, KT_HAM_TRK_WIDE, KT_TRK_FILTER_64,
-       // svo_export_frame / svo_import_frame: the kernels of a context that carries no SAD windows, then those of one that does
-       KT_EXPORT, KT_IMPORT, KT_EXPORT_WIN, KT_IMPORT_WIN,
-       // dmFASTER (only a context that selects it counts a call here)
-       KT_FASTER, KT_FASTER_NMS,
-       // svo_gather_windows: the slot-selecting window gather (only a caller of that entry point counts a call here)
-       KT_GATHER_WIN,
-       // svo_set_pose_covariance (only a context that enables it counts a call here)
-       KT_POSE_COV,      // keep these two in this order, behind every name a context always lists: svo_kernel_times lists each only while its feature is on
-       // svo_set_landmarks (only a context that enables it counts a call here)
-       KT_LANDMARKS,
-       // svo_lk_track: listed behind all of the above, and only once the context has made such a call (svo_kernel_times)
-       // svo_gftt_detect: listed behind the frame's names and before the LK ones, and only once the context has made such a call
-       KT_GFTT_RESPONSE, KT_GFTT_CANDIDATES, KT_GFTT_SELECT,
-       KT_LK_PYRDOWN, KT_LK_TRACK,
-       KT_COUNT,
-       // the resident KLT front end: "klt_select", listed behind the LK names once the context has made a step.  Behind KT_COUNT: the
-       // name lives outside kt_names (kt_name below), whose last entries stay the LK ones
-       // ... and "klt_topup" behind it, once the context has topped up (the three kernels of k_klt.hip around the detector and the tracker)
-       KT_KLT_SELECT = KT_COUNT, KT_KLT_TOPUP, KT_ALL };
-// ... and "ransac_feed" (svo_ransac_tracked, or a step under svo_klt_set_ransac) and "klt_prune" (a step in mode 2) behind those, each
-// once the context has launched it.  The RANSAC launches between them count under their names of a frame
-// ... and "klt_predict" (a step under svo_klt_set_prediction(1), svo_klt_predicted, svo_debug_klt_predict) last of all
-// ... and "lk_track_row" (svo_lk_track_rows, or a step under svo_klt_set_stereo(1)) behind that
-enum { KT_RANSAC_FEED = KT_ALL, KT_KLT_PRUNE, KT_KLT_PREDICT, KT_LK_TRACK_ROW, KT_EVERY };
-static_assert(KT_EVERY <= 64, "kt_mask is one 64-bit word");
-static const char* kt_names[KT_COUNT] = { "begin_frame", "resize", "fast", "select", "describe", "nms_rowsort", "hamming_lr",
-    "match_lr_filter", "hamming_track", "track_filter", "ransac_hyp", "ransac_count", "track_finalize", "gauss_newton",
-    "ransac_hyp_1", "ransac_count_1", "ransac_hyp_2", "ransac_count_2", "sad_patch", "match_lr_sad", "track_sad",
-    "select_8192", "nms_rowsort_16", "hamming_lr_wide", "hamming_track_wide", "track_filter_64",
-    "export_frame", "import_frame", "export_frame_win", "import_frame_win", "faster", "faster_nms", "gather_windows", "pose_covariance", "landmarks",
-    "gftt_response", "gftt_candidates", "gftt_select",
-    "lk_pyrdown", "lk_track" };
-static const char* kt_name(int i) { return i < KT_COUNT ? kt_names[i] : "klt_select"; }
-static const char* kt_name_all(int i) { return i == KT_KLT_TOPUP ? "klt_topup" : i == KT_RANSAC_FEED ? "ransac_feed" : i == KT_KLT_PRUNE ? "klt_prune" : i == KT_KLT_PREDICT ? "klt_predict" : i == KT_LK_TRACK_ROW ? "lk_track_row" : kt_name(i); }
-
-struct TimedSpan { int id; hipEvent_t a, b; };
 
 // ---- profiler sections ---------------------------------------------------------------------------------------------------
 // The reference brackets its stages with mrpt's CTimeLogger: m_profiler.enter / leave("processNewImagePair", "_stg1" ... "_stg5",
@@ -102,123 +50,13 @@ struct Section {                                       // m_profiler.enter(name)
 }
 extern "C" int svo_profiler_sections_enabled(void) { return roctx_api().push != nullptr; }
 
-struct svo_ctx {
-    svo_config cfg;
-    Knobs knobs;                                       // the SVO_* environment of svo_create (svo_knobs.hpp): read once, before the first allocation
-    svo_params params;
-    int fast_th, orb_th;
-    int klt_win;                                       // TDetectParams::KLT_win (S2:47): the window of dmFASTER's response, (2 klt_win + 1)^2 pixels
-    hipStream_t stream, stream0; bool own_stream;      // stream0: the stream the context was created with / owns
-    DevCtx dc;
-    bool geom_ready, geom_once;                        // geom_once: DevCtx has held a frame's geometry (svo_set_params clears geom_ready only; the lists of the last frame keep theirs)
-    int geom_w, geom_h, geom_nfe, geom_nlevels, geom_method, geom_noct;
-    int raw_cap_alloc;
-    uint8_t* d_img0; int img0_pitch_internal;
-    // host-fed frames (process_new_image_pair.cpp:100-120 hands over host images): a ring of two device level-0 buffers
-    // filled by a dedicated copy stream, so that the upload of frame t+1 overlaps the kernels of frame t
-    uint8_t* d_img0_ring[2]; uint8_t* h_stage[2]; size_t slot_bytes;
-    hipStream_t s_copy; hipEvent_t ev_h2d[2], ev_det[2]; bool ev_det_valid[2], ev_h2d_valid[2], up_ready; int up_slot, det_slot;
-    long long pyr_bytes_alloc; int cand_total_alloc, rtab_alloc, tile_tab_alloc;
-    std::vector<void*> allocs;
-    std::string last_error;
-    std::vector<TimedSpan> spans; std::vector<hipEvent_t> free_events;
-    double kt_total[KT_EVERY]; long long kt_calls[KT_EVERY]; unsigned long long kt_mask;
-    unsigned* d_ham_out; uint8_t* d_ham_q, *d_ham_t; int ham_cap_q, ham_cap_t;
-    // svo_lk_track: buffers of its own, made by its first call, grown on demand, freed with the context -- the pyramids of the call's
-    // images, the job records, the flat point arrays (pts, init, out: float2; status; err).  lk_jobs: the records of the last call, for
-    // svo_debug_lk_get_level.  lk_used: the context has made such a call (svo_kernel_times then lists its two names)
-    uint8_t* d_lk_pyr; size_t lk_pyr_cap; LkJobDev* d_lk_jobs; int lk_jobs_cap;
-    float2* d_lk_pts, *d_lk_init, *d_lk_out; uint8_t* d_lk_status; float* d_lk_err; int lk_pts_cap;
-    std::vector<LkJobDev> lk_jobs; bool lk_used;
-    // svo_gftt_detect: buffers of its own as well -- the response maps, the copies of host images, the job records, per job the
-    // candidate keys, the cell lists and the decision states, the flat seed and result arrays, four counters per job.  gftt_jobs: the
-    // records of the last call, for svo_debug_gftt_get_response.  gftt_used: the context has made such a call (svo_kernel_times)
-    float* d_gftt_map; size_t gftt_map_cap; uint8_t* d_gftt_img; size_t gftt_img_cap; GfttJobDev* d_gftt_jobs; int gftt_jobs_cap;
-    unsigned long long* d_gftt_keys; int* d_gftt_items; uint8_t* d_gftt_state; int* d_gftt_info;
-    float2* d_gftt_seeds; int gftt_seeds_cap; float2* d_gftt_pts; float* d_gftt_resp; int gftt_pts_cap;
-    std::vector<GfttJobDev> gftt_jobs; bool gftt_used;
-    // the resident KLT front end (svo_klt_enable; the plan: klt_call.hpp): nothing is allocated until it is enabled.  Host side: the
-    // parameters in force, the table half that is live (every lane's: k_klt_select moves idle lanes along), per lane the pyramid parity
-    // its last pair went to and whether it has a last pair, the image size of the last step.  used: svo_kernel_times lists "klt_select"
-    struct Klt {
-        bool enabled, used; svo_klt_params p; svo_klt::Plan plan;
-        KltDev dev; uint8_t* d_pyr; LkJobDev* d_pyr_jobs, * d_trk_jobs; float2* d_stage;
-        int half, w, h; LaneMask parity, has_img;
-        int ransac;                                    // svo_klt_set_ransac: 0 off, 1 filter the tracked pairs, 2 and drop the rejected tracks
-        bool prune_used;                               // a step has launched k_klt_prune (svo_kernel_times)
-        // svo_klt_set_prediction: 0 off, 1 constant-velocity pose prediction.  The one buffer of mode 1 (klt_call.hpp: plan_predict), made
-        // by the first call with mode 1 and dropped with the front end's buffers: the guesses and a byte per slot
-        int predict; float2* d_guess; uint8_t* d_gused;
-        // svo_klt_set_stereo: 0 the right list is tracked through time, 1 it is found along the row in the new pair.  The buffers of mode 1
-        // (klt_call.hpp: plan_stereo), made by the first call with mode 1 and dropped with the front end's buffers
-        int stereo; LkJobDev* d_row_jobs; float2* d_row_guess;
-        // the resident top-up (svo_klt_topup_enable; the plan: klt_call.hpp), buffers of its own: the response maps, the detector's job
-        // records, keys, cell lists, states and counters, the corners with their responses, the first guesses, the tracker's records and
-        // results, four ints per lane for svo_klt_topup_info.  topup_used: a top-up has run (svo_kernel_times, svo_klt_topup_enable)
-        bool topup_enabled, topup_used; svo_klt_topup_params tp; svo_klt::TopupPlan tplan;
-        float* d_tmap; GfttJobDev* d_tgjobs; unsigned long long* d_tkeys; int* d_titems; uint8_t* d_tstate; int* d_tginfo, * d_tinfo;
-        float2* d_tcorners, * d_tinit, * d_tout; float* d_tresp, * d_terr; uint8_t* d_tstatus; LkJobDev* d_tlk_jobs;
-    } klt;
-    bool params_set;                                   // svo_set_params has been called (the front end needs the parameters stage 5 runs with)
-    bool ransac_feed_used;                             // the context has launched k_ransac_feed (svo_kernel_times)
-    bool klt_predict_used;                             // the context has launched k_klt_predict (svo_kernel_times)
-    bool lk_row_used;                                  // the context has launched k_lk_track_row (svo_kernel_times)
-    bool frame_parallel;                               // the context is a member of a frame-parallel stream (svo_internal_mark_frame_parallel): no KLT front end
-    // stage 1 (svo_set_rectify_map, SVO_FLAG_BGR_IMAGES): all allocated on first use
-    uint8_t* d_src; int src_pitch;                    // staging of host source images (grey or BGR)
-    uint2** d_map_ptrs; std::vector<uint2*> map_ptrs;  // per image: fixed-point map on the device or nullptr
-    int map_w, map_h, n_maps;
-    std::vector<uint2*> map_bufs;                      // per image: the allocation of its own behind map_ptrs (kept across clear / set cycles)
-    // maps from a calibration (svo_set_undistort_rectify, svo_set_stereo_calibration): the table of a side that lane = -1 built ONCE and
-    // every lane's map_ptrs entry points at until the lane is set or cleared on its own; the models k_rectify_map reads.  First use.
-    uint2* map_shared[2]; RectifyImage* d_rect_models;
-    // getChangeInPose works on temporaries (common.cpp:362-400): a one-lane scratch view of the device context
-    DevCtx cip; bool cip_ready;
-    // svo_get_values: device packing buffer and its page-locked host mirror
-    uint8_t* d_vals; uint8_t* h_vals; size_t vals_bytes;
-    uint32_t* d_anms;                                  // scratch of k_fastorb_anms (3 x n_img x cand_total), allocated on first use
-    // svo_set_pose_covariance: one record per lane and the array k_gauss_newton leaves its final mask in; nullptr until first enabled
-    bool pose_cov; svo_pose_cov* d_cov; uint8_t* d_cov_mask;      // (d_cov_mask: made by whichever of this feature and the next is enabled first)
-    // svo_set_landmarks: [n_lanes][max_kps] records, one info per lane, the 4 counter words per lane of k_landmarks; nullptr until first enabled
-    bool landmarks; double lmk_std; svo_landmark* d_lmk; svo_landmarks_info* d_lmk_info; int* d_lmk_cnt;
-    // svo_set_dyn_fast_threshold: dmFASTER's m_threshold[octave] of every lane (the `next` member) with its statistics; nullptr until first enabled.
-    // Persistent detector scratch: read and written by detect calls alone, ordered on the stream they run on, like fast_th_dyn
-    bool dyn_fast; double dyn_target; svo_faster_stats* d_fstats;
-    // svo_set_faster_adaptive_nms: the opt-in, and the scratch of k_faster_anms (3 x n_img x cand_total 64-bit words), allocated by the setter.
-    // svo_adaptive_nms has buffers of its own (keys, scratch, positions out), allocated by its first call: it touches nothing a frame uses
-    bool faster_anms; unsigned long long* d_fanms; unsigned long long* d_anms_list; uint32_t* d_anms_pos;
-    unsigned long long* d_cand64;                      // dmFASTER's 64-bit candidate keys (n_img x cand_total), allocated by the first svo_process made while it is selected
-    // smSAD / ifmSAD (k_sad_patch): which frames of a lane have their 8 x 8 windows in DevCtx.sad_patch.  Kept on the HOST, per lane,
-    // so that a stage that selects SAD on a frame without them is refused before anything is enqueued.  "true" also stands for "no
-    // such frame yet" (the kernels then read nothing).  The device decides the prev/cur shift (the recovery rule of P:86-95 needs
-    // m_error), so the previous frame after a shift is known to have patches only when both candidates for it had them.
-    svo_call::SadWindows sad;                          // sad.drop: the lane's next shift forgets its previous frame (svo_hip.h)
-    LaneMask imported;                                 // lanes that svo_import_frame has written and that have not had a svo_process call since (an idle lane keeps its bit)
-    // svo_process_lanes: the active mask of the call that began the frame in flight.  The later calls of a multi-call frame (the post
-    // call of a detect call, stages run with SVO_FLAG_NO_SHIFT) must carry the same one.
-    LaneMask frame_active; bool frame_active_set;
-    int sampler_nmax;                                  // > 0: holds a reference on the shared sampler table of (device, sampler_nmax)
-    hipEvent_t post_event;                             // svo_record_after_post: armed for the next call that runs the detector's post-processing
-    // svo_use_graphs: the kernel sequence of a frame captured once per (flags, ring slot, thresholds) and replayed
-    struct GraphEntry { uint32_t flags; int slot, fast_th, orb_th; hipGraphExec_t exec; };
-    std::vector<GraphEntry> graphs; bool use_graphs; unsigned graph_replays;      // graph_replays: calls served by an earlier capture (svo_debug_get_graph_count)
-    bool capturing;                                    // the call being enqueued is capturing its launches on the stream (CaptureGuard)
-    // every stream that has had work of this context enqueued since the last full synchronisation (svo_set_stream), each with
-    // a context-owned event recorded behind the last work enqueued on it.  Synchronising waits on the EVENTS, never on the
-    // foreign stream handles: a caller may synchronise and destroy its own stream and switch back with svo_set_stream(NULL);
-    // an event recorded on a stream that has since been destroyed is simply complete.
-    struct UsedStream { hipStream_t s; hipEvent_t ev; bool dirty; };
-    std::vector<UsedStream> used_streams;
-};
-
 using namespace svo_call;
 static void drop_graphs(svo_ctx* ctx);
-static void klt_free(svo_ctx* ctx);
 static int dyn_fast_init(svo_ctx* ctx, int lane);
 static int ensure_sad_buffers(svo_ctx* ctx);
 static int sampler_table_acquire(svo_ctx* ctx, int nmax);
 static void sampler_table_release(int device, int nmax);
-static void note_stream(svo_ctx* ctx)
+void note_stream(svo_ctx* ctx)
 {
     for (auto& u : ctx->used_streams) if (u.s == ctx->stream) { u.dirty = true; return; }
     hipEvent_t ev = nullptr;
@@ -227,7 +65,7 @@ static void note_stream(svo_ctx* ctx)
 }
 // record "everything enqueued so far" on the current stream (behind the last launch of an entry point, on its error exits too;
 // never while capturing)
-static void mark_stream(svo_ctx* ctx)
+void mark_stream(svo_ctx* ctx)
 {
     if (ctx->stream == ctx->stream0 && ctx->own_stream) return;  // the context's own stream is synchronised by handle
     for (auto& u : ctx->used_streams) if (u.s == ctx->stream) {
@@ -308,13 +146,6 @@ extern "C" const char* svo_strerror(int s)
         case SVO_ERR_STATE: return "call not valid in the current state";
         default: return "unknown status";
     }
-}
-// Every entry point runs on the context's GPU whatever device the calling thread had current (a host may own one
-// estimator per GPU and call them from one thread, or from one thread each: SURVEY.md 8b "Threading")
-static inline void use_device(const svo_ctx* ctx)
-{
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != ctx->cfg.device) (void)hipSetDevice(ctx->cfg.device);
 }
 extern "C" const char* svo_last_error(const svo_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
@@ -456,12 +287,12 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
-    ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0; ctx->lk_used = false;
+    ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0;
     ctx->d_lk_pts = ctx->d_lk_init = ctx->d_lk_out = nullptr; ctx->d_lk_status = nullptr; ctx->d_lk_err = nullptr;
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;
-    ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0; ctx->gftt_used = false;
-    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->ransac_feed_used = false; ctx->klt_predict_used = false; ctx->lk_row_used = false;
+    ctx->d_gftt_seeds = nullptr; ctx->gftt_seeds_cap = 0; ctx->d_gftt_pts = nullptr; ctx->d_gftt_resp = nullptr; ctx->gftt_pts_cap = 0;
+    memset(&ctx->klt, 0, sizeof(ctx->klt)); ctx->params_set = false; ctx->frame_parallel = false; ctx->kt_seen = 0;
     ctx->d_src = nullptr; ctx->src_pitch = 0; ctx->d_map_ptrs = nullptr; ctx->map_w = ctx->map_h = ctx->n_maps = 0;
     ctx->map_shared[0] = ctx->map_shared[1] = nullptr; ctx->d_rect_models = nullptr;
     memset(&ctx->imported, 0, sizeof(ctx->imported)); ctx->graph_replays = 0; ctx->capturing = false; ctx->frame_active_set = false; memset(&ctx->frame_active, 0, sizeof(ctx->frame_active)); ctx->use_graphs = false; ctx->d_anms = nullptr; ctx->post_event = nullptr; ctx->pose_cov = false; ctx->d_cov = nullptr; ctx->d_cov_mask = nullptr;
@@ -470,7 +301,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->cip_ready = false; ctx->d_vals = nullptr; ctx->h_vals = nullptr; ctx->vals_bytes = 0;
     ctx->up_ready = false; ctx->up_slot = 0; ctx->det_slot = -1; ctx->s_copy = nullptr; ctx->slot_bytes = 0;
     for (int i = 0; i < 2; i++) { ctx->d_img0_ring[i] = nullptr; ctx->h_stage[i] = nullptr; ctx->ev_det_valid[i] = ctx->ev_h2d_valid[i] = false; }
-    for (int i = 0; i < KT_EVERY; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     ctx->kt_mask = ~0ull;
     *out = ctx;                                           // so that the caller can read last_error and destroy
     knobs_read(&ctx->knobs, knobs_env);
@@ -849,7 +680,7 @@ extern "C" int svo_set_dyn_fast_threshold(svo_ctx* ctx, int enable, double targe
 {
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
-    { std::string why; const int rc = check_dyn_fast_target(target_feats_per_pixel, why); if (rc) { ctx->last_error = why; return rc; } }
+    SVO_REFUSE(check_dyn_fast_target(target_feats_per_pixel, why));
     const bool on = enable != 0;
     if (on == ctx->dyn_fast && target_feats_per_pixel == ctx->dyn_target) return SVO_OK;
     drop_graphs(ctx);                                        // the launches of a detect call and one of their arguments change
@@ -909,7 +740,7 @@ extern "C" int svo_adaptive_nms(svo_ctx* ctx, const svo_keypoint* kps, int n, in
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     const int n_cap = std::min(std::max(1024, ctx->cfg.max_cand), faster_anms_max_candidates());
-    { std::string why; const int rc = check_adaptive_nms_args(kps, n, num_out_points, img_w, img_h, out_order, cap, n_cap, ctx->dc.max_kps, why); if (rc) { ctx->last_error = why; return rc; } }
+    SVO_REFUSE(check_adaptive_nms_args(kps, n, num_out_points, img_w, img_h, out_order, cap, n_cap, ctx->dc.max_kps, why));
     const int actual = std::min(num_out_points, n);                               // S2:151
     if (actual <= 0) return 0;                                                   // S2:152
     if (!ctx->d_anms_list) {
@@ -1166,7 +997,7 @@ static void drop_graphs(svo_ctx* ctx)
     ctx->graphs.clear();
 }
 
-static int ensure_geometry(svo_ctx* ctx, int w, int h)
+int ensure_geometry(svo_ctx* ctx, int w, int h)
 {
     const svo_params& p = ctx->params;
     // dmFAST_ORB and dmFASTER both work on the x1/2 octave pyramid and keep one list per octave (S2:502-515, 519-576): same geometry,
@@ -1268,16 +1099,11 @@ static int ensure_geometry(svo_ctx* ctx, int w, int h)
 }
 
 // ---- kernel timing ------------------------------------------------------------------------------------------
-static hipEvent_t get_event(svo_ctx* ctx)
+hipEvent_t get_event(svo_ctx* ctx)
 {
     if (!ctx->free_events.empty()) { hipEvent_t e = ctx->free_events.back(); ctx->free_events.pop_back(); return e; }
     hipEvent_t e; hipEventCreate(&e); return e;
 }
-struct Span {
-    svo_ctx* ctx; int id; hipEvent_t a, b; bool on; hipStream_t st;
-    Span(svo_ctx* c, int i, hipStream_t on_stream = nullptr) : ctx(c), id(i), on(c->cfg.kernel_times != 0 && ((c->kt_mask >> i) & 1ull)), st(on_stream ? on_stream : c->stream) { if (on) { a = get_event(ctx); b = get_event(ctx); hipEventRecord(a, st); } }
-    ~Span() { if (on) { hipEventRecord(b, st); ctx->spans.push_back({ id, a, b }); } }
-};
 static void collect_spans(svo_ctx* ctx)
 {
     for (auto& s : ctx->spans) {
@@ -1302,31 +1128,13 @@ extern "C" int svo_kernel_times(svo_ctx* ctx, const char** names, double* total_
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    // "pose_covariance" is listed while svo_set_pose_covariance is on, and "landmarks" (behind it, then with "pose_covariance" whatever its
-    // switch) while svo_set_landmarks is on: a context that has both off reports the list it always did
-    int n = ctx->landmarks ? KT_LANDMARKS + 1 : (ctx->pose_cov ? KT_LANDMARKS : KT_POSE_COV);
-    for (int i = 0; i < n && i < cap; i++) { if (names) names[i] = kt_names[i]; if (total_ms) total_ms[i] = ctx->kt_total[i]; if (calls) calls[i] = ctx->kt_calls[i]; }
-    // the three names of svo_gftt_detect behind whatever was listed, once the context has made such a call
-    for (int k = KT_GFTT_RESPONSE; (ctx->gftt_used || ctx->klt.topup_used) && k <= KT_GFTT_SELECT; k++, n++)
-        if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
-    // "lk_pyrdown" and "lk_track" behind those, once the context has made a svo_lk_track call
-    for (int k = KT_LK_PYRDOWN; (ctx->lk_used || ctx->klt.used || ctx->klt.topup_used) && k <= KT_LK_TRACK; k++, n++)
-        if (n < cap) { if (names) names[n] = kt_names[k]; if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
-    // "klt_select" behind the LK names (which a step counts its pyramid and tracking launches under), once the context has made a step
-    if (ctx->klt.used || ctx->klt.topup_used) {
-        if (n < cap) { if (names) names[n] = kt_name(KT_KLT_SELECT); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_SELECT]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_SELECT]; }
-        n++;
-    }
-    // "klt_topup" behind it, once the context has topped up (the detector and tracker launches of a top-up count under their own names)
-    if (ctx->klt.topup_used) {
-        if (n < cap) { if (names) names[n] = kt_name_all(KT_KLT_TOPUP); if (total_ms) total_ms[n] = ctx->kt_total[KT_KLT_TOPUP]; if (calls) calls[n] = ctx->kt_calls[KT_KLT_TOPUP]; }
-        n++;
-    }
-    // "ransac_feed", "klt_prune", "klt_predict" and "lk_track_row" behind everything else, each once the context has launched the kernel
-    for (int k = KT_RANSAC_FEED; k <= KT_LK_TRACK_ROW; k++) {
-        if (!(k == KT_RANSAC_FEED ? ctx->ransac_feed_used : k == KT_KLT_PRUNE ? ctx->klt.prune_used : k == KT_KLT_PREDICT ? ctx->klt_predict_used : ctx->lk_row_used)) continue;
-        if (n < cap) { if (names) names[n] = kt_name_all(k); if (total_ms) total_ms[n] = ctx->kt_total[k]; if (calls) calls[n] = ctx->kt_calls[k]; }
-        n++;
+    // which names, in which order: kernel_names.cpp (a context that has made none of the optional calls reports the list it always did)
+    int ids[KT_COUNT];
+    const int n = kernel_time_listing(ctx->kt_seen, ctx->pose_cov, ctx->landmarks, ids);
+    for (int i = 0; i < n && i < cap; i++) {
+        if (names) names[i] = kernel_names[ids[i]].name;
+        if (total_ms) total_ms[i] = ctx->kt_total[ids[i]];
+        if (calls) calls[i] = ctx->kt_calls[ids[i]];
     }
     return n;
 }
@@ -1335,8 +1143,10 @@ extern "C" int svo_kernel_times_select(svo_ctx* ctx, const char* name)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     if (!name || !*name) { ctx->kt_mask = ~0ull; return SVO_OK; }
-    for (int i = 0; i < KT_EVERY; i++) if (!strcmp(name, kt_name_all(i))) { ctx->kt_mask = 1ull << i; return SVO_OK; }
-    return SVO_ERR_ARG;
+    const int id = kernel_time_id(name);
+    if (id < 0) return SVO_ERR_ARG;
+    ctx->kt_mask = 1ull << id;
+    return SVO_OK;
 }
 
 extern "C" int svo_kernel_times_reset(svo_ctx* ctx)
@@ -1344,7 +1154,7 @@ extern "C" int svo_kernel_times_reset(svo_ctx* ctx)
     if (ctx) use_device(ctx);
     if (!ctx) return SVO_ERR_ARG;
     int rc = svo_wait(ctx); if (rc) return rc;
-    for (int i = 0; i < KT_EVERY; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
+    for (int i = 0; i < KT_COUNT; i++) { ctx->kt_total[i] = 0; ctx->kt_calls[i] = 0; }
     return SVO_OK;
 }
 
@@ -1581,14 +1391,12 @@ static hipError_t release_ring_slot(svo_ctx* ctx)
 struct PostDisarm { svo_ctx* c; bool consumes; ~PostDisarm() { (void)record_post_event(c, consumes, true); } };
 // whatever was enqueued before an error exit is still covered by the stream's event (declared before the capture guard: a capture is
 // closed first)
-struct MarkGuard { svo_ctx* c; ~MarkGuard() { mark_stream(c); } };
 // the idle lanes travel in DevCtx to every launch of a call; outside it the mask is all zero (the other entry points launch with it)
-struct IdleGuard { DevCtx* d; ~IdleGuard() { memset(&d->idle, 0, sizeof(d->idle)); } };
 // a capture that an error exit leaves open is closed and thrown away
 struct CaptureGuard { svo_ctx* c; ~CaptureGuard() { if (c->capturing) { hipGraph_t g = nullptr; hipStreamEndCapture(c->stream, &g); if (g) hipGraphDestroy(g); c->capturing = false; } } };
 
 // ---- the launches of a frame, one function per stage --------------------------------------------------------------------
-// kernel_times: the instantiations of a 16384-entry context are counted under their own names (kt_names)
+// kernel_times: the instantiations of a 16384-entry context are counted under their own names (kernel_names.cpp)
 static int kt_select(const DevCtx& d) { return d.sel_max > 4096 ? KT_SELECT_8192 : KT_SELECT; }
 static int kt_nms(const DevCtx& d) { return nms_rowsort_items(d) > 8 ? KT_NMS_16 : KT_NMS; }
 static bool wide_lists(const DevCtx& d) { return d.max_kps > 8192; }
@@ -1702,16 +1510,16 @@ static void enqueue_track(svo_ctx* ctx, const FrameCall& call, hipStream_t st)
 }
 // svo_ransac_tracked, and the gate of a step under svo_klt_set_ransac: the RANSAC of stage 4 on the tracked pairs the lanes hold, for
 // the lanes DevCtx.idle leaves in.  No bad-tracking gate: the precomputed-data bypass has none
-static void enqueue_ransac_tracked(svo_ctx* ctx, hipStream_t st)
+void enqueue_ransac_tracked(svo_ctx* ctx, hipStream_t st)
 {
     DevCtx& d = ctx->dc;
     set_ransac_chunks(ctx);
     { Span s(ctx, KT_RANSAC_FEED); launch_ransac_feed(d, st); }
     enqueue_ransac_chunks(ctx, st);
     { Span s(ctx, KT_TRK_FINAL); launch_track_finalize_ungated(d, st); }
-    ctx->ransac_feed_used = true;
+    ctx->seen(KG_RANSAC_FEED);
 }
-static void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
+void enqueue_optimize(svo_ctx* ctx, const FrameCall&, hipStream_t st)
 {
     DevCtx& d = ctx->dc; const svo_params& p = ctx->params;
     Section sec("_stg5");                                                        // S5:398, 729
@@ -1858,9 +1666,7 @@ extern "C" int svo_process(svo_ctx* ctx, const svo_frame* frames, uint32_t flags
 // svo_process for the lanes whose bit is set; for the others as if the call had not been made (svo_hip.h)
 extern "C" int svo_process_lanes(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t active[2])
 {
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
+    SVO_ENTER(ctx);
     return process_lanes_body(ctx, active, true, frames, flags);
 }
 
@@ -2240,9 +2046,7 @@ extern "C" int svo_put_tracked_oct(svo_ctx* ctx, int lane, int octave, const svo
 // that, hence k_publish_img0 for the level-0 pointer table.
 extern "C" int svo_gather_windows(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, int which, const uint64_t lanes[2])
 {
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
+    SVO_ENTER(ctx);
     char msg[200];
     if (which != 0 && which != 1) { snprintf(msg, sizeof(msg), "which = %d: 0 (current frame) or 1 (previous frame)", which); ctx->last_error = msg; return SVO_ERR_ARG; }
     if (flags & ~(uint32_t)(SVO_FLAG_DEVICE_IMAGES | SVO_FLAG_PINNED_IMAGES | SVO_FLAG_BGR_IMAGES)) {
@@ -2656,868 +2460,6 @@ extern "C" int svo_hamming_match(svo_ctx* ctx, const uint8_t* query, int nq, con
     HIPCHECK(hipStreamSynchronize(st));
     for (int i = 0; i < nq; i++) { idx[i] = (int)(out[i] & 0xFFFFu); dist[i] = (int)(out[i] >> 16); }
     return SVO_OK;
-}
-
-// ---- pyramidal Lucas-Kanade tracking on caller lists (svo_hip.h; the decisions: lk_call.hpp, the kernels: k_lk.hip) ---------------
-template <typename T>
-static hipError_t lk_realloc(T** p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return hipMalloc((void**)p, n * sizeof(T));
-}
-
-// svo_lk_track and svo_lk_track_rows: one call, the tracker apart (rows: k_lk_track_row, counted under its own name)
-static int lk_track_call(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags, bool rows)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_lk_params p;
-    if (params) p = *params; else svo_lk_default_params(&p);
-    const svo_lk::Caps caps{ ctx->dc.max_kps, 4 * ctx->cfg.n_lanes * ctx->dc.oct_cap, ctx->cfg.max_w, ctx->cfg.max_h };
-    { std::string why; const int rc = svo_lk::check_lk_call(jobs, n_jobs, p, flags, caps, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (n_jobs == 0) return SVO_OK;
-    const bool dev = (flags & SVO_FLAG_DEVICE_IMAGES) != 0;
-    const svo_lk::Plan plan = svo_lk::plan_lk_call(jobs, n_jobs, p, dev);
-    const size_t NP = (size_t)plan.n_pts;
-    // the buffers: a failed growth leaves the capacity at 0, so that the next call allocates afresh
-    ctx->lk_jobs.clear();
-    if ((size_t)plan.pyr_bytes > ctx->lk_pyr_cap) { ctx->lk_pyr_cap = 0; HIPCHECK(lk_realloc(&ctx->d_lk_pyr, (size_t)plan.pyr_bytes)); ctx->lk_pyr_cap = (size_t)plan.pyr_bytes; }
-    if (n_jobs > ctx->lk_jobs_cap) { ctx->lk_jobs_cap = 0; HIPCHECK(lk_realloc(&ctx->d_lk_jobs, (size_t)n_jobs)); ctx->lk_jobs_cap = n_jobs; }
-    if (plan.n_pts > ctx->lk_pts_cap) {
-        ctx->lk_pts_cap = 0;
-        HIPCHECK(lk_realloc(&ctx->d_lk_pts, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_init, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_out, NP));
-        HIPCHECK(lk_realloc(&ctx->d_lk_status, NP)); HIPCHECK(lk_realloc(&ctx->d_lk_err, NP));
-        ctx->lk_pts_cap = plan.n_pts;
-    }
-    ctx->lk_used = true;
-    if (rows) ctx->lk_row_used = true;
-    const hipStream_t st = ctx->stream;
-    // the job records; host images go to level 0 of their block, device images are read where they are
-    std::vector<LkJobDev> recs((size_t)n_jobs);
-    int lw[svo_lk::LK_MAX_LEVELS] = { 0 }, lh[svo_lk::LK_MAX_LEVELS] = { 0 };
-    for (int j = 0; j < n_jobs; j++) {
-        const svo_lk::Geometry& g = plan.geom[(size_t)j];
-        LkJobDev& r = recs[(size_t)j];
-        memset(&r, 0, sizeof(r));
-        r.nl = g.nl; r.pt0 = plan.pt0[(size_t)j]; r.n = jobs[j].n; r.has_init = (jobs[j].n > 0 && jobs[j].init) ? 1 : 0;
-        for (int l = 0; l < g.nl; l++) { r.w[l] = g.w[l]; r.h[l] = g.h[l]; if (g.w[l] > lw[l]) lw[l] = g.w[l]; if (g.h[l] > lh[l]) lh[l] = g.h[l]; }
-        for (int s = 0; s < 2; s++) {
-            const svo_image& im = s ? jobs[j].next : jobs[j].prev;
-            uint8_t* block = ctx->d_lk_pyr + plan.img_off[(size_t)(2 * j + s)];
-            for (int l = 1; l < g.nl; l++) { r.img[s][l] = block + g.off[l]; r.pitch[s][l] = g.w[l]; }
-            if (dev) { r.img[s][0] = im.data; r.pitch[s][0] = (int)im.stride; }
-            else {
-                r.img[s][0] = block; r.pitch[s][0] = g.w[0];
-                HIPCHECK(hipMemcpy2DAsync(block, (size_t)g.w[0], im.data, (size_t)im.stride, (size_t)g.w[0], (size_t)g.h[0], hipMemcpyHostToDevice, st));
-            }
-        }
-    }
-    HIPCHECK(hipMemcpyAsync(ctx->d_lk_jobs, recs.data(), sizeof(LkJobDev) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
-    std::vector<float> h_pts(2 * NP), h_init(plan.any_init ? 2 * NP : 0);
-    for (int j = 0; j < n_jobs; j++) {
-        if (jobs[j].n <= 0) continue;
-        const size_t o = 2 * (size_t)plan.pt0[(size_t)j], nb = sizeof(float) * 2 * (size_t)jobs[j].n;
-        memcpy(h_pts.data() + o, jobs[j].pts, nb);
-        if (jobs[j].init) memcpy(h_init.data() + o, jobs[j].init, nb);
-    }
-    if (NP) HIPCHECK(hipMemcpyAsync(ctx->d_lk_pts, h_pts.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
-    if (NP && plan.any_init) HIPCHECK(hipMemcpyAsync(ctx->d_lk_init, h_init.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
-    { Span s(ctx, KT_LK_PYRDOWN); for (int l = 1; l < plan.max_nl; l++) launch_lk_pyrdown(ctx->d_lk_jobs, n_jobs, l, lw[l], lh[l], st); }
-    LkTrackArgs a;
-    a.jobs = ctx->d_lk_jobs; a.n_jobs = n_jobs; a.n_pts = plan.n_pts;
-    a.pts = ctx->d_lk_pts; a.aux = ctx->d_lk_init;
-    a.out = ctx->d_lk_out; a.status = ctx->d_lk_status; a.err = ctx->d_lk_err;
-    a.p = p; a.backward = 0;
-    {
-        Span s(ctx, rows ? KT_LK_TRACK_ROW : KT_LK_TRACK);
-        const int ppl = svo_lk::lk_pixels_per_lane(p.win);
-        if (rows) launch_lk_track_row(a, ppl, st); else launch_lk_track(a, ppl, st);
-        if (p.fb_max > 0.0f) {                               // the same kernel with the image roles swapped, from the results back
-            LkTrackArgs b = a;
-            b.pts = ctx->d_lk_out; b.aux = ctx->d_lk_pts; b.out = nullptr; b.err = nullptr; b.backward = 1;
-            if (rows) launch_lk_track_row(b, ppl, st); else launch_lk_track(b, ppl, st);
-        }
-    }
-    HIPCHECK(hipGetLastError());
-    std::vector<float> h_out(2 * NP), h_err(NP);
-    std::vector<uint8_t> h_status(NP);
-    if (NP) {
-        HIPCHECK(hipMemcpyAsync(h_out.data(), ctx->d_lk_out, sizeof(float) * 2 * NP, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(h_status.data(), ctx->d_lk_status, NP, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(h_err.data(), ctx->d_lk_err, sizeof(float) * NP, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHECK(hipStreamSynchronize(st));
-    ctx->lk_jobs = recs;
-    for (int j = 0; j < n_jobs; j++) {
-        if (jobs[j].n <= 0) continue;
-        const size_t o = (size_t)plan.pt0[(size_t)j], n = (size_t)jobs[j].n;
-        memcpy(jobs[j].next_pts, h_out.data() + 2 * o, sizeof(float) * 2 * n);
-        memcpy(jobs[j].status, h_status.data() + o, n);
-        if (jobs[j].err) memcpy(jobs[j].err, h_err.data() + o, sizeof(float) * n);
-    }
-    return SVO_OK;
-}
-
-extern "C" int svo_lk_track(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
-{
-    return lk_track_call(ctx, jobs, n_jobs, params, flags, false);
-}
-
-extern "C" int svo_lk_track_rows(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* params, uint32_t flags)
-{
-    return lk_track_call(ctx, jobs, n_jobs, params, flags, true);
-}
-
-extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx || which < 0 || which > 1 || job < 0 || level < 0) return SVO_ERR_ARG;
-    if ((size_t)job >= ctx->lk_jobs.size() || level >= ctx->lk_jobs[(size_t)job].nl) return 0;
-    int rc = svo_wait(ctx); if (rc) return rc;
-    const LkJobDev& r = ctx->lk_jobs[(size_t)job];
-    if (w) *w = r.w[level]; if (h) *h = r.h[level];
-    if (!out) return r.w[level] * r.h[level];
-    if (cap < r.w[level] * r.h[level]) return SVO_ERR_CAPACITY;
-    HIPCHECK(hipMemcpy2D(out, (size_t)r.w[level], r.img[which][level], (size_t)r.pitch[which][level], (size_t)r.w[level], (size_t)r.h[level], hipMemcpyDeviceToHost));
-    return r.w[level] * r.h[level];
-}
-
-// ---- the resident KLT front end (svo_hip.h; the decisions: klt_call.hpp, the kernels: k_klt.hip and k_lk.hip) ----------------------
-static void klt_free(svo_ctx* ctx)
-{
-    svo_ctx::Klt& k = ctx->klt;
-    for (void* p : { (void*)k.dev.pts[0], (void*)k.dev.pts[1], (void*)k.dev.meta[0], (void*)k.dev.meta[1], (void*)k.dev.lane, (void*)k.dev.out, (void*)k.dev.status,
-                     (void*)k.dev.err, (void*)k.dev.appended, (void*)k.d_pyr, (void*)k.d_pyr_jobs, (void*)k.d_trk_jobs, (void*)k.d_stage,
-                     (void*)k.d_tmap, (void*)k.d_tgjobs, (void*)k.d_tkeys, (void*)k.d_titems, (void*)k.d_tstate, (void*)k.d_tginfo, (void*)k.d_tinfo, (void*)k.d_tcorners,
-                     (void*)k.d_tinit, (void*)k.d_tout, (void*)k.d_tresp, (void*)k.d_terr, (void*)k.d_tstatus, (void*)k.d_tlk_jobs,
-                     (void*)k.d_guess, (void*)k.d_gused, (void*)k.d_row_jobs, (void*)k.d_row_guess }) if (p) (void)hipFree(p);
-    memset(&k, 0, sizeof(k));
-}
-static svo_klt::Caps klt_caps(const svo_ctx* ctx) { return { ctx->cfg.n_lanes, ctx->dc.max_kps, ctx->cfg.max_w, ctx->cfg.max_h }; }
-static svo_klt::State klt_state(svo_ctx* ctx)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    return { ctx->klt.enabled, ctx->params_set, ctx->capturing || cs != hipStreamCaptureStatusNone, ctx->frame_parallel };
-}
-static LaneMask klt_all_lanes(const svo_ctx* ctx)
-{
-    LaneMask a, i; std::string why;
-    parse_lane_mask(nullptr, false, ctx->cfg.n_lanes, a, i, why);
-    return a;
-}
-
-// svo_fpstream_create tells its member contexts what they are (svo_batch.cpp; not part of the public interface)
-extern "C" void svo_internal_mark_frame_parallel(svo_ctx* ctx) { if (ctx) ctx->frame_parallel = true; }
-
-extern "C" int svo_klt_enable(svo_ctx* ctx, const svo_klt_params* params)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    const svo_klt::Caps caps = klt_caps(ctx);
-    const svo_klt_params p = svo_klt::klt_resolve_params(params, caps.max_kps);
-    bool empty = true;
-    if (k.enabled && memcmp(&p, &k.p, sizeof(p)) != 0) {                // other parameters: only while no lane holds a track
-        { const int rc = svo_wait(ctx); if (rc) return rc; }
-        std::vector<KltLaneDev> lanes((size_t)caps.n_lanes);
-        HIPCHECK(hipMemcpy(lanes.data(), k.dev.lane, sizeof(KltLaneDev) * lanes.size(), hipMemcpyDeviceToHost));
-        for (const KltLaneDev& l : lanes) if (l.n > 0) empty = false;
-    }
-    bool realloc = false;
-    { std::string why; const int rc = svo_klt::check_klt_enable(p, caps, k.enabled, k.p, empty, ctx->frame_parallel, realloc, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (!realloc) return SVO_OK;
-    const svo_klt::Plan plan = svo_klt::plan_klt(p, caps);
-    if (plan.select_lds_bytes > 60 * 1024) {
-        char msg[160]; snprintf(msg, sizeof(msg), "max_h = %d: the selection keeps three row tables of max_h + 1 words in 60 KB of LDS", caps.max_h);
-        ctx->last_error = msg; return SVO_ERR_UNSUPPORTED;
-    }
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    const int ransac = k.ransac;                            // (the mode outlives the buffers)
-    klt_free(ctx);
-    k.ransac = ransac;
-    k.p = p; k.plan = plan;
-    k.dev.n_lanes = caps.n_lanes; k.dev.cap = p.cap;
-    const size_t NS = (size_t)plan.n_slots;
-    for (int hf = 0; hf < 2; hf++) { HIPCHECK(lk_realloc(&k.dev.pts[hf], NS)); HIPCHECK(lk_realloc(&k.dev.meta[hf], (size_t)plan.meta_ints)); }
-    HIPCHECK(lk_realloc(&k.dev.lane, (size_t)caps.n_lanes)); HIPCHECK(lk_realloc(&k.dev.appended, (size_t)1));
-    HIPCHECK(lk_realloc(&k.dev.out, NS)); HIPCHECK(lk_realloc(&k.dev.status, NS)); HIPCHECK(lk_realloc(&k.dev.err, NS));
-    HIPCHECK(lk_realloc(&k.d_pyr, (size_t)plan.pyr_bytes));
-    HIPCHECK(lk_realloc(&k.d_pyr_jobs, (size_t)plan.n_pyr_jobs)); HIPCHECK(lk_realloc(&k.d_trk_jobs, (size_t)plan.n_trk_jobs));
-    HIPCHECK(lk_realloc(&k.d_stage, 2 * (size_t)p.cap));
-    HIPCHECK(hipMemsetAsync(k.dev.status, 0, NS, ctx->stream));
-    HIPCHECK(hipMemsetAsync(k.dev.out, 0, sizeof(float2) * NS, ctx->stream));
-    const LaneMask all = klt_all_lanes(ctx);
-    note_stream(ctx);
-    launch_klt_clear(ctx->dc, k.dev, 0, all, ctx->stream);
-    launch_klt_clear(ctx->dc, k.dev, 1, all, ctx->stream);
-    mark_stream(ctx);
-    HIPCHECK(hipGetLastError());
-    k.enabled = true;
-    return SVO_OK;
-}
-
-extern "C" int svo_klt_reset(svo_ctx* ctx, const uint64_t lanes[2])
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_klt_ready(klt_state(ctx), "svo_klt_reset", why); if (rc) { ctx->last_error = why; return rc; } }
-    LaneMask active, idle; std::string why;
-    if (!parse_lane_mask(lanes, false, ctx->cfg.n_lanes, active, idle, why)) { ctx->last_error = why; return SVO_ERR_ARG; }
-    note_stream(ctx);
-    launch_klt_clear(ctx->dc, k.dev, k.half, active, ctx->stream);
-    mark_stream(ctx);
-    for (int wd = 0; wd < 2; wd++) k.has_img.w[wd] &= ~active.w[wd];
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-extern "C" int svo_klt_add_points(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, int n)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_klt_add_points", lane, n, n <= 0 || (left_xy && right_xy), klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    if (n == 0) return 0;
-    const int m = n < k.p.cap ? n : k.p.cap;                             // (what lies beyond cap cannot go in whatever the live count is)
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    HIPCHECK(hipMemcpyAsync(k.d_stage, left_xy, sizeof(float2) * (size_t)m, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(k.d_stage + k.p.cap, right_xy, sizeof(float2) * (size_t)m, hipMemcpyHostToDevice, st));
-    launch_klt_append(k.dev, k.half, lane, k.d_stage, k.d_stage + k.p.cap, m, st);
-    int appended = 0;
-    HIPCHECK(hipMemcpyAsync(&appended, k.dev.appended, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    HIPCHECK(hipGetLastError());
-    return appended;
-}
-
-extern "C" int svo_klt_get_tracks(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, int32_t* ids, int32_t* age, int cap)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_klt_get_tracks", lane, cap, true, klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    KltLaneDev kl;
-    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
-    const int n = kl.n, m = n < cap ? n : cap, C = k.p.cap;
-    if (m <= 0) return n;
-    const float2* pts = k.dev.pts[k.half] + (size_t)lane * 2 * C;
-    const int* meta = k.dev.meta[k.half] + (size_t)lane * KLT_META * C;
-    if (left_xy) HIPCHECK(hipMemcpy(left_xy, pts, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
-    if (right_xy) HIPCHECK(hipMemcpy(right_xy, pts + C, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
-    if (ids) HIPCHECK(hipMemcpy(ids, meta + KLT_ID * C, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
-    if (age) HIPCHECK(hipMemcpy(age, meta + KLT_AGE * C, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
-    return n;
-}
-
-// steps 1 and 4 of a step for the lanes of `active`: the shift (k_begin_frame as a svo_process call without a run bit launches it, with
-// that call's host bookkeeping) and the selection.  fresh: the lanes whose points stand as they are
-static int klt_shift(svo_ctx* ctx, const LaneMask& active, const LaneMask& idle, hipStream_t st)
-{
-    DevCtx& d = ctx->dc;
-    const FrameCall shift = make_frame_call(0, ctx->params, ctx->faster_anms);
-    SadStep step = sad_window_step(ctx->sad, idle, shift);              // (no SAD stage runs: never a bad lane)
-    ctx->sad = std::move(step.next);
-    ctx->frame_active = active; ctx->frame_active_set = true;
-    for (int wd = 0; wd < 2; wd++) ctx->imported.w[wd] &= ~active.w[wd];
-    d.fast_th = ctx->fast_th; d.orb_th = ctx->orb_th; d.det_ahead = 0;
-    { Span s(ctx, KT_BEGIN); launch_begin_frame(d, nullptr, 0, step.drop_prev, st); }
-    return SVO_OK;
-}
-static void klt_select(svo_ctx* ctx, const LaneMask& active, const LaneMask& fresh, hipStream_t st)
-{
-    svo_ctx::Klt& k = ctx->klt; const DevCtx& d = ctx->dc;
-    KltSelectArgs a; memset(&a, 0, sizeof(a));
-    a.t = k.dev; a.half = k.half; a.fresh = fresh;
-    a.max_dy = k.p.max_dy; a.min_disp = k.p.min_disp; a.max_disp = k.p.max_disp; a.kp_size = (float)k.p.lk.win;
-    a.H = std::max(0, std::min(d.oh[0], d.max_h));
-    { Span s(ctx, KT_KLT_SELECT); launch_klt_select(d, a, st); }
-    k.half ^= 1; k.used = true;
-    for (int l = 0; l < d.n_lanes; l++) if (lane_in(active, l)) ctx->sad.cur[(size_t)l] = 0;      // lists without an image behind them: no SAD windows
-}
-// between the selection and stage 5, under svo_klt_set_ransac: the RANSAC on the tracked pairs the selection wrote, for the step's active
-// lanes (DevCtx.idle is the step's); mode 2: the rejected tracks then leave the live half
-static void klt_ransac_gate(svo_ctx* ctx, hipStream_t st)
-{
-    svo_ctx::Klt& k = ctx->klt;
-    if (k.ransac == svo_klt::KLT_RANSAC_OFF) return;
-    enqueue_ransac_tracked(ctx, st);
-    if (k.ransac == svo_klt::KLT_RANSAC_PRUNE) { Span s(ctx, KT_KLT_PRUNE); launch_klt_prune(ctx->dc, k.dev, k.half, st); k.prune_used = true; }
-}
-
-extern "C" int svo_klt_set_ransac(svo_ctx* ctx, int mode)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    { std::string why; const int rc = svo_klt::check_klt_set_ransac(klt_state(ctx), mode, why); if (rc) { ctx->last_error = why; return rc; } }
-    ctx->klt.ransac = mode;
-    return SVO_OK;
-}
-extern "C" int svo_klt_get_ransac(const svo_ctx* ctx) { return ctx ? ctx->klt.ransac : SVO_ERR_ARG; }
-
-// ---- the pose prediction of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernel: k_klt_predict in k_gn.hip) ----
-// the guesses for the table as it stands: the lanes of `tracks` may predict; only_lane >= 0: that lane alone; delta6: the caller's
-// increment and `valid` in place of the lanes' records (svo_debug_klt_predict)
-static void klt_predict(svo_ctx* ctx, const LaneMask& tracks, int only_lane, const double* delta6, int valid, hipStream_t st)
-{
-    svo_ctx::Klt& k = ctx->klt;
-    KltPredictArgs a; memset(&a, 0, sizeof(a));
-    a.t = k.dev; a.half = k.half;
-    a.guess = k.d_guess; a.used = k.d_gused;
-    a.tracks = tracks;
-    a.x_max = (float)(k.w - 1); a.y_max = (float)(k.h - 1);
-    a.only_lane = only_lane;
-    if (delta6) { a.forced = 1; a.forced_valid = valid; for (int i = 0; i < 6; i++) a.forced_delta[i] = delta6[i]; }
-    { Span s(ctx, KT_KLT_PREDICT); launch_klt_predict(ctx->dc, a, st); }
-    ctx->klt_predict_used = true;
-}
-
-extern "C" int svo_klt_set_prediction(svo_ctx* ctx, int mode)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    bool alloc = false;
-    { std::string why; const int rc = svo_klt::check_klt_set_prediction(klt_state(ctx), mode, k.d_guess != nullptr, alloc, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (alloc) {
-        const svo_klt::PredictPlan plan = svo_klt::plan_predict(k.p, klt_caps(ctx));
-        hipError_t e = lk_realloc(&k.d_guess, (size_t)plan.n_guess);
-        if (e == hipSuccess) e = lk_realloc(&k.d_gused, (size_t)plan.n_used);
-        if (e != hipSuccess) {                              // the mode stays as it was
-            (void)hipGetLastError();
-            if (k.d_guess) { (void)hipFree(k.d_guess); k.d_guess = nullptr; }
-            if (k.d_gused) { (void)hipFree(k.d_gused); k.d_gused = nullptr; }
-            HIPCHECK(e);
-        }
-    }
-    k.predict = mode;
-    return SVO_OK;
-}
-extern "C" int svo_klt_get_prediction(const svo_ctx* ctx) { return ctx ? ctx->klt.predict : SVO_ERR_ARG; }
-
-// ---- the stereo re-association of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernels: k_lk_track_row, k_klt_row_guess) ----
-extern "C" int svo_klt_set_stereo(svo_ctx* ctx, int mode)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    bool alloc = false;
-    { std::string why; const int rc = svo_klt::check_klt_set_stereo(klt_state(ctx), mode, k.d_row_jobs != nullptr, alloc, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (alloc) {
-        const svo_klt::StereoPlan plan = svo_klt::plan_stereo(k.p, klt_caps(ctx));
-        hipError_t e = lk_realloc(&k.d_row_jobs, (size_t)plan.n_jobs);
-        if (e == hipSuccess) e = lk_realloc(&k.d_row_guess, (size_t)plan.n_guess);
-        if (e != hipSuccess) {                              // the mode stays as it was
-            (void)hipGetLastError();
-            if (k.d_row_jobs) { (void)hipFree(k.d_row_jobs); k.d_row_jobs = nullptr; }
-            if (k.d_row_guess) { (void)hipFree(k.d_row_guess); k.d_row_guess = nullptr; }
-            HIPCHECK(e);
-        }
-    }
-    k.stereo = mode;
-    return SVO_OK;
-}
-extern "C" int svo_klt_get_stereo(const svo_ctx* ctx) { return ctx ? ctx->klt.stereo : SVO_ERR_ARG; }
-
-// svo_klt_predicted and svo_debug_klt_predict: the kernel on one lane, then the lane's count and its guesses back
-static int klt_predict_lane(svo_ctx* ctx, const char* entry, int lane, const double* delta6, bool forced, int valid, float* left_xy, float* right_xy, uint8_t* used, int cap)
-{
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_klt_predict_call(klt_state(ctx), entry, k.predict, lane, cap, !forced || delta6 != nullptr, klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    LaneMask tracks; memset(&tracks, 0, sizeof(tracks));
-    if (lane_in(k.has_img, lane)) tracks.w[lane >> 6] = 1ull << (lane & 63);
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    klt_predict(ctx, tracks, lane, forced ? delta6 : nullptr, valid, st);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));
-    KltLaneDev kl;
-    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
-    const int C = k.p.cap, n = kl.n < C ? kl.n : C, m = n < cap ? n : cap;
-    if (m <= 0) return n;
-    const float2* g = k.d_guess + (size_t)lane * 2 * C;
-    if (left_xy) HIPCHECK(hipMemcpy(left_xy, g, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
-    if (right_xy) HIPCHECK(hipMemcpy(right_xy, g + C, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
-    if (used) HIPCHECK(hipMemcpy(used, k.d_gused + (size_t)lane * C, (size_t)m, hipMemcpyDeviceToHost));
-    return n;
-}
-
-extern "C" int svo_klt_predicted(svo_ctx* ctx, int lane, float* left_xy, float* right_xy, uint8_t* used, int cap)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    return klt_predict_lane(ctx, "svo_klt_predicted", lane, nullptr, false, 0, left_xy, right_xy, used, cap);
-}
-
-extern "C" int svo_debug_klt_predict(svo_ctx* ctx, int lane, const double* delta6, int valid, float* left_xy, float* right_xy, uint8_t* used, int cap)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    return klt_predict_lane(ctx, "svo_debug_klt_predict", lane, delta6, true, valid, left_xy, right_xy, used, cap);
-}
-
-extern "C" int svo_ransac_tracked(svo_ctx* ctx, const uint64_t lanes[2])
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    LaneMask active, idle;
-    { std::string why; const int rc = svo_klt::check_ransac_tracked(ctx->params_set, ctx->geom_ready, klt_state(ctx).capturing, lanes, ctx->cfg.n_lanes, active, idle, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (!lane_any(active)) return SVO_OK;                   // nobody takes part: nothing is enqueued
-    DevCtx& d = ctx->dc;
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    d.idle = idle;
-    IdleGuard idle_guard{ &d };
-    enqueue_ransac_tracked(ctx, st);
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flags, const uint64_t lanes[2])
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    const svo_klt::Caps caps = klt_caps(ctx);
-    LaneMask active, idle; int w = 0, h = 0;
-    { std::string why; const int rc = svo_klt::check_klt_step(frames, flags, lanes, caps, klt_state(ctx), active, idle, w, h, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (!lane_any(active)) return SVO_OK;                   // nobody takes part: nothing is enqueued
-    const FrameCall opt = make_frame_call(SVO_RUN_OPTIMIZE | SVO_FLAG_NO_SHIFT, ctx->params, ctx->faster_anms);
-    { std::string why; const int rc = check_frame_call(opt, ctx->params, active, nullptr, why); if (rc) { ctx->last_error = why; return rc; } }
-    { const int rc = ensure_geometry(ctx, w, h); if (rc) return rc; }
-    DevCtx& d = ctx->dc;
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    d.idle = idle;
-    IdleGuard idle_guard{ &d };
-    // 0. under svo_klt_set_prediction(1): the first guesses of the lanes that will track, AHEAD of the shift -- k_begin_frame starts the
-    //    lanes' records afresh, and the prediction reads them as the last step left them (images of another size track nothing)
-    if (k.predict == svo_klt::KLT_PREDICT_POSE) {
-        LaneMask tracks; memset(&tracks, 0, sizeof(tracks));
-        if (w == k.w && h == k.h) for (int wd = 0; wd < 2; wd++) tracks.w[wd] = active.w[wd] & k.has_img.w[wd];
-        klt_predict(ctx, tracks, -1, nullptr, 0, st);
-    }
-    // 1. the shift
-    { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
-    // 2. the new pair of every active lane into the parity its last pair did not go to; images of another size than the last step's
-    //    cannot be tracked from it
-    if (w != k.w || h != k.h) { memset(&k.has_img, 0, sizeof(k.has_img)); k.w = w; k.h = h; }
-    const svo_lk::Geometry g = svo_klt::klt_geometry(k.p, w, h);
-    const hipMemcpyKind kind = (flags & SVO_FLAG_DEVICE_IMAGES) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    LaneMask fresh, empty = idle;
-    bool any_tracks = false;
-    for (int wd = 0; wd < 2; wd++) { k.parity.w[wd] ^= active.w[wd]; fresh.w[wd] = active.w[wd] & ~k.has_img.w[wd]; empty.w[wd] |= fresh.w[wd]; any_tracks |= (active.w[wd] & k.has_img.w[wd]) != 0; }
-    for (int l = 0; l < d.n_lanes; l++) {
-        if (!lane_in(active, l)) continue;
-        for (int sd = 0; sd < 2; sd++) {
-            const svo_image& im = sd ? frames[l].right : frames[l].left;
-            uint8_t* block = k.d_pyr + ((long long)((lane_in(k.parity, l) ? 1 : 0) * d.n_lanes + l) * 2 + sd) * k.plan.img_stride;
-            HIPCHECK(hipMemcpy2DAsync(block, (size_t)w, im.data, (size_t)im.stride, (size_t)w, (size_t)h, kind, st));
-        }
-    }
-    KltJobArgs ja; memset(&ja, 0, sizeof(ja));
-    const bool rows = k.stereo == svo_klt::KLT_STEREO_ROW;
-    ja.pyr_jobs = k.d_pyr_jobs; ja.trk_jobs = k.d_trk_jobs; ja.row_jobs = rows ? k.d_row_jobs : nullptr; ja.pyr = k.d_pyr; ja.img_stride = k.plan.img_stride;
-    ja.n_lanes = d.n_lanes; ja.cap = k.p.cap; ja.nl = g.nl;
-    for (int l = 0; l < g.nl; l++) { ja.w[l] = g.w[l]; ja.h[l] = g.h[l]; ja.off[l] = g.off[l]; }
-    ja.parity = k.parity; ja.empty = empty; ja.idle = idle;
-    { Span s(ctx, KT_LK_PYRDOWN); launch_klt_jobs(ja, k.predict == svo_klt::KLT_PREDICT_POSE ? 1 : 0, st); for (int l = 1; l < g.nl; l++) launch_lk_pyrdown(k.d_pyr_jobs, d.n_lanes, l, g.w[l], g.h[l], st); }
-    // 3. one tracking launch over every lane's two jobs (and the way back under fb_max); no lane has a last pair: nothing to track
-    if (any_tracks) {
-        LkTrackArgs a;
-        a.jobs = k.d_trk_jobs; a.n_jobs = 2 * d.n_lanes; a.n_pts = 2 * d.n_lanes * k.p.cap;
-        a.pts = k.dev.pts[k.half]; a.aux = k.predict == svo_klt::KLT_PREDICT_POSE ? k.d_guess : nullptr;      // (read for records with has_init)
-        a.out = k.dev.out; a.status = k.dev.status; a.err = k.dev.err;
-        a.p = k.p.lk; a.backward = 0;
-        Span s(ctx, KT_LK_TRACK);
-        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
-        launch_lk_track(a, ppl, st);
-        if (k.p.lk.fb_max > 0.0f) {
-            LkTrackArgs b = a;
-            b.pts = k.dev.out; b.aux = k.dev.pts[k.half]; b.out = nullptr; b.err = nullptr; b.backward = 1;
-            launch_lk_track(b, ppl, st);
-        }
-    }
-    // 3b. under svo_klt_set_stereo(1) the right records of 3 were empty: the right partner of every left result is found in the NEW pair
-    //     along the row (and back under fb_max), from guesses formed on the device.  A lane without a last pair takes part: its left
-    //     points stand (k_klt_row_guess writes them as results with status 1), so the selection has no fresh lane to treat apart
-    if (rows) {
-        KltRowGuessArgs ga; memset(&ga, 0, sizeof(ga));
-        ga.t = k.dev; ga.half = k.half; ga.guess = k.d_row_guess; ga.active = active; ga.fresh = fresh;
-        const int C = k.p.cap;
-        LkTrackArgs a;
-        a.jobs = k.d_row_jobs; a.n_jobs = d.n_lanes; a.n_pts = (2 * d.n_lanes - 1) * C;       // lane l: slots [2 l C, 2 l C + C), results C behind
-        a.pts = k.dev.out; a.aux = k.d_row_guess;
-        a.out = k.dev.out + C; a.status = k.dev.status + C; a.err = k.dev.err + C;
-        a.p = k.p.lk; a.backward = 0;
-        Span s(ctx, KT_LK_TRACK_ROW);
-        launch_klt_row_guess(ga, st);
-        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
-        launch_lk_track_row(a, ppl, st);
-        if (k.p.lk.fb_max > 0.0f) {
-            LkTrackArgs b = a;
-            b.pts = k.dev.out + C; b.aux = k.dev.out; b.out = nullptr; b.err = nullptr; b.backward = 1;
-            launch_lk_track_row(b, ppl, st);
-        }
-        ctx->lk_row_used = true;
-        memset(&fresh, 0, sizeof(fresh));
-    }
-    // 4. the selection
-    klt_select(ctx, active, fresh, st);
-    klt_ransac_gate(ctx, st);
-    for (int wd = 0; wd < 2; wd++) k.has_img.w[wd] |= active.w[wd];
-    // 5. stage 5.  The recipe's stage-5 call starts the lane's record afresh (k_begin_frame), the gate's counters included: a gated
-    //    step that optimises leaves them at zero as well, one that does not leaves them standing
-    if (flags & SVO_RUN_OPTIMIZE) {
-        if (k.ransac != svo_klt::KLT_RANSAC_OFF) { Span s(ctx, KT_RANSAC_FEED); launch_ransac_stats_clear(d, st); }
-        enqueue_optimize(ctx, opt, st);
-    }
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-extern "C" int svo_debug_klt_select(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status_l, const uint8_t* status_r, int n)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_klt_lane_call(klt_state(ctx), "svo_debug_klt_select", lane, n, n <= 0 || (left_xy && right_xy && status_l && status_r), klt_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    if (!ctx->geom_ready) { ctx->last_error = "svo_debug_klt_select: no geometry yet: the row tables need the image size of a step or of put lists"; return SVO_ERR_STATE; }
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    KltLaneDev kl;
-    HIPCHECK(hipMemcpy(&kl, k.dev.lane + lane, sizeof(kl), hipMemcpyDeviceToHost));
-    if (n != kl.n) { char msg[128]; snprintf(msg, sizeof(msg), "svo_debug_klt_select: n = %d, the lane's table holds %d tracks", n, kl.n); ctx->last_error = msg; return SVO_ERR_ARG; }
-    const uint64_t words[2] = { lane < 64 ? 1ull << lane : 0ull, lane >= 64 ? 1ull << (lane - 64) : 0ull };
-    LaneMask active, idle, fresh; std::string why;
-    parse_lane_mask(words, true, ctx->cfg.n_lanes, active, idle, why);
-    memset(&fresh, 0, sizeof(fresh));
-    DevCtx& d = ctx->dc;
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    const size_t C = (size_t)k.p.cap, o = (size_t)(2 * lane) * C;
-    if (n > 0) {
-        HIPCHECK(hipMemcpyAsync(k.dev.out + o, left_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(k.dev.out + o + C, right_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(k.dev.status + o, status_l, (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(k.dev.status + o + C, status_r, (size_t)n, hipMemcpyHostToDevice, st));
-    }
-    d.idle = idle;
-    IdleGuard idle_guard{ &d };
-    { const int rc = klt_shift(ctx, active, idle, st); if (rc) return rc; }
-    klt_select(ctx, active, fresh, st);
-    klt_ransac_gate(ctx, st);
-    HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays are free
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-// ---- the resident top-up of the front end (svo_hip.h; the decisions: klt_call.hpp; the kernels: k_klt.hip around k_gftt.hip and k_lk.hip) ----
-static svo_klt::TopupCaps topup_caps(const svo_ctx* ctx)
-{
-    const int cap = ctx->klt.enabled ? ctx->klt.p.cap : std::min(1024, ctx->dc.max_kps);
-    return { cap, ctx->cfg.max_cand };
-}
-static void topup_free(svo_ctx::Klt& k)
-{
-    void** all[] = { (void**)&k.d_tmap, (void**)&k.d_tgjobs, (void**)&k.d_tkeys, (void**)&k.d_titems, (void**)&k.d_tstate, (void**)&k.d_tginfo, (void**)&k.d_tinfo,
-                     (void**)&k.d_tcorners, (void**)&k.d_tinit, (void**)&k.d_tout, (void**)&k.d_tresp, (void**)&k.d_terr, (void**)&k.d_tstatus, (void**)&k.d_tlk_jobs };
-    for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    k.topup_enabled = false;
-}
-
-extern "C" void svo_klt_topup_default_params(const svo_ctx* ctx, svo_klt_topup_params* p)
-{
-    if (!p) return;
-    *p = svo_klt::topup_default_params(ctx ? topup_caps(ctx).cap : 1024);
-}
-
-extern "C" int svo_klt_topup_enable(svo_ctx* ctx, const svo_klt_topup_params* params)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    const svo_klt::Caps caps = klt_caps(ctx);
-    const svo_klt::TopupCaps tc = topup_caps(ctx);
-    const svo_klt_topup_params p = params ? *params : svo_klt::topup_default_params(tc.cap);
-    bool empty = true;
-    if (k.enabled && k.topup_enabled && k.topup_used && memcmp(&p, &k.tp, sizeof(p)) != 0) {      // other parameters after a top-up: only while no lane holds a track
-        { const int rc = svo_wait(ctx); if (rc) return rc; }
-        std::vector<KltLaneDev> lanes((size_t)caps.n_lanes);
-        HIPCHECK(hipMemcpy(lanes.data(), k.dev.lane, sizeof(KltLaneDev) * lanes.size(), hipMemcpyDeviceToHost));
-        for (const KltLaneDev& l : lanes) if (l.n > 0) empty = false;
-    }
-    bool realloc = false, adopt = false;
-    { std::string why; const int rc = svo_klt::check_topup_enable(p, caps, tc, klt_state(ctx), k.topup_enabled, k.tp, k.topup_used, empty, realloc, adopt, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (adopt) { k.tp = p; return SVO_OK; }
-    if (!realloc) return SVO_OK;
-    const svo_klt::TopupPlan plan = svo_klt::plan_topup(k.p, caps, tc);
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    // the response maps are the large buffer (4 bytes per pixel of n_lanes images of max_w x max_h): failing to get them is a capacity refusal
-    if (lk_realloc(&k.d_tmap, (size_t)plan.map_floats) != hipSuccess) {
-        (void)hipGetLastError(); k.d_tmap = nullptr;
-        char msg[200]; snprintf(msg, sizeof(msg), "%d lanes of %d x %d need a response-map buffer of %lld bytes, which the device could not provide", caps.n_lanes, caps.max_w, caps.max_h, plan.map_floats * 4ll);
-        ctx->last_error = msg; return SVO_ERR_CAPACITY;
-    }
-    const size_t NP = (size_t)plan.n_pts, NJ = (size_t)plan.n_jobs;
-    hipError_t e = hipSuccess;
-    auto grow = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    grow(lk_realloc(&k.d_tgjobs, NJ)); grow(lk_realloc(&k.d_tginfo, 4 * NJ)); grow(lk_realloc(&k.d_tinfo, 4 * NJ)); grow(lk_realloc(&k.d_tlk_jobs, NJ));
-    grow(lk_realloc(&k.d_tkeys, (size_t)plan.n_keys)); grow(lk_realloc(&k.d_titems, (size_t)plan.n_items)); grow(lk_realloc(&k.d_tstate, (size_t)plan.n_state));
-    grow(lk_realloc(&k.d_tcorners, NP)); grow(lk_realloc(&k.d_tinit, NP)); grow(lk_realloc(&k.d_tout, NP));
-    grow(lk_realloc(&k.d_tresp, NP)); grow(lk_realloc(&k.d_terr, NP)); grow(lk_realloc(&k.d_tstatus, NP));
-    if (e != hipSuccess) { (void)hipGetLastError(); topup_free(k); HIPCHECK(e); }
-    // before the first call every lane's record says "not in the mask"
-    std::vector<int> none(4 * NJ, 0);
-    for (size_t l = 0; l < NJ; l++) none[4 * l + 3] = KLT_TOPUP_NOT_ASKED;
-    HIPCHECK(hipMemcpy(k.d_tinfo, none.data(), sizeof(int) * none.size(), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemset(k.d_tginfo, 0, sizeof(int) * 4 * NJ));
-    k.tp = p; k.tplan = plan; k.topup_enabled = true;
-    return SVO_OK;
-}
-
-// the arguments of the three kernels for the front end's state as it is
-static KltTopupArgs topup_args(svo_ctx* ctx, const LaneMask& lanes)
-{
-    svo_ctx::Klt& k = ctx->klt;
-    KltTopupArgs a; memset(&a, 0, sizeof(a));
-    a.t = k.dev; a.half = k.half;
-    a.gjobs = k.d_tgjobs; a.ginfo = k.d_tginfo; a.tinfo = k.d_tinfo;
-    a.map = k.d_tmap; a.map_stride = k.tplan.map_stride;
-    a.lk_jobs = k.d_tlk_jobs; a.pyr = k.d_pyr; a.img_stride = k.plan.img_stride;
-    a.cell = 1;
-    if (k.w > 0 && k.h > 0) {
-        const svo_lk::Geometry g = svo_klt::klt_geometry(k.p, k.w, k.h);
-        a.nl = g.nl;
-        for (int l = 0; l < g.nl; l++) { a.w[l] = g.w[l]; a.h[l] = g.h[l]; a.off[l] = g.off[l]; }
-        const svo_gftt::Cells cells = svo_gftt::gftt_cells(k.w, k.h, k.tp.gftt.min_distance);
-        a.cell = cells.cell; a.gw = cells.gw; a.gh = cells.gh;
-    }
-    a.below = k.tp.below; a.target = k.tp.target; a.init_disp = k.tp.init_disp;
-    a.max_dy = k.p.max_dy; a.min_disp = k.p.min_disp; a.max_disp = k.p.max_disp;
-    a.lanes = lanes; a.has_img = k.has_img; a.parity = k.parity;
-    a.corners = k.d_tcorners; a.init = k.d_tinit; a.out = k.d_tout; a.status = k.d_tstatus;
-    return a;
-}
-
-extern "C" int svo_klt_topup(svo_ctx* ctx, const uint64_t lanes[2])
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    LaneMask active;
-    { std::string why; const int rc = svo_klt::check_topup_call(klt_state(ctx), k.topup_enabled, lanes, klt_caps(ctx), active, why); if (rc) { ctx->last_error = why; return rc; } }
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    const KltTopupArgs a = topup_args(ctx, active);
-    const int n_lanes = k.dev.n_lanes;
-    bool any = false;                                        // a lane of the mask has a last pair: only then is there an image to look at
-    for (int wd = 0; wd < 2; wd++) any |= (active.w[wd] & k.has_img.w[wd]) != 0;
-    k.topup_used = true;
-    // 1. the detector's records, decided on the device from the live counts
-    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_jobs(a, st); }
-    if (any && a.nl > 0) {
-        // 2 .. 4. the detector as svo_gftt_detect launches it, on the top-up's own buffers; the seeds are the table's left points
-        GfttArgs g;
-        g.jobs = k.d_tgjobs; g.n_jobs = n_lanes; g.cand_cap = k.tplan.cand_cap; g.key_stride = k.tplan.key_stride; g.seed_cap = k.p.cap; g.items_stride = (int)k.tplan.items_stride;
-        g.keys = k.d_tkeys; g.items = k.d_titems; g.state = k.d_tstate;
-        g.seeds = k.dev.pts[k.half]; g.pts = k.d_tcorners; g.resp = k.d_tresp; g.info = k.d_tginfo; g.p = k.tp.gftt;
-        { Span s(ctx, KT_GFTT_RESPONSE); launch_gftt_response(g, k.w, k.h, st); }
-        { Span s(ctx, KT_GFTT_CANDIDATES); launch_gftt_candidates(g, k.w, k.h, st); }
-        { Span s(ctx, KT_GFTT_SELECT); launch_gftt_select(g, st); }
-        // 5. the tracking records and the first guesses
-        { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_prepare(a, st); }
-        // 6. left -> right over every lane (and the way back under fb_max), as svo_lk_track launches it
-        LkTrackArgs t;
-        t.jobs = k.d_tlk_jobs; t.n_jobs = n_lanes; t.n_pts = n_lanes * k.p.cap;
-        t.pts = k.d_tcorners; t.aux = k.d_tinit;
-        t.out = k.d_tout; t.status = k.d_tstatus; t.err = k.d_terr;
-        t.p = k.p.lk; t.backward = 0;
-        Span s(ctx, KT_LK_TRACK);
-        const int ppl = svo_lk::lk_pixels_per_lane(k.p.lk.win);
-        launch_lk_track(t, ppl, st);
-        if (k.p.lk.fb_max > 0.0f) {
-            LkTrackArgs b = t;
-            b.pts = k.d_tout; b.aux = k.d_tcorners; b.out = nullptr; b.err = nullptr; b.backward = 1;
-            launch_lk_track(b, ppl, st);
-        }
-    }
-    // 7. the gate and the append
-    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_append(a, -1, st); }
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-extern "C" int svo_klt_topup_info(svo_ctx* ctx, int lane, int32_t info[4])
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_topup_lane_call(klt_state(ctx), k.topup_enabled, "svo_klt_topup_info", lane, 0, info != nullptr, klt_caps(ctx), topup_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    { const int rc = svo_wait(ctx); if (rc) return rc; }
-    HIPCHECK(hipMemcpy(info, k.d_tinfo + 4 * lane, sizeof(int32_t) * 4, hipMemcpyDeviceToHost));
-    return SVO_OK;
-}
-
-extern "C" int svo_debug_klt_topup_append(svo_ctx* ctx, int lane, const float* left_xy, const float* right_xy, const uint8_t* status, int n)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_ctx::Klt& k = ctx->klt;
-    { std::string why; const int rc = svo_klt::check_topup_lane_call(klt_state(ctx), k.topup_enabled, "svo_debug_klt_topup_append", lane, n, n <= 0 || (left_xy && right_xy && status), klt_caps(ctx), topup_caps(ctx), why); if (rc) { ctx->last_error = why; return rc; } }
-    const hipStream_t st = ctx->stream;
-    note_stream(ctx);
-    MarkGuard mark_guard{ ctx };
-    LaneMask none; memset(&none, 0, sizeof(none));
-    const KltTopupArgs a = topup_args(ctx, none);
-    const size_t o = (size_t)lane * (size_t)k.p.cap;
-    if (n > 0) {
-        HIPCHECK(hipMemcpyAsync(k.d_tcorners + o, left_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(k.d_tout + o, right_xy, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(k.d_tstatus + o, status, (size_t)n, hipMemcpyHostToDevice, st));
-    }
-    // the records the kernel reads: n corners, no overflow, the lane takes part
-    const int ginfo[4] = { n, n, 0, 0 }, tinfo[4] = { 0, 0, 0, KLT_TOPUP_OK };
-    HIPCHECK(hipMemcpyAsync(k.d_tginfo + 4 * lane, ginfo, sizeof(ginfo), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(k.d_tinfo + 4 * lane, tinfo, sizeof(tinfo), hipMemcpyHostToDevice, st));
-    k.topup_used = true;
-    { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_append(a, lane, st); }
-    HIPCHECK(hipStreamSynchronize(st));                      // the caller's arrays (and the two records above) are free
-    HIPCHECK(hipGetLastError());
-    return SVO_OK;
-}
-
-// ---- Shi-Tomasi corner detection on caller images (svo_hip.h; the decisions: gftt_call.hpp, the kernels: k_gftt.hip) --------------
-extern "C" int svo_gftt_detect(svo_ctx* ctx, const svo_gftt_job* jobs, int n_jobs, const svo_gftt_params* params, uint32_t flags)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx) return SVO_ERR_ARG;
-    ctx->last_error.clear();
-    svo_gftt_params p;
-    if (params) p = *params; else svo_gftt_default_params(&p);
-    const svo_gftt::Caps caps{ ctx->dc.max_kps, 4 * ctx->cfg.n_lanes * ctx->dc.oct_cap, ctx->cfg.max_w, ctx->cfg.max_h, ctx->cfg.max_cand };
-    { std::string why; const int rc = svo_gftt::check_gftt_call(jobs, n_jobs, p, flags, caps, why); if (rc) { ctx->last_error = why; return rc; } }
-    if (n_jobs == 0) return SVO_OK;
-    const bool dev = (flags & SVO_FLAG_DEVICE_IMAGES) != 0;
-    const svo_gftt::Plan plan = svo_gftt::plan_gftt_call(jobs, n_jobs, p, dev);
-    const int cand_cap = svo_gftt::gftt_cand_cap(ctx->cfg.max_cand), key_stride = svo_gftt::gftt_key_stride(cand_cap), seed_cap = ctx->dc.max_kps;
-    const long long items_stride = (5ll * cand_cap + 2ll * seed_cap + 3) / 4 * 4;
-    // the buffers: a failed growth leaves the capacity at 0, so that the next call allocates afresh.  The map buffer is the large one
-    // (4 bytes per pixel of the call): failing to get it is a capacity refusal, before anything is enqueued
-    ctx->gftt_jobs.clear();
-    if ((size_t)plan.map_floats > ctx->gftt_map_cap) {
-        ctx->gftt_map_cap = 0;
-        if (lk_realloc(&ctx->d_gftt_map, (size_t)plan.map_floats) != hipSuccess) {
-            (void)hipGetLastError(); ctx->d_gftt_map = nullptr;
-            char msg[200]; snprintf(msg, sizeof(msg), "%d jobs need a response-map buffer of %lld bytes, which the device could not provide", n_jobs, plan.map_floats * 4ll);
-            ctx->last_error = msg; return SVO_ERR_CAPACITY;
-        }
-        ctx->gftt_map_cap = (size_t)plan.map_floats;
-    }
-    if ((size_t)plan.img_bytes > ctx->gftt_img_cap) { ctx->gftt_img_cap = 0; HIPCHECK(lk_realloc(&ctx->d_gftt_img, (size_t)plan.img_bytes)); ctx->gftt_img_cap = (size_t)plan.img_bytes; }
-    if (n_jobs > ctx->gftt_jobs_cap) {
-        ctx->gftt_jobs_cap = 0;
-        HIPCHECK(lk_realloc(&ctx->d_gftt_jobs, (size_t)n_jobs)); HIPCHECK(lk_realloc(&ctx->d_gftt_info, 4 * (size_t)n_jobs));
-        HIPCHECK(lk_realloc(&ctx->d_gftt_keys, (size_t)n_jobs * (size_t)key_stride)); HIPCHECK(lk_realloc(&ctx->d_gftt_state, (size_t)n_jobs * (size_t)cand_cap));
-        HIPCHECK(lk_realloc(&ctx->d_gftt_items, (size_t)n_jobs * (size_t)items_stride));
-        ctx->gftt_jobs_cap = n_jobs;
-    }
-    if (plan.n_seeds > ctx->gftt_seeds_cap) { ctx->gftt_seeds_cap = 0; HIPCHECK(lk_realloc(&ctx->d_gftt_seeds, (size_t)plan.n_seeds)); ctx->gftt_seeds_cap = plan.n_seeds; }
-    if (plan.n_pts > ctx->gftt_pts_cap) {
-        ctx->gftt_pts_cap = 0;
-        HIPCHECK(lk_realloc(&ctx->d_gftt_pts, (size_t)plan.n_pts)); HIPCHECK(lk_realloc(&ctx->d_gftt_resp, (size_t)plan.n_pts));
-        ctx->gftt_pts_cap = plan.n_pts;
-    }
-    ctx->gftt_used = true;
-    const hipStream_t st = ctx->stream;
-    // the job records; host images are copied tightly packed, device images are read where they are
-    std::vector<GfttJobDev> recs((size_t)n_jobs);
-    std::vector<float> h_seeds(2 * (size_t)plan.n_seeds);
-    for (int j = 0; j < n_jobs; j++) {
-        const svo_image& im = jobs[j].img;
-        GfttJobDev& r = recs[(size_t)j];
-        memset(&r, 0, sizeof(r));
-        r.w = im.w; r.h = im.h; r.map = ctx->d_gftt_map + plan.map_off[(size_t)j];
-        r.seed0 = plan.seed0[(size_t)j]; r.n_seeds = jobs[j].n_seeds; r.pts0 = plan.pts0[(size_t)j]; r.cap = jobs[j].cap;
-        r.cell = plan.cells[(size_t)j].cell; r.gw = plan.cells[(size_t)j].gw; r.gh = plan.cells[(size_t)j].gh;
-        if (dev) { r.img = im.data; r.pitch = (int)im.stride; }
-        else {
-            uint8_t* copy = ctx->d_gftt_img + plan.img_off[(size_t)j];
-            r.img = copy; r.pitch = im.w;
-            HIPCHECK(hipMemcpy2DAsync(copy, (size_t)im.w, im.data, (size_t)im.stride, (size_t)im.w, (size_t)im.h, hipMemcpyHostToDevice, st));
-        }
-        if (jobs[j].n_seeds > 0) memcpy(h_seeds.data() + 2 * (size_t)r.seed0, jobs[j].seeds, sizeof(float) * 2 * (size_t)jobs[j].n_seeds);
-    }
-    HIPCHECK(hipMemcpyAsync(ctx->d_gftt_jobs, recs.data(), sizeof(GfttJobDev) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
-    if (plan.n_seeds) HIPCHECK(hipMemcpyAsync(ctx->d_gftt_seeds, h_seeds.data(), sizeof(float) * 2 * (size_t)plan.n_seeds, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemsetAsync(ctx->d_gftt_info, 0, sizeof(int) * 4 * (size_t)n_jobs, st));
-    GfttArgs a;
-    a.jobs = ctx->d_gftt_jobs; a.n_jobs = n_jobs; a.cand_cap = cand_cap; a.key_stride = key_stride; a.seed_cap = seed_cap; a.items_stride = (int)items_stride;
-    a.keys = ctx->d_gftt_keys; a.items = ctx->d_gftt_items; a.state = ctx->d_gftt_state;
-    a.seeds = ctx->d_gftt_seeds; a.pts = ctx->d_gftt_pts; a.resp = ctx->d_gftt_resp; a.info = ctx->d_gftt_info; a.p = p;
-    { Span s(ctx, KT_GFTT_RESPONSE); launch_gftt_response(a, plan.max_w, plan.max_h, st); }
-    { Span s(ctx, KT_GFTT_CANDIDATES); launch_gftt_candidates(a, plan.max_w, plan.max_h, st); }
-    { Span s(ctx, KT_GFTT_SELECT); launch_gftt_select(a, st); }
-    HIPCHECK(hipGetLastError());
-    std::vector<int> h_info(4 * (size_t)n_jobs);
-    std::vector<float> h_pts(2 * (size_t)plan.n_pts), h_resp((size_t)plan.n_pts);
-    HIPCHECK(hipMemcpyAsync(h_info.data(), ctx->d_gftt_info, sizeof(int) * 4 * (size_t)n_jobs, hipMemcpyDeviceToHost, st));
-    if (plan.n_pts) {
-        HIPCHECK(hipMemcpyAsync(h_pts.data(), ctx->d_gftt_pts, sizeof(float) * 2 * (size_t)plan.n_pts, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(h_resp.data(), ctx->d_gftt_resp, sizeof(float) * (size_t)plan.n_pts, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHECK(hipStreamSynchronize(st));
-    ctx->gftt_jobs = recs;
-    for (int j = 0; j < n_jobs; j++) {
-        const int* inf = h_info.data() + 4 * (size_t)j;
-        const size_t o = (size_t)plan.pts0[(size_t)j], n = (size_t)(inf[0] < jobs[j].cap ? inf[0] : jobs[j].cap);
-        if (n) {
-            memcpy(jobs[j].pts, h_pts.data() + 2 * o, sizeof(float) * 2 * n);
-            if (jobs[j].response) memcpy(jobs[j].response, h_resp.data() + o, sizeof(float) * n);
-        }
-        jobs[j].info[0] = (int32_t)n; jobs[j].info[1] = inf[1]; jobs[j].info[2] = inf[2];
-    }
-    return SVO_OK;
-}
-
-extern "C" int svo_debug_gftt_get_response(svo_ctx* ctx, int job, float* out, int cap, int* w, int* h)
-{
-    if (ctx) use_device(ctx);
-    if (!ctx || job < 0) return SVO_ERR_ARG;
-    if ((size_t)job >= ctx->gftt_jobs.size()) return 0;
-    int rc = svo_wait(ctx); if (rc) return rc;
-    const GfttJobDev& r = ctx->gftt_jobs[(size_t)job];
-    if (w) *w = r.w; if (h) *h = r.h;
-    if (!out) return r.w * r.h;
-    if (cap < r.w * r.h) return SVO_ERR_CAPACITY;
-    HIPCHECK(hipMemcpy(out, r.map, sizeof(float) * (size_t)r.w * (size_t)r.h, hipMemcpyDeviceToHost));
-    return r.w * r.h;
 }
 
 // ---- probes ------------------------------------------------------------------------------------------------

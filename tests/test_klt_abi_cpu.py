@@ -51,11 +51,3 @@ def test_null_context_is_an_argument_error():
     assert L.svo_klt_step(None, None, 0, None) == SVO_ERR_ARG
     assert L.svo_klt_get_tracks(None, 0, None, None, None, None, 0) == SVO_ERR_ARG
     assert L.svo_debug_klt_select(None, 0, None, None, None, None, 0) == SVO_ERR_ARG
-
-
-def test_kernel_time_name_lives_behind_the_table():
-    """"klt_select" is listed behind the LK names without joining kt_names, whose tail other readers rely on; 64 names still suffice"""
-    src = open(os.path.join(ROOT, "stereo_vo_amd", "csrc", "svo_api.hip")).read()
-    names = re.findall(r'"([a-z0-9_]+)"', re.search(r"kt_names\[KT_COUNT\] = \{(.*?)\};", src, re.S).group(1))
-    assert "klt_select" not in names and len(names) + 1 <= 64
-    assert 'return i < KT_COUNT ? kt_names[i] : "klt_select"' in src

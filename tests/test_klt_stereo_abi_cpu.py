@@ -66,8 +66,10 @@ def test_the_step_forms_its_guesses_on_the_device():
     src = read("stereo_vo_amd", "csrc", "k_klt.hip")
     body = re.search(r"__global__[^\n]*\bk_klt_row_guess\b.*?\n}\n", src, re.S).group(0)
     assert "nl.x - (pl.x - pr.x)" in body                                 # the rule as written
-    api = read("stereo_vo_amd", "csrc", "svo_api.hip")
-    step = api[api.index('extern "C" int svo_klt_step('):api.index('extern "C" int svo_debug_klt_select(')]
+    klt, lk = read("stereo_vo_amd", "csrc", "svo_klt.hip"), read("stereo_vo_amd", "csrc", "svo_lk.hip")
+    step = klt[klt.index('extern "C" int svo_klt_step('):klt.index('extern "C" int svo_debug_klt_select(')]
+    assert "enqueue_lk_track(" in step                                    # the tracking launches are the helper's: it belongs to the step
+    step += lk[lk.index("void enqueue_lk_track("):lk.index("// svo_lk_track and svo_lk_track_rows")]
     assert "launch_klt_row_guess(" in step and "launch_lk_track_row(" in step
     assert "hipStreamSynchronize" not in step and "hipMalloc" not in step and "lk_realloc" not in step
 

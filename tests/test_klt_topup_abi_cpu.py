@@ -88,13 +88,6 @@ def test_reason_codes_match_the_kernels():
     assert (abi.TOPUP_OK, abi.TOPUP_OVERFLOW, abi.TOPUP_ENOUGH, abi.TOPUP_NO_PAIR, abi.TOPUP_NOT_ASKED) == (0, 1, 2, 3, 4)
 
 
-def test_kernel_time_name_lives_behind_klt_select():
-    src = open(os.path.join(ROOT, "stereo_vo_amd", "csrc", "svo_api.hip")).read()
-    names = re.findall(r'"([a-z0-9_]+)"', re.search(r"kt_names\[KT_COUNT\] = \{(.*?)\};", src, re.S).group(1))
-    assert "klt_topup" not in names and len(names) + 2 <= 64
-    assert "KT_KLT_SELECT = KT_COUNT, KT_KLT_TOPUP, KT_ALL" in src
-
-
 def test_the_host_check_is_part_of_hostcheck():
     mk = open(os.path.join(ROOT, "stereo_vo_amd", "csrc", "Makefile")).read()
     assert re.search(r"^hostcheck:.*\$\(TOPUPCHECK\)", mk, re.M) and "TOPUPCHECK = ../../tools/klt_topup_check" in mk

@@ -43,11 +43,3 @@ def test_defaults():
     assert (p.win, p.max_level, p.max_iters) == (21, 3, 30)
     assert p.eps == C.c_float(0.01).value and p.min_eig == C.c_float(1e-4).value and p.fb_max == 0.0
     hip.lib().svo_lk_default_params(None)               # NULL is ignored
-
-
-def test_kernel_time_names_fit_the_python_reader():
-    """Context.kernel_times reads up to 64 names: the C table, with the two LK names appended, must fit"""
-    src = open(os.path.join(ROOT, "stereo_vo_amd", "csrc", "svo_api.hip")).read()
-    names = re.search(r"kt_names\[KT_COUNT\] = \{(.*?)\};", src, re.S).group(1)
-    listed = re.findall(r'"([a-z0-9_]+)"', names)
-    assert listed[-2:] == ["lk_pyrdown", "lk_track"] and len(listed) <= 64 and len(set(listed)) == len(listed)

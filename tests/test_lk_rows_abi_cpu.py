@@ -47,10 +47,3 @@ def test_the_kernel_is_one_of_its_own():
     for np_, back in ((2, "true"), (2, "false"), (7, "true"), (7, "false"), (16, "true"), (16, "false")):
         assert "k_lk_track_row<%d, %s>" % (np_, back) in src
     assert "void launch_lk_track_row(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);" in read("stereo_vo_amd", "csrc", "svo_kernels.h")
-
-
-def test_the_kernel_time_name_is_the_last():
-    src = read("stereo_vo_amd", "csrc", "svo_api.hip")
-    assert re.search(r"KT_KLT_PREDICT, KT_LK_TRACK_ROW, KT_EVERY", src) and '"lk_track_row"' in src
-    names = re.search(r"kt_names\[KT_COUNT\] = \{(.*?)\};", src, re.S).group(1)
-    assert re.findall(r'"([a-z0-9_]+)"', names)[-2:] == ["lk_pyrdown", "lk_track"]        # the table of the always-listed names is as it was
