@@ -631,6 +631,28 @@ int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t*
  *   - under fb_max the way back runs from next to prev along the row of the forward result, and the distance is |back.x - pts.x|.
  * svo_lk_track itself is untouched by it. */
 int svo_lk_track_rows(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const svo_lk_params* p, uint32_t flags);
+/* PHOTOMETRIC COMPENSATION: a mode of the context's TRACKER.  In mode 0 (the default) both trackers minimise sum (J - I)^2 on raw grey
+ * values: a patch has to keep its brightness from prev to next.  In mode 1 every LK launch of the context estimates and removes an
+ * affine brightness change J ~ (1 + a) I + b between template and target -- per window, per level and per iteration, so auto-exposure,
+ * two cameras with gains and offsets of their own and slow vignetting no longer move or lose the points.  a and b are eliminated in
+ * closed form from exact integer window sums; nothing photometric is carried between iterations or levels and nothing new is returned.
+ * tests/lk_photo_ref.py is the definition of mode 1 and the device equals it bit for bit; against tests/lk_ref.py / lk_row_ref.py:
+ *   - the gradient matrix and the right-hand side are the centred window moments with the template's own direction removed
+ *     (A11 = (Cxx - CxI^2 / CII) / n, b1 = (Cdx - CxI CdI / CII) / n, ...; n = win^2, C.. = n S.. - S. S.);
+ *   - a template flat to 1/32 grey level (CII == 0) skips the level like a small eigenvalue does; a template that is an exact ramp cannot
+ *     be told from an offset and is lost by the min_eig test on the reduced matrix;
+ *   - err is the mean |difference - its window mean| in grey levels: the offset is removed from it, the gain is not;
+ *   - the forward-backward pass (fb_max > 0) is compensated too, with the image roles swapped.
+ * The mode applies to svo_lk_track, svo_lk_track_rows, the tracker passes of svo_klt_step (the temporal passes and the row pass of
+ * svo_klt_set_stereo(1)) and the left-to-right pass of svo_klt_topup.  It is read when a call is enqueued.  Every contract of the front
+ * end below that is phrased as "what this recipe of public calls leaves" holds verbatim in mode 1: the recipe's svo_lk_track /
+ * svo_lk_track_rows calls run on a context in the same mode.  Launch counts and kernel-time names ("lk_track", "lk_track_row") are those
+ * of mode 0.
+ * The setter is accepted at any time after svo_create: it needs no svo_set_params and no svo_klt_enable.  The mode belongs to the
+ * tracker, not to the front end: an svo_klt_enable that re-makes the front end's buffers does NOT reset it.  Any mode but 0 and 1 is
+ * SVO_ERR_ARG with a text, and inside a captured graph the setter is SVO_ERR_STATE; a refused call leaves the mode as it was. */
+int svo_lk_set_photometric(svo_ctx* ctx, int mode);   /* 0 raw differences (default), 1 gain and bias removed per window */
+int svo_lk_get_photometric(const svo_ctx* ctx);
 
 /* Shi-Tomasi corner detection on caller images, batched over many images: the capability under the reference's dmKLT
  * (stage2_detect.cpp:444-449: cv::goodFeaturesToTrack with quality 0.01, minimum distance 20, block 3), offered like svo_lk_track as a

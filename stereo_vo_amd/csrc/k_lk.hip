@@ -73,6 +73,24 @@ static __device__ __forceinline__ long long lk_wave_sum(int v)
     const int lo = lk_wave_sum32(v & 0xffff), hi = lk_wave_sum32(v >> 16);
     return (long long)hi * 65536 + (long long)lo;
 }
+// ---- photometric compensation (svo_lk_set_photometric(ctx, 1); the walk: tests/lk_photo_ref.py) --------------------------------------
+// The model J ~ (1 + a) I + b per window; a and b are eliminated from exact integer window sums.  n = win^2 <= 961; over the window
+// |I|, |d| <= 8160 (a byte with 5 fractional bits), |Ix|, |Iy| <= 4080.  The centred moments times n are 64-bit scalar work behind the
+// reductions: n * S and S * S stay below 961 * 961 * 8160^2 < 6.2e13 < 2^53, so the conversion to double is exact as well.
+// n S_ab - S_a S_b
+static __device__ __forceinline__ long long lk_centred(long long n, long long Sab, long long Sa, long long Sb) { return n * Sab - Sa * Sb; }
+// (C - Ca Cb / CII) / n * 2^-20 in the walk's order: the product, the quotient, the difference, / n, * 2^-20 (one IEEE operation each)
+static __device__ __forceinline__ double lk_reduce(long long C, double Ca, long long Cb, double CII, double n)
+{
+    return ((double)C - Ca * (double)Cb / CII) / n * 0x1p-20;
+}
+// a wave-uniform double into scalar registers: the values a level keeps for its iterations cost no vector register there
+static __device__ __forceinline__ double lk_scalar(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 static __device__ __forceinline__ bool lk_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the window whose corner is the float position (px, py): its integer corner and the four 14-bit weights; false when it is not inside
@@ -107,8 +125,9 @@ static __device__ __forceinline__ int lk_sample(const uint8_t* tile, int base, i
     return ((int)tile[base] * w00 + (int)tile[base + 1] * w01 + (int)tile[base + T] * w10 + (int)tile[base + T + 1] * w11 + 256) >> 9;
 }
 
-// NP: the window pixels a lane owns at most; BACK: the forward-backward pass (LkTrackArgs::backward)
-template <int NP, bool BACK>
+// NP: the window pixels a lane owns at most; BACK: the forward-backward pass (LkTrackArgs::backward); PHOTO: gain and bias removed per
+// window (LkTrackArgs::photo).  PHOTO == false is the tracker of tests/lk_ref.py and compiles to what it was before the mode existed.
+template <int NP, bool BACK, bool PHOTO = false>
 __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
 {
     __shared__ uint8_t tiles[4][LK_TILE_BYTES];
@@ -157,11 +176,17 @@ __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
         int ix, iy, w00, w01, w10, w11;
         bool ok = lk_window(pt.x * sc - half, pt.y * sc - half, w, h, win, ix, iy, w00, w01, w10, w11);
         double A11 = 0.0, A12 = 0.0, A22 = 0.0, D = 0.0;
+        // PHOTO: the level's plain sums and the centred moments an iteration needs again (scalars)
+        int SI = 0, Sx = 0, Sy = 0;
+        double CxI = 0.0, CyI = 0.0, CII = 1.0;
         if (ok) {
             // 1. template: I with 5 fractional bits, Ix and Iy from the Scharr derivatives at the four taps
             const int T = win + 3;
             lk_stage(tile, J.img[sp][L], J.pitch[sp][L], ix - 1, iy - 1, T, lane);
             int s11 = 0, s12 = 0, s22 = 0;
+            // PHOTO, per lane over its NP <= 16 pixels: sum I <= 16 * 8160 < 2^17, |sum Ix| <= 16 * 4080 < 2^16 (their wave totals stay
+            // inside 32 bits: one lk_wave_sum32 each); sum I I <= 16 * 8160^2 = 1 065 369 600 < 2^30; |sum Ix I| <= 16 * 4080 * 8160 < 2^29
+            int sI = 0, sII = 0, sx = 0, sy = 0, sxI = 0, syI = 0;
 #pragma unroll
             for (int k = 0; k < NP; k++) {
                 const int q = pk[k] & 0xffff, m = (q << 16) >> 31;                          // m: all ones for a pixel of the window
@@ -187,12 +212,37 @@ __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
             }
             lk_wave_sync();                                        // every lane has read the tile before the iterations overwrite it
             // 2. gradient matrix
+            if constexpr (PHOTO) {
+                const long long n = nwin;
+                const long long Sxx = lk_wave_sum(s11), Sxy = lk_wave_sum(s12), Syy = lk_wave_sum(s22);
+                // the six sums with I in a pass of their own over the packed registers, behind the taps: the template pass is where the
+                // kernel's registers peak.  Ix, Iy are masked already; I is not: an index behind the window sits on pixel 0
+#pragma unroll
+                for (int k = 0; k < NP; k++) {
+                    int q = pk[k], gq = gxy[k];
+                    asm volatile("" : "+v"(q), "+v"(gq));
+                    const int Im = (int)((unsigned)q >> 16) & ((q << 16) >> 31), Ix = (int)(short)(gq & 0xffff), Iy = gq >> 16;
+                    sI += Im; sII += Im * Im; sx += Ix; sy += Iy; sxI += Ix * Im; syI += Iy * Im;
+                }
+                SI = lk_wave_sum32(sI); Sx = lk_wave_sum32(sx); Sy = lk_wave_sum32(sy);
+                const long long SII = lk_wave_sum(sII), SxI = lk_wave_sum(sxI), SyI = lk_wave_sum(syI);
+                const long long cII = lk_centred(n, SII, SI, SI), cxI = lk_centred(n, SxI, Sx, SI), cyI = lk_centred(n, SyI, Sy, SI);
+                if (cII == 0) ok = false;                          // a flat template: nothing is divided by CII
+                else {
+                    CII = lk_scalar((double)cII); CxI = lk_scalar((double)cxI); CyI = lk_scalar((double)cyI);
+                    A11 = lk_scalar(lk_reduce(lk_centred(n, Sxx, Sx, Sx), CxI, cxI, CII, (double)nwin));
+                    A12 = lk_scalar(lk_reduce(lk_centred(n, Sxy, Sx, Sy), CxI, cyI, CII, (double)nwin));
+                    A22 = lk_scalar(lk_reduce(lk_centred(n, Syy, Sy, Sy), CyI, cyI, CII, (double)nwin));
+                }
+            } else {
             A11 = (double)lk_wave_sum(s11) * 0x1p-20;
             A12 = (double)lk_wave_sum(s12) * 0x1p-20;
             A22 = (double)lk_wave_sum(s22) * 0x1p-20;
+            }
             D = A11 * A22 - A12 * A12;
+            if constexpr (PHOTO) D = lk_scalar(D);
             const double min_eig = (A22 + A11 - sqrt((A11 - A22) * (A11 - A22) + 4.0 * A12 * A12)) / (2.0 * win * win);
-            if (min_eig < (double)A.p.min_eig || D < 0x1p-23) ok = false;
+            if (min_eig < (double)A.p.min_eig || D < 0x1p-23) ok = false;        // PHOTO with a flat template: A = 0, D = 0, ok stays false
         }
         if (!ok) {                                                 // the level is skipped; at level 0 the point is lost
             if (L == 0) { lost = true; break; }
@@ -210,15 +260,26 @@ __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
             if (!lk_window(gx - half, gy - half, w, h, win, jx, jy, v00, v01, v10, v11)) { outside = true; break; }
             lk_stage(tile, nimg, npitch, jx, jy, T1, lane);
             int s1 = 0, s2 = 0;
+            // PHOTO, per lane: |sum d| <= 16 * 8160 < 2^17 (one lk_wave_sum32); |sum d I| <= 16 * 8160^2 = 1 065 369 600 < 2^30.  d is
+            // masked for both: the difference at an index behind the window is pixel 0's and counts for nothing
+            int sd = 0, sdI = 0;
 #pragma unroll
             for (int k = 0; k < NP; k++) {
                 int q = pk[k], gq = gxy[k];
                 asm volatile("" : "+v"(q), "+v"(gq));              // unpack here, every iteration: hoisted out of the loop the fields take four registers per pixel
                 const int d = lk_sample(tile, q & 1023, T1, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
                 s1 += d * (int)(short)(gq & 0xffff); s2 += d * (gq >> 16);
+                if constexpr (PHOTO) { const int dm = d & ((q << 16) >> 31); sd += dm; sdI += dm * (int)((unsigned)q >> 16); }
             }
             lk_wave_sync();
-            const double b1 = (double)lk_wave_sum(s1) * 0x1p-20, b2 = (double)lk_wave_sum(s2) * 0x1p-20;
+            double b1, b2;
+            if constexpr (PHOTO) {
+                // four independent reductions: their DPP chains interleave, no readlane waits on another sum's
+                const long long n = nwin, Sd = lk_wave_sum32(sd), SdI = lk_wave_sum(sdI), Sdx = lk_wave_sum(s1), Sdy = lk_wave_sum(s2);
+                const long long cdI = lk_centred(n, SdI, SI, Sd);
+                b1 = lk_reduce(lk_centred(n, Sdx, Sx, Sd), CxI, cdI, CII, (double)nwin);
+                b2 = lk_reduce(lk_centred(n, Sdy, Sy, Sd), CyI, cdI, CII, (double)nwin);
+            } else { b1 = (double)lk_wave_sum(s1) * 0x1p-20; b2 = (double)lk_wave_sum(s2) * 0x1p-20; }
             const float dx = (float)((A12 * b2 - A22 * b1) / D), dy = (float)((A12 * b1 - A11 * b2) / D);
             gx = gx + dx; gy = gy + dy;
             if ((double)dx * (double)dx + (double)dy * (double)dy <= (double)A.p.eps * (double)A.p.eps) break;
@@ -231,12 +292,33 @@ __global__ __launch_bounds__(256) void k_lk_track(const LkTrackArgs A)
             if (lk_window(gx - half, gy - half, w, h, win, jx, jy, v00, v01, v10, v11)) {
                 lk_stage(tile, nimg, npitch, jx, jy, T1, lane);
                 int s = 0;
+                if constexpr (PHOTO) {
+                    // the mean absolute centred difference: Sd first, then sum |n d - Sd| over the window.  |n d|, |Sd| <= 961 * 8160 < 2^23,
+                    // so a term is below 2^24 and a lane's 16 below 2^28
+                    int sd = 0;
+#pragma unroll
+                    for (int k = 0; k < NP; k++) {
+                        const int q = pk[k], d = lk_sample(tile, q & 1023, T1, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
+                        sd += d & ((q << 16) >> 31);
+                    }
+                    const int Sd = lk_wave_sum32(sd);
+#pragma unroll
+                    for (int k = 0; k < NP; k++) {
+                        int q = pk[k];
+                        asm volatile("" : "+v"(q));                // sampled again, not kept from the pass above: NP registers less
+                        const int d = lk_sample(tile, q & 1023, T1, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
+                        const int c = nwin * d - Sd;
+                        s += (c < 0 ? -c : c) & ((q << 16) >> 31);
+                    }
+                    err = (float)((double)lk_wave_sum(s) / (double)(32 * nwin * nwin));
+                } else {
 #pragma unroll
                 for (int k = 0; k < NP; k++) {
                     const int q = pk[k], d = lk_sample(tile, q & 1023, T1, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
                     s += (d < 0 ? -d : d) & ((q << 16) >> 31);
                 }
                 err = (float)((double)lk_wave_sum(s) / (double)(32 * nwin));
+                }
             }
             break;
         }
@@ -274,9 +356,9 @@ static __device__ __forceinline__ void lk_stage_strip(uint8_t* tile, const uint8
     lk_wave_sync();
 }
 
-// NP, BACK: as k_lk_track.  BACK compares along x alone.  A point index behind its job's count leaves at once: the records of a step
+// NP, BACK, PHOTO: as k_lk_track.  BACK compares along x alone.  A point index behind its job's count leaves at once: the records of a step
 // (k_klt_jobs) give lane l the slots [2 l cap, 2 l cap + cap) and leave the cap slots behind them to nobody.
-template <int NP, bool BACK>
+template <int NP, bool BACK, bool PHOTO = false>
 __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
 {
     __shared__ uint8_t tiles[4][LK_TILE_BYTES];
@@ -322,11 +404,14 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
         int ix, iy, w00, w01, w10, w11;
         bool ok = lk_window(pt.x * sc - half, pt.y * sc - half, w, h, win, ix, iy, w00, w01, w10, w11);
         double A11 = 0.0;
+        int SI = 0, Sx = 0;                                        // PHOTO: as in k_lk_track, one unknown
+        double CxI = 0.0, CII = 1.0;
         if (ok) {
             // 1. template: I and Ix
             const int T = win + 3;
             lk_stage(tile, J.img[sp][L], J.pitch[sp][L], ix - 1, iy - 1, T, lane);
             int s11 = 0;
+            int sI = 0, sII = 0, sx = 0, sxI = 0;                  // PHOTO: the bounds of k_lk_track's sums hold
 #pragma unroll
             for (int k = 0; k < NP; k++) {
                 const int q = pk[k] & 0xffff, m = (q << 16) >> 31;
@@ -346,9 +431,18 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
                 const int Ix = ((dx[0][0] * w00 + dx[0][1] * w01 + dx[1][0] * w10 + dx[1][1] * w11 + 8192) >> 14) & m;
                 pk[k] = q | (I << 16); gi[k] = Ix;
                 s11 += Ix * Ix;
+                if constexpr (PHOTO) { const int Im = I & m; sI += Im; sII += Im * Im; sx += Ix; sxI += Ix * Im; }
             }
             lk_wave_sync();                                        // every lane has read the tile before the strip overwrites it
             // 2. the gradient sum
+            if constexpr (PHOTO) {
+                const long long n = nwin;
+                SI = lk_wave_sum32(sI); Sx = lk_wave_sum32(sx);
+                const long long SII = lk_wave_sum(sII), SxI = lk_wave_sum(sxI), Sxx = lk_wave_sum(s11);
+                const long long cII = lk_centred(n, SII, SI, SI), cxI = lk_centred(n, SxI, Sx, SI);
+                if (cII != 0) { CII = (double)cII; CxI = (double)cxI; A11 = lk_reduce(lk_centred(n, Sxx, Sx, Sx), CxI, cxI, CII, (double)nwin); }
+                else ok = false;                                   // a flat template: A11 stays 0 and fails the test below as well
+            } else
             A11 = (double)lk_wave_sum(s11) * 0x1p-20;
             if (A11 / (double)nwin < (double)A.p.min_eig || A11 < 0x1p-23) ok = false;
         }
@@ -379,6 +473,7 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
             cover();
             const int off = jx - x0;
             int s1 = 0;
+            int sd = 0, sdI = 0;                                   // PHOTO: masked, bounded as in k_lk_track
 #pragma unroll
             for (int k = 0; k < NP; k++) {
                 int q = pk[k], g = gi[k];
@@ -386,9 +481,15 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
                 const int base = (q & 1023) + ((q >> 10) & 31) * dS + off;
                 const int d = lk_sample(tile, base, S, v00, v01, v10, v11) - (int)((unsigned)q >> 16);
                 s1 += d * g;
+                if constexpr (PHOTO) { const int dm = d & ((q << 16) >> 31); sd += dm; sdI += dm * (int)((unsigned)q >> 16); }
             }
             lk_wave_sync();
-            const double b1 = (double)lk_wave_sum(s1) * 0x1p-20;
+            const long long Sdx = lk_wave_sum(s1);
+            double b1;
+            if constexpr (PHOTO) {
+                const long long n = nwin, Sd = lk_wave_sum32(sd), SdI = lk_wave_sum(sdI);
+                b1 = lk_reduce(lk_centred(n, Sdx, Sx, Sd), CxI, lk_centred(n, SdI, SI, Sd), CII, (double)nwin);
+            } else b1 = (double)Sdx * 0x1p-20;
             const float dx = (float)(-b1 / A11);
             gx = gx + dx;
             if ((double)dx * (double)dx <= (double)A.p.eps * (double)A.p.eps) break;
@@ -402,6 +503,24 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
                 cover();
                 const int off = jx - x0;
                 int s = 0;
+                if constexpr (PHOTO) {                             // as in k_lk_track: Sd, then sum |n d - Sd|
+                    int sd = 0;
+#pragma unroll
+                    for (int k = 0; k < NP; k++) {
+                        const int q = pk[k], base = (q & 1023) + ((q >> 10) & 31) * dS + off;
+                        sd += (lk_sample(tile, base, S, v00, v01, v10, v11) - (int)((unsigned)q >> 16)) & ((q << 16) >> 31);
+                    }
+                    const int Sd = lk_wave_sum32(sd);
+#pragma unroll
+                    for (int k = 0; k < NP; k++) {
+                        int q = pk[k];
+                        asm volatile("" : "+v"(q));                // sampled again, not kept from the pass above
+                        const int base = (q & 1023) + ((q >> 10) & 31) * dS + off;
+                        const int c = nwin * (lk_sample(tile, base, S, v00, v01, v10, v11) - (int)((unsigned)q >> 16)) - Sd;
+                        s += (c < 0 ? -c : c) & ((q << 16) >> 31);
+                    }
+                    err = (float)((double)lk_wave_sum(s) / (double)(32 * nwin * nwin));
+                } else {
 #pragma unroll
                 for (int k = 0; k < NP; k++) {
                     const int q = pk[k], base = (q & 1023) + ((q >> 10) & 31) * dS + off;
@@ -409,6 +528,7 @@ __global__ __launch_bounds__(256) void k_lk_track_row(const LkTrackArgs A)
                     s += (d < 0 ? -d : d) & ((q << 16) >> 31);
                 }
                 err = (float)((double)lk_wave_sum(s) / (double)(32 * nwin));
+                }
             }
             break;
         }
@@ -430,6 +550,12 @@ void launch_lk_track_row(const LkTrackArgs& a, int pixels_per_lane, hipStream_t 
 {
     if (a.n_pts <= 0) return;
     const dim3 grid((unsigned)((a.n_pts + 3) / 4)), block(256);
+    if (a.photo) {
+        if (pixels_per_lane <= 2) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<2, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<2, false, true>), grid, block, 0, st, a); }
+        else if (pixels_per_lane <= 7) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<7, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<7, false, true>), grid, block, 0, st, a); }
+        else { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<16, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<16, false, true>), grid, block, 0, st, a); }
+        return;
+    }
     if (pixels_per_lane <= 2) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<2, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<2, false>), grid, block, 0, st, a); }
     else if (pixels_per_lane <= 7) { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<7, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<7, false>), grid, block, 0, st, a); }
     else { if (a.backward) hipLaunchKernelGGL((k_lk_track_row<16, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track_row<16, false>), grid, block, 0, st, a); }
@@ -439,6 +565,12 @@ void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st)
 {
     if (a.n_pts <= 0) return;
     const dim3 grid((unsigned)((a.n_pts + 3) / 4)), block(256);
+    if (a.photo) {
+        if (pixels_per_lane <= 2) { if (a.backward) hipLaunchKernelGGL((k_lk_track<2, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<2, false, true>), grid, block, 0, st, a); }
+        else if (pixels_per_lane <= 7) { if (a.backward) hipLaunchKernelGGL((k_lk_track<7, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<7, false, true>), grid, block, 0, st, a); }
+        else { if (a.backward) hipLaunchKernelGGL((k_lk_track<16, true, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<16, false, true>), grid, block, 0, st, a); }
+        return;
+    }
     if (pixels_per_lane <= 2) { if (a.backward) hipLaunchKernelGGL((k_lk_track<2, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<2, false>), grid, block, 0, st, a); }
     else if (pixels_per_lane <= 7) { if (a.backward) hipLaunchKernelGGL((k_lk_track<7, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<7, false>), grid, block, 0, st, a); }
     else { if (a.backward) hipLaunchKernelGGL((k_lk_track<16, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_lk_track<16, false>), grid, block, 0, st, a); }

@@ -96,6 +96,18 @@ Plan plan_lk_call(const svo_lk_job* jobs, int n_jobs, const svo_lk_params& p, bo
     return pl;
 }
 
+int check_lk_set_photometric(int mode, bool capturing, std::string& why)
+{
+    why.clear();
+    if (capturing) { why = "svo_lk_set_photometric: the context's stream is capturing a graph: the call cannot run inside one"; return SVO_ERR_STATE; }
+    if (mode != LK_PHOTO_RAW && mode != LK_PHOTO_GAIN_BIAS) {
+        char msg[192];
+        snprintf(msg, sizeof(msg), "svo_lk_set_photometric: mode %d: 0 (raw differences) or 1 (gain and bias removed per window) is expected", mode);
+        why = msg; return SVO_ERR_ARG;
+    }
+    return SVO_OK;
+}
+
 int lk_pixels_per_lane(int win)
 {
     const int n = (win * win + 63) / 64;

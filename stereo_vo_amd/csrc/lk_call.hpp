@@ -35,6 +35,11 @@ struct Plan {
 };
 Plan plan_lk_call(const svo_lk_job* jobs, int n_jobs, const svo_lk_params& p, bool device_images);
 
+// svo_lk_set_photometric, in order: a capturing stream (SVO_ERR_STATE), then the mode, 0 .. 1 (SVO_ERR_ARG).  Nothing else is asked: the
+// setter needs no svo_set_params and no front end
+enum { LK_PHOTO_RAW = 0, LK_PHOTO_GAIN_BIAS = 1 };
+int check_lk_set_photometric(int mode, bool capturing, std::string& why);
+
 // the kernel instantiation a window size runs: the number of window pixels a lane owns at most, ceil(win^2 / 64) rounded up to 2, 7 or 16
 int lk_pixels_per_lane(int win);
 

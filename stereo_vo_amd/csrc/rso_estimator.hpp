@@ -384,6 +384,9 @@ public:
     /** How stepKLT finds a track's right point (svo_klt_set_stereo): 0 the right list is tracked through time (default), 1 the partner
      *  of every new left point is found in the new pair along its row, so that the halves of a pair cannot drift apart. */
     void setKltStereo(int mode) { check(svo_klt_set_stereo(m_ctx, mode), "svo_klt_set_stereo"); }
+    /** What the LK trackers minimise (svo_lk_set_photometric): 0 raw grey differences (default), 1 with gain and bias removed per window. */
+    void setLkPhotometric(int mode) { check(svo_lk_set_photometric(m_ctx, mode), "svo_lk_set_photometric"); }
+    int getLkPhotometric() const { return svo_lk_get_photometric(m_ctx); }
     int getKltStereo() const { return svo_klt_get_stereo(m_ctx); }
     /** saveStateToFile / loadStateFromFile (H:184-185, C:475-543, C:261-350): false on error, like the reference */
     bool saveStateToFile(const std::string& filename) { return svo_save_state(m_ctx, 0, filename.c_str()) == SVO_OK; }

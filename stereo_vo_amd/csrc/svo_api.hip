@@ -287,7 +287,7 @@ extern "C" int svo_create(const svo_config* cfg, svo_ctx** out)
     ctx->sampler_nmax = 0;
     ctx->geom_ready = false; ctx->geom_once = false;
     ctx->d_ham_out = nullptr; ctx->d_ham_q = ctx->d_ham_t = nullptr; ctx->ham_cap_q = ctx->ham_cap_t = 0;
-    ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0;
+    ctx->lk_photo = 0; ctx->d_lk_pyr = nullptr; ctx->lk_pyr_cap = 0; ctx->d_lk_jobs = nullptr; ctx->lk_jobs_cap = 0; ctx->lk_pts_cap = 0;
     ctx->d_lk_pts = ctx->d_lk_init = ctx->d_lk_out = nullptr; ctx->d_lk_status = nullptr; ctx->d_lk_err = nullptr;
     ctx->d_gftt_map = nullptr; ctx->gftt_map_cap = 0; ctx->d_gftt_img = nullptr; ctx->gftt_img_cap = 0; ctx->d_gftt_jobs = nullptr; ctx->gftt_jobs_cap = 0;
     ctx->d_gftt_keys = nullptr; ctx->d_gftt_items = nullptr; ctx->d_gftt_state = nullptr; ctx->d_gftt_info = nullptr;

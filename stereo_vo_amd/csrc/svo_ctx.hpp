@@ -54,6 +54,9 @@ struct svo_ctx {
     uint8_t* d_lk_pyr; size_t lk_pyr_cap; LkJobDev* d_lk_jobs; int lk_jobs_cap;
     float2* d_lk_pts, *d_lk_init, *d_lk_out; uint8_t* d_lk_status; float* d_lk_err; int lk_pts_cap;
     std::vector<LkJobDev> lk_jobs;
+    // svo_lk_set_photometric: 0 raw differences, 1 gain and bias removed per window.  The tracker's, not the front end's: every LK launch
+    // of the context reads it when it is enqueued, and svo_klt_enable leaves it alone
+    int lk_photo;
     // svo_gftt_detect: buffers of its own as well -- the response maps, the copies of host images, the job records, per job the
     // candidate keys, the cell lists and the decision states, the flat seed and result arrays, four counters per job.  gftt_jobs: the
     // records of the last call, for svo_debug_gftt_get_response

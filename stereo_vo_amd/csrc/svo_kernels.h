@@ -128,12 +128,13 @@ struct LkJobDev {
     int nl, pt0, n, has_init;
 };
 // backward = 0: the forward pass (pts -> out, status, err; aux = the first guesses, read for jobs with has_init).  backward = 1: the
-// forward-backward check with the image roles swapped: pts = the forward results, aux = the points they came from; only status is written
+// forward-backward check with the image roles swapped: pts = the forward results, aux = the points they came from; only status is written.
+// photo: the context's svo_lk_set_photometric mode when the launch is enqueued (1: the PHOTO instantiations, tests/lk_photo_ref.py)
 struct LkTrackArgs {
     const LkJobDev* jobs; int n_jobs, n_pts;
     const float2* pts; const float2* aux;
     float2* out; uint8_t* status; float* err;
-    svo_lk_params p; int backward;
+    svo_lk_params p; int backward, photo;
 };
 void launch_lk_pyrdown(const LkJobDev* jobs, int n_jobs, int level, int max_w, int max_h, hipStream_t st);   // max_w x max_h: the largest level `level` of the call
 void launch_lk_track(const LkTrackArgs& a, int pixels_per_lane, hipStream_t st);                             // pixels_per_lane: lk_pixels_per_lane(win)

@@ -379,7 +379,7 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
     // 3. one tracking launch over every lane's two jobs (and the way back under fb_max); no lane has a last pair: nothing to track
     if (any_tracks) {
         const float2* guess = k.predict == svo_klt::KLT_PREDICT_POSE ? k.d_guess : nullptr;                     // (read for records with has_init)
-        const LkTrackArgs a{ k.d_trk_jobs, 2 * d.n_lanes, 2 * d.n_lanes * k.p.cap, k.dev.pts[k.half], guess, k.dev.out, k.dev.status, k.dev.err, k.p.lk, 0 };
+        const LkTrackArgs a{ k.d_trk_jobs, 2 * d.n_lanes, 2 * d.n_lanes * k.p.cap, k.dev.pts[k.half], guess, k.dev.out, k.dev.status, k.dev.err, k.p.lk, 0, ctx->lk_photo };
         Span s(ctx, KT_LK_TRACK);
         enqueue_lk_track(a, false, st);
     }
@@ -391,7 +391,7 @@ extern "C" int svo_klt_step(svo_ctx* ctx, const svo_frame* frames, uint32_t flag
         ga.t = k.dev; ga.half = k.half; ga.guess = k.d_row_guess; ga.active = active; ga.fresh = fresh;
         const int C = k.p.cap;
         // lane l: slots [2 l C, 2 l C + C), results C behind
-        const LkTrackArgs a{ k.d_row_jobs, d.n_lanes, (2 * d.n_lanes - 1) * C, k.dev.out, k.d_row_guess, k.dev.out + C, k.dev.status + C, k.dev.err + C, k.p.lk, 0 };
+        const LkTrackArgs a{ k.d_row_jobs, d.n_lanes, (2 * d.n_lanes - 1) * C, k.dev.out, k.d_row_guess, k.dev.out + C, k.dev.status + C, k.dev.err + C, k.p.lk, 0, ctx->lk_photo };
         Span s(ctx, KT_LK_TRACK_ROW);
         launch_klt_row_guess(ga, st);
         enqueue_lk_track(a, true, st);
@@ -551,7 +551,7 @@ extern "C" int svo_klt_topup(svo_ctx* ctx, const uint64_t lanes[2])
         // 5. the tracking records and the first guesses
         { Span s(ctx, KT_KLT_TOPUP); launch_klt_topup_prepare(a, st); }
         // 6. left -> right over every lane (and the way back under fb_max), as svo_lk_track launches it
-        const LkTrackArgs t{ k.d_tlk_jobs, n_lanes, n_lanes * k.p.cap, k.d_tcorners, k.d_tinit, k.d_tout, k.d_tstatus, k.d_terr, k.p.lk, 0 };
+        const LkTrackArgs t{ k.d_tlk_jobs, n_lanes, n_lanes * k.p.cap, k.d_tcorners, k.d_tinit, k.d_tout, k.d_tstatus, k.d_terr, k.p.lk, 0, ctx->lk_photo };
         Span s(ctx, KT_LK_TRACK);
         enqueue_lk_track(t, false, st);
     }

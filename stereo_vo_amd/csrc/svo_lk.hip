@@ -1,4 +1,4 @@
-// svo_lk.hip -- pyramidal Lucas-Kanade tracking on caller lists: svo_lk_track, svo_lk_track_rows, svo_debug_lk_get_level
+// svo_lk.hip -- pyramidal Lucas-Kanade tracking on caller lists: svo_lk_track, svo_lk_track_rows, svo_lk_set_photometric, svo_debug_lk_get_level
 // (svo_hip.h; the decisions: lk_call.hpp, the kernels: k_lk.hip).  No kernel lives here: the unit uses the HIP runtime and the launchers.
 #include "svo_ctx.hpp"
 
@@ -66,8 +66,8 @@ static int lk_track_call(svo_ctx* ctx, const svo_lk_job* jobs, int n_jobs, const
     if (NP) HIPCHECK(hipMemcpyAsync(ctx->d_lk_pts, h_pts.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
     if (NP && plan.any_init) HIPCHECK(hipMemcpyAsync(ctx->d_lk_init, h_init.data(), sizeof(float) * 2 * NP, hipMemcpyHostToDevice, st));
     { Span s(ctx, KT_LK_PYRDOWN); for (int l = 1; l < plan.max_nl; l++) launch_lk_pyrdown(ctx->d_lk_jobs, n_jobs, l, lw[l], lh[l], st); }
-    // (jobs, n_jobs, n_pts; pts, aux: the first guesses; out, status, err; the parameters; forward)
-    const LkTrackArgs a{ ctx->d_lk_jobs, n_jobs, plan.n_pts, ctx->d_lk_pts, ctx->d_lk_init, ctx->d_lk_out, ctx->d_lk_status, ctx->d_lk_err, p, 0 };
+    // (jobs, n_jobs, n_pts; pts, aux: the first guesses; out, status, err; the parameters; forward; the context's photometric mode)
+    const LkTrackArgs a{ ctx->d_lk_jobs, n_jobs, plan.n_pts, ctx->d_lk_pts, ctx->d_lk_init, ctx->d_lk_out, ctx->d_lk_status, ctx->d_lk_err, p, 0, ctx->lk_photo };
     { Span s(ctx, rows ? KT_LK_TRACK_ROW : KT_LK_TRACK); enqueue_lk_track(a, rows, st); }
     HIPCHECK(hipGetLastError());
     std::vector<float> h_out(2 * NP), h_err(NP);
@@ -98,6 +98,18 @@ extern "C" int svo_lk_track_rows(svo_ctx* ctx, const svo_lk_job* jobs, int n_job
 {
     return lk_track_call(ctx, jobs, n_jobs, params, flags, true);
 }
+
+// svo_lk_set_photometric / svo_lk_get_photometric: the mode every later LK launch of the context carries (LkTrackArgs::photo)
+extern "C" int svo_lk_set_photometric(svo_ctx* ctx, int mode)
+{
+    SVO_ENTER(ctx);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    SVO_REFUSE(svo_lk::check_lk_set_photometric(mode, ctx->capturing || cs != hipStreamCaptureStatusNone, why));
+    ctx->lk_photo = mode;
+    return SVO_OK;
+}
+extern "C" int svo_lk_get_photometric(const svo_ctx* ctx) { return ctx ? ctx->lk_photo : SVO_ERR_ARG; }
 
 extern "C" int svo_debug_lk_get_level(svo_ctx* ctx, int job, int which, int level, uint8_t* out, int cap, int* w, int* h)
 {

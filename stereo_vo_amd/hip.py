@@ -38,6 +38,7 @@ EXPORTS = [
     "svo_ransac_tracked", "svo_klt_set_ransac", "svo_klt_get_ransac",
     "svo_klt_set_prediction", "svo_klt_get_prediction", "svo_klt_predicted", "svo_debug_klt_predict",
     "svo_lk_track_rows", "svo_klt_set_stereo", "svo_klt_get_stereo",
+    "svo_lk_set_photometric", "svo_lk_get_photometric",
     "svo_debug_get_level", "svo_debug_get_raw_keypoints", "svo_debug_get_status_word", "svo_debug_get_redo_count", "svo_debug_get_graph_count", "svo_debug_timeline", "svo_profiler_sections_enabled",
     "svo_kernel_times", "svo_kernel_times_reset", "svo_kernel_times_select", "svo_abi_sizes",
     "svo_get_values", "svo_put_features_oct", "svo_put_matches_oct", "svo_put_match_ids_oct",
@@ -177,6 +178,9 @@ def lib():
             L.svo_lk_track_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
             L.svo_klt_set_stereo.argtypes = [C.c_void_p, C.c_int]
             L.svo_klt_get_stereo.argtypes = [C.c_void_p]
+        if hasattr(L, "svo_lk_set_photometric"):    # (as above)
+            L.svo_lk_set_photometric.argtypes = [C.c_void_p, C.c_int]
+            L.svo_lk_get_photometric.argtypes = [C.c_void_p]
         L.svo_process_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_batch_step_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.svo_gather_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
@@ -1057,6 +1061,17 @@ class Context:
     def klt_get_stereo(self):
         """the mode svo_klt_set_stereo left"""
         return self._ck(self.L.svo_klt_get_stereo(self.h), "svo_klt_get_stereo")
+
+    # -- the photometric mode of the trackers (svo_lk_set_photometric) ------------------------------------------------
+    def lk_set_photometric(self, mode):
+        """what every LK launch of the context minimises: 0 (the default) raw differences, 1 the differences with an affine brightness
+        change between template and target removed per window (tests/lk_photo_ref.py).  lk_track, lk_track_rows, klt_step and klt_topup
+        follow it; klt_enable does not reset it.  Any time after the context exists."""
+        self._ck(self.L.svo_lk_set_photometric(self.h, int(mode)), "svo_lk_set_photometric")
+
+    def lk_get_photometric(self):
+        """the mode svo_lk_set_photometric left"""
+        return self._ck(self.L.svo_lk_get_photometric(self.h), "svo_lk_get_photometric")
 
     def _klt_guesses(self, what, call):
         n = self._ck(call(None, None, None, 0), what)

@@ -12,7 +12,9 @@ tools/klt_predict_times.py.
   survivors        live tracks per lane after the last frame, and the lanes whose last timed step ended valid
 Also, as information: the rotation / translation error of both modes against SyntheticStereoWorld.gt_delta on the 160x120 sequence of
 tests/klt_scenes.py, as profiles/klt_times.json has it for mode 0.
-Prints one JSON line (profiles/klt_stereo_times.json).  No threshold hangs on these figures."""
+Prints one JSON line (profiles/klt_stereo_times.json).  No threshold hangs on these figures.
+  --photometric   every leg runs under svo_lk_set_photometric(ctx, 1); --configs a,b restricts the run to those configurations and
+                  --no-accuracy leaves the 160x120 sequence out (profiles/lk_photo_times.json holds mode_0 and mode_1 both ways)."""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -54,6 +56,8 @@ def leg(a):
     kp = hip.default_klt_params()
     kp.cap = CAP
     kp.lk.fb_max = a.fb_max
+    if a.photometric:                                      # (the tracker's mode: before or after svo_klt_enable alike)
+        c.lk_set_photometric(1)
     c.klt_enable(kp)
     if a.mode:                                             # (mode 0 never calls the setter)
         c.klt_set_stereo(a.mode)
@@ -72,7 +76,7 @@ def leg(a):
     valid = sum(int(r.valid) for r in c.results())
     kt = c.kernel_times(appended=True) if a.kernel_times else None
     live = [len(c.klt_tracks(g)[2]) for g in range(a.lanes)]
-    out = {"mode": a.mode, "fb_max": a.fb_max, "ms_per_step": round(ms, 4), "lanes_valid_last_frame": valid,
+    out = {"mode": a.mode, "fb_max": a.fb_max, "photometric": c.lk_get_photometric(), "ms_per_step": round(ms, 4), "lanes_valid_last_frame": valid,
            "survivors_per_lane_last_frame": {"min": min(live), "mean": round(sum(live) / len(live), 1), "max": max(live)}}
     if a.kernel_times:
         out["kernel_us_per_step"] = {k: round(1e3 * kt[k][0] / a.steps, 2) for k in STEP_NAMES if k in kt}
@@ -80,7 +84,7 @@ def leg(a):
     print("LEG " + json.dumps(out))
 
 
-def accuracy_leg():
+def accuracy_leg(photometric=False):
     """both modes on the 160x120 sequence: per frame 1 .. 4 [valid, rotation error rad, translation error m, live tracks]"""
     from stereo_vo_amd import hip
     from stereo_vo_amd.abi import north_star_params
@@ -98,6 +102,8 @@ def accuracy_leg():
         p = north_star_params(hip.default_params()); p.orb_nlevels, p.orb_nfeats = 2, 300      # (the detector is never run; its list capacity must fit max_kps)
         c.set_params(p); c.set_camera(world.camera())
         c.klt_enable(kp); c.klt_set_stereo(mode); c.klt_add_points(0, *KS.sequence_points())
+        if photometric:
+            c.lk_set_photometric(1)
         rows = []
         for t in range(KS.SEQ_FRAMES):
             c.klt_step([frames[t]])
@@ -112,6 +118,8 @@ def accuracy_leg():
 
 def run_leg(a, name, kernel_times=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--lanes", str(a.lanes), "--worlds", str(a.worlds), "--warmup", str(a.warmup), "--steps", str(a.steps)]
+    if a.photometric:
+        cmd.append("--photometric")
     if name == "accuracy":
         cmd.append("--accuracy")
     else:
@@ -144,23 +152,28 @@ def main():
     ap.add_argument("--fb-max", type=float, default=0.0)
     ap.add_argument("--kernel-times", action="store_true")
     ap.add_argument("--leg-timeout", type=int, default=240)
+    ap.add_argument("--photometric", action="store_true", help="every leg under svo_lk_set_photometric(ctx, 1)")
+    ap.add_argument("--configs", default=",".join(CONFIGS), help="the configurations to run, comma separated")
+    ap.add_argument("--no-accuracy", action="store_true")
     a = ap.parse_args()
     if a.leg:
-        return accuracy_leg() if a.accuracy else leg(a)
-    ms = {name: [] for name in CONFIGS}
+        return accuracy_leg(a.photometric) if a.accuracy else leg(a)
+    configs = {name: CONFIGS[name] for name in a.configs.split(",")}
+    ms = {name: [] for name in configs}
     info = {}
     for _ in range(a.reps):
-        for name in CONFIGS:
+        for name in configs:
             r = run_leg(a, name)
             ms[name].append(r["ms_per_step"]); info[name] = r
-    kernels = {name: run_leg(a, name, kernel_times=True)["kernel_us_per_step"] for name in CONFIGS}
-    acc = run_leg(a, "accuracy")
+    kernels = {name: run_leg(a, name, kernel_times=True)["kernel_us_per_step"] for name in configs}
+    acc = {} if a.no_accuracy else run_leg(a, "accuracy")
     out = {"shape": "%d lanes of %dx%d in one context, %d tracks per lane at the start, default tracker parameters but fb_max (win 21, 4 levels), device images, "
                     "%d warm-up + %d timed frames, %d rendered trajectories shared by the lanes; %d legs per configuration, a process each, alternating"
                     % (a.lanes, W, H, CAP, a.warmup, a.steps, a.worlds, a.reps),
-           "configurations": {name: {"mode": m, "fb_max": fb} for name, (m, fb) in CONFIGS.items()},
-           "ms_per_step": {name: spread(ms[name]) for name in CONFIGS},
-           "last_leg": {name: {k: v for k, v in info[name].items() if k not in ("mode", "fb_max", "ms_per_step")} for name in CONFIGS},
+           "photometric": int(a.photometric),
+           "configurations": {name: {"mode": m, "fb_max": fb} for name, (m, fb) in configs.items()},
+           "ms_per_step": {name: spread(ms[name]) for name in configs},
+           "last_leg": {name: {k: v for k, v in info[name].items() if k not in ("mode", "fb_max", "ms_per_step")} for name in configs},
            "kernel_us_per_step": kernels,
            "accuracy_160x120": {"columns": "per frame 1..4: [valid, rotation error rad, translation error m, live tracks] against gt_delta", **acc}}
     print(json.dumps(out))

@@ -111,6 +111,22 @@ int main()
     // the kernels divide a tile index by the tile side with a multiplication: exact for every side and index they use
     for (int T = 5; T <= 34; T++) { const unsigned M = (65536u + (unsigned)T - 1u) / (unsigned)T; for (int t = 0; t < T * T; t++) CHECK((int)(((unsigned)t * M) >> 16) == t / T); }
 
+    // svo_lk_set_photometric: modes 0 and 1, anything else SVO_ERR_ARG with the mode in the text; a capturing stream comes first
+    { static_assert(LK_PHOTO_RAW == 0 && LK_PHOTO_GAIN_BIAS == 1, "the modes of svo_lk_set_photometric");
+      std::string t;
+      CHECK(check_lk_set_photometric(0, false, t) == SVO_OK && t.empty());
+      CHECK(check_lk_set_photometric(1, false, t) == SVO_OK && t.empty());
+      CHECK(check_lk_set_photometric(2, false, t) == SVO_ERR_ARG && t.find("mode 2") != std::string::npos);
+      CHECK(check_lk_set_photometric(-1, false, t) == SVO_ERR_ARG && t.find("mode -1") != std::string::npos);
+      CHECK(check_lk_set_photometric(INT32_MIN, false, t) == SVO_ERR_ARG && check_lk_set_photometric(INT32_MAX, false, t) == SVO_ERR_ARG);
+      CHECK(check_lk_set_photometric(1, true, t) == SVO_ERR_STATE && t.find("capturing") != std::string::npos);
+      CHECK(check_lk_set_photometric(7, true, t) == SVO_ERR_STATE); }
+    // the photometric sums of k_lk.hip: a lane's 16 pixels of I I or d I stay inside a signed 32-bit partial sum, the centred moments
+    // times n inside the 2^53 a double holds exactly
+    { const long long lane = 16ll * 8160 * 8160, n = 31 * 31;
+      CHECK(lane == 1065369600ll && lane < (1ll << 30));
+      CHECK(n * (n * 8160 * 8160) < (1ll << 53) && 16ll * (n * 8160 + n * 8160) < (1ll << 28)); }
+
     if (failures) { printf("lk_check: %d check(s) failed\n", failures); return 1; }
     printf("lk_check: ok\n");
     return 0;

@@ -10,7 +10,9 @@ each, win 21, max_level 3, default iteration limits, on device images (read in p
     the tiles come out of L2 / MALL, not HBM.  The iteration count is not known to the host; the figure uses `--iters-per-point`
     (default 9: tests/test_lk_scenes_cpu.py measures 7.7 - 11.0 on this kind of texture, all levels together).
 Every job has images of its own (seeded, generated on the device).  Prints one JSON line (profiles/lk_times.json).  No threshold hangs
-on these figures."""
+on these figures.
+  --photometric   a second leg of the same shape on the same context and images under svo_lk_set_photometric(ctx, 1), behind the first:
+                  its spans, call time and result counts under "photometric", beside the mode-0 figures (profiles/lk_photo_times.json)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--iters-per-point", type=float, default=9.0)
+    ap.add_argument("--photometric", action="store_true", help="add a leg in mode 1 of svo_lk_set_photometric")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("lk_times: no GPU; these figures are measured on the device or not at all")
@@ -59,16 +62,19 @@ def main():
         pts = np.stack([rng.uniform(40, W - 40, a.points), rng.uniform(40, H - 40, a.points)], 1).astype(np.float32)
         jobs.append(((prev.data_ptr(), W, H, W), (nxt.data_ptr(), W, H, W), pts))
     torch.cuda.synchronize()
-    for _ in range(a.warmup):
-        res = ctx.lk_track(jobs, p, device=True)
-    ctx.kernel_times_reset()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        res = ctx.lk_track(jobs, p, device=True)
-    wall = (time.perf_counter() - t0) / a.steps
-    kt = ctx.kernel_times(appended=True)
-    tracked = int(sum(int(r[1].sum()) for r in res))
-    moved = np.concatenate([r[0][r[1] == 1] - j[2][r[1] == 1] for r, j in zip(res, jobs)])
+
+    def leg():
+        """(seconds per call, the spans, tracked points, their motion) of warm-up + timed calls in the context's mode"""
+        for _ in range(a.warmup):
+            res = ctx.lk_track(jobs, p, device=True)
+        ctx.kernel_times_reset()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            res = ctx.lk_track(jobs, p, device=True)
+        wall = (time.perf_counter() - t0) / a.steps
+        kt = ctx.kernel_times(appended=True)
+        return wall, kt, int(sum(int(r[1].sum()) for r in res)), np.concatenate([r[0][r[1] == 1] - j[2][r[1] == 1] for r, j in zip(res, jobs)])
+    wall, kt, tracked, moved = leg()
     lv = [(W, H)]
     while len(lv) <= p.max_level and (lv[-1][0] + 1) // 2 >= p.win + 4 and (lv[-1][1] + 1) // 2 >= p.win + 4:
         lv.append(((lv[-1][0] + 1) // 2, (lv[-1][1] + 1) // 2))
@@ -89,6 +95,17 @@ def main():
         "track_tile_GBps": round(tile_bytes / (1e6 * kt["lk_track"][0] / kt["lk_track"][1]), 1),
         "track_Mpoints_per_s": round(a.jobs * a.points / (1e3 * kt["lk_track"][0] / kt["lk_track"][1]), 2),
     }
+    if a.photometric:
+        ctx.lk_set_photometric(1)
+        wall1, kt1, tracked1, moved1 = leg()
+        out["photometric"] = {
+            "lk_track_ms_per_call": round(kt1["lk_track"][0] / kt1["lk_track"][1], 3),
+            "lk_pyrdown_ms_per_call": round(kt1["lk_pyrdown"][0] / kt1["lk_pyrdown"][1], 3),
+            "spans": {k: list(kt1[k]) for k in ("lk_pyrdown", "lk_track")},
+            "call_ms": round(1e3 * wall1, 3), "tracked": tracked1,
+            "median_motion_px": [round(float(np.median(moved1[:, 0])), 3), round(float(np.median(moved1[:, 1])), 3)],
+            "lk_track_ratio_to_mode_0": round((kt1["lk_track"][0] / kt1["lk_track"][1]) / (kt["lk_track"][0] / kt["lk_track"][1]), 3),
+        }
     ctx.close()
     print(json.dumps(out))
 
